@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: Mpixels/s segmented on synthetic 6-band 40000x40000 tiled imagery.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5] [--dump-outputs DIR]
     (N > 1 without a launcher: bench.py starts the N ranks itself; under
      `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` it is one rank)
 
@@ -16,6 +16,9 @@ Workloads (BASELINE.json configs):
       1.6 Gpx label raster of 50 M segments (4 x 8-pixel blocks), rasters resident in HBM, the
       result columns copied to the host.
 value = image pixels / step time.
+--dump-outputs DIR (one GPU): after the timed steps, what the last step computed is written as DIR/<name>.npy
+(float32 / float64, under 64 MB: the arrays too large to keep whole as a fixed seeded sample); the inputs are the
+same on every run, so two builds can be compared output for output.
 
 No torch anywhere: with N > 1 the ranks talk over RCCL bound directly behind the C-ABI
 (pyshepseg_amd/comm.py); the product path is pyshepseg_amd -> ctypes -> libshepseg_hip.so.
@@ -31,8 +34,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# must be in the environment before the HIP runtime starts
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
 
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
@@ -59,7 +60,14 @@ def parse():
                          'runs after the headline timing (0 = skip)')
     ap.add_argument('--cpu-sample', type=int, default=14336,
                     help='window edge of the cpu_baseline sample (0 = skip)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy '
+                         '(float32 / float64, a fixed seeded sample of the arrays too large to keep whole)')
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error('--dump-outputs needs --steps >= 1')
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error('--dump-outputs is for one-GPU runs')
     if args.bands is None:
         args.bands = {'c3': 6, 'c4': 10, 'c5': 1}[args.workload]
     args.seed = 13 if args.workload == 'c4' else 11
@@ -155,6 +163,60 @@ def gpu_window_check(args, w, centres, mosaic, mosaicMax, mosaicHist):
     if not ok:
         sys.stderr.write('bench.py: the device mosaic of the %d x %d cpu_baseline window DIFFERS from the oracle\n' % (w, w))
     return bool(ok)
+
+
+DUMP_SEED = 1234                 # the --dump-outputs samples: the same positions on every run
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(n, k, seed):
+    """k sorted distinct indices of range(n), the same on every run (all n of them when n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def write_outputs(dirpath, arrays):
+    """--dump-outputs: every array as dirpath/<name>.npy"""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(dirpath, exist_ok=True)
+    for (name, a) in sorted(arrays.items()):
+        np.save(os.path.join(dirpath, name + '.npy'), a)
+    sys.stderr.write('bench.py: %d arrays (%.1f MB) written to %s\n' % (len(arrays), total / 1e6, dirpath))
+
+
+def dump_segmentation(args, r, dst):
+    """The last timed step's result as its caller receives it: the stitched labels (a seeded 1536 x 1536
+    grid of rows and columns), the histogram (whole up to 4 M ids, else a seeded 2 M sample), maxSegId,
+    maxSpectralDiff and the k-means centres."""
+    from pyshepseg_amd import _lib
+    rows = dump_sample(args.size, 1536, DUMP_SEED)
+    cols = dump_sample(args.size, 1536, DUMP_SEED + 1)
+    if args.source == 'hbm':
+        (ptr, nr, nc, _nbytes) = r.outDev
+        assert ptr and (nr, nc) == (args.size, args.size)
+        lab = np.empty((len(rows), len(cols)), dtype=np.uint32)
+        (ri, ci) = (rows.astype(np.uint32), cols.astype(np.uint32))
+        c = _lib.ctx()
+        c.check(c._L.shp_dev_subsample(c.handle, ctypes.c_void_p(ptr), _lib.SHP_DTYPES[lab.dtype], 1, nr, nc,
+                                       _lib.ptr(ri), len(ri), _lib.ptr(ci), len(ci), _lib.ptr(lab)))
+    else:
+        lab = np.load(dst, mmap_mode='r')[np.ix_(rows, cols)]
+    out = {'labels_sample': lab.astype(np.float64), 'labels_sample_rows': rows.astype(np.float64),
+           'labels_sample_cols': cols.astype(np.float64),
+           'max_seg_id': np.array([int(r.maxSegId)], dtype=np.float64),
+           'max_spectral_diff': np.array([float(r.maxSpectralDiff)], dtype=np.float64),
+           'centres': np.asarray(r.kmeans.cluster_centers_, dtype=np.float64)}
+    hist = np.asarray(r.hist)
+    if hist.size <= (4 << 20):
+        out['hist'] = hist.astype(np.float64)
+    else:
+        ids = dump_sample(hist.size, 2 << 20, DUMP_SEED + 2)
+        out['hist_sample'] = hist[ids].astype(np.float64)
+        out['hist_sample_ids'] = ids.astype(np.float64)
+    write_outputs(args.dump_outputs, out)
 
 
 def spawn_ranks(args):
@@ -264,12 +326,12 @@ def bench_segmentation(args):
             sys.stderr.write('bench.py: wrote %s (%.1f GB) in %.1f s\n' % (src, ras.nbytes / 1e9, time.time() - t0))
         ras.free()                        # the pipeline brings the file into HBM itself
 
-    def step():
+    def step(keep=False):
         r = tiling.doTiledShepherdSegmentation(
             src, dst, tileSize=args.tile, overlapSize=args.overlap,
             minSegmentSize=50, numClusters=60, fixedKMeansInit=True, concurrencyCfg=cfg,
             simpleTileRecode=bool(args.simple_recode))
-        if args.source == 'hbm':
+        if args.source == 'hbm' and not keep:
             tiling.freeDeviceOutput(r)
         return r
 
@@ -280,13 +342,18 @@ def bench_segmentation(args):
     c.check(c._L.shp_sync(c.handle))
     t0 = time.time()
     step_s = []
-    for _ in range(args.steps):
+    for i in range(args.steps):
         ts = time.time()
-        r = step()
+        # --dump-outputs: the last step's labels stay in HBM until they are sampled
+        r = step(keep=args.dump_outputs is not None and i == args.steps - 1)
         step_s.append(round(time.time() - ts, 4))
     c.check(c._L.shp_sync(c.handle))
     dt = (time.time() - t0) / max(args.steps, 1)
     prof = prof_totals(_lib.pool_contexts())
+    if args.dump_outputs is not None:
+        dump_segmentation(args, r, dst)
+        if args.source == 'hbm':
+            tiling.freeDeviceOutput(r)
 
     npix = args.size * args.size
     value = npix / dt / 1e6
@@ -355,8 +422,10 @@ def also_runs(args):
     import copy
     from pyshepseg_amd import tiling
     res = {}
-    for (name, over) in (('c5', dict(workload='c5', bands=1, seed=11, steps=2, warmup=1, cpu_sample=0, source='hbm')),
-                         ('c3_npy', dict(workload='c3', bands=6, seed=11, steps=2, warmup=1, cpu_sample=0, source='npy'))):
+    for (name, over) in (('c5', dict(workload='c5', bands=1, seed=11, steps=2, warmup=1, cpu_sample=0, source='hbm',
+                                     dump_outputs=None)),
+                         ('c3_npy', dict(workload='c3', bands=6, seed=11, steps=2, warmup=1, cpu_sample=0, source='npy',
+                                         dump_outputs=None))):
         a = copy.copy(args)
         for (k, v) in over.items():
             setattr(a, k, v)
@@ -408,6 +477,17 @@ def bench_stats(args):
     c.check(c._L.shp_sync(c.handle))
     dt = (time.time() - t0) / max(args.steps, 1)
     ms, cnt = prof_totals([c]).get(8, (0.0, 0))
+    if args.dump_outputs is not None:
+        # the last step's result columns, at a seeded sample of 1 M segment ids (0 included when drawn)
+        ids = dump_sample(S + 1, 1 << 20, DUMP_SEED + 3)
+        out = {'segment_ids': ids.astype(np.float64)}
+        for (i, (_col, stat)) in enumerate(sel):
+            j = fast[i, tilingstats.STATSEL_COLARRAYINDEX]
+            if fast[i, tilingstats.STATSEL_COLTYPE] == tilingstats.STAT_DTYPE_INT:
+                out[stat] = ic[j, ids].astype(np.float64)
+            else:
+                out[stat] = fc[j, ids].astype(np.float32)
+        write_outputs(args.dump_outputs, out)
     assert int(ic[fast[3, 3]].sum()) == N * N
     npix = N * N
     alg = 6 * npix + 4 * len(sel) * (S + 1)            # 6 B/px + 4 * nCols B/segment
@@ -462,6 +542,9 @@ def main():
     os.environ.setdefault('SHEPSEG_DEVICE', str(local_rank))
     force_dist = os.environ.get('SHEPSEG_FORCE_DIST', '0') == '1' and 'RANK' in os.environ
     if world > 1 or force_dist:
+        if args.dump_outputs is not None:
+            sys.stderr.write('bench.py: --dump-outputs is for one-GPU runs\n')
+            sys.exit(2)
         # RCCL brings streams of its own: two walker streams fewer keep the process inside its hardware queues
         # (LABNOTES, round 4: 522 -> 477 ms per step at world 1; must be set before the library loads)
         if os.environ.get('SHEPSEG_COMM', 'rccl') == 'rccl':

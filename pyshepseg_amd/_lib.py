@@ -8,10 +8,6 @@ import ctypes
 import os
 import threading
 
-# more hardware queues than ROCm's default of 4, so that the per-tile worker streams do not
-# queue behind each other's long-running kernels (must be set before the HIP runtime starts)
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '24')
-
 import numpy
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
