@@ -392,12 +392,15 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
             kept = [j for j in jobs if j.row * ncolsT + j.col <= bad]
             redo = [j for j in jobs if j.row * ncolsT + j.col > bad]
             ownsBad = t0 <= bad < t1
+            # the next rank redoes all its tiles: this rank's boundary strips go to it below
+            sendsOn = nextRank is not None and t1 - 1 >= bad
             # final ids for what is kept: output rows, the kept tiles' strips, and (on the rank that owns
             # `bad`) the previous rank's strips, which arrived with provisional ids
-            # (a rank all of whose tiles are redone has nothing to renumber; one that redoes none never reads
-            #  its strips again: only its output rows get their final ids)
+            # (a rank all of whose tiles are redone has nothing to renumber; one that redoes none reads its
+            #  strips again only when it sends them on -- when `bad` is its last tile -- and otherwise only its
+            #  output rows get their final ids)
             if kept:
-                engine.renumberKept(stride, base, kept if redo else [],
+                engine.renumberKept(stride, base, kept if (redo or sendsOn) else [],
                                     list(fromPrevProv.values()) if (ownsBad and redo) else [])
             if redo:
                 if ownsBad:
@@ -415,7 +418,7 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
                 maxSegId = engine.getMaxSegId()
             elif ownsBad:
                 maxSegId = mAfter
-            if nextRank is not None and t1 - 1 >= bad:          # the next rank redoes all its tiles
+            if sendsOn:
                 plan = boundaryPlan(tileInfo, shards, comm.rank, overlapSize)
                 engine.sendBoundary(comm, nextRank, maxSegId,
                                     [(kind, jobmap[(c, r)], h, w) for (kind, c, r, h, w) in plan])
@@ -436,6 +439,14 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
             maxSegId = _resume(bad, base, mAfter, stride, fromPrevProv)
     else:
         maxSegId = _sequential()
+    # A tile hands out at most one id per pixel, so no stitch ends above the tiles' total area.  Every rank
+    # holds the same all-gathered value and raises alike, instead of sizing the histogram (and the all-reduce
+    # that follows) by ids that are still provisional.
+    maxPossible = sum(xs * ys for (_x, _y, xs, ys) in tileInfo.tiles.values())
+    if not 0 <= maxSegId <= maxPossible:
+        raise tiling.PyShepSegTilingError(
+            "stitch ended with maxSegId %d, more than the %d pixels of all tiles (stitch form %s)"
+            % (maxSegId, maxPossible, stitchMode))
     _mark('tiles + stitch')
     hist = engine.histogram(maxSegId) if haveTiles else numpy.zeros(maxSegId + 1, numpy.int64)
     hist = comm.allreduce_sum_i64(numpy.asarray(hist, dtype=numpy.int64)).astype(numpy.uint32)

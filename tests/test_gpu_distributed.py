@@ -4,7 +4,6 @@ RCCL communicator itself runs (ncclCommInitRank, its collectives and a self send
 exercised separately).  Result must equal the single-process tiled run."""
 import os
 import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -12,22 +11,15 @@ import pytest
 
 from conftest import ROOT
 
+import dist_cases
+
 pytestmark = pytest.mark.gpu
 
 
 def _run_ranks(world, argv, tmp_path, timeout=900, extra=None):
-    procs = []
-    import secrets
-    nonce = secrets.token_hex(8)
-    for r in range(world):
-        env = dict(os.environ, SHEPSEG_LAUNCH_NONCE=nonce, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world),
-                   MASTER_ADDR='127.0.0.1', MASTER_PORT='0', SHEPSEG_COMM_DIR=str(tmp_path / 'comm'))
-        env.update(extra or {})
-        procs.append(subprocess.Popen([sys.executable] + argv, env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.PIPE, text=True))
-    outs = [p.communicate(timeout=timeout) for p in procs]
-    for (p, (_o, e)) in zip(procs, outs):
-        assert p.returncode == 0, e[-3000:]
+    """`world` rank processes, each with `timeout` seconds: the first that fails or runs out of time stops
+    them all (none keeps the GPU), never retried"""
+    return dist_cases.runRanks(world, argv, tmp_path, timeout, extra_env=extra)
 
 
 def test_rccl_comm_world_one(tmp_path):
@@ -103,6 +95,49 @@ def test_hip_engine_chain_matches_single_process(world, mode, tmp_path):
         st = np.load(tmp_path / ('stats%d.npz' % r))
         assert np.array_equal(st['ic'], wic)
         assert np.array_equal(st['fc'].view(np.uint32), wfc.view(np.uint32))
+
+
+# Partial redo of the parallel stitch on the HIP engine (renumberKept: shp_renumber_dev over the kept tiles'
+# strips in d_strips and over the strips received with provisional ids; the device recode of the redone chain),
+# with the rank boundaries placed around `bad` on purpose.  Rasters of the fuzz recipe of
+# test_distributed_cpu.py; the ranges were chosen by its search: (seed, [t0, t1) per rank, placement).
+HIP_REDO_CASES = [
+    pytest.param(7, [(0, 11), (11, 20)], 'bad_last_of_sender_midrow', id='seed7-bad-last-of-rank0-world2'),
+    pytest.param(7, [(0, 11), (11, 15), (15, 20)], 'bad_last_of_sender', id='seed7-bad-last-of-rank0-world3'),
+    pytest.param(13, [(0, 8), (8, 16)], 'bad_first_of_rank', id='seed13-bad-first-of-rank1'),
+    pytest.param(31, [(0, 7), (7, 20)], 'midrow_boundary', id='seed31-midrow-boundary'),
+]
+
+
+@pytest.mark.parametrize('seed,ranges,placement', HIP_REDO_CASES)
+def test_hip_engine_partial_redo_across_ranks(seed, ranges, placement, tmp_path, oracle):
+    """The HIP engine's partial redo with explicit shard ranges, ranks sharing GPU 0 over the socket
+    transport: every rank's mosaic rows, maxSegId and histogram == the oracle's sequential stitch with the
+    same centres and MSD, and the redo starts after the tile the oracle engine's one-rank run names."""
+    case = dist_cases.fuzzCase(seed, oracle)
+    bad = dist_cases.badTile(case, oracle)
+    assert bad is not None
+    dist_cases.checkShardRanges(ranges, case['ncols'], case['ntiles'])
+    dist_cases.checkNeighboursDelivered(dist_cases.tileInfoOf(case['nr'], case['nc'], case['tile'], case['ov']),
+                                        ranges, case['ov'])
+    assert placement in dist_cases.placementsOf(ranges, bad, case['ncols'])
+    np.save(tmp_path / 'img.npy', case['img'])
+    np.save(tmp_path / 'centres.npy', case['centres'])
+    world = len(ranges)
+    _run_ranks(world, [os.path.join(ROOT, 'tests', 'dist_worker_gpu.py'), str(tmp_path), 'socket', 'npy',
+                       str(tmp_path / 'img.npy'), str(tmp_path / 'centres.npy'), repr(case['msd']), str(case['tile']),
+                       str(case['ov']), str(case['minseg']), str(-1 if case['null'] is None else case['null']),
+                       str(int(case['four'])), '--ranges=' + dist_cases.encodeRanges(ranges)],
+               tmp_path, timeout=600, extra={'SHEPSEG_STITCH': 'parallel'})
+    parts = [np.load(tmp_path / ('rank%d.npz' % r)) for r in range(world)]
+    for (r, q) in enumerate(parts):
+        print('seed %d ranges %s bad %d: rank %d stitchMode %s chainStepsRedone %d'
+              % (seed, ranges, bad, r, q['mode'], int(q['redone'])))
+    for q in parts:
+        assert str(q['mode']) == 'parallel->sequential'
+        assert int(q['redone']) == case['ntiles'] - 1 - bad
+    assert [tuple(int(v) for v in q['tiles']) for q in parts] == [tuple(t) for t in ranges]
+    dist_cases.checkRanksAgainst(dist_cases.sequentialReference(case, oracle), parts, 'seed %d %s' % (seed, ranges))
 
 
 class _ThreadDevComm(object):
