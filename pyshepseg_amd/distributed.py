@@ -36,9 +36,38 @@ What shards and what does not
   (shp_kmeans_fit_planar_dist).  Other transports fit on rank 0 and broadcast the centres.
 
 The driver below is engine-agnostic: ``HipEngine`` drives libshepseg_hip.so on this rank's GPU;
-the CPU tests plug in an engine built on the oracle to exercise the sharding / exchange logic
-with world_size 2 over gloo.
+the CPU tests plug in an engine built on the oracle (tests/dist_oracle_engine.py) to exercise the
+sharding / exchange logic with several ranks over sockets.
+
+The engine
+----------
+What the two drivers below call on it (j: a tiling.makeTileJobs job; strip: the engine's handle of a
+recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six numbers):
+  setup(tileInfo, jobs, total, yLo, yHi, outLo, outHi, nCols, overlapSize): first call of a run;
+      raster rows [yLo, yHi), output rows [outLo, outHi) reading 0 where no tile of this rank writes.
+  subsample(rows, cols) -> (nBands, len(rows), len(cols)); fit(img, numClusters, imgNullVal,
+      fixedKMeansInit) -> a model with cluster_centers_ (optional fitSharded: the E-step over the ranks).
+  startSegmentation(centres, msd, imgNullVal, fourConnected, minSegmentSize) may return at once;
+      waitTile(j) returns when tile j is segmented and raises if it failed.
+  setMaxSegId(v); stitchTile(j, top, left, win, simple): tile j's new ids follow the running maxSegId,
+      its trimmed window goes to the output, the running maxSegId becomes that window's largest id;
+      getMaxSegId() waits for the chain.  bottomStripOf(j) / rightStripOf(j): strips of local tiles.
+  beginProvisional(stride, ntAll); stitchTileAt(j, top, left, win, t, stride, slot): stitchTile
+      numbering after t * stride, its counts (K ids handed out, R the largest in the window, both
+      minus the base) in slot `slot`; tileCounts(n) -> the n (K, R) pairs.
+  sendStrip(comm, dst, item, j) / recvStrip(comm, src, item) -> strip: one boundaryPlan item.  An
+      engine whose transfers may return before the data has moved also provides drainStrips(),
+      which returns once all of it has; without one they count as done on return.
+  renumber(stride, base): id -> base[id / stride] + id % stride over the output rows;
+      renumberKept(stride, base, keptJobs, recvStrips): the same over the output rows, the strips of
+      exactly keptJobs and exactly recvStrips, and no other buffer (final ids must stay as they are).
+  sendBoundary(comm, dst, maxSegId, items) / recvBoundary(comm, src, plan) -> (maxSegId,
+      {(kind, col, row): strip}): maxSegId, then the strips in plan order.
+  histogram(maxSegId) -> pixel counts per id of the output rows (after finish too, if kept);
+      finish(): the run's buffers released, bar a kept output.
+  localStats, gatherFlagged, statsOfPairs (optional statsOnDevice): calcPerSegmentStatsDistributed.
 """
+import collections
 import ctypes
 import sys
 import json
@@ -157,10 +186,198 @@ def boundaryPlan(tileInfo, shards, p, overlapSize):
 
 
 def Comm(_unused=None, device=None):
-    """World-size-1 communicator (kept for callers that ran the sharded driver in one process);
-    multi-rank communicators come from pyshepseg_amd.comm."""
+    """World-size-1 communicator for callers that run the sharded driver in one process (kept as a
+    public name: scripts and tests call it); multi-rank communicators come from pyshepseg_amd.comm."""
     from . import comm as _comm
     return _comm.LocalComm()
+
+
+# ------------------------------------------------------------------------------------------
+# the cross-tile stitch
+# ------------------------------------------------------------------------------------------
+# What the parallel form found: the final maxSegId `total` (every tile safe), `redoAll` (a tile outgrew
+# the provisional id range) or a partial redo after tile `bad` (base: the final bases of all tiles,
+# mAfter: the maxSegId after `bad`, fromPrev: the strips received with provisional ids)
+ParallelOutcome = collections.namedtuple('ParallelOutcome', 'total redoAll bad base mAfter stride fromPrev',
+                                         defaults=(None, False, None, None, None, None, None))
+
+
+class _Stitch(object):
+    """This rank's part of the stitch (the two forms of the module docstring).  The messages between
+    ranks, in the order the communicators and both engines rely on -- sequential: maxSegId and the
+    boundary strips from the previous rank, the chain, the same to the next rank, an all-gather of the
+    final maxSegId; parallel: strips tile by tile in chain order, an all-gather of the tiles' counts,
+    then nothing more, or the sequential form for all tiles or for the tiles after `bad` only."""
+
+    def __init__(self, engine, comm, tileInfo, shards, jobs, overlap, simple, mark):
+        (self.engine, self.comm, self.tileInfo, self.shards) = (engine, comm, tileInfo, shards)
+        (self.jobs, self.overlap, self.simple, self.mark) = (jobs, overlap, simple, mark)
+        self.jobmap = {(j.col, j.row): j for j in jobs}
+        (self.t0, self.t1) = shards[comm.rank]
+        self.ntAll = tileInfo.ncols * tileInfo.nrows
+        self.nonEmpty = [i for i, (a, b) in enumerate(shards) if b > a]
+        pos = self.nonEmpty.index(comm.rank) if jobs else -1
+        self.prevRank = self.nonEmpty[pos - 1] if pos > 0 else None
+        self.nextRank = self.nonEmpty[pos + 1] if jobs and pos + 1 < len(self.nonEmpty) else None
+
+    def run(self, mode):
+        """(maxSegId, stitch form, chain steps redone)"""
+        if mode == 'sequential':
+            return self.sequential(), mode, 0
+        o = self.parallel()
+        if o.redoAll:
+            return self.sequential(), 'parallel->sequential', self.ntAll
+        if o.bad is not None:
+            return self.resume(o), 'parallel->sequential', self.ntAll - (o.bad + 1)
+        return o.total, mode, 0
+
+    def index(self, j):
+        return j.row * self.tileInfo.ncols + j.col
+
+    def winOf(self, j):
+        return tiling.trimmedWindow(self.tileInfo, j.col, j.row, j.xpos, j.ypos, j.xsize, j.ysize, self.overlap)
+
+    def neighbours(self, j, fromPrev):
+        top = left = None
+        if not self.simple:
+            if j.row > 0:
+                a = self.jobmap.get((j.col, j.row - 1))
+                top = self.engine.bottomStripOf(a) if a is not None else fromPrev[('b', j.col, j.row - 1)]
+            if j.col > 0:
+                a = self.jobmap.get((j.col - 1, j.row))
+                left = self.engine.rightStripOf(a) if a is not None else fromPrev[('r', j.col - 1, j.row)]
+        return top, left
+
+    def chain(self, jobs, maxSegId, fromPrev):
+        """The sequential chain over `jobs`, numbering after maxSegId; returns the maxSegId after them."""
+        self.engine.setMaxSegId(maxSegId)
+        for j in jobs:
+            self.engine.waitTile(j)
+            (top, left) = self.neighbours(j, fromPrev)
+            self.engine.stitchTile(j, top, left, self.winOf(j), self.simple)
+        self.mark('chain issued')
+        maxSegId = self.engine.getMaxSegId()
+        self.mark('chain done')
+        return maxSegId
+
+    def receiveBoundary(self):
+        """(maxSegId, strips) as the previous rank passed them on; (0, {}) on the first rank"""
+        if self.prevRank is None:
+            return 0, {}
+        return self.engine.recvBoundary(self.comm, self.prevRank,
+                                        boundaryPlan(self.tileInfo, self.shards, self.prevRank, self.overlap))
+
+    def passOn(self, maxSegId):
+        if self.nextRank is not None:
+            plan = boundaryPlan(self.tileInfo, self.shards, self.comm.rank, self.overlap)
+            self.engine.sendBoundary(self.comm, self.nextRank, maxSegId,
+                                     [(kind, self.jobmap[(c, r)], h, w) for (kind, c, r, h, w) in plan])
+
+    def finalMaxSegId(self, local):
+        """the maxSegId of the last rank that has tiles, on every rank"""
+        vals = self.comm.allgather_obj(int(local))
+        return vals[self.nonEmpty[-1]] if self.nonEmpty else 0
+
+    def sequential(self):
+        maxSegId = 0
+        if self.jobs:
+            maxSegId = self.chain(self.jobs, *self.receiveBoundary())
+            self.passOn(maxSegId)
+        return self.finalMaxSegId(maxSegId)
+
+    def parallel(self):
+        (engine, comm, ntAll) = (self.engine, self.comm, self.ntAll)
+        stride = 0xFFFFFFFF // max(ntAll, 1)
+        (mine, fromPrev) = ([], {})
+        if self.jobs:
+            # With provisional ids a chain step needs its two neighbours only, so a rank takes its
+            # tiles along anti-diagonals (row + col ascending): the tiles of its LAST row are then
+            # done two steps apart instead of a row apart, and the next rank, which waits for them
+            # one by one, follows two steps behind instead of a row behind.  Strips cross the rank
+            # boundary tile by tile in that order ('b' before 'r'); both sides derive it.
+            wave = os.environ.get('SHEPSEG_CHAIN_ORDER', 'diagonal') != 'rowmajor'
+            tkey = (lambda c, r: (r + c, r)) if wave else (lambda c, r: (r * self.tileInfo.ncols + c, 0))
+
+            def order(p):
+                return sorted(boundaryPlan(self.tileInfo, self.shards, p, self.overlap),
+                              key=lambda it: tkey(it[1], it[2]) + (it[0] != 'b',))
+            planPrev = order(self.prevRank) if self.prevRank is not None else []
+            sendOf = {}
+            for it in (order(comm.rank) if self.nextRank is not None else []):
+                sendOf.setdefault((it[1], it[2]), []).append(it)
+
+            def need(key):
+                while key not in fromPrev:
+                    it = planPrev[len(fromPrev)]
+                    fromPrev[it[:3]] = engine.recvStrip(comm, self.prevRank, it)
+            engine.beginProvisional(stride, ntAll)
+            for (slot, j) in sorted(enumerate(self.jobs), key=lambda sj: tkey(sj[1].col, sj[1].row)):
+                if j.row > 0 and (j.col, j.row - 1) not in self.jobmap:
+                    need(('b', j.col, j.row - 1))
+                if j.col > 0 and (j.col - 1, j.row) not in self.jobmap:
+                    need(('r', j.col - 1, j.row))
+                engine.waitTile(j)
+                (top, left) = self.neighbours(j, fromPrev)
+                engine.stitchTileAt(j, top, left, self.winOf(j), self.index(j), stride, slot)
+                for it in sendOf.get((j.col, j.row), ()):
+                    engine.sendStrip(comm, self.nextRank, it, j)
+            while len(fromPrev) < len(planPrev):          # (every planned strip has a reader; be safe)
+                need(planPrev[len(fromPrev)][:3])
+            if hasattr(engine, 'drainStrips'):
+                engine.drainStrips()           # strips in flight must land before anything is renumbered
+            counts = engine.tileCounts(len(self.jobs))
+            mine = [(self.index(j), int(k), int(r), int(j.maxLocal)) for (j, (k, r)) in zip(self.jobs, counts)]
+        everyone = [x for part in comm.allgather_obj(mine) for x in part]
+        K = numpy.zeros(ntAll, dtype=numpy.int64)
+        R = numpy.zeros(ntAll, dtype=numpy.int64)
+        hard = len(everyone) != ntAll
+        for (t, k, r, mloc) in everyone:
+            K[t] = k
+            R[t] = r
+            if mloc >= stride or k >= stride:
+                hard = True
+        if hard or int(K.sum()) > 0xFFFFFFFF:
+            return ParallelOutcome(redoAll=True)
+        base = numpy.concatenate(([0], numpy.cumsum(K)[:-1])).astype(numpy.uint32)
+        off = numpy.nonzero(K != R)[0]
+        if len(off) == 0:
+            if self.jobs:
+                engine.renumber(stride, base)
+            return ParallelOutcome(total=int(K.sum()))
+        # Tile `bad` is the first (row-major) to hide ids it handed out from its trimmed window.  Up to
+        # and including it the sequential run has maxSegId = sum of the earlier tiles' K at every step
+        # (the induction of the safety test), so every decision taken so far -- bad's own recode
+        # included -- stands and the provisional ids of tiles <= bad renumber to the final ones.  What
+        # changes is where the NEXT tile starts: at base[bad] + R[bad], not + K[bad] (tiling.py:1029-1043:
+        # maxSegId follows trimmed.max()).  The chain is redone from there only.
+        bad = int(off[0])
+        return ParallelOutcome(bad=bad, base=base, mAfter=int(base[bad]) + int(R[bad]), stride=stride,
+                               fromPrev=fromPrev)
+
+    def resume(self, o):
+        """The partial redo: the tiles up to o.bad are kept, the chain runs again from o.bad + 1 on."""
+        maxSegId = 0
+        if self.jobs:
+            kept = [j for j in self.jobs if self.index(j) <= o.bad]
+            redo = [j for j in self.jobs if self.index(j) > o.bad]
+            ownsBad = self.t0 <= o.bad < self.t1
+            sendsOn = self.nextRank is not None and self.t1 - 1 >= o.bad     # (the next rank redoes all its tiles)
+            # Final ids for what is kept, in each buffer that is read again: the output rows always (in
+            # renumberKept); the kept tiles' strips when this rank redoes tiles or sends them on; the strips
+            # that came from the previous rank with provisional ids on the rank that owns `bad` and redoes
+            # tiles (a later rank receives its previous rank's strips again, with final ids).
+            keptStripsReread = bool(redo) or sendsOn
+            prevStripsReread = ownsBad and bool(redo)
+            if kept:
+                self.engine.renumberKept(o.stride, o.base, kept if keptStripsReread else [],
+                                         list(o.fromPrev.values()) if prevStripsReread else [])
+            if redo:
+                maxSegId = self.chain(redo, *((o.mAfter, o.fromPrev) if ownsBad else self.receiveBoundary()))
+            elif ownsBad:
+                maxSegId = o.mAfter
+            if sendsOn:
+                self.passOn(maxSegId)
+        return self.finalMaxSegId(maxSegId)
 
 
 # ------------------------------------------------------------------------------------------
@@ -175,7 +392,8 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
                    fixedKMeansInit=True, fourConnected=True, simpleTileRecode=False,
                    spectDistPcntile=50, kmeansObj=None, stitchMode=None):
     """Tiled segmentation of an (nRows x nCols) raster, its tiles sharded over comm.world ranks.
-    ``engine`` owns this rank's slice of the raster and of the output (see HipEngine).  Returns a
+    ``engine`` owns this rank's slice of the raster and of the output (the module docstring says
+    what it provides; HipEngine).  Returns a
     DistResult with maxSegId, hist (global), kmeans, maxSpectralDiff, tileRange (row-major tile
     indices of this rank), rowRange (the tile rows they touch) and outRows (image rows of the
     output buffer this rank holds: its tiles' trimmed windows are written, the rest is 0) and
@@ -183,12 +401,11 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
     had to be redone -- chainStepsRedone says how many tiles, from the first one whose ids the
     provisional numbering cannot express; argument / SHEPSEG_STITCH: None = parallel when
     comm.world > 1)."""
-    import time as _time
-    _t = [_time.time()]
+    _t = [time.time()]
     _marks = []
 
     def _mark(what):                       # SHEPSEG_IO_TIMING: this rank's milestones of the step, to stderr at its end
-        now = _time.time()
+        now = time.time()
         _marks.append('%s %.3f' % (what, now - _t[0]))
         _t[0] = now
     if stitchMode is None:
@@ -207,32 +424,24 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
     shardBy = os.environ.get('SHEPSEG_SHARD') or ('rows' if stitchMode == 'parallel' else 'tiles')
     shards = shardTiles(tileInfo, comm.world, wholeRows=(shardBy == 'rows'))
     (t0, t1) = shards[comm.rank]
-    haveTiles = t1 > t0
-    myTiles = [(t % ncolsT, t // ncolsT) for t in range(t0, t1)]
-    (r0, r1) = (t0 // ncolsT, (t1 - 1) // ncolsT + 1) if haveTiles else (0, 0)
-    jobs, total = tiling.makeTileJobs(tileInfo, tiles=set(myTiles))
-
-    def _winOf(col, row):
-        return tiling.trimmedWindow(tileInfo, col, row, *tileInfo.getTile(col, row), overlapSize)
+    jobs, total = tiling.makeTileJobs(tileInfo, tiles={(t % ncolsT, t // ncolsT) for t in range(t0, t1)})
+    st = _Stitch(engine, comm, tileInfo, shards, jobs, overlapSize, simpleTileRecode, _mark)
+    (r0, r1) = (t0 // ncolsT, (t1 - 1) // ncolsT + 1) if jobs else (0, 0)
     # image rows this rank needs (its tiles) and writes in the output (their trimmed windows)
-    if haveTiles:
-        yLo = min(tileInfo.getTile(c, r)[1] for (c, r) in myTiles)
-        yHi = max(tileInfo.getTile(c, r)[1] + tileInfo.getTile(c, r)[3] for (c, r) in myTiles)
-        wins = [_winOf(c, r) for (c, r) in myTiles]
+    (yLo, yHi, outLo, outHi, sLo, sHi) = (0,) * 6
+    if jobs:
+        yLo = min(j.ypos for j in jobs)
+        yHi = max(j.ypos + j.ysize for j in jobs)
+        wins = [st.winOf(j) for j in jobs]
         outLo = min(w[5] for w in wins)
         outHi = max(w[5] + (w[1] - w[0]) for w in wins)
-    else:
-        yLo = yHi = outLo = outHi = 0
-    # a disjoint split of the image rows for the k-means sample: from the first output row of this
-    # rank's first tile to that of the next rank's first tile (inside both ranks' slices)
-    nonEmpty = [i for i, (a, b) in enumerate(shards) if b > a]
-    firstRow = {i: _winOf(shards[i][0] % ncolsT, shards[i][0] // ncolsT)[5] for i in nonEmpty}
-    if haveTiles:
-        pos = nonEmpty.index(comm.rank)
-        sLo = 0 if pos == 0 else firstRow[comm.rank]
-        sHi = nRows if pos + 1 == len(nonEmpty) else max(sLo, firstRow[nonEmpty[pos + 1]])
-    else:
-        sLo = sHi = 0
+        # a disjoint split of the image rows for the k-means sample: from the first output row of this
+        # rank's first tile to that of the next rank's first tile (inside both ranks' slices)
+        def firstRow(p):
+            (c, r) = (shards[p][0] % ncolsT, shards[p][0] // ncolsT)
+            return tiling.trimmedWindow(tileInfo, c, r, *tileInfo.getTile(c, r), overlapSize)[5]
+        sLo = 0 if st.prevRank is None else firstRow(comm.rank)
+        sHi = nRows if st.nextRank is None else max(sLo, firstRow(st.nextRank))
     engine.setup(tileInfo, jobs, total, yLo, yHi, outLo, outHi, nCols, overlapSize)
     _mark('setup')
 
@@ -274,171 +483,7 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
     _mark('workers started')
 
     # ---- the stitch ----
-    jobmap = {(j.col, j.row): j for j in jobs}
-    pos = nonEmpty.index(comm.rank) if haveTiles else -1
-    prevRank = nonEmpty[pos - 1] if pos > 0 else None
-    nextRank = nonEmpty[pos + 1] if haveTiles and pos + 1 < len(nonEmpty) else None
-
-    def _neighbours(j, fromPrev):
-        top = left = None
-        if not simpleTileRecode:
-            if j.row > 0:
-                a = jobmap.get((j.col, j.row - 1))
-                top = engine.bottomStripOf(a) if a is not None else fromPrev[('b', j.col, j.row - 1)]
-            if j.col > 0:
-                a = jobmap.get((j.col - 1, j.row))
-                left = engine.rightStripOf(a) if a is not None else fromPrev[('r', j.col - 1, j.row)]
-        return top, left
-
-    def _sequential():
-        maxSegId = 0
-        if haveTiles:
-            fromPrev = {}
-            if prevRank is not None:
-                maxSegId, fromPrev = engine.recvBoundary(
-                    comm, prevRank, boundaryPlan(tileInfo, shards, prevRank, overlapSize))
-            engine.setMaxSegId(maxSegId)
-            for j in jobs:
-                engine.waitTile(j)
-                (top, left) = _neighbours(j, fromPrev)
-                engine.stitchTile(j, top, left, _winOf(j.col, j.row), simpleTileRecode)
-            _mark('chain issued')
-            maxSegId = engine.getMaxSegId()
-            _mark('chain done')
-            if nextRank is not None:
-                plan = boundaryPlan(tileInfo, shards, comm.rank, overlapSize)
-                engine.sendBoundary(comm, nextRank, maxSegId,
-                                    [(kind, jobmap[(c, r)], h, w) for (kind, c, r, h, w) in plan])
-        # final maxSegId lives on the last rank that has tiles
-        vals = comm.allgather_obj(int(maxSegId))
-        return vals[nonEmpty[-1]] if nonEmpty else 0
-
-    def _parallel():
-        """Returns the final maxSegId, or None when some tile makes the provisional form unsafe."""
-        ntAll = ncolsT * tileInfo.nrows
-        stride = 0xFFFFFFFF // max(ntAll, 1)
-        mine = []
-        if haveTiles:
-            # With provisional ids a chain step needs its two neighbours only, so a rank takes its
-            # tiles along anti-diagonals (row + col ascending): the tiles of its LAST row are then
-            # done two steps apart instead of a row apart, and the next rank, which waits for them
-            # one by one, follows two steps behind instead of a row behind.  Strips cross the rank
-            # boundary tile by tile in that order ('b' before 'r'); both sides derive it.
-            wave = os.environ.get('SHEPSEG_CHAIN_ORDER', 'diagonal') != 'rowmajor'
-            tkey = (lambda c, r: (r + c, r)) if wave else (lambda c, r: (r * ncolsT + c, 0))
-            order = lambda plan: sorted(plan, key=lambda it: tkey(it[1], it[2]) + (it[0] != 'b',))
-            planPrev = order(boundaryPlan(tileInfo, shards, prevRank, overlapSize)) if prevRank is not None else []
-            sendOf = {}
-            if nextRank is not None:
-                for it in order(boundaryPlan(tileInfo, shards, comm.rank, overlapSize)):
-                    sendOf.setdefault((it[1], it[2]), []).append(it)
-            fromPrev = {}
-            got = [0]
-
-            def need(key):
-                while key not in fromPrev:
-                    it = planPrev[got[0]]
-                    got[0] += 1
-                    fromPrev[(it[0], it[1], it[2])] = engine.recvStrip(comm, prevRank, it)
-            engine.beginProvisional(stride, ntAll)
-            for (slot, j) in sorted(enumerate(jobs), key=lambda sj: tkey(sj[1].col, sj[1].row)):
-                if j.row > 0 and (j.col, j.row - 1) not in jobmap:
-                    need(('b', j.col, j.row - 1))
-                if j.col > 0 and (j.col - 1, j.row) not in jobmap:
-                    need(('r', j.col - 1, j.row))
-                engine.waitTile(j)
-                (top, left) = _neighbours(j, fromPrev)
-                t = j.row * ncolsT + j.col
-                engine.stitchTileAt(j, top, left, _winOf(j.col, j.row), t, stride, slot)
-                for it in sendOf.get((j.col, j.row), ()):
-                    engine.sendStrip(comm, nextRank, it, j)
-            while got[0] < len(planPrev):          # (every planned strip has a reader; be safe)
-                need((planPrev[got[0]][0], planPrev[got[0]][1], planPrev[got[0]][2]))
-            if hasattr(engine, 'drainStrips'):
-                engine.drainStrips()               # strips in flight must land before anything is renumbered
-            counts = engine.tileCounts(len(jobs))
-            mine = [(j.row * ncolsT + j.col, int(k), int(r), int(j.maxLocal))
-                    for (j, (k, r)) in zip(jobs, counts)]
-        everyone = [x for part in comm.allgather_obj(mine) for x in part]
-        K = numpy.zeros(ntAll, dtype=numpy.int64)
-        R = numpy.zeros(ntAll, dtype=numpy.int64)
-        hard = len(everyone) != ntAll
-        for (t, k, r, mloc) in everyone:
-            K[t] = k
-            R[t] = r
-            if mloc >= stride or k >= stride:
-                hard = True
-        if hard or int(K.sum()) > 0xFFFFFFFF:
-            return None
-        base = numpy.concatenate(([0], numpy.cumsum(K)[:-1])).astype(numpy.uint32)
-        off = numpy.nonzero(K != R)[0]
-        if len(off) == 0:
-            if haveTiles:
-                engine.renumber(stride, base)
-            return int(K.sum())
-        # Tile `bad` is the first (row-major) to hide ids it handed out from its trimmed window.  Up to
-        # and including it the sequential run has maxSegId = sum of the earlier tiles' K at every step
-        # (the induction of the safety test), so every decision taken so far -- bad's own recode
-        # included -- stands and the provisional ids of tiles <= bad renumber to the final ones.  What
-        # changes is where the NEXT tile starts: at base[bad] + R[bad], not + K[bad] (tiling.py:1029-1043:
-        # maxSegId follows trimmed.max()).  The chain is redone from there only.
-        bad = int(off[0])
-        return ('partial', bad, base, int(base[bad]) + int(R[bad]), stride, fromPrev if haveTiles else {})
-
-    def _resume(bad, base, mAfter, stride, fromPrevProv):
-        """The sequential chain from tile bad + 1 on, after the tiles up to `bad` were kept."""
-        maxSegId = 0
-        if haveTiles:
-            kept = [j for j in jobs if j.row * ncolsT + j.col <= bad]
-            redo = [j for j in jobs if j.row * ncolsT + j.col > bad]
-            ownsBad = t0 <= bad < t1
-            # the next rank redoes all its tiles: this rank's boundary strips go to it below
-            sendsOn = nextRank is not None and t1 - 1 >= bad
-            # final ids for what is kept: output rows, the kept tiles' strips, and (on the rank that owns
-            # `bad`) the previous rank's strips, which arrived with provisional ids
-            # (a rank all of whose tiles are redone has nothing to renumber; one that redoes none reads its
-            #  strips again only when it sends them on -- when `bad` is its last tile -- and otherwise only its
-            #  output rows get their final ids)
-            if kept:
-                engine.renumberKept(stride, base, kept if (redo or sendsOn) else [],
-                                    list(fromPrevProv.values()) if (ownsBad and redo) else [])
-            if redo:
-                if ownsBad:
-                    (maxSegId, fromPrev) = (mAfter, fromPrevProv)
-                else:
-                    (maxSegId, fromPrev) = (0, {})
-                    if prevRank is not None:
-                        maxSegId, fromPrev = engine.recvBoundary(
-                            comm, prevRank, boundaryPlan(tileInfo, shards, prevRank, overlapSize))
-                engine.setMaxSegId(maxSegId)
-                for j in redo:
-                    engine.waitTile(j)
-                    (top, left) = _neighbours(j, fromPrev)
-                    engine.stitchTile(j, top, left, _winOf(j.col, j.row), simpleTileRecode)
-                maxSegId = engine.getMaxSegId()
-            elif ownsBad:
-                maxSegId = mAfter
-            if sendsOn:
-                plan = boundaryPlan(tileInfo, shards, comm.rank, overlapSize)
-                engine.sendBoundary(comm, nextRank, maxSegId,
-                                    [(kind, jobmap[(c, r)], h, w) for (kind, c, r, h, w) in plan])
-        vals = comm.allgather_obj(int(maxSegId))
-        return vals[nonEmpty[-1]] if nonEmpty else 0
-
-    chainRedone = 0
-    if stitchMode == 'parallel':
-        maxSegId = _parallel()
-        if maxSegId is None:               # (a tile outgrew the provisional id range: everything again)
-            stitchMode = 'parallel->sequential'
-            chainRedone = ncolsT * tileInfo.nrows
-            maxSegId = _sequential()
-        elif isinstance(maxSegId, tuple):
-            (_tag, bad, base, mAfter, stride, fromPrevProv) = maxSegId
-            stitchMode = 'parallel->sequential'
-            chainRedone = ncolsT * tileInfo.nrows - (bad + 1)
-            maxSegId = _resume(bad, base, mAfter, stride, fromPrevProv)
-    else:
-        maxSegId = _sequential()
+    (maxSegId, stitchMode, chainRedone) = st.run(stitchMode)
     # A tile hands out at most one id per pixel, so no stitch ends above the tiles' total area.  Every rank
     # holds the same all-gathered value and raises alike, instead of sizing the histogram (and the all-reduce
     # that follows) by ids that are still provisional.
@@ -448,7 +493,7 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
             "stitch ended with maxSegId %d, more than the %d pixels of all tiles (stitch form %s)"
             % (maxSegId, maxPossible, stitchMode))
     _mark('tiles + stitch')
-    hist = engine.histogram(maxSegId) if haveTiles else numpy.zeros(maxSegId + 1, numpy.int64)
+    hist = engine.histogram(maxSegId) if jobs else numpy.zeros(maxSegId + 1, numpy.int64)
     hist = comm.allreduce_sum_i64(numpy.asarray(hist, dtype=numpy.int64)).astype(numpy.uint32)
     hist[0] = 0
     _mark('histogram')
@@ -639,20 +684,10 @@ class HipEngine(object):
                 self.ras.free()
             self.ras = self.makeSlice(yLo, yHi) if yHi > yLo else None
             self._sliceKey = (yLo, yHi)
-        self.nbTiles = max(total, 1) * 4
-        self.nbOut = max((outHi - outLo) * nCols, 1) * 4
-        self.d_tiles = tiling._devAlloc(self.c, self.nbTiles)
-        self.d_out = tiling._devAlloc(self.c, self.nbOut)
-        # other ranks' tiles share these rows: what this rank does not write must read as null
-        self.c.check(self.L.shp_dev_memset(self.c.handle, self.d_out, 0, self.nbOut))
-        self.d_scal = tiling._devAlloc(self.c, 256)
-        self.c.check(self.L.shp_dev_memset(self.c.handle, self.d_scal, 0, 256))
-        self.nbStrips = max(tiling.layoutStrips(jobs, overlapSize), 1) * 4
-        self.d_strips = tiling._devAlloc(self.c, self.nbStrips)
-        self.arena = tiling._MetaArena(self.c, 16 * (total // 8 + 1024))
-        self.simple = False
+        # other ranks' tiles share the output rows: what this rank does not write must read as null
+        self.bufs = tiling._StitchBuffers(self.c, tileInfo, jobs, total, outLo, outHi, nCols, overlapSize,
+                                          zeroOut=True)
         self.threads, self.forceExit = [], None
-        self.recvBufs = []
         self.recvDev = []
 
     def subsample(self, rowsGlobal, cols):
@@ -679,42 +714,33 @@ class HipEngine(object):
         if not self.jobs:
             return
         self.threads, self.forceExit = tiling.startSegmentationWorkers(
-            self.ras, self.jobs, self.d_tiles, centres, msd, imgNullVal, fourConnected,
+            self.ras, self.jobs, self.bufs.d_tiles, centres, msd, imgNullVal, fourConnected,
             minSegmentSize, self.numWorkers, self.timings, yOrigin=self.yLo,
-            stitchPrep=(self.tileInfo, self.overlap, self.arena, self.simple))
+            stitchPrep=(self.tileInfo, self.overlap, self.bufs.arena, False))
 
     def waitTile(self, j):
         tiling.waitForTile(j, self.jobs, self.threads, self.forceExit, 600)
 
     def setMaxSegId(self, v):
         a = numpy.array([v], dtype=numpy.uint32)
-        self.c.check(self.L.shp_dev_upload(self.c.handle, self.d_scal, _lib.ptr(a), 4))
+        self.c.check(self.L.shp_dev_upload(self.c.handle, self.bufs.d_scal, _lib.ptr(a), 4))
 
     def getMaxSegId(self):
         a = numpy.zeros(1, dtype=numpy.uint32)
         self.c.check(self.L.shp_sync(self.c.handle))
-        self.c.check(self.L.shp_dev_download(self.c.handle, _lib.ptr(a), self.d_scal, 4))
+        self.c.check(self.L.shp_dev_download(self.c.handle, _lib.ptr(a), self.bufs.d_scal, 4))
         return int(a[0])
 
     # strips are (device pointer, row pitch in elements)
     def bottomStripOf(self, a):      # dense recoded strip written by the chain step of tile a
-        return (self.d_strips.value + 4 * a.bottomOff, a.xsize)
+        return self.bufs.bottomStrip(a)
 
     def rightStripOf(self, a):
-        return (self.d_strips.value + 4 * a.rightOff, min(self.overlap, a.xsize))
+        return self.bufs.rightStrip(a)
 
     def stitchTile(self, j, top, left, win, simple):
-        (t, b, l, r, xout, yout) = win
         with self.timings.interval('stitchtiles'):
-            # every tile's strips are written: a later rank may need the last row's bottom strips
-            self.c.check(self.L.shp_stitch_chain_dev(
-                self.c.handle, ctypes.c_void_p(self.d_tiles.value + 4 * j.offset), j.ysize, j.xsize,
-                self.overlap, ctypes.c_void_p(top[0]) if top else None, top[1] if top else 0,
-                ctypes.c_void_p(left[0]) if left else None, left[1] if left else 0, j.maxLocal,
-                int(bool(simple)), self.d_scal, t, b, l, r, ctypes.c_void_p(j.meta),
-                ctypes.c_void_p(self.d_strips.value + 4 * j.rightOff),
-                ctypes.c_void_p(self.d_strips.value + 4 * j.bottomOff), self.d_out, self.nCols, xout,
-                yout - self.outLo, j.crossPx[0], j.crossPx[1]))
+            self.bufs.step(j, top, left, win, simple)
 
     # ---- parallel stitch: provisional bases, per-tile counts, eager strips ----
     def beginProvisional(self, stride, ntAll):
@@ -728,16 +754,8 @@ class HipEngine(object):
     def stitchTileAt(self, j, top, left, win, t, stride, slot):
         """The chain step of tile t with its provisional base (a device word of its own, so nothing
         is uploaded or read back per tile), then its two counts into slot `slot`."""
-        (tt, b, l, r, xout, yout) = win
         with self.timings.interval('stitchtiles'):
-            self.c.check(self.L.shp_stitch_chain_dev(
-                self.c.handle, ctypes.c_void_p(self.d_tiles.value + 4 * j.offset), j.ysize, j.xsize,
-                self.overlap, ctypes.c_void_p(top[0]) if top else None, top[1] if top else 0,
-                ctypes.c_void_p(left[0]) if left else None, left[1] if left else 0, j.maxLocal,
-                0, ctypes.c_void_p(self.d_bases.value + 4 * t), tt, b, l, r, ctypes.c_void_p(j.meta),
-                ctypes.c_void_p(self.d_strips.value + 4 * j.rightOff),
-                ctypes.c_void_p(self.d_strips.value + 4 * j.bottomOff), self.d_out, self.nCols, xout,
-                yout - self.outLo, j.crossPx[0], j.crossPx[1]))
+            self.bufs.step(j, top, left, win, False, scalar=self.d_bases.value + 4 * t)
             self.c.check(self.L.shp_stitch_counts_dev(
                 self.c.handle, ctypes.c_void_p(j.meta), j.maxLocal, (t * stride) & 0xFFFFFFFF,
                 ctypes.c_void_p(self.d_bases.value + 4 * (self.ntAll + 2 * slot))))
@@ -754,7 +772,7 @@ class HipEngine(object):
     def renumber(self, stride, base):
         self.c.check(self.L.shp_sync(self.c.handle))
         base = numpy.ascontiguousarray(base, dtype=numpy.uint32)
-        self.c.check(self.L.shp_renumber_dev(self.c.handle, self.d_out, (self.outHi - self.outLo) * self.nCols,
+        self.c.check(self.L.shp_renumber_dev(self.c.handle, self.bufs.d_out, (self.outHi - self.outLo) * self.nCols,
                                              int(stride), _lib.ptr(base), len(base)))
 
     def renumberKept(self, stride, base, keptJobs, recvStrips):
@@ -775,7 +793,7 @@ class HipEngine(object):
             else:
                 runs.append([j.rightOff, n])
         for (o, n) in runs:
-            self.c.check(self.L.shp_renumber_dev(self.c.handle, ctypes.c_void_p(self.d_strips.value + 4 * o),
+            self.c.check(self.L.shp_renumber_dev(self.c.handle, ctypes.c_void_p(self.bufs.d_strips.value + 4 * o),
                                                  n, int(stride), _lib.ptr(base), len(base)))
         sizes = {d.value: nbytes for (d, nbytes) in self.recvDev}
         for (ptr, _w) in recvStrips:
@@ -846,7 +864,7 @@ class HipEngine(object):
 
     def histogram(self, maxSegId):
         hist = numpy.zeros(maxSegId + 1, dtype=numpy.uint32)
-        self.c.check(self.L.shp_histogram_dev(self.c.handle, self.d_out,
+        self.c.check(self.L.shp_histogram_dev(self.c.handle, self.bufs.d_out,
                                               (self.outHi - self.outLo) * self.nCols, self.nCols, maxSegId,
                                               _lib.ptr(hist)))
         return hist
@@ -911,21 +929,15 @@ class HipEngine(object):
             t.join()
         self.drainStrips()
         self.c.check(self.L.shp_sync(self.c.handle))
-        self.recvBufs = []
         for (d, nbytes) in self.recvDev:
             tiling._devRelease(self.c, d, nbytes)
         self.recvDev = []
-        tiling._devRelease(self.c, self.d_tiles, self.nbTiles)
-        tiling._devRelease(self.c, self.d_scal, 256)
-        tiling._devRelease(self.c, self.d_strips, self.nbStrips)
-        self.arena.release()
+        self.bufs.release(keepOut=self.keepOutput)
         if self.keepOutput:
-            self._lastOut = self.d_out               # caller must releaseOutput()
-        else:
-            tiling._devRelease(self.c, self.d_out, self.nbOut)
+            self._lastOut = self.bufs.d_out          # caller must releaseOutput()
 
     def releaseOutput(self):
-        tiling._devRelease(self.c, self.d_out, self.nbOut)
+        tiling._devRelease(self.c, self.bufs.d_out, self.bufs.nbOut)
 
 
 # ------------------------------------------------------------------------------------------

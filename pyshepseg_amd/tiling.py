@@ -767,6 +767,64 @@ def layoutStrips(jobs, overlapSize):
     return total
 
 
+class _StitchBuffers(object):
+    """The device blocks of one stitch chain on context c: the label block of the tiles in `jobs`,
+    the stitched output rows [outLo, outHi) (zeroed when asked), the running-maxSegId word, the
+    tiles' recoded overlap strips (layoutStrips) and their stitch tables (_MetaArena).  A strip is
+    (device address, row pitch in elements).  A chain step writes its tile's right and bottom
+    strips except the right strip of the last tile column and the bottom strip of the last tile
+    row: no tile reads those, and no rank boundary (distributed.boundaryPlan) sends them."""
+
+    def __init__(self, c, tileInfo, jobs, total, outLo, outHi, nCols, overlapSize, zeroOut=False):
+        (self.c, self.tileInfo, self.outLo, self.nCols, self.overlap) = (c, tileInfo, outLo, nCols, overlapSize)
+        self.nbTiles = max(total, 1) * 4
+        self.nbOut = max((outHi - outLo) * nCols, 1) * 4
+        self.d_tiles = _devAlloc(c, self.nbTiles)
+        self.d_out = _devAlloc(c, self.nbOut)
+        if zeroOut:
+            c.check(c._L.shp_dev_memset(c.handle, self.d_out, 0, self.nbOut))
+        self.d_scal = _devAlloc(c, 256)
+        c.check(c._L.shp_dev_memset(c.handle, self.d_scal, 0, 256))
+        self.nbStrips = max(layoutStrips(jobs, overlapSize), 1) * 4
+        self.d_strips = _devAlloc(c, self.nbStrips)
+        self.arena = _MetaArena(c, 16 * (total // 8 + 1024))
+
+    def bottomStrip(self, j):
+        return (self.d_strips.value + 4 * j.bottomOff, j.xsize)
+
+    def rightStrip(self, j):
+        return (self.d_strips.value + 4 * j.rightOff, min(self.overlap, j.xsize))
+
+    def step(self, j, top, left, win, simple, scalar=None):
+        """The chain step of tile j (asynchronous): top / left are the strips of the tiles above and to
+        its left (None: none), win its trimmedWindow; the new ids are numbered after the device word
+        `scalar` (default: the running maxSegId, which the step advances)."""
+        (t, b, l, r, xout, yout) = win
+        rightOut = None if j.col == self.tileInfo.ncols - 1 else ctypes.c_void_p(self.rightStrip(j)[0])
+        bottomOut = None if j.row == self.tileInfo.nrows - 1 else ctypes.c_void_p(self.bottomStrip(j)[0])
+        self.c.check(self.c._L.shp_stitch_chain_dev(
+            self.c.handle, ctypes.c_void_p(self.d_tiles.value + 4 * j.offset), j.ysize, j.xsize, self.overlap,
+            ctypes.c_void_p(top[0]) if top else None, top[1] if top else 0,
+            ctypes.c_void_p(left[0]) if left else None, left[1] if left else 0, j.maxLocal, int(bool(simple)),
+            self.d_scal if scalar is None else ctypes.c_void_p(scalar), t, b, l, r, ctypes.c_void_p(j.meta),
+            rightOut, bottomOut, self.d_out, self.nCols, xout, yout - self.outLo, j.crossPx[0], j.crossPx[1]))
+
+    def release(self, keepOut=False):
+        """Every block back to the cache of device blocks; keepOut: but d_out (nbOut bytes), which
+        is then the caller's."""
+        for (d, n) in ((self.d_tiles, self.nbTiles), (None if keepOut else self.d_out, self.nbOut),
+                       (self.d_scal, 256), (self.d_strips, self.nbStrips)):
+            _devRelease(self.c, d, n)
+        self.arena.release()
+
+    def free(self):
+        """After a failed run: hipFree instead of returning the blocks to the cache."""
+        for d in (self.d_tiles, self.d_out, self.d_scal, self.d_strips):
+            if d is not None and d.value:
+                self.c._L.shp_dev_free(self.c.handle, d)
+        self.arena.free()
+
+
 def trimmedWindow(tileInfo, col, row, xpos, ypos, xsize, ysize, overlapSize):
     """(top, bottom, left, right, xout, yout) of a tile: the part of it that is written to the
     output, i.e. the tile minus half the overlap on interior sides (reference tiling.py:997-1022)."""
@@ -1157,14 +1215,8 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
         # one device block for every tile's labels, one for the stitched raster
         jobs, total = makeTileJobs(tileInfo)
         jobmap = {(j.col, j.row): j for j in jobs}
-        nbTiles, nbOut = max(total, 1) * 4, max(inYsize * inXsize, 1) * 4
-        d_tiles = _devAlloc(main, nbTiles)
-        d_out = _devAlloc(main, nbOut)
-        d_scal = _devAlloc(main, 256)
-        main.check(L.shp_dev_memset(main.handle, d_scal, 0, 256))
-        nbStrips = max(layoutStrips(jobs, overlapSize), 1) * 4
-        d_strips = _devAlloc(main, nbStrips)
-        arena = _MetaArena(main, 16 * (total // 8 + 1024))
+        bufs = _StitchBuffers(main, tileInfo, jobs, total, 0, inYsize, inXsize, overlapSize)
+        d_out = bufs.d_out
         forceExit = None
         threads = []
         ok = False
@@ -1174,10 +1226,10 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
             if concurrencyCfg.concurrencyType != CONC_NONE:
                 numWorkers = max(1, int(concurrencyCfg.numWorkers))
             threads, forceExit = startSegmentationWorkers(
-                workSrc, jobs, d_tiles, centres, msd, imgNullVal, fourConnected, minSegmentSize,
+                workSrc, jobs, bufs.d_tiles, centres, msd, imgNullVal, fourConnected, minSegmentSize,
                 numWorkers, timings, bands=(None if streamer is not None else bands),
                 maxConcurrentReads=concurrencyCfg.maxConcurrentReads,
-                verbose=verbose, stitchPrep=(tileInfo, overlapSize, arena, bool(simpleTileRecode)),
+                verbose=verbose, stitchPrep=(tileInfo, overlapSize, bufs.arena, bool(simpleTileRecode)),
                 rowGate=streamer)
             # finished rows of the stitched raster stream out while the rest is still in the making
             writer = None
@@ -1226,30 +1278,15 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
             with timings.interval('stitchtiles'):
                 for j in jobs:
                     waitForTile(j, jobs, threads, forceExit, concurrencyCfg.tileCompletionTimeout)
-                    (top, bottom, left, right, xout, yout) = trimmedWindow(
-                        tileInfo, j.col, j.row, j.xpos, j.ypos, j.xsize, j.ysize, overlapSize)
+                    win = trimmedWindow(tileInfo, j.col, j.row, j.xpos, j.ypos, j.xsize, j.ysize, overlapSize)
+                    (top, bottom, left, right, xout, yout) = win
                     topB = leftB = None
-                    (topPitch, leftPitch) = (0, 0)
                     if not simpleTileRecode:
                         if j.row > 0:
-                            a = jobmap[(j.col, j.row - 1)]
-                            topB = ctypes.c_void_p(d_strips.value + 4 * a.bottomOff)
-                            topPitch = a.xsize
+                            topB = bufs.bottomStrip(jobmap[(j.col, j.row - 1)])
                         if j.col > 0:
-                            a = jobmap[(j.col - 1, j.row)]
-                            leftB = ctypes.c_void_p(d_strips.value + 4 * a.rightOff)
-                            leftPitch = min(overlapSize, a.xsize)
-                    rightOut = bottomOut = None
-                    if j.col != tileInfo.ncols - 1:
-                        rightOut = ctypes.c_void_p(d_strips.value + 4 * j.rightOff)
-                    if j.row != tileInfo.nrows - 1:
-                        bottomOut = ctypes.c_void_p(d_strips.value + 4 * j.bottomOff)
-                    main.check(L.shp_stitch_chain_dev(
-                        main.handle, ctypes.c_void_p(d_tiles.value + 4 * j.offset), j.ysize, j.xsize,
-                        overlapSize, topB, topPitch, leftB, leftPitch, j.maxLocal,
-                        int(bool(simpleTileRecode)), d_scal, top, bottom, left, right,
-                        ctypes.c_void_p(j.meta), rightOut, bottomOut, d_out, inXsize, xout, yout,
-                        j.crossPx[0], j.crossPx[1]))
+                            leftB = bufs.rightStrip(jobmap[(j.col - 1, j.row)])
+                    bufs.step(j, topB, leftB, win, simpleTileRecode)
                     for (lvl, d, oh, ow) in ovDev:
                         main.check(L.shp_overview_window_dev(main.handle, d_out, inXsize, xout, yout,
                                                              right - left, bottom - top, lvl, d, ow, oh))
@@ -1269,7 +1306,7 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
             ioMark('output written')
 
             scal = numpy.zeros(1, dtype=numpy.uint32)
-            main.check(L.shp_dev_download(main.handle, _lib.ptr(scal), d_scal, 4))
+            main.check(L.shp_dev_download(main.handle, _lib.ptr(scal), bufs.d_scal, 4))
             maxSegId = int(scal[0])
             hist = numpy.zeros(maxSegId + 1, dtype=numpy.uint32)
             ioMark('maxSegId read')
@@ -1289,8 +1326,7 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
                 main.check(L.shp_dev_download(main.handle, _lib.ptr(a), d, a.nbytes))
                 result.overviews[lvl] = a
             if outfile is _KEEP_ON_DEVICE:
-                result.outDev = (d_out.value, inYsize, inXsize, nbOut)
-                d_out = None                        # ownership moves to the caller
+                result.outDev = (d_out.value, inYsize, inXsize, bufs.nbOut)     # ownership moves to the caller
             elif outfile is None:
                 result.segimg = segimg if segimg is not None else numpy.zeros((inYsize, inXsize), shepseg.SegIdType)
             elif isinstance(outfile, str) and outfile.endswith('.npy'):
@@ -1326,16 +1362,9 @@ def doTiledShepherdSegmentation(infile, outfile, tileSize=DFLT_TILESIZE,
                 sys.stderr.write("pyshepseg_amd: a worker did not stop after a failure; its device "
                                  "buffers are leaked rather than reused\n")
             elif ok:
-                _devRelease(main, d_tiles, nbTiles)
-                _devRelease(main, d_out, nbOut)
-                _devRelease(main, d_scal, 256)
-                _devRelease(main, d_strips, nbStrips)
-                arena.release()
+                bufs.release(keepOut=outfile is _KEEP_ON_DEVICE)
             else:           # failed run: free, do not recycle
-                for (p_, n_) in ((d_tiles, nbTiles), (d_out, nbOut), (d_scal, 256), (d_strips, nbStrips)):
-                    if p_ is not None and p_.value:
-                        L.shp_dev_free(main.handle, p_)
-                arena.free()
+                bufs.free()
             if devRas is not None and not stuck:
                 devRas.free()
             if not stuck:
