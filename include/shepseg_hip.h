@@ -391,6 +391,36 @@ int shp_spatialstats_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band
                          int func, const double *params, int64_t missing, int nint, int nflt,
                          int64_t *intcols_out, float *floatcols_out);
 
+/* The spatial statistics split by rows over the ranks (the data path of
+ * distributed.calcPerSegmentSpatialStatsDistributed), modelled on shp_dstats_local_dev / _merge_dev.
+ *  shp_dspatial_local_dev: this rank's rows [row0, row0 + nrows) of an img_rows-row raster in place (d_seg,
+ *    d_band: nrows x ncols), with rows_up halo rows just above them (d_seg_up / d_band_up) and rows_dn just
+ *    below (d_seg_dn / d_band_dn) -- other ranks' rows; the halo must reach the needed distance or the
+ *    image's border (edges: 1 row each way, variogram: maxDist rows below, mean coordinates: none).  The own
+ *    pixels are accumulated, then every id is judged against the GLOBAL label histogram d_hist as in
+ *    shp_dstats_local_dev: rows of segments complete here are finished, ids nobody holds get their "missing"
+ *    row where keep_unheld != 0, all other rows of d_cols are zero.  The straddlers' partial sums are packed
+ *    as records of *rec_words_out uint64 words -- (id, cnt, sumx, sumy), (id, cnt, edges) or (id, cnt,
+ *    vcnt[maxDist], vsum[maxDist]) -- *n_rec_out of them at *d_rec_out in the context's workspace, valid until
+ *    its next call.  checks_out[3]: ids with more pixels here than d_hist says, labelled pixels here, pixels
+ *    of d_hist (a wrong histogram shows in them; the caller decides, after a collective, whether to raise).
+ *    func, params, null_val, missing, nint, nflt: as shp_spatialstats.  Each of the own rows and the two
+ *    halos must hold fewer than 2^32 pixels; the raster as a whole may hold more.
+ *  shp_dspatial_merge_dev: after the all-gather of the records -- `world` slots of `slot` records, counts[r]
+ *    valid in slot r -- the records with id_lo <= id < id_hi are summed, those ids (*n_ids_out of them)
+ *    finished and their rows written into d_cols.
+ *  Summing d_cols over the ranks as int64 words gives the columns shp_spatialstats returns, bit for bit. */
+int shp_dspatial_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                           int64_t ncols, const uint32_t *d_seg_up, const void *d_band_up, int64_t rows_up,
+                           const uint32_t *d_seg_dn, const void *d_band_dn, int64_t rows_dn, int64_t row0,
+                           int64_t img_rows, uint32_t max_seg_id, int64_t null_val, int func, const double *params,
+                           int64_t missing, int nint, int nflt, const uint32_t *d_hist, int keep_unheld,
+                           void *d_cols, void **d_rec_out, int64_t *n_rec_out, int64_t *rec_words_out,
+                           int64_t *checks_out);
+int shp_dspatial_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, int world, const uint32_t *counts,
+                           uint32_t max_seg_id, int func, const double *params, int64_t missing, int nint, int nflt,
+                           uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_ids_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

@@ -152,6 +152,13 @@ _SIGS = {
                                         _c.c_int64, _vp, _c.c_int, _c.c_int64, _vp, _c.c_int, _vp,
                                         _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_c.c_int64),
                                         _c.POINTER(_c.c_int64)]),
+    'shp_dspatial_local_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _vp, _c.c_int64,
+                                          _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int64,
+                                          _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int, _vp,
+                                          _c.POINTER(_vp), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _vp]),
+    'shp_dspatial_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_uint32, _c.c_int, _vp,
+                                          _c.c_int64, _c.c_int, _c.c_int, _c.c_uint32, _c.c_uint32, _vp,
+                                          _c.POINTER(_c.c_int64)]),
     'shp_dstats_merge_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int, _c.c_uint32, _c.c_int,
                                         _c.c_int64, _vp, _c.c_int, _c.c_int64, _c.c_uint32, _c.c_uint32, _vp,
                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),

@@ -1276,6 +1276,59 @@ API int shp_spatialstats(shp_ctx *ctx, const uint32_t *seg, const void *band, in
                             floatcols_out);
 }
 
+// the multi-GPU split with everything left in device memory (spatial.h: run_dspatial_local / run_dspatial_merge)
+static int dspatial_check(shp_ctx *ctx, int func, const double *params, uint32_t max_seg_id, int nint, int nflt)
+{
+    if (!params || nint < 0 || nflt < 0 || nint + nflt < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (func < 0 || func > 2) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown built-in spatial function %d", func);
+    if (func == 2 && !(params[0] >= 1.0 && params[0] <= 255.0))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "variogram maxDist must be 1..255 (got %g)", params[0]);
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    return 0;
+}
+
+API int shp_dspatial_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                               int64_t ncols, const uint32_t *d_seg_up, const void *d_band_up, int64_t rows_up,
+                               const uint32_t *d_seg_dn, const void *d_band_dn, int64_t rows_dn, int64_t row0,
+                               int64_t img_rows, uint32_t max_seg_id, int64_t null_val, int func, const double *params,
+                               int64_t missing, int nint, int nflt, const uint32_t *d_hist, int keep_unheld,
+                               void *d_cols, void **d_rec_out, int64_t *n_rec_out, int64_t *rec_words_out,
+                               int64_t *checks_out)
+{
+    CHK(enter(ctx));
+    if (!d_hist || !d_cols || !d_rec_out || !n_rec_out || !rec_words_out || !checks_out || dtype_size(dtype) == 0 ||
+        nrows < 0 || ncols < 0 || rows_up < 0 || rows_dn < 0 || row0 < 0 ||
+        (nrows > 0 && (!d_seg || !d_band)) || (rows_up > 0 && (!d_seg_up || !d_band_up)) ||
+        (rows_dn > 0 && (!d_seg_dn || !d_band_dn)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(dspatial_check(ctx, func, params, max_seg_id, nint, nflt));
+    if (rows_up > row0 || row0 + nrows + rows_dn > img_rows)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "window rows %lld..%lld outside the image's %lld rows", (long long)(row0 - rows_up),
+                 (long long)(row0 + nrows + rows_dn), (long long)img_rows);
+    // per rank: the own rows and each halo must stay below 2^32 pixels, the whole raster need not
+    if ((uint64_t)nrows * (uint64_t)ncols >= 0xffffffffull || (uint64_t)rows_up * (uint64_t)ncols >= 0xffffffffull ||
+        (uint64_t)rows_dn * (uint64_t)ncols >= 0xffffffffull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "shard too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    SpatialWin w{d_seg, d_seg_up, d_seg_dn, d_band, d_band_up, d_band_dn, dtype, (uint32_t)ncols, (uint32_t)nrows,
+                 (uint32_t)rows_up, (uint32_t)rows_dn, max_seg_id, (long long)null_val, (unsigned long long)row0};
+    return run_dspatial_local(ctx, w, func, params, missing, nint, nflt, d_hist, keep_unheld, d_cols, d_rec_out,
+                              n_rec_out, rec_words_out, checks_out);
+}
+
+API int shp_dspatial_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, int world, const uint32_t *counts,
+                               uint32_t max_seg_id, int func, const double *params, int64_t missing, int nint, int nflt,
+                               uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_ids_out)
+{
+    CHK(enter(ctx));
+    if (!counts || !d_cols || !n_ids_out || slot < 0 || world < 1 || slot >= 0xffffffffll || (slot > 0 && !d_recs))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(dspatial_check(ctx, func, params, max_seg_id, nint, nflt));
+    if (id_hi > max_seg_id + 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "id share beyond max_seg_id");
+    for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
+    return run_dspatial_merge(ctx, (const unsigned long long *)d_recs, (uint32_t)slot, (uint32_t)world, counts, max_seg_id,
+                              func, params, missing, nint, nflt, id_lo, id_hi, d_cols, n_ids_out);
+}
+
 // Grow the context's workspace for tiles of up to npix pixels now (the buffers are grow-only and
 // a regrow synchronises and reallocates in the middle of a run): the tiled drivers call this once
 // per worker with the largest tile of the job, so that a pooled context does not keep growing

@@ -123,6 +123,33 @@ __global__ __launch_bounds__(256) void k_spatial_vario(SpatialGeom g, const uint
     }
 }
 
+// One output row: id s of columns of ns rows, from the accumulators at index a (a == s on one GPU; the
+// merge of the multi-GPU split keeps its accumulators per id share, a = s - id_lo).
+__device__ __forceinline__ void spatial_finish_row(
+    int func, size_t a, size_t s, size_t ns, const uint32_t *__restrict__ cnt,
+    const unsigned long long *__restrict__ sumx, const unsigned long long *__restrict__ sumy,
+    const uint32_t *__restrict__ edges, const uint32_t *__restrict__ vcnt,
+    const unsigned long long *__restrict__ vsum, uint32_t maxd, const double *__restrict__ prm,
+    long long missing, int nint, int nflt, long long *intcols, float *fltcols)
+{
+    for (int c = 0; c < nint; c++) intcols[(size_t)c * ns + s] = s ? missing : 0;
+    for (int c = 0; c < nflt; c++) fltcols[(size_t)c * ns + s] = s ? (float)missing : 0.0f;
+    if (s == 0u || cnt[a] == 0u) return;
+    const double n = (double)cnt[a];
+    if (func == 0) {
+        const double sx = (double)sumx[a], sy = (double)sumy[a];
+        if (nflt > 0) fltcols[s] = (float)((prm[0] * n + prm[1] * sx + prm[2] * sy) / n);
+        if (nflt > 1) fltcols[ns + s] = (float)((prm[3] * n + prm[4] * sx + prm[5] * sy) / n);
+    } else if (func == 1) {
+        if (nint > 0) intcols[s] = (long long)(int)edges[a];
+    } else {
+        for (uint32_t d = 0; d < maxd && (int)d < nflt; d++) {
+            const uint32_t c = vcnt[a * maxd + d];
+            if (c) fltcols[(size_t)d * ns + s] = (float)sqrt((double)vsum[a * maxd + d] / (double)c);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_spatial_finish(
     int func, uint32_t S, const uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ sumx,
     const unsigned long long *__restrict__ sumy, const uint32_t *__restrict__ edges,
@@ -132,23 +159,36 @@ __global__ __launch_bounds__(256) void k_spatial_finish(
 {
     const uint32_t s = blockIdx.x * 256u + threadIdx.x;
     if (s > S) return;
-    const size_t ns = (size_t)S + 1;
-    for (int c = 0; c < nint; c++) intcols[(size_t)c * ns + s] = s ? missing : 0;
-    for (int c = 0; c < nflt; c++) fltcols[(size_t)c * ns + s] = s ? (float)missing : 0.0f;
-    if (s == 0u || cnt[s] == 0u) return;
-    const double n = (double)cnt[s];
-    if (func == 0) {
-        const double sx = (double)sumx[s], sy = (double)sumy[s];
-        if (nflt > 0) fltcols[s] = (float)((prm[0] * n + prm[1] * sx + prm[2] * sy) / n);
-        if (nflt > 1) fltcols[ns + s] = (float)((prm[3] * n + prm[4] * sx + prm[5] * sy) / n);
-    } else if (func == 1) {
-        if (nint > 0) intcols[s] = (long long)(int)edges[s];
-    } else {
-        for (uint32_t d = 0; d < maxd && (int)d < nflt; d++) {
-            const uint32_t c = vcnt[(size_t)s * maxd + d];
-            if (c) fltcols[(size_t)d * ns + s] = (float)sqrt((double)vsum[(size_t)s * maxd + d] / (double)c);
-        }
-    }
+    spatial_finish_row(func, s, s, (size_t)S + 1, cnt, sumx, sumy, edges, vcnt, vsum, maxd, prm, missing, nint,
+                       nflt, intcols, fltcols);
+}
+
+// the variogram's (yo, xo) offsets in 1..maxd, packed (bin << 16 | yo << 8 | xo) and sorted by bin (1-based),
+// yo, xo -- the order k_spatial_vario visits them in
+static std::vector<uint32_t> spatial_vario_offsets(uint32_t maxd)
+{
+    std::vector<uint32_t> offs;
+    for (uint32_t b = 1; b <= maxd; b++)
+        for (uint32_t yo = 1; yo <= maxd; yo++)
+            for (uint32_t xo = 1; xo <= maxd; xo++)
+                if ((uint32_t)__builtin_sqrt((double)(yo * yo + xo * xo)) == b)
+                    offs.push_back((b << 16) | (yo << 8) | xo);
+    return offs;
+}
+
+// the six parameters to d_prm and the variogram's offsets to d_offs, through the context's pinned block
+static int spatial_upload_params(shp_ctx *ctx, const double *params, const std::vector<uint32_t> &offs,
+                                 double *d_prm, uint32_t *d_offs)
+{
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    double *pin = (double *)(ctx->h_pinned + 16);
+    memcpy(pin, params, 48);
+    if (!offs.empty()) memcpy(pin + 8, offs.data(), offs.size() * 4);
+    HIPCHK(ctx, hipMemcpyAsync(d_prm, pin, 48, hipMemcpyHostToDevice, st));
+    if (!offs.empty())
+        HIPCHK(ctx, hipMemcpyAsync(d_offs, pin + 8, offs.size() * 4, hipMemcpyHostToDevice, st));
+    return 0;
 }
 
 // d_seg / d_band: device rasters (nrows x ncols).  Outputs are HOST arrays.
@@ -166,11 +206,7 @@ static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
         if (!(params[0] >= 1.0 && params[0] <= 255.0))
             SHP_FAIL(ctx, SHP_ERR_ARG, "variogram maxDist must be 1..255 (got %g)", params[0]);
         maxd = (uint32_t)params[0];
-        for (uint32_t b = 1; b <= maxd; b++)
-            for (uint32_t yo = 1; yo <= maxd; yo++)
-                for (uint32_t xo = 1; xo <= maxd; xo++)
-                    if ((uint32_t)__builtin_sqrt((double)(yo * yo + xo * xo)) == b)
-                        offs.push_back((b << 16) | (yo << 8) | xo);
+        offs = spatial_vario_offsets(maxd);
     }
     const size_t vrows = func == 2 ? ns * maxd : 1;
     CHK(buf_ensure(ctx, ctx->segsz, ns * 4));                                   // cnt
@@ -188,13 +224,7 @@ static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
     uint32_t *d_offs = bp<uint32_t>(ctx->small) + 64;
     long long *d_int = (long long *)ctx->ssum.p;
     float *d_flt = (float *)(d_int + (size_t)nint * ns);
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    double *pin = (double *)(ctx->h_pinned + 16);
-    memcpy(pin, params, 48);
-    if (!offs.empty()) memcpy(pin + 8, offs.data(), offs.size() * 4);
-    HIPCHK(ctx, hipMemcpyAsync(d_prm, pin, 48, hipMemcpyHostToDevice, st));
-    if (!offs.empty())
-        HIPCHK(ctx, hipMemcpyAsync(d_offs, pin + 8, offs.size() * 4, hipMemcpyHostToDevice, st));
+    CHK(spatial_upload_params(ctx, params, offs, d_prm, d_offs));
     HIPCHK(ctx, hipMemsetAsync(cnt, 0, ns * 4, st));
     SpatialGeom g{d_seg, d_band, dtype, nrows, ncols, S, (long long)null_val};
     const unsigned grid = grid_for(n, 256);
@@ -220,5 +250,370 @@ static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
     if (nint) HIPCHK(ctx, hipMemcpyAsync(intcols_out, d_int, (size_t)nint * ns * 8, hipMemcpyDeviceToHost, st));
     if (nflt) HIPCHK(ctx, hipMemcpyAsync(fltcols_out, d_flt, (size_t)nflt * ns * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// ---- multi-GPU split, device-resident (pyshepseg_amd/distributed.py: deviceSpatialStats) ------------------
+// A rank holds rows [row0, row0 + h) of the label raster and of the band.  Edges and the variogram look past a
+// pixel's own row, so they also read `ha` halo rows just above row0 and `hb` just below row0 + h -- other ranks'
+// rows, all-gathered into buffers of their own.  Window row r in [-ha, h + hb) is global row row0 + r, and the
+// window ends only where the image ends (the halo plan asks for whatever rows the image has there), so a
+// neighbour outside the window is outside the image.  Only the rank's own pixels are accumulated: each pixel,
+// and each variogram pair (by its upper pixel), is counted by exactly one rank, and every accumulator is an
+// integer sum (uint32 / uint64, wrapping as on one GPU), so the ranks' partial sums add up to the one-GPU sums
+// bit for bit and k_spatial_finish's arithmetic (spatial_finish_row) gives the same columns.
+struct SpatialWin {
+    const uint32_t *seg, *seg_up, *seg_dn;
+    const void *band, *band_up, *band_dn;
+    int dtype;
+    uint32_t ncols, h, ha, hb, S;
+    long long null_val;
+    unsigned long long row0;
+};
+
+// the id of window pixel (r, col) when it is a non-nodata pixel of a segment, else 0; r in [-ha, h + hb)
+__device__ __forceinline__ uint32_t win_member(const SpatialWin &w, long long r, uint32_t col)
+{
+    const uint32_t *sg;
+    const void *bd;
+    size_t i;
+    if (r < 0) { sg = w.seg_up; bd = w.band_up; i = (size_t)(r + w.ha) * w.ncols + col; }
+    else if (r < (long long)w.h) { sg = w.seg; bd = w.band; i = (size_t)r * w.ncols + col; }
+    else { sg = w.seg_dn; bd = w.band_dn; i = (size_t)(r - (long long)w.h) * w.ncols + col; }
+    const uint32_t s = sg[i];
+    if (s == 0u || s > w.S) return 0u;
+    return ld_px(bd, w.dtype, i) != w.null_val ? s : 0u;
+}
+
+// the rank's own pixel p (64-bit: the window of a shard is not indexed by a 32-bit flat index)
+#define WIN_PIXEL(w)                                                                   \
+    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;                          \
+    const bool inb = p < (size_t)(w).h * (w).ncols;                                    \
+    const uint32_t row = inb ? (uint32_t)(p / (w).ncols) : 0u;                         \
+    const uint32_t col = inb ? (uint32_t)(p - (size_t)row * (w).ncols) : 0u;
+
+// k_spatial_sums over the own rows: sumy of the GLOBAL row
+__global__ __launch_bounds__(256) void k_spatial_wsums(SpatialWin w, uint32_t *cnt, unsigned long long *sumx,
+                                                       unsigned long long *sumy)
+{
+    WIN_PIXEL(w)
+    const uint32_t s = inb ? win_member(w, row, col) : 0u;
+    const uint32_t len = spatial_runlen(s, col, inb);
+    if (len) {
+        atomicAdd(&cnt[s], len);
+        if (sumx) {
+            atomicAdd(&sumx[s], (unsigned long long)len * col + (unsigned long long)len * (len - 1u) / 2ull);
+            atomicAdd(&sumy[s], (unsigned long long)len * (w.row0 + row));
+        }
+    }
+}
+
+// k_spatial_edges over the own rows, the rows above and below read across the own / halo split
+__global__ __launch_bounds__(256) void k_spatial_wedges(SpatialWin w, int four, uint32_t *edges)
+{
+    WIN_PIXEL(w)
+    const uint32_t s = inb ? win_member(w, row, col) : 0u;
+    uint32_t key = 0u;
+    if (s) {
+        const long long r = row;
+        const bool up = r - 1 >= -(long long)w.ha, dn = r + 1 < (long long)w.h + (long long)w.hb;
+        const bool lf = col > 0u, rt = col + 1u < w.ncols;
+#define MEM(ok, rr, cc) ((ok) && win_member(w, (rr), (cc)) == s)
+        bool inside = MEM(up, r - 1, col) && MEM(dn, r + 1, col) && MEM(lf, r, col - 1u) && MEM(rt, r, col + 1u);
+        if (inside && !four)        // the reference's 8-connected test: (y-1, x+1) is never looked at
+            inside = MEM(up && lf, r - 1, col - 1u) && MEM(dn && rt, r + 1, col + 1u) &&
+                     MEM(dn && lf, r + 1, col - 1u);
+#undef MEM
+        if (!inside) key = s;
+    }
+    const uint32_t len = spatial_runlen(key, col, inb);
+    if (len) atomicAdd(&edges[key], len);
+}
+
+// k_spatial_vario over the own rows; the partners (yo rows below) may lie in the halo below
+__global__ __launch_bounds__(256) void k_spatial_wvario(SpatialWin w, const uint32_t *__restrict__ offs,
+                                                        uint32_t noffs, uint32_t maxd, uint32_t *vcnt,
+                                                        unsigned long long *vsum)
+{
+    WIN_PIXEL(w)
+    if (!inb) return;
+    const uint32_t s = win_member(w, row, col);
+    if (s == 0u) return;
+    const long long v = ld_px(w.band, w.dtype, p);
+    const long long wend = (long long)w.h + (long long)w.hb;
+    uint32_t bin = 0, c = 0;
+    unsigned long long acc = 0;
+    for (uint32_t i = 0; i <= noffs; i++) {
+        const uint32_t o = i < noffs ? offs[i] : 0xFFFFFFFFu;
+        const uint32_t b = o >> 16;
+        if (b != bin) {
+            if (c) {
+                atomicAdd(&vcnt[(size_t)s * maxd + (bin - 1u)], c);
+                atomicAdd(&vsum[(size_t)s * maxd + (bin - 1u)], acc);
+            }
+            bin = b; c = 0; acc = 0;
+            if (i == noffs) break;
+        }
+        const uint32_t yo = (o >> 8) & 255u, xo = o & 255u;
+        const long long rq = (long long)row + yo;
+        if (rq < wend && col + xo < w.ncols && win_member(w, rq, col + xo) == s) {
+            const long long u = rq < (long long)w.h ? ld_px(w.band, w.dtype, p + (size_t)yo * w.ncols + xo)
+                                                    : ld_px(w.band_dn, w.dtype, (size_t)(rq - (long long)w.h) * w.ncols + col + xo);
+            const unsigned long long d = (unsigned long long)(v - u);
+            c++;
+            acc += d * d;                 // (unsigned: the square of a 32-bit difference may wrap)
+        }
+    }
+}
+#undef WIN_PIXEL
+
+// Every id judged against the global histogram gh (the reference's segSize): complete here (local label count
+// == global) -> its finished row goes into cols; ids nobody holds (global 0, row 0 among them) -> their
+// "missing" row, on the one rank with keep_unheld; every other row -> zero, so that the ranks' column blocks
+// ADD UP to the one-GPU block.  ctr[0] += ids with more pixels here than the histogram says (a wrong
+// histogram), ctr[1] += labelled pixels here, ctr[2] += pixels of the histogram (one atomic triple per wave).
+__global__ __launch_bounds__(256) void k_dspatial_classify(
+    int func, uint32_t S, const uint32_t *__restrict__ lh, const uint32_t *__restrict__ gh, int keep_unheld,
+    const uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ sumx,
+    const unsigned long long *__restrict__ sumy, const uint32_t *__restrict__ edges,
+    const uint32_t *__restrict__ vcnt, const unsigned long long *__restrict__ vsum, uint32_t maxd,
+    const double *__restrict__ prm, long long missing, int nint, int nflt, long long *intcols, float *fltcols,
+    unsigned long long *ctr)
+{
+    const size_t ns = (size_t)S + 1;
+    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+    unsigned long long l = 0, g = 0;
+    if (id < ns) {
+        l = id ? lh[id] : 0u;
+        g = id ? gh[id] : 0u;
+        if ((l > 0u && l == g) || (keep_unheld && g == 0u)) {
+            spatial_finish_row(func, id, id, ns, cnt, sumx, sumy, edges, vcnt, vsum, maxd, prm, missing, nint, nflt,
+                               intcols, fltcols);
+        } else {
+            for (int c = 0; c < nint; c++) intcols[(size_t)c * ns + id] = 0;
+            for (int c = 0; c < nflt; c++) fltcols[(size_t)c * ns + id] = 0.0f;
+        }
+    }
+    const unsigned long long over = __ballot(l > g);
+    for (int o = 32; o > 0; o >>= 1) { l += __shfl_xor(l, o); g += __shfl_xor(g, o); }
+    if (lane_id() == 0) {
+        if (over) atomicAdd(&ctr[0], (unsigned long long)__popcll(over));
+        if (l) atomicAdd(&ctr[1], l);
+        if (g) atomicAdd(&ctr[2], g);
+    }
+}
+
+// 1 for a straddler: some but not all of its pixels here (the scan of these places the packed records)
+struct DspStradFn {
+    const uint32_t *lh, *gh;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const
+    {
+        if (i == 0u) return 0u;
+        const uint32_t l = lh[i];
+        return (l > 0u && l < gh[i]) ? 1u : 0u;
+    }
+};
+
+// words of one straddler record (uint64 each): id, cnt, then sumx, sumy | edges | vcnt[maxd], vsum[maxd]
+static inline uint32_t dspatial_rec_words(int func, uint32_t maxd)
+{
+    return func == 0 ? 4u : func == 1 ? 3u : 2u + 2u * maxd;
+}
+
+__global__ __launch_bounds__(256) void k_dspatial_pack(
+    int func, uint32_t S, const uint32_t *__restrict__ lh, const uint32_t *__restrict__ gh,
+    const uint32_t *__restrict__ pos, const uint32_t *__restrict__ cnt, const unsigned long long *__restrict__ sumx,
+    const unsigned long long *__restrict__ sumy, const uint32_t *__restrict__ edges,
+    const uint32_t *__restrict__ vcnt, const unsigned long long *__restrict__ vsum, uint32_t maxd, uint32_t W,
+    unsigned long long *__restrict__ rec)
+{
+    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (id == 0 || id > S) return;
+    const uint32_t l = lh[id];
+    if (!(l > 0u && l < gh[id])) return;
+    unsigned long long *o = rec + (size_t)pos[id] * W;
+    o[0] = id;
+    o[1] = cnt[id];
+    if (func == 0) {
+        o[2] = sumx[id];
+        o[3] = sumy[id];
+    } else if (func == 1) {
+        o[2] = edges[id];
+    } else {
+        for (uint32_t d = 0; d < maxd; d++) {
+            o[2 + d] = vcnt[id * maxd + d];
+            o[2 + maxd + d] = vsum[id * maxd + d];
+        }
+    }
+}
+
+// the accumulators of one call: per id (local part) or per id of the share (merge)
+struct SpatialAcc {
+    uint32_t *cnt, *edges, *vcnt;
+    unsigned long long *sumx, *sumy, *vsum;
+    double *prm;
+    uint32_t *offs;
+};
+
+// cnt, edges, sumx | sumy, vsum | vcnt for `rows` ids, the parameters and the variogram's offsets
+static int spatial_acc(shp_ctx *ctx, int func, size_t rows, uint32_t maxd, const double *params,
+                       const std::vector<uint32_t> &offs, SpatialAcc *a)
+{
+    hipStream_t st = ctx->stream;
+    const size_t vrows = func == 2 ? rows * maxd : 1;
+    if (offs.size() * 4 + 64 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "maxDist too large");
+    CHK(buf_ensure(ctx, ctx->segsz, rows * 4));
+    CHK(buf_ensure(ctx, ctx->origsz, rows * 4));
+    CHK(buf_ensure(ctx, ctx->aux, rows * 16));
+    CHK(buf_ensure(ctx, ctx->aux2, vrows * 12 + 64));
+    CHK(buf_ensure(ctx, ctx->small, 4096 + offs.size() * 4));
+    a->cnt = bp<uint32_t>(ctx->segsz);
+    a->edges = bp<uint32_t>(ctx->origsz);
+    a->sumx = (unsigned long long *)ctx->aux.p;
+    a->sumy = a->sumx + rows;
+    a->vsum = (unsigned long long *)ctx->aux2.p;
+    a->vcnt = (uint32_t *)(a->vsum + vrows);
+    a->prm = (double *)ctx->small.p;
+    a->offs = bp<uint32_t>(ctx->small) + 64;
+    CHK(spatial_upload_params(ctx, params, offs, a->prm, a->offs));
+    HIPCHK(ctx, hipMemsetAsync(a->cnt, 0, rows * 4, st));
+    if (func == 0) HIPCHK(ctx, hipMemsetAsync(a->sumx, 0, rows * 16, st));
+    if (func == 1) HIPCHK(ctx, hipMemsetAsync(a->edges, 0, rows * 4, st));
+    if (func == 2) HIPCHK(ctx, hipMemsetAsync(a->vsum, 0, vrows * 12, st));
+    return 0;
+}
+
+// Rank-local part: accumulate over the own rows, classify every id, pack the straddlers' records (a scan over
+// the ids places them: no atomic per id) into the context's workspace.  checks[0..2] = ctr of k_dspatial_classify.
+static int run_dspatial_local(shp_ctx *ctx, const SpatialWin &w, int func, const double *params, int64_t missing,
+                              int nint, int nflt, const uint32_t *d_hist, int keep_unheld, void *d_cols,
+                              void **d_rec, int64_t *n_rec, int64_t *rec_words, int64_t *checks)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)w.S + 1;
+    const size_t n = (size_t)w.h * w.ncols;
+    const uint32_t maxd = func == 2 ? (uint32_t)params[0] : 0u;
+    const std::vector<uint32_t> offs = func == 2 ? spatial_vario_offsets(maxd) : std::vector<uint32_t>();
+    const uint32_t W = dspatial_rec_words(func, maxd);
+    SpatialAcc a;
+    CHK(spatial_acc(ctx, func, ns, maxd, params, offs, &a));
+    // the local label histogram (all pixels of a label, valid or not) | scan positions | counters
+    CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->tcount, ns * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->chtail, 64));
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
+    uint32_t *lh = bp<uint32_t>(ctx->chnext), *pos = bp<uint32_t>(ctx->tcount);
+    unsigned long long *ctr = (unsigned long long *)ctx->chtail.p;
+    uint32_t *d_total = (uint32_t *)(ctr + 3);        // the scan's total: the low word of ctr[3]
+    HIPCHK(ctx, hipMemsetAsync(lh, 0, ns * 4, st));
+    HIPCHK(ctx, hipMemsetAsync(ctr, 0, 32, st));
+    if (n) {
+        const unsigned grid = grid_for(n, 256);
+        hipLaunchKernelGGL(k_label_hist, dim3(grid), dim3(256), 0, st, w.seg, (uint32_t)n, w.S, lh);
+        hipLaunchKernelGGL(k_spatial_wsums, dim3(grid), dim3(256), 0, st, w, a.cnt,
+                           func == 0 ? a.sumx : (unsigned long long *)nullptr, func == 0 ? a.sumy : (unsigned long long *)nullptr);
+        if (func == 1)
+            hipLaunchKernelGGL(k_spatial_wedges, dim3(grid), dim3(256), 0, st, w, params[0] != 0.0, a.edges);
+        if (func == 2)
+            hipLaunchKernelGGL(k_spatial_wvario, dim3(grid), dim3(256), 0, st, w, a.offs, (uint32_t)offs.size(), maxd,
+                               a.vcnt, a.vsum);
+        KCHK(ctx);
+    }
+    long long *cint = (long long *)d_cols;
+    float *cflt = (float *)(cint + (size_t)nint * ns);
+    hipLaunchKernelGGL(k_dspatial_classify, dim3(grid_for(ns, 256)), dim3(256), 0, st, func, w.S, lh, d_hist,
+                       keep_unheld, a.cnt, a.sumx, a.sumy, a.edges, a.vcnt, a.vsum, maxd, a.prm, (long long)missing,
+                       nint, nflt, cint, cflt, ctr);
+    KCHK(ctx);
+    DspStradFn f{lh, d_hist};
+    CHK(scan_exclusive(ctx, f, (uint32_t)ns, pos, d_total, bp<uint32_t>(ctx->scan_tmp)));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(h, ctr, 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    const uint32_t nr = (uint32_t)h[3];
+    CHK(buf_ensure(ctx, ctx->tlist, (size_t)nr * W * 8 + 64));
+    if (nr)
+        hipLaunchKernelGGL(k_dspatial_pack, dim3(grid_for(ns, 256)), dim3(256), 0, st, func, w.S, lh, d_hist, pos,
+                           a.cnt, a.sumx, a.sumy, a.edges, a.vcnt, a.vsum, maxd, W,
+                           (unsigned long long *)ctx->tlist.p);
+    KCHK(ctx);
+    *d_rec = ctx->tlist.p;
+    *n_rec = (int64_t)nr;
+    *rec_words = (int64_t)W;
+    for (int i = 0; i < 3; i++) checks[i] = (int64_t)h[i];
+    return 0;
+}
+
+// Merge part: the records as the all-gather left them (`world` slots of `slot` records, counts[r] valid in slot
+// r) whose id lies in [id_lo, id_hi) are added into zeroed accumulators of that share; the ids that occur are
+// finished and their rows written into cols (every rank's classify step left them zero).
+__global__ __launch_bounds__(256) void k_dspatial_scatter(
+    const unsigned long long *__restrict__ rec, uint32_t slot, uint32_t world, const uint32_t *__restrict__ counts,
+    uint32_t W, int func, uint32_t maxd, uint32_t id_lo, uint32_t id_hi, uint32_t *present, SpatialAcc a)
+{
+    const size_t q = (size_t)blockIdx.x * 256u + threadIdx.x;     // one word of one record
+    if (q >= (size_t)slot * world * W) return;
+    const size_t k = q / W;
+    const uint32_t wd = (uint32_t)(q - k * W);
+    const uint32_t r = (uint32_t)(k / slot), e = (uint32_t)(k - (size_t)r * slot);
+    if (e >= counts[r]) return;
+    const unsigned long long id = rec[k * W];
+    if (id < id_lo || id >= id_hi) return;
+    const size_t i = (size_t)(id - id_lo);
+    const unsigned long long v = rec[q];
+    if (wd == 0) { present[i] = 1u; return; }
+    if (v == 0ull) return;
+    if (wd == 1) atomicAdd(&a.cnt[i], (uint32_t)v);
+    else if (func == 0) atomicAdd(wd == 2 ? &a.sumx[i] : &a.sumy[i], v);
+    else if (func == 1) atomicAdd(&a.edges[i], (uint32_t)v);
+    else if (wd < 2u + maxd) atomicAdd(&a.vcnt[i * maxd + (wd - 2u)], (uint32_t)v);
+    else atomicAdd(&a.vsum[i * maxd + (wd - 2u - maxd)], v);
+}
+
+__global__ __launch_bounds__(256) void k_dspatial_finish_share(int func, uint32_t S, uint32_t id_lo, uint32_t nshare,
+                                                               const uint32_t *__restrict__ present, SpatialAcc a,
+                                                               uint32_t maxd, long long missing, int nint, int nflt,
+                                                               long long *intcols, float *fltcols, uint32_t *n_ids)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    const bool here = i < nshare && present[i] != 0u;
+    const unsigned long long m = __ballot(here);
+    if (m != 0ull && lane_id() == 0) atomicAdd(n_ids, (uint32_t)__popcll(m));
+    if (here)
+        spatial_finish_row(func, i, (size_t)id_lo + i, (size_t)S + 1, a.cnt, a.sumx, a.sumy, a.edges, a.vcnt, a.vsum,
+                           maxd, a.prm, missing, nint, nflt, intcols, fltcols);
+}
+
+static int run_dspatial_merge(shp_ctx *ctx, const unsigned long long *d_rec, uint32_t slot, uint32_t world,
+                              const uint32_t *counts_host, uint32_t S, int func, const double *params, int64_t missing,
+                              int nint, int nflt, uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_ids)
+{
+    hipStream_t st = ctx->stream;
+    *n_ids = 0;
+    if ((size_t)slot * world == 0 || id_lo >= id_hi) return 0;
+    const uint32_t maxd = func == 2 ? (uint32_t)params[0] : 0u;
+    const uint32_t W = dspatial_rec_words(func, maxd);
+    const size_t words = (size_t)slot * world * W;
+    if (words / 256u >= 0x7fffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "too many gathered records");
+    const uint32_t nshare = id_hi - id_lo;
+    SpatialAcc a;
+    CHK(spatial_acc(ctx, func, nshare, maxd, params, std::vector<uint32_t>(), &a));
+    CHK(buf_ensure(ctx, ctx->chnext, (size_t)nshare * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->chtail, (size_t)world * 4 + 128));
+    uint32_t *present = bp<uint32_t>(ctx->chnext);
+    uint32_t *d_counts = bp<uint32_t>(ctx->chtail) + 16, *d_n = bp<uint32_t>(ctx->chtail);
+    HIPCHK(ctx, hipMemsetAsync(present, 0, (size_t)nshare * 4, st));
+    HIPCHK(ctx, hipMemsetAsync(d_n, 0, 4, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_counts, counts_host, (size_t)world * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_dspatial_scatter, dim3(grid_for(words, 256)), dim3(256), 0, st, d_rec, slot, world, d_counts,
+                       W, func, maxd, id_lo, id_hi, present, a);
+    long long *cint = (long long *)d_cols;
+    float *cflt = (float *)(cint + (size_t)nint * ((size_t)S + 1));
+    hipLaunchKernelGGL(k_dspatial_finish_share, dim3(grid_for(nshare, 256)), dim3(256), 0, st, func, S, id_lo, nshare,
+                       present, a, maxd, (long long)missing, nint, nflt, cint, cflt, d_n);
+    KCHK(ctx);
+    uint32_t ids = 0;
+    CHK(read_u32(ctx, d_n, &ids));
+    *n_ids = (int64_t)ids;
     return 0;
 }

@@ -66,6 +66,7 @@ recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six nu
   histogram(maxSegId) -> pixel counts per id of the output rows (after finish too, if kept);
       finish(): the run's buffers released, bar a kept output.
   localStats, gatherFlagged, statsOfPairs (optional statsOnDevice): calcPerSegmentStatsDistributed.
+  spatialOnDevice (optional): calcPerSegmentSpatialStatsDistributed.
 """
 import collections
 import ctypes
@@ -587,6 +588,31 @@ def calcPerSegmentStatsDistributed(engine, comm, hist, imgbandnum, statsSelectio
     return ic, fc, fast
 
 
+def calcPerSegmentSpatialStatsDistributed(engine, comm, hist, imgbandnum, colTypes, userFunc, userParam,
+                                          missingStatsValue=-9999, imgNullVal=None, info=None):
+    """Per-segment spatial statistics (tilingstats.calcPerSegmentSpatialStats with its built-in user functions)
+    of one image band against the label raster that runDistributed left sharded by rows over the ranks.  As in
+    calcPerSegmentStatsDistributed, ``hist`` (DistResult.hist) plays the part of segSize: segments complete on a
+    rank are finished there, the straddlers' partial sums travel as packed records and every rank reduces those
+    of its id share (idRange).  Edge pixels and the variogram also read rows of the neighbouring ranks (halo
+    rows, spatialHaloPlan): they need disjoint output rows (SHEPSEG_SHARD=rows; mean coordinates do not).
+    Needs a device engine (HipEngine.spatialOnDevice); a communicator that is not on the device carries the
+    device buffers through the host (comm.HostStagedDev).  ``info`` (a dict, optional) receives 'straddlers'
+    (segments), 'halo_rows' (of all ranks) and 'path'.  Returns (intcols int64 (nInt, maxSegId+1), floatcols
+    float32 (nFloat, maxSegId+1)) on every rank -- bit-identical to calcPerSegmentSpatialStats of the whole
+    raster: every accumulator is an integer sum, so the ranks' partial sums add up exactly."""
+    from . import comm as _comm
+    from . import tilingstats
+    if not hasattr(engine, 'spatialOnDevice'):
+        raise tilingstats.PyShepSegStatsError("the distributed spatial statistics need a device engine (HipEngine)")
+    dcomm = comm if getattr(comm, 'onDevice', False) else _comm.HostStagedDev(comm, engine.c)
+    (ic, fc, nStrad, haloRows) = engine.spatialOnDevice(dcomm, hist, imgbandnum, colTypes, userFunc, userParam,
+                                                        missingStatsValue, imgNullVal)
+    if info is not None:
+        info.update(straddlers=nStrad, halo_rows=haloRows, path='device')
+    return ic, fc
+
+
 def deviceStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, hist, fast, nInt, nFloat, missing, imgNullVal,
                 fetch=True):
     """The device-resident data path of calcPerSegmentStatsDistributed for ONE rank: label rows d_seg
@@ -653,6 +679,197 @@ def deviceStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, hist, fast, nIn
             tiling._devRelease(c, p, sz)
     # the job's figures: the ranks' id shares partition the straddlers, the ranks' rows their pixels
     tot = comm.allgather_obj((int(nIds.value), int(nPairs.value)))
+    return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
+
+
+def spatialHaloPlan(rowRanges, rank, nRows, above, below):
+    """Where rank ``rank`` finds the halo rows of the spatial statistics.  rowRanges: every rank's output rows
+    (outLo, outHi); ``above`` / ``below``: rows needed above / below the shard (mean coordinates 0 / 0, edge
+    pixels 1 / 1, the variogram 0 / maxDist).  Every rank contributes its first min(h, below) rows to slot rows
+    [0, below) and its last min(h, above) rows to slot rows [below, below + above) of one all-gather of
+    ``slot`` = above + below rows per rank; a halo may span several ranks (thin or empty shards) and stops at
+    the image's border.  Returns a dict: 'above' / 'below' = halo rows this rank gets (ha, hb), 'slot',
+    'send' = [(own row, slot row, rows)], 'recvAbove' / 'recvBelow' = [(halo row, source rank, slot row,
+    rows)] (halo row 0 = global row outLo - ha, resp. outHi).  Output rows shared by several ranks (tile
+    sharding) are refused when a halo is needed, as are rows of a halo that no rank holds."""
+    from .tilingstats import PyShepSegStatsError
+    ranges = [(int(a), int(b)) for (a, b) in rowRanges]
+    (above, below, nRows) = (int(above), int(below), int(nRows))
+    (lo, hi) = ranges[rank]
+    live = sorted((a, b) for (a, b) in ranges if b > a)
+    if above or below:
+        for (x, y) in zip(live, live[1:]):
+            if x[1] > y[0]:
+                raise PyShepSegStatsError(
+                    "edge pixels and the variogram need ranks with disjoint output rows (rows %d..%d and %d..%d "
+                    "overlap): run the segmentation with SHEPSEG_SHARD=rows" % (x[0], x[1], y[0], y[1]))
+    h = max(hi - lo, 0)
+    plan = {'slot': above + below, 'send': [], 'recvAbove': [], 'recvBelow': [], 'above': 0, 'below': 0}
+    first, last = min(h, below), min(h, above)
+    if first:
+        plan['send'].append((0, 0, first))
+    if last:
+        plan['send'].append((h - last, below, last))
+    if h == 0:
+        return plan
+
+    def owner(y):
+        for (r, (a, b)) in enumerate(ranges):
+            if a <= y < b:
+                return r
+        raise PyShepSegStatsError("row %d of the spatial statistics' halo is held by no rank" % y)
+
+    def runs(rows, slotRowOf):
+        out = []
+        for (k, y) in enumerate(rows):
+            o = owner(y)
+            sr = slotRowOf(o, y)
+            if out and out[-1][1] == o and out[-1][2] + out[-1][3] == sr:
+                out[-1][3] += 1
+            else:
+                out.append([k, o, sr, 1])
+        return [tuple(x) for x in out]
+    up = list(range(max(0, lo - above), lo))
+    dn = list(range(hi, min(nRows, hi + below)))
+    plan['above'], plan['below'] = len(up), len(dn)
+    plan['recvAbove'] = runs(up, lambda o, y: below + y - (ranges[o][1] - min(ranges[o][1] - ranges[o][0], above)))
+    plan['recvBelow'] = runs(dn, lambda o, y: y - ranges[o][0])
+    return plan
+
+
+_DTYPE_SIZE = {0: 1, 1: 2, 2: 2, 3: 4, 4: 4}
+
+
+def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange, hist, colTypes, userFunc, userParam,
+                       missing=-9999, imgNullVal=None, fetch=True):
+    """The device-resident data path of calcPerSegmentSpatialStatsDistributed for ONE rank: output rows rowRange =
+    (outLo, outHi) of an nRows x nCols raster (nRows None: the largest outHi of the ranks), labels d_seg (uint32)
+    and band d_band (dtypeCode; -1 on a rank without rows: the other ranks' code) in the HBM of context ``c``;
+    comm: allgather_obj, allgather_dev, allreduce_dev_i64.  ``hist``: the global histogram, a numpy array or
+    ('dev', address, length).  Halo rows (spatialHaloPlan) travel in one all-gather of labels and one of band
+    values; shp_dspatial_local_dev -> all-gather of the straddlers' records -> shp_dspatial_merge_dev by id share
+    -> all-reduce of the column block.  Every error that depends on a rank's data is all-gathered first, so all
+    ranks raise it.  Returns (ic, fc, straddling segments, halo rows of all ranks); fetch=False: ic = fc = None."""
+    from . import tilingstats
+    Err = tilingstats.PyShepSegStatsError
+    L = c._L
+    params = numpy.zeros(6, dtype=numpy.float64)
+    pv = numpy.atleast_1d(numpy.asarray(0 if userParam is None else userParam, dtype=numpy.float64))
+    params[:min(len(pv), 6)] = pv[:6]
+    nInt = sum(1 for t in colTypes if t == tilingstats.GFT_Integer)
+    nFloat = sum(1 for t in colTypes if t == tilingstats.GFT_Real)
+    func = getattr(userFunc, 'funcId', None) if isinstance(userFunc, tilingstats._BuiltinSpatialFunc) else None
+    err = None
+    if func is None:
+        err = ("only the built-in user functions (userFuncMeanCoord, userFuncNumEdgePixels, userFuncVariogram) are "
+               "supported on the GPU")
+    elif imgNullVal is None:
+        err = "NoData value must be set on imgfile"
+    elif nInt + nFloat != len(colTypes) or not colTypes:
+        err = "column types must be GFT_Integer or GFT_Real, one or more of them"
+    elif func == 2 and not (1.0 <= params[0] <= 255.0):
+        err = "variogram maxDist must be 1..255 (got %g)" % params[0]
+    ctrl = comm.allgather_obj((int(rowRange[0]), int(rowRange[1]), int(dtypeCode), err))
+    errs = [x[3] for x in ctrl if x[3]]
+    if errs:
+        raise Err(errs[0])
+    ranges = [(x[0], x[1]) for x in ctrl]
+    codes = {x[2] for x in ctrl if x[2] >= 0}
+    if len(codes) != 1:
+        raise Err("the ranks' bands differ in data type (%s)" % sorted(codes))
+    dtypeCode = codes.pop()
+    isz = _DTYPE_SIZE[dtypeCode]
+    if nRows is None:
+        nRows = max(b for (a, b) in ranges)
+    (above, below) = {0: (0, 0), 1: (1, 1), 2: (0, int(params[0]))}[func]
+    plan = spatialHaloPlan(ranges, comm.rank, nRows, above, below)     # (raises alike on every rank)
+    (lo, hi) = (int(rowRange[0]), int(rowRange[1]))
+    h = max(hi - lo, 0)
+    (ha, hb) = (plan['above'], plan['below'])
+    toFree = []
+
+    def alloc(nbytes):
+        p = tiling._devAlloc(c, nbytes)
+        toFree.append((p, nbytes))
+        return p
+    if isinstance(hist, tuple):
+        (d_hist, ns) = (ctypes.c_void_p(hist[1]), int(hist[2]))
+    else:
+        h32 = numpy.ascontiguousarray(hist, dtype=numpy.uint32)
+        ns = len(h32)
+        d_hist = alloc(ns * 4)
+        c.check(L.shp_dev_upload(c.handle, d_hist, _lib.ptr(h32), ns * 4))
+    S = ns - 1
+    colWords = ((nInt * 8 + nFloat * 4) * ns + 7) // 8
+    try:
+        d_cols = alloc(colWords * 8)
+        c.check(L.shp_dev_memset(c.handle, ctypes.c_void_p(d_cols.value + (colWords - 1) * 8), 0, 8))
+        # ---- halo rows: every rank's first / last rows in one all-gather of labels and one of band values
+        halo = {'segUp': None, 'bandUp': None, 'segDn': None, 'bandDn': None}
+        slot = plan['slot']
+        if slot and comm.world > 1:
+            rowB = (nCols * 4, nCols * isz)
+            sends = [alloc(max(slot * nCols * b, 1)) for b in rowB]
+            alls = [alloc(max(comm.world * slot * nCols * b, 1)) for b in rowB]
+            for (ownRow, slotRow, n) in plan['send']:
+                for (k, src) in enumerate((d_seg, d_band)):
+                    c.check(L.shp_dev_copy(c.handle, ctypes.c_void_p(sends[k].value + slotRow * rowB[k]),
+                                           ctypes.c_void_p(src + ownRow * rowB[k]), n * rowB[k]))
+            for k in range(2):
+                comm.allgather_dev(sends[k].value, alls[k].value, slot * rowB[k])
+            for (key, rows, recv) in (('Up', ha, plan['recvAbove']), ('Dn', hb, plan['recvBelow'])):
+                if not rows:
+                    continue
+                bufs = [alloc(rows * b) for b in rowB]
+                halo['seg' + key], halo['band' + key] = bufs
+                for (dstRow, src, slotRow, n) in recv:
+                    for k in range(2):
+                        c.check(L.shp_dev_copy(c.handle, ctypes.c_void_p(bufs[k].value + dstRow * rowB[k]),
+                                               ctypes.c_void_p(alls[k].value + (src * slot + slotRow) * rowB[k]),
+                                               n * rowB[k]))
+        # ---- own rows, the straddlers' records
+        (pRec, nRec, W) = (ctypes.c_void_p(), ctypes.c_int64(0), ctypes.c_int64(0))
+        checks = numpy.zeros(3, dtype=numpy.int64)
+        c.check(L.shp_dspatial_local_dev(
+            c.handle, ctypes.c_void_p(d_seg if h else None), ctypes.c_void_p(d_band if h else None), dtypeCode, h,
+            nCols, halo['segUp'], halo['bandUp'], ha, halo['segDn'], halo['bandDn'], hb, lo if h else 0, nRows, S,
+            int(imgNullVal), func, _lib.ptr(params), int(missing), nInt, nFloat, d_hist, int(comm.rank == 0), d_cols,
+            ctypes.byref(pRec), ctypes.byref(nRec), ctypes.byref(W), _lib.ptr(checks)))
+        got = comm.allgather_obj((int(nRec.value), [int(x) for x in checks]))
+        over = sum(g[1][0] for g in got)
+        (px, hpx) = (sum(g[1][1] for g in got), got[0][1][2])
+        if over or px != hpx:
+            raise Err("the segment histogram does not match the label raster (%d ids with more pixels on one rank "
+                      "than the histogram says; %d labelled pixels, %d in the histogram)" % (over, px, hpx))
+        counts = [g[0] for g in got]
+        recSlot = max(counts)
+        nIds = ctypes.c_int64(0)
+        if recSlot > 0:
+            nb = recSlot * int(W.value) * 8
+            d_send = alloc(nb)
+            d_all = alloc(comm.world * nb)
+            if nRec.value:
+                c.check(L.shp_dev_copy(c.handle, d_send, pRec, nRec.value * int(W.value) * 8))
+            comm.allgather_dev(d_send.value, d_all.value, nb)
+            (idLo, idHi) = idRange(comm.rank, comm.world, S)
+            cnts = numpy.array(counts, dtype=numpy.uint32)
+            c.check(L.shp_dspatial_merge_dev(c.handle, d_all, recSlot, comm.world, _lib.ptr(cnts), S, func,
+                                             _lib.ptr(params), int(missing), nInt, nFloat, idLo, idHi, d_cols,
+                                             ctypes.byref(nIds)))
+        if comm.world > 1:
+            comm.allreduce_dev_i64(d_cols.value, colWords)
+        (ic, fc) = (None, None)
+        if fetch:
+            ic = numpy.empty((nInt, ns), dtype=numpy.int64)
+            fc = numpy.empty((nFloat, ns), dtype=numpy.float32)
+        if fetch and nInt:
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(ic), d_cols, ic.nbytes))
+        if fetch and nFloat:
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(fc), ctypes.c_void_p(d_cols.value + nInt * 8 * ns), fc.nbytes))
+    finally:
+        for (p, sz) in toFree:
+            tiling._devRelease(c, p, sz)
+    tot = comm.allgather_obj((int(nIds.value), ha + hb))
     return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
 
 
@@ -918,6 +1135,14 @@ class HipEngine(object):
         return deviceStats(self.c, comm, self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut),
                            self._bandPtr(imgbandnum), _lib.SHP_DTYPES[self.ras.dtype], self.outHi - self.outLo,
                            self.nCols, hist, fast, nInt, nFloat, missing, imgNullVal)
+
+    def spatialOnDevice(self, comm, hist, imgbandnum, colTypes, userFunc, userParam, missing, imgNullVal):
+        """calcPerSegmentSpatialStatsDistributed's path for this rank's output rows (deviceSpatialStats)."""
+        held = self.ras is not None and self.outHi > self.outLo
+        d_out = (self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut)) if held else 0
+        return deviceSpatialStats(self.c, comm, d_out, self._bandPtr(imgbandnum) if held else 0,
+                                  _lib.SHP_DTYPES[self.ras.dtype] if self.ras is not None else -1, None, self.nCols,
+                                  (self.outLo, self.outHi), hist, colTypes, userFunc, userParam, missing, imgNullVal)
 
     def localOutput(self):
         out = numpy.empty((self.outHi - self.outLo, self.nCols), dtype=numpy.uint32)
