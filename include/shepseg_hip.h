@@ -380,7 +380,8 @@ int shp_subset_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t img_rows,
  * insists on a nodata value, :1325-1333).  nint / nflt = number of integer / real columns of
  * colNamesAndTypes; intcols_out: nint x (max_seg_id+1) int64, floatcols_out: nflt x
  * (max_seg_id+1) float32; entries the function does not set, and segments without a valid pixel,
- * hold `missing`; row 0 is zero.  Arbitrary njit callbacks are not supported. */
+ * hold `missing`; row 0 is zero.  A user-defined function (tilingstats.spatialUserFunc) runs on the host
+ * over the point lists of shp_segpoints_build / shp_segpoints_emit (tilingstats.calcPerSegmentSpatialStats). */
 int shp_spatialstats(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows,
                      int64_t ncols, uint32_t max_seg_id, int64_t null_val, int func,
                      const double *params, int64_t missing, int nint, int nflt,
@@ -390,6 +391,32 @@ int shp_spatialstats_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band
                          int64_t nrows, int64_t ncols, uint32_t max_seg_id, int64_t null_val,
                          int func, const double *params, int64_t missing, int nint, int nflt,
                          int64_t *intcols_out, float *floatcols_out);
+
+/* Per-segment point lists for user-defined spatial functions: replace accumulateSegSpatial
+ * (tilingstats.py:1652-1699) and the segment-completion bookkeeping of calcPerSegmentSpatialStatsTiled
+ * (:1262-1390, :1703-1741).  A point is a pixel whose label is in 1..max_seg_id and whose band value differs
+ * from null_val; a segment's points come in the reference's visit order: tile_size x tile_size tiles in
+ * row-major order, pixels row-major inside a tile (the result is a stable sort of all points by id in that order).
+ *  shp_segpoints_count: counts_out (max_seg_id + 1 uint32) = points per id (0 for id 0).
+ *  shp_segpoints_build: sorts the points of the whole raster by id; *npts_out = their number.  The result stays
+ *    in the context's workspace for shp_segpoints_emit, which must be the context's next calls; the _dev variant
+ *    reads the band from d_band then, so it must stay in place.
+ *  shp_segpoints_emit: the points of ids [id_lo, id_hi) (id_hi <= max_seg_id + 1): offs_out (id_hi - id_lo + 1
+ *    int64) = where each id's points start, relative to the first, and pts_out = *npts_out records of 16 bytes,
+ *    {uint32 x (column); uint32 y (row); int64 val} (the reference's SegPoint, :1225-1240, with val as
+ *    numbaTypeForImageType).  More points than cap: SHP_ERR_ARG, *npts_out says how many.
+ * The raster must hold fewer than 2^32 pixels. */
+int shp_segpoints_count(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows,
+                        int64_t ncols, uint32_t max_seg_id, int64_t null_val, uint32_t *counts_out);
+int shp_segpoints_count_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                            int64_t ncols, uint32_t max_seg_id, int64_t null_val, uint32_t *counts_out);
+int shp_segpoints_build(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows,
+                        int64_t ncols, uint32_t max_seg_id, int64_t null_val, int64_t tile_size, int64_t *npts_out);
+int shp_segpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                            int64_t ncols, uint32_t max_seg_id, int64_t null_val, int64_t tile_size,
+                            int64_t *npts_out);
+int shp_segpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *offs_out, void *pts_out, int64_t cap,
+                       int64_t *npts_out);
 
 /* The spatial statistics split by rows over the ranks (the data path of
  * distributed.calcPerSegmentSpatialStatsDistributed), modelled on shp_dstats_local_dev / _merge_dev.

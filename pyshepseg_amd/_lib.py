@@ -132,6 +132,16 @@ _SIGS = {
     'shp_spatialstats_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32,
                                         _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int,
                                         _vp, _vp]),
+    'shp_segpoints_count': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int64,
+                                       _vp]),
+    'shp_segpoints_count_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32,
+                                           _c.c_int64, _vp]),
+    'shp_segpoints_build': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int64,
+                                       _c.c_int64, _c.POINTER(_c.c_int64)]),
+    'shp_segpoints_build_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32,
+                                           _c.c_int64, _c.c_int64, _c.POINTER(_c.c_int64)]),
+    'shp_segpoints_emit': (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_int64,
+                                      _c.POINTER(_c.c_int64)]),
     'shp_comm_unique_id': (_c.c_int, [_vp]),
     'shp_comm_create': (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp, _c.POINTER(_vp)]),
     'shp_comm_destroy': (None, [_vp]),

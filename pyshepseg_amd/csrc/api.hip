@@ -14,6 +14,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "segstats.h"
 #include "subset.h"
 #include "spatial.h"
+#include "segpoints.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -94,7 +95,8 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->pix, &ctx->segsz, &ctx->origsz, &ctx->off, &ctx->ssum, &ctx->chnext,
                  &ctx->chtail, &ctx->mergeto, &ctx->tcount, &ctx->toff, &ctx->tfill, &ctx->tlist,
                  &ctx->tsorted, &ctx->small, &ctx->cen, &ctx->fit_x, &ctx->fit_lab, &ctx->fit_part, &ctx->fit_lb,
-                 &ctx->big, &ctx->srclist, &ctx->tgtlist, &ctx->bigbits, &ctx->singles, &ctx->dbg, &ctx->snap};
+                 &ctx->big, &ctx->srclist, &ctx->tgtlist, &ctx->bigbits, &ctx->singles, &ctx->dbg, &ctx->snap,
+                 &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage};
     *out = ctx;
     return SHP_OK;
 }
@@ -134,6 +136,7 @@ static int enter(shp_ctx *ctx)
 {
     if (!ctx) return SHP_ERR_ARG;
     ctx->err.clear();
+    ctx->pts.valid = false;             // (shp_segpoints_emit keeps it)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (ctx->prof_used) {                       // events of an earlier (synchronised) call
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1274,6 +1277,92 @@ API int shp_spatialstats(shp_ctx *ctx, const uint32_t *seg, const void *band, in
     return run_spatialstats(ctx, bp<uint32_t>(ctx->seg), ctx->img.p, dtype, (uint32_t)nrows, (uint32_t)ncols,
                             max_seg_id, null_val, func, params, missing, nint, nflt, intcols_out,
                             floatcols_out);
+}
+
+// ---- per-segment point lists for user-defined spatial statistics (segpoints.h) -----------------------------
+static int pts_check(shp_ctx *ctx, const void *seg, const void *band, int dtype, int64_t nrows, int64_t ncols,
+                     uint32_t max_seg_id)
+{
+    if (!seg || !band) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (dtype_size(dtype) == 0 || nrows < 0 || ncols < 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if ((uint64_t)nrows * (uint64_t)ncols >= 0xffffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "raster too large");
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    return 0;
+}
+
+// the two rasters into the context's workspace
+static int pts_upload(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows, int64_t ncols)
+{
+    const size_t npix = (size_t)nrows * (size_t)ncols;
+    CHK(buf_ensure(ctx, ctx->seg, npix * 4));
+    CHK(buf_ensure(ctx, ctx->img, npix * dtype_size(dtype)));
+    if (npix) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->seg.p, seg, npix * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->img.p, band, npix * dtype_size(dtype), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return 0;
+}
+
+API int shp_segpoints_count_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                                int64_t ncols, uint32_t max_seg_id, int64_t null_val, uint32_t *counts_out)
+{
+    CHK(enter(ctx));
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(pts_check(ctx, d_seg, d_band, dtype, nrows, ncols, max_seg_id));
+    return run_segpoints_count(ctx, d_seg, d_band, dtype, (uint32_t)nrows, (uint32_t)ncols, max_seg_id, null_val,
+                               counts_out);
+}
+
+API int shp_segpoints_count(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows,
+                            int64_t ncols, uint32_t max_seg_id, int64_t null_val, uint32_t *counts_out)
+{
+    CHK(enter(ctx));
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(pts_check(ctx, seg, band, dtype, nrows, ncols, max_seg_id));
+    CHK(pts_upload(ctx, seg, band, dtype, nrows, ncols));
+    return run_segpoints_count(ctx, bp<uint32_t>(ctx->seg), ctx->img.p, dtype, (uint32_t)nrows, (uint32_t)ncols,
+                               max_seg_id, null_val, counts_out);
+}
+
+API int shp_segpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                                int64_t ncols, uint32_t max_seg_id, int64_t null_val, int64_t tile_size,
+                                int64_t *npts_out)
+{
+    CHK(enter(ctx));
+    if (!npts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(pts_check(ctx, d_seg, d_band, dtype, nrows, ncols, max_seg_id));
+    if (tile_size < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "tile_size must be positive (got %lld)", (long long)tile_size);
+    const uint32_t ts = tile_size > 0xffffffffll ? 0xffffffffu : (uint32_t)tile_size;
+    return run_segpoints_build(ctx, d_seg, d_band, dtype, (uint32_t)nrows, (uint32_t)ncols, max_seg_id, null_val,
+                               ts, npts_out);
+}
+
+API int shp_segpoints_build(shp_ctx *ctx, const uint32_t *seg, const void *band, int dtype, int64_t nrows,
+                            int64_t ncols, uint32_t max_seg_id, int64_t null_val, int64_t tile_size,
+                            int64_t *npts_out)
+{
+    CHK(enter(ctx));
+    if (!npts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(pts_check(ctx, seg, band, dtype, nrows, ncols, max_seg_id));
+    if (tile_size < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "tile_size must be positive (got %lld)", (long long)tile_size);
+    const uint32_t ts = tile_size > 0xffffffffll ? 0xffffffffu : (uint32_t)tile_size;
+    CHK(pts_upload(ctx, seg, band, dtype, nrows, ncols));
+    return run_segpoints_build(ctx, bp<uint32_t>(ctx->seg), ctx->img.p, dtype, (uint32_t)nrows, (uint32_t)ncols,
+                               max_seg_id, null_val, ts, npts_out);
+}
+
+API int shp_segpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *offs_out, void *pts_out,
+                           int64_t cap, int64_t *npts_out)
+{
+    const bool built = ctx && ctx->pts.valid;
+    CHK(enter(ctx));
+    if (!offs_out || !npts_out || (cap > 0 && !pts_out) || cap < 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (!built) SHP_FAIL(ctx, SHP_ERR_STATE, "no point lists: shp_segpoints_build must be the context's previous call");
+    ctx->pts.valid = true;
+    if (id_lo > id_hi || (uint64_t)id_hi > (uint64_t)ctx->pts.S + 1u)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id range %u..%u outside 0..%llu", id_lo, id_hi,
+                 (unsigned long long)ctx->pts.S + 1ull);
+    return run_segpoints_emit(ctx, id_lo, id_hi, offs_out, pts_out, cap, npts_out);
 }
 
 // the multi-GPU split with everything left in device memory (spatial.h: run_dspatial_local / run_dspatial_merge)

@@ -23,7 +23,7 @@
 // pinned block) instead of by a copy command queued behind it -- under load every command on a
 // stream costs 40-80 us, and there were ten such copies per tile.
 #define PIN_MIRROR (SHP_PINNED_BYTES / 4u - 64u)
-enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5 };
+enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5, MIR_PTS = 8 };     // (MIR_PTS: 8 words, segpoints.h)
 #define MIRROR_STORE(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
 
 struct DevBuf {
@@ -33,6 +33,16 @@ struct DevBuf {
 
 struct StageTimer {
     hipEvent_t a = nullptr, b = nullptr;
+};
+
+// what shp_segpoints_build leaves for shp_segpoints_emit (segpoints.h); any other call of the context clears
+// `valid`, since it may reuse the workspace the sorted runs live in
+struct SegPointsState {
+    const uint32_t *skeys = nullptr, *order = nullptr, *roff = nullptr;
+    const void *band = nullptr;
+    int dtype = 0;
+    uint32_t ncols = 0, S = 0, m = 0, npts = 0;
+    bool valid = false;
 };
 
 struct shp_ctx {
@@ -46,7 +56,9 @@ struct shp_ctx {
     // named workspace buffers (grow-only)
     DevBuf img, clus, lab, seg, aux, aux2, stack, scan_tmp, sort_k0, sort_k1, sort_v1, sort_hist,
         pix, segsz, origsz, off, ssum, chnext, chtail, mergeto, tcount, toff, tfill, tlist, tsorted,
-        small, cen, fit_x, fit_lab, fit_part, fit_lb, big, srclist, tgtlist, bigbits, singles, dbg, snap;
+        small, cen, fit_x, fit_lab, fit_part, fit_lb, big, srclist, tgtlist, bigbits, singles, dbg, snap,
+        pts_runs, pts_off, pts_offs, pts_stage;
+    SegPointsState pts;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)
     int fit_path = 0;               // last k-means fit: 0 the fast (Lloyd) path, 1 the reference's Elkan path
     double *h_fit = nullptr;        // pinned, grow-only: the centred k-means sample

@@ -10,16 +10,27 @@ bit-identical for mean / stddev on the reference's golden vectors.
 
 Rasters: numpy arrays or ``.npy`` paths (GDAL optional, imported lazily).  Without GDAL the
 columns are returned in ``result.columns`` (name -> array indexed by segment id) instead of
-being written to the RAT.  Out of scope: the spatial statistics with user njit callbacks
-(tilingstats.py:1262-1390) and the RIOS variants.
+being written to the RAT.
+
+Spatial statistics (``calcPerSegmentSpatialStatsTiled``, tilingstats.py:1262-1390): the reference's
+three example user functions (``userFuncMeanCoord``, ``userFuncNumEdgePixels``,
+``userFuncVariogram``) are fixed reductions on the GPU.  Any other ``userFunc(pts, imgNullVal,
+intArr, floatArr, userParam)``, decorated with ``spatialUserFunc`` (the reference's @njit
+requirement; @jit / @njit functions pass as they are), is called on the host once per segment with
+that segment's points,
+which the GPU groups by segment in the reference's visit order (``iterSegmentPoints``); segments
+are called in ascending id order rather than in the reference's order of completion.  Out of
+scope: the RIOS variants.
 """
+import concurrent.futures
+import contextlib
 import ctypes
 
 import numpy
 
 from . import _lib
 from . import shepseg
-from .tiling import Timers
+from .tiling import Timers, TILESIZE
 
 STATID_MIN = 0
 STATID_MAX = 1
@@ -575,15 +586,37 @@ userFuncMeanCoord = _BuiltinSpatialFunc(0, 'userFuncMeanCoord')             # ti
 userFuncNumEdgePixels = _BuiltinSpatialFunc(1, 'userFuncNumEdgePixels')     # tilingstats.py:1146
 userFuncVariogram = _BuiltinSpatialFunc(2, 'userFuncVariogram')             # tilingstats.py:1037
 
+def spatialUserFunc(func):
+    """Decorator: marks a plain Python callable ``func(pts, imgNullVal, intArr, floatArr, userParam)``
+    as a spatial user function for calcPerSegmentSpatialStats(Tiled).  It stands where the
+    reference requires @jit / @njit (tilingstats.py:1330-1331: an undecorated callable is refused);
+    numba-decorated functions are accepted as they are.  Returns ``func`` itself, or a wrapper when
+    ``func`` takes no attributes."""
+    try:
+        func.shepsegSpatialUserFunc = True
+        return func
+    except AttributeError:
+        def wrapper(*args):
+            return func(*args)
+        wrapper.shepsegSpatialUserFunc = True
+        wrapper.__name__ = getattr(func, '__name__', 'userFunc')
+        return wrapper
 
-def calcPerSegmentSpatialStats(seg, band, colTypes, userFunc, userParam, imgNullVal,
-                               missingStatsValue=-9999, maxSegId=None):
-    """The compute step on arrays: colTypes = list of GFT_Integer / GFT_Real in column order.
-    Returns (intcols int64 (nInt, maxSegId+1), floatcols float32 (nFloat, maxSegId+1))."""
-    if not isinstance(userFunc, _BuiltinSpatialFunc):
-        raise PyShepSegStatsError(
-            "only the built-in user functions (userFuncMeanCoord, userFuncNumEdgePixels, "
-            "userFuncVariogram) are supported on the GPU")
+
+def _isUserFunc(userFunc):
+    """A callable marked by spatialUserFunc, or a numba dispatcher (the reference's own test)."""
+    return callable(userFunc) and (getattr(userFunc, 'shepsegSpatialUserFunc', False) is True or
+                                   'targetoptions' in getattr(userFunc, '__dict__', {}))
+
+
+# one point of a segment: the reference's SegPoint (tilingstats.py:1225-1240), column x and row y of the whole
+# image, val widened to numbaTypeForImageType (int64)
+SEGPOINT_DTYPE = numpy.dtype([('x', numpy.uint32), ('y', numpy.uint32), ('val', numpy.int64)])
+POINTS_BATCH = 1 << 24              # default points per batch of iterSegmentPoints (256 MiB of records)
+
+
+def _spatialArrays(seg, band):
+    """(seg uint32, band in a library dtype), both C-contiguous 2-D and of one shape."""
     seg = numpy.ascontiguousarray(seg, dtype=shepseg.SegIdType)
     band = numpy.ascontiguousarray(band)
     if band.dtype.kind == 'f':
@@ -593,12 +626,205 @@ def calcPerSegmentSpatialStats(seg, band, colTypes, userFunc, userParam, imgNull
         band = b3[0]
     if band.shape != seg.shape or seg.ndim != 2:
         raise PyShepSegStatsError("Images are different sizes")
+    return seg, band
+
+
+class _PinnedBuffer(object):
+    """Pinned host memory of a context.  Arrays over it keep it (and so the context) alive: it is freed when
+    the last of them goes, not when the generator that filled it ends."""
+    def __init__(self, c, nbytes):
+        self.c = c
+        self.p = ctypes.c_void_p()
+        c.check(c._L.shp_host_alloc(c.handle, nbytes, ctypes.byref(self.p)))
+
+    def points(self, n):
+        raw = (ctypes.c_uint8 * (n * SEGPOINT_DTYPE.itemsize)).from_address(self.p.value)
+        raw._owner = self
+        pts = numpy.frombuffer(raw, dtype=SEGPOINT_DTYPE).view(numpy.recarray)
+        pts.flags.writeable = False
+        return pts
+
+    def __del__(self):
+        if self.p.value and self.c.handle is not None:
+            self.c._L.shp_host_free(self.c.handle, self.p)
+            self.p = ctypes.c_void_p()
+
+
+def planPointBatches(counts, batchPoints, idLo=1, idHi=None):
+    """Split the ids [idLo, idHi) (idHi defaults to len(counts)) into consecutive ranges (lo, hi) whose
+    points (counts[id] each) add up to at most batchPoints.  A segment with more points than that gets a
+    range of its own.  Every id lies in exactly one range, the ranges in ascending order."""
+    counts = numpy.asarray(counts, dtype=numpy.int64)
+    if idHi is None:
+        idHi = len(counts)
+    batchPoints = max(1, int(batchPoints))
+    cum = numpy.zeros(max(idHi - idLo, 0) + 1, dtype=numpy.int64)
+    numpy.cumsum(counts[idLo:idHi], out=cum[1:])
+    ranges = []
+    start = 0
+    nIds = len(cum) - 1
+    while start < nIds:
+        # the last end whose batch [start, end) keeps within the budget (ids without points ride along)
+        end = int(numpy.searchsorted(cum, cum[start] + batchPoints, side='right')) - 1
+        if end <= start:
+            end = start + 1                     # one segment larger than the budget
+        ranges.append((idLo + start, idLo + end))
+        start = end
+    return ranges
+
+
+def iterSegmentPoints(seg, band, imgNullVal, tileSize=TILESIZE, maxSegId=None, batchPoints=None):
+    """
+    Every segment's points, batch by batch: yields (ids, offsets, pts) for consecutive id ranges,
+    ascending from 1 to maxSegId (default: the largest label).  The points of ids[k] are
+    pts[offsets[k]:offsets[k + 1]]; an id without points has an empty slice.  ``pts`` is a read-only
+    numpy.recarray of SEGPOINT_DTYPE (fields x = column, y = row, val = band value as int64), so
+    ``pt.x`` and ``pts.x`` both work.
+
+    A point is a pixel whose label is not 0 and whose band value is not imgNullVal (None: every
+    labelled pixel).  A segment's points come in the order in which the reference's
+    accumulateSegSpatial appends them (tilingstats.py:1652-1699): the raster is visited in
+    tileSize x tileSize tiles, tiles in row-major order, pixels row-major inside a tile.
+
+    The GPU sorts the points once, then builds batch b + 1 into a second pinned host buffer while
+    the caller works on batch b: a batch's points are overwritten once the generator advances past
+    the next batch (copy what must outlive it).  Each batch holds at most ``batchPoints`` points (default POINTS_BATCH), except
+    that a segment with more points than that comes in a batch of its own.
+    """
+    (seg, band) = _spatialArrays(seg, band)
+    if maxSegId is None:
+        maxSegId = int(seg.max()) if seg.size else 0
+    maxSegId = int(maxSegId)
+    if batchPoints is None:
+        batchPoints = POINTS_BATCH
+    if int(tileSize) < 1:
+        raise PyShepSegStatsError("tileSize must be positive")
+    nullV = numpy.iinfo(numpy.int64).min if imgNullVal is None else int(imgNullVal)
+    dt = _lib.SHP_DTYPES[band.dtype]
+    (nrows, ncols) = seg.shape
+    c = _lib.Context()              # its own context: the sorted points live in its workspace between calls
+    L = c._L
+    devBufs = []
+    hostBufs = []                   # (the context goes with the generator or with the last batch, later)
+
+    def devAlloc(nbytes):
+        p = ctypes.c_void_p()
+        c.check(L.shp_dev_alloc(c.handle, nbytes, ctypes.byref(p)))
+        devBufs.append(p)
+        return p
+
+    try:
+        dseg = devAlloc(seg.nbytes)
+        dband = devAlloc(band.nbytes)
+        c.check(L.shp_dev_upload(c.handle, dseg, _lib.ptr(seg), seg.nbytes))
+        c.check(L.shp_dev_upload(c.handle, dband, _lib.ptr(band), band.nbytes))
+        counts = numpy.zeros(maxSegId + 1, dtype=numpy.uint32)
+        c.check(L.shp_segpoints_count_dev(c.handle, dseg, dband, dt, nrows, ncols, maxSegId, nullV,
+                                          _lib.ptr(counts)))
+        batches = planPointBatches(counts, batchPoints)
+        cum = numpy.concatenate([[0], numpy.cumsum(counts, dtype=numpy.int64)])
+        cap = max([int(cum[hi] - cum[lo]) for (lo, hi) in batches] + [1])
+        hostBufs = [_PinnedBuffer(c, cap * SEGPOINT_DTYPE.itemsize) for _k in range(min(2, len(batches)))]
+        npts = ctypes.c_int64(0)
+        c.check(L.shp_segpoints_build_dev(c.handle, dseg, dband, dt, nrows, ncols, maxSegId, nullV,
+                                          int(tileSize), ctypes.byref(npts)))
+        if npts.value != int(cum[-1]):
+            raise PyShepSegStatsError("internal: %d points sorted, %d counted" % (npts.value, int(cum[-1])))
+
+        def emit(b):
+            (lo, hi) = batches[b]
+            offs = numpy.empty(hi - lo + 1, dtype=numpy.int64)
+            n = ctypes.c_int64(0)
+            c.check(L.shp_segpoints_emit(c.handle, lo, hi, _lib.ptr(offs), hostBufs[b % 2].p, cap,
+                                         ctypes.byref(n)))
+            return (offs, n.value)
+
+        with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
+            nxt = pool.submit(emit, 0) if batches else None
+            for b in range(len(batches)):
+                (offs, n) = nxt.result()
+                nxt = pool.submit(emit, b + 1) if b + 1 < len(batches) else None
+                pts = hostBufs[b % 2].points(n)
+                offs.flags.writeable = False
+                (lo, hi) = batches[b]
+                yield (numpy.arange(lo, hi, dtype=shepseg.SegIdType), offs, pts)
+            # (leaving the block waits for an emission still running: its buffer is freed below)
+    finally:
+        for p in devBufs:
+            L.shp_dev_free(c.handle, p)
+
+
+def convertPtsInto2DArray(pts, imgNullVal):
+    """A segment's points (a recarray of SEGPOINT_DTYPE, or anything with x, y and val fields) as an
+    int64 array over their bounding box: each point's value at (y - ymin, x - xmin), imgNullVal
+    elsewhere (reference tilingstats.py:1744-1793)."""
+    (x, y) = (numpy.asarray(pts.x, dtype=numpy.int64), numpy.asarray(pts.y, dtype=numpy.int64))
+    (xmin, ymin) = (x.min(), y.min())
+    tile = numpy.full((y.max() - ymin + 1, x.max() - xmin + 1), imgNullVal, dtype=numpy.int64)
+    tile[y - ymin, x - xmin] = pts.val
+    return tile
+
+
+def convertPtsInto2DMaskArray(pts, imgNullVal):
+    """As convertPtsInto2DArray, with uint8 1 at the segment's points and 0 elsewhere (reference
+    tilingstats.py:1796-1844; imgNullVal is not used, as there)."""
+    (x, y) = (numpy.asarray(pts.x, dtype=numpy.int64), numpy.asarray(pts.y, dtype=numpy.int64))
+    (xmin, ymin) = (x.min(), y.min())
+    tile = numpy.zeros((y.max() - ymin + 1, x.max() - xmin + 1), dtype=numpy.uint8)
+    tile[y - ymin, x - xmin] = 1
+    return tile
+
+
+def runUserFunc(batches, numRows, userFunc, userParam, imgNullVal, numIntCols, numFloatCols,
+                missingStatsValue=-9999):
+    """The per-segment calls of calcStatsForCompletedSegsSpatial (reference tilingstats.py:1847-1932)
+    over (ids, offsets, pts) batches as iterSegmentPoints yields them: for every id with points,
+    intArr (int32, numIntCols) and floatArr (float64, numFloatCols) are filled with
+    missingStatsValue, ``userFunc(pts, imgNullVal, intArr, floatArr, userParam)`` is called, and the
+    arrays become the id's row of intcols (int64) and floatcols (float32).  Ids without points (all
+    nodata, or no pixels at all) keep missingStatsValue; row 0 is zero.  Returns (intcols
+    (numIntCols, numRows), floatcols (numFloatCols, numRows)).  An exception of userFunc propagates."""
+    intcols = numpy.full((numIntCols, numRows), missingStatsValue, dtype=numpy.int64)
+    floatcols = numpy.full((numFloatCols, numRows), missingStatsValue, dtype=numpy.float32)
+    if numRows:
+        intcols[:, 0] = 0
+        floatcols[:, 0] = 0
+    intArr = numpy.empty(numIntCols, dtype=numpy.int32)
+    floatArr = numpy.empty(numFloatCols, dtype=numpy.float64)
+    for (ids, offs, pts) in batches:
+        for k in numpy.flatnonzero(offs[1:] != offs[:-1]):
+            intArr.fill(missingStatsValue)
+            floatArr.fill(missingStatsValue)
+            userFunc(pts[offs[k]:offs[k + 1]], imgNullVal, intArr, floatArr, userParam)
+            segId = ids[k]
+            intcols[:, segId] = intArr
+            floatcols[:, segId] = floatArr
+    return intcols, floatcols
+
+
+def calcPerSegmentSpatialStats(seg, band, colTypes, userFunc, userParam, imgNullVal,
+                               missingStatsValue=-9999, maxSegId=None, tileSize=TILESIZE):
+    """The compute step on arrays: colTypes = list of GFT_Integer / GFT_Real in column order.
+    Returns (intcols int64 (nInt, maxSegId+1), floatcols float32 (nFloat, maxSegId+1)).  The
+    built-in user functions run on the GPU; a user function (decorated with spatialUserFunc, or
+    @jit / @njit) is called per segment with the points of iterSegmentPoints(seg, band, imgNullVal,
+    tileSize) (see runUserFunc).  Any other userFunc is refused."""
+    (seg, band) = _spatialArrays(seg, band)
     if maxSegId is None:
         maxSegId = int(seg.max()) if seg.size else 0
     nInt = sum(1 for t in colTypes if t == GFT_Integer)
     nFloat = sum(1 for t in colTypes if t == GFT_Real)
     if nInt + nFloat != len(colTypes):
         raise PyShepSegStatsError("column types must be GFT_Integer or GFT_Real")
+    if not isinstance(userFunc, _BuiltinSpatialFunc):
+        if not _isUserFunc(userFunc):
+            raise PyShepSegStatsError(
+                "userFunc must be one of the built-in user functions (userFuncMeanCoord, "
+                "userFuncNumEdgePixels, userFuncVariogram), or a function decorated with "
+                "tilingstats.spatialUserFunc (or @jit / @njit)")
+        with contextlib.closing(iterSegmentPoints(seg, band, imgNullVal, tileSize, maxSegId)) as batches:
+            return runUserFunc(batches, maxSegId + 1, userFunc, userParam, imgNullVal, nInt, nFloat,
+                               missingStatsValue)
     params = numpy.zeros(6, dtype=numpy.float64)
     pv = numpy.atleast_1d(numpy.asarray(0 if userParam is None else userParam, dtype=numpy.float64))
     params[:min(len(pv), 6)] = pv[:6]
@@ -613,17 +839,29 @@ def calcPerSegmentSpatialStats(seg, band, colTypes, userFunc, userParam, imgNull
 
 
 def calcPerSegmentSpatialStatsTiled(imgfile, imgbandnum, segfile, colNamesAndTypes, userFunc,
-        userParam=None, missingStatsValue=-9999, imgNullVal=None):
+        userParam=None, missingStatsValue=-9999, imgNullVal=None, tileSize=TILESIZE):
     """
-    Spatial per-segment statistics (reference tilingstats.py:1262-1390) for the reference's
-    built-in user functions: pass this module's ``userFuncMeanCoord`` (userParam = the six
-    geotransform numbers; two Real columns), ``userFuncNumEdgePixels`` (userParam =
-    fourConnected; one Integer column) or ``userFuncVariogram`` (userParam = maxDist; maxDist Real
-    columns).  ``colNamesAndTypes`` is the reference's list of (name, GFT_Integer | GFT_Real); the
-    order of the integer / real columns is the order of the function's intArr / floatArr.
+    Spatial per-segment statistics (reference tilingstats.py:1262-1390).  ``userFunc`` is a
+    callable ``userFunc(pts, imgNullVal, intArr, floatArr, userParam)`` decorated with
+    ``spatialUserFunc`` (where the reference requires @jit / @njit, which is accepted too; an
+    undecorated callable is refused, as in the reference), called once for every
+    segment with at least one non-nodata pixel: ``pts`` holds those pixels as points with fields
+    x, y (column and row in the whole image) and val, in the reference's order (tileSize x tileSize
+    tiles row-major, pixels row-major inside a tile); ``intArr`` (int32) and ``floatArr``
+    (float64), one entry per Integer / Real column in the order of ``colNamesAndTypes``, arrive
+    filled with missingStatsValue and are stored as int64 / float32 columns.  Unlike the reference,
+    which calls the function as segments complete, segments are called in ascending id order.
+    ``convertPtsInto2DArray`` / ``convertPtsInto2DMaskArray`` give a segment's bounding-box tile.
+
+    This module's ``userFuncMeanCoord`` (userParam = the six geotransform numbers; two Real
+    columns), ``userFuncNumEdgePixels`` (userParam = fourConnected; one Integer column) and
+    ``userFuncVariogram`` (userParam = maxDist; maxDist Real columns) stand for the reference's
+    examples and run as reductions on the GPU (their mean coordinates do not depend on tileSize).
+    ``colNamesAndTypes`` is the reference's list of (name, GFT_Integer | GFT_Real).
     ``imgNullVal`` stands for the image band's nodata value, which must be set (the reference
-    raises the same error, tilingstats.py:1325-1333).  Arbitrary njit callbacks are not supported.
-    Returns a TiledStatsResult whose ``columns`` maps column name -> array (one row per id).
+    raises the same error, tilingstats.py:1325-1333).  Segments whose pixels are all nodata, and
+    ids without pixels, get missingStatsValue; row 0 is zero.  Returns a TiledStatsResult whose
+    ``columns`` maps column name -> array (one row per id).
     """
     timings = Timers()
     if imgNullVal is None:
@@ -638,7 +876,7 @@ def calcPerSegmentSpatialStatsTiled(imgfile, imgbandnum, segfile, colNamesAndTyp
     with timings.interval('accumulation'):
         (intcols, floatcols) = calcPerSegmentSpatialStats(
             seg, img, [t for (_n, t) in colNamesAndTypes], userFunc, userParam, imgNullVal,
-            missingStatsValue)
+            missingStatsValue, tileSize=tileSize)
     cols = {}
     ni = nf = 0
     for (name, t) in colNamesAndTypes:
