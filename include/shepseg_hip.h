@@ -132,16 +132,19 @@ int shp_make_seg_size(shp_ctx *ctx, const uint32_t *seg, int64_t npix, uint32_t 
                       uint32_t *seg_size_out);
 
 /* replaces shepseg.eliminateSinglePixels (shepseg.py:572-615): seg relabelled in place;
- * max_seg_id_inout: in = largest id in seg, out = seg.max() after the relabel. */
+ * max_seg_id_inout: in = largest id in seg, out = seg.max() after the relabel (when an id
+ * >= min_seg_id survives).  min_seg_id >= 1: relabelSegments keeps the ids up to it and closes
+ * the gaps above it (shepseg.py:766-769). */
 int shp_eliminate_single(shp_ctx *ctx, const void *img, int dtype, int nbands, int nrows,
                          int ncols, int four_connected, uint32_t *seg_inout,
-                         uint32_t *max_seg_id_inout);
+                         uint32_t *max_seg_id_inout, uint32_t min_seg_id);
 
-/* replaces shepseg.eliminateSmallSegments (shepseg.py:918-1000) */
+/* replaces shepseg.eliminateSmallSegments (shepseg.py:918-1000); min_seg_id >= 1: segments with
+ * smaller ids are never eliminated (segIdRange, shepseg.py:964), and the relabel is as above */
 int shp_eliminate_small(shp_ctx *ctx, const void *img, int dtype, int nbands, int nrows,
                         int ncols, int four_connected, int min_seg_size,
                         double max_spectral_diff, uint32_t *seg_inout,
-                        uint32_t *max_seg_id_inout, int64_t *num_elim_out);
+                        uint32_t *max_seg_id_inout, int64_t *num_elim_out, uint32_t min_seg_id);
 
 /* replaces shepseg.doShepherdSegmentation with a supplied k-means model
  * (shepseg.py:130-249, stages :206 :212 :219 :225 :235), fused on the device. */

@@ -54,10 +54,10 @@ _SIGS = {
                              _c.POINTER(_c.c_uint32)]),
     'shp_make_seg_size': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_uint32, _vp]),
     'shp_eliminate_single': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
-                                        _c.c_int, _vp, _c.POINTER(_c.c_uint32)]),
+                                        _c.c_int, _vp, _c.POINTER(_c.c_uint32), _c.c_uint32]),
     'shp_eliminate_small': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                        _c.c_int, _c.c_double, _vp, _c.POINTER(_c.c_uint32),
-                                       _c.POINTER(_c.c_int64)]),
+                                       _c.POINTER(_c.c_int64), _c.c_uint32]),
     'shp_segment_locations': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int, _c.c_uint32, _vp, _vp]),
     'shp_build_segment_spectra': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                              _c.c_uint32, _vp]),

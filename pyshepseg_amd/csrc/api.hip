@@ -330,11 +330,12 @@ static int check_seg_ids(shp_ctx *ctx, const uint32_t *seg, uint32_t n, uint32_t
 
 API int shp_eliminate_single(shp_ctx *ctx, const void *img, int dtype, int nbands, int nrows,
                              int ncols, int four_connected, uint32_t *seg_inout,
-                             uint32_t *max_seg_id_inout)
+                             uint32_t *max_seg_id_inout, uint32_t min_seg_id)
 {
     CHK(enter(ctx));
     CHK(check_img_args(ctx, img, dtype, nbands, nrows, ncols));
     if (!seg_inout || !max_seg_id_inout) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (min_seg_id < 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "min_seg_id must be >= 1");
     const uint32_t n = (uint32_t)nrows * (uint32_t)ncols;
     if (n == 0) return 0;
     CHK(check_seg_ids(ctx, seg_inout, n, *max_seg_id_inout));
@@ -342,7 +343,7 @@ API int shp_eliminate_single(shp_ctx *ctx, const void *img, int dtype, int nband
     CHK(buf_ensure(ctx, ctx->seg, (size_t)n * 4));
     HIPCHK(ctx, hipMemcpyAsync(ctx->seg.p, seg_inout, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     CHK(run_eliminate_single(ctx, ctx->img.p, dtype, nbands, nrows, ncols, four_connected,
-                             bp<uint32_t>(ctx->seg), max_seg_id_inout));
+                             bp<uint32_t>(ctx->seg), max_seg_id_inout, 0, 0, 0, nullptr, min_seg_id));
     HIPCHK(ctx, hipMemcpyAsync(seg_inout, ctx->seg.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
@@ -351,11 +352,12 @@ API int shp_eliminate_single(shp_ctx *ctx, const void *img, int dtype, int nband
 API int shp_eliminate_small(shp_ctx *ctx, const void *img, int dtype, int nbands, int nrows,
                             int ncols, int four_connected, int min_seg_size,
                             double max_spectral_diff, uint32_t *seg_inout,
-                            uint32_t *max_seg_id_inout, int64_t *num_elim_out)
+                            uint32_t *max_seg_id_inout, int64_t *num_elim_out, uint32_t min_seg_id)
 {
     CHK(enter(ctx));
     CHK(check_img_args(ctx, img, dtype, nbands, nrows, ncols));
     if (!seg_inout || !max_seg_id_inout) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (min_seg_id < 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "min_seg_id must be >= 1");
     const uint32_t n = (uint32_t)nrows * (uint32_t)ncols;
     if (num_elim_out) *num_elim_out = 0;
     if (n == 0) return 0;
@@ -366,7 +368,7 @@ API int shp_eliminate_small(shp_ctx *ctx, const void *img, int dtype, int nbands
     int64_t ne = 0;
     CHK(run_eliminate_small(ctx, ctx->img.p, dtype, nbands, nrows, ncols, four_connected,
                             min_seg_size, max_spectral_diff, bp<uint32_t>(ctx->seg),
-                            max_seg_id_inout, &ne));
+                            max_seg_id_inout, &ne, 0, nullptr, min_seg_id));
     if (num_elim_out) *num_elim_out = ne;
     HIPCHK(ctx, hipMemcpyAsync(seg_inout, ctx->seg.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

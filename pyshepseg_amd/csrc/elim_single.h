@@ -232,18 +232,20 @@ __global__ __launch_bounds__(1024) void k_single_tail(
     }
 }
 
-// relabelSegments (shepseg.py:739-777): newid[k] = k - #{1 <= j < k : segsz[j] == 0}
-struct EmptyFn {      // f(i) = 1 if id i (>= 1) is unused; f(0) = 0
+// relabelSegments (shepseg.py:739-777): newid[k] = k - #{minSegId <= j < k : segsz[j] == 0}
+// (ids up to minSegId keep their number)
+struct EmptyFn {      // f(i) = 1 if id i (>= min_id) is unused; f(i) = 0 below min_id
     const uint32_t *segsz;
+    uint32_t min_id;
     __device__ __forceinline__ uint32_t operator()(uint32_t i) const
     {
-        return (i >= 1u && segsz[i] == 0u) ? 1u : 0u;
+        return (i >= min_id && segsz[i] == 0u) ? 1u : 0u;
     }
     __device__ __forceinline__ bool get4(uint32_t base, uint32_t v[4]) const
     {
         if (!scan_load4(segsz, base, v)) return false;
 #pragma unroll
-        for (uint32_t i = 0; i < 4u; i++) v[i] = (base + i >= 1u && v[i] == 0u) ? 1u : 0u;
+        for (uint32_t i = 0; i < 4u; i++) v[i] = (base + i >= min_id && v[i] == 0u) ? 1u : 0u;
         return true;
     }
 };
@@ -309,17 +311,19 @@ __global__ __launch_bounds__(256) void k_relabel4(uint32_t *__restrict__ seg,
     }
 }
 
-// Compacts ids in d_seg given segsz[0..max_id].  *new_max_host = max_id - (#unused ids >= 1)
-// which equals seg.max() after the relabel (0 when every pixel is null).
+// Compacts ids in d_seg given segsz[0..max_id].  *new_max_host = max_id - (#unused ids >= min_id)
+// which equals seg.max() after the relabel (0 when every pixel is null) when an id >= min_id survives.
+// min_id >= 1 (the reference's minSegId); d_sizes_out only with min_id 1.
 static int run_relabel(shp_ctx *ctx, uint32_t *d_seg, uint32_t n, const uint32_t *d_segsz,
-                       uint32_t max_id, uint32_t *new_max_host, uint32_t *d_sizes_out = nullptr)
+                       uint32_t max_id, uint32_t *new_max_host, uint32_t *d_sizes_out = nullptr,
+                       uint32_t min_id = 1u)
 {
     const uint32_t ns = max_id + 1u;
     CHK(buf_ensure(ctx, ctx->toff, (size_t)ns * 4 + 16));
     CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
     uint32_t *sub = bp<uint32_t>(ctx->toff);
     uint32_t *tot = sub + ns;
-    EmptyFn f{d_segsz};
+    EmptyFn f{d_segsz, min_id};
     const uint32_t *boff = nullptr;
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_RELABEL;        // the scan stores its total there
     CHK(scan_exclusive(ctx, f, ns, sub, tot, bp<uint32_t>(ctx->scan_tmp), &boff, mir));
@@ -359,7 +363,7 @@ static int run_seg_size(shp_ctx *ctx, const uint32_t *d_seg, uint32_t n, uint32_
 static int run_eliminate_single(shp_ctx *ctx, const void *d_img, int dtype, int nb, uint32_t nrows,
                                 uint32_t ncols, int four, uint32_t *d_seg, uint32_t *max_id,
                                 int sizes_ready = 0, int singles_ready = 0, uint32_t nsingles = 0,
-                                const ImgGeom *geom_in = nullptr)
+                                const ImgGeom *geom_in = nullptr, uint32_t min_id = 1u)
 {
     const uint32_t n = nrows * ncols;
     const ImgGeom geom = geom_in ? *geom_in : geom_compact(n, ncols);
@@ -415,7 +419,8 @@ static int run_eliminate_single(shp_ctx *ctx, const void *d_img, int dtype, int 
         merged = ctx->h_pinned[0];
     }
     uint32_t new_max = 0;
-    CHK(run_relabel(ctx, d_seg, n, segsz, *max_id, &new_max, bp<uint32_t>(ctx->origsz)));
+    CHK(run_relabel(ctx, d_seg, n, segsz, *max_id, &new_max, min_id == 1u ? bp<uint32_t>(ctx->origsz) : nullptr,
+                    min_id));
     *max_id = new_max;
     return 0;
 }

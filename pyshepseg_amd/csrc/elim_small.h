@@ -459,6 +459,7 @@ struct SmallArgs {
                         // the original segments' runs in pix[] (one 16-byte load per hop)
     uint32_t *mergeto, *tcount, *toff, *tfill, *tlist, *tsorted, *srclist, *tgtlist;
     uint32_t S, min_seg, nrows, ncols;
+    uint32_t min_id;    // the reference's minSegId: segments below it are never sources (shepseg.py:964)
     int nb, four;
     double thr2;
     int poll;           // s_sleep(8) repetitions between two polls of a grid barrier
@@ -1053,7 +1054,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
                 uint32_t nfound = 0;
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) {
-                    const bool ok = id[u] != 0u && szv[u] == target;
+                    const bool ok = id[u] >= a.min_id && id[u] != 0u && szv[u] == target;
                     const unsigned long long m = __ballot(ok);
                     if (ok) wids[w][nfound + (uint32_t)__popcll(m & lanemask_lt())] = id[u];
                     nfound += (uint32_t)__popcll(m);
@@ -1094,7 +1095,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const uint32_t sid = base + (uint32_t)u * stride + lane + 1u;
-                    sz[u] = sid <= a.S ? a.segsz[sid] : 0xFFFFFFFFu;
+                    sz[u] = sid <= a.S && sid >= a.min_id ? a.segsz[sid] : 0xFFFFFFFFu;
                 }
                 const uint32_t npairs = target * (a.four ? 4u : 8u);
                 uint32_t nfound = 0;                 // sources of these four slices, gathered in wids[w]
@@ -1303,7 +1304,7 @@ static const int g_small_max = getenv("SHEPSEG_SMALL_MAX") ? atoi(getenv("SHEPSE
 static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int nb, uint32_t nrows,
                                uint32_t ncols, int four, int min_seg_size, double max_spectral_diff,
                                uint32_t *d_seg, uint32_t *max_id, int64_t *num_elim,
-                               int sizes_in_origsz = 0, const ImgGeom *geom_in = nullptr)
+                               int sizes_in_origsz = 0, const ImgGeom *geom_in = nullptr, uint32_t min_id = 1u)
 {
     const uint32_t n = nrows * ncols;
     const ImgGeom geom = geom_in ? *geom_in : geom_compact(n, ncols);
@@ -1368,7 +1369,7 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
     args.pix = pix; args.off = off; args.origsz = origsz; args.ch = ch;
     args.mergeto = mergeto; args.tcount = tcount; args.toff = toff; args.tfill = tfill;
     args.tlist = tlist; args.tsorted = tsorted; args.srclist = srclist; args.tgtlist = tgtlist;
-    args.S = S; args.min_seg = min_seg; args.nrows = nrows; args.ncols = ncols;
+    args.S = S; args.min_seg = min_seg; args.nrows = nrows; args.ncols = ncols; args.min_id = min_id;
     args.nb = nb; args.four = four; args.thr2 = thr2;
     static const int poll_env = getenv("SHEPSEG_SMALL_POLL") ? atoi(getenv("SHEPSEG_SMALL_POLL")) : 4;
     args.poll = poll_env < 1 ? 1 : poll_env;
@@ -1437,7 +1438,7 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
     }
     *num_elim = (int64_t)pin->nelim;
     uint32_t new_max = 0;
-    CHK(run_relabel(ctx, d_seg, n, segsz, S, &new_max));
+    CHK(run_relabel(ctx, d_seg, n, segsz, S, &new_max, nullptr, min_id));
     *max_id = new_max;
     return 0;
 }

@@ -345,10 +345,18 @@ def makeSegSize(seg):
     return out
 
 
+def _check_min_seg_id(minSegId):
+    # the reference's minSegId 0 would make the null segment a merge source and renumber segment 1 as 0
+    if int(minSegId) < 1 or int(minSegId) > 0xFFFFFFFF:
+        raise ValueError("minSegId must lie in 1..2**32-1 (got %r)" % (minSegId,))
+
+
 def eliminateSinglePixels(img, seg, segSize, minSegId, maxSegId, fourConnected):
     """Merge single-pixel segments into their spectrally nearest neighbouring pixel's
     segment and relabel; seg is modified in place (reference shepseg.py:572-615).
-    segSize is recomputed on the device from seg (the reference's copy is stale on return)."""
+    segSize is recomputed on the device from seg (the reference's copy is stale on return).
+    The relabel keeps the ids up to minSegId and closes the gaps above it (shepseg.py:766-769)."""
+    _check_min_seg_id(minSegId)
     img_c, dt = _lib.as_image(img)
     (nBands, nRows, nCols) = img_c.shape
     if seg.dtype != SegIdType or not seg.flags.c_contiguous:
@@ -356,14 +364,17 @@ def eliminateSinglePixels(img, seg, segSize, minSegId, maxSegId, fourConnected):
     mx = ctypes.c_uint32(int(maxSegId))
     c = _lib.ctx()
     c.check(c._L.shp_eliminate_single(c.handle, _lib.ptr(img_c), dt, nBands, nRows, nCols,
-                                      int(bool(fourConnected)), _lib.ptr(seg), ctypes.byref(mx)))
+                                      int(bool(fourConnected)), _lib.ptr(seg), ctypes.byref(mx),
+                                      int(minSegId)))
 
 
 def eliminateSmallSegments(seg, img, maxSegId, minSegSize, maxSpectralDiff, fourConnected,
         minSegId):
     """Iteratively merge segments smaller than minSegSize into their spectrally closest
     larger neighbour; seg modified in place; returns the number eliminated
-    (reference shepseg.py:918-1000)."""
+    (reference shepseg.py:918-1000).  Segments with ids below minSegId are never eliminated
+    (segIdRange, shepseg.py:964); the relabel is eliminateSinglePixels'."""
+    _check_min_seg_id(minSegId)
     img_c, dt = _lib.as_image(img)
     (nBands, nRows, nCols) = img_c.shape
     if seg.dtype != SegIdType or not seg.flags.c_contiguous:
@@ -374,7 +385,7 @@ def eliminateSmallSegments(seg, img, maxSegId, minSegSize, maxSpectralDiff, four
     c.check(c._L.shp_eliminate_small(c.handle, _lib.ptr(img_c), dt, nBands, nRows, nCols,
                                      int(bool(fourConnected)), int(minSegSize),
                                      float(maxSpectralDiff), _lib.ptr(seg), ctypes.byref(mx),
-                                     ctypes.byref(ne)))
+                                     ctypes.byref(ne), int(minSegId)))
     return int(ne.value)
 
 

@@ -26,6 +26,21 @@ def test_library_exports_header_symbols():
     assert L.shp_version() >= 100
 
 
+def test_binding_argument_counts_match_header():
+    """_lib's ctypes signatures take as many arguments as the header's prototypes (shp_eliminate_single /
+    shp_eliminate_small take min_seg_id last)"""
+    from pyshepseg_amd import _lib
+    txt = open(os.path.join(ROOT, 'include', 'shepseg_hip.h')).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    protos = dict(re.findall(r'\b(shp_[a-z0-9_]+)\s*\(([^)]*)\)\s*;', txt))
+    for name, args in protos.items():
+        args = args.strip()
+        n = 0 if args in ('', 'void') else args.count(',') + 1
+        assert len(_lib._SIGS[name][1]) == n, name
+    assert protos['shp_eliminate_single'].split(',')[-1].split() == ['uint32_t', 'min_seg_id']
+    assert protos['shp_eliminate_small'].split(',')[-1].split() == ['uint32_t', 'min_seg_id']
+
+
 def test_no_cpu_fallback_without_gpu():
     from pyshepseg_amd import _lib, shepseg
     if _lib.lib().shp_device_count() > 0:

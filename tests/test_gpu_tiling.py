@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from seg_cases import oracle_tiled
 
 pytestmark = pytest.mark.gpu
 STITCH = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'stitch_*.npz')))
@@ -53,14 +54,7 @@ def test_golden_tiled(name, workers, golden):
     assert np.array_equal(r.hist, g['hist'])
 
 
-def _oracle_tiled(oracle, img, centres, tile, ov, minseg, msd, null, four, simple=False):
-    nr, nc = img.shape[1:]
-    tiles, ntc, ntr = oracle.get_tiles(nr, nc, tile, ov)
-    local = {}
-    for (c, r), (x, y, xs, ys) in tiles.items():
-        sub = np.ascontiguousarray(img[:, y:y + ys, x:x + xs])
-        local[(c, r)] = oracle.segment_tile(sub, centres, minseg, msd, null, four)['segimg']
-    return oracle.stitch_tiles(local, tiles, ntc, ntr, nr, nc, ov, simple=simple)
+_oracle_tiled = oracle_tiled
 
 
 @pytest.mark.parametrize('simple', [False, True])
