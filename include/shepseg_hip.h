@@ -421,6 +421,33 @@ int shp_segpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
 int shp_segpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *offs_out, void *pts_out, int64_t cap,
                        int64_t *npts_out);
 
+/* Per-segment point lists of row shards: the data path of distributed.deviceSpatialStats with a user function
+ * (calcPerSegmentSpatialStatsDistributed).  Replace, per rank, what shp_segpoints_build / _emit replace for one
+ * raster (accumulateSegSpatial, tilingstats.py:1652-1699, and the completion bookkeeping of
+ * calcPerSegmentSpatialStatsTiled, :1262-1390 / :1703-1741): every segment's points in the WHOLE raster's visit
+ * order (tile_size x tile_size tiles of the img_rows x ncols raster), although its rows lie on several ranks.
+ *  shp_dsegpoints_build_dev: this rank's rows [row0, row0 + nrows) in place (d_seg, d_band: nrows x ncols, fewer
+ *    than 2^32 pixels; the raster as a whole may hold more).  Sorts the rows' points by id in visit order and judges
+ *    every id against the GLOBAL label histogram d_hist: complete here (local label count == d_hist), straddler
+ *    (fewer) or absent.  lh_out / pts_out (max_seg_id + 1 uint32 each, host) = labelled pixels / points per id
+ *    here.  The straddlers' points are packed as *n_rec_out records of 24 bytes, {uint64 global visit index;
+ *    uint32 id; uint32 x; uint32 y; uint32 value bits}, in (id, visit index) order, at *d_rec_out in the context's
+ *    workspace (valid until its next call).
+ *  shp_dsegpoints_merge_dev: must be the context's next call.  After the all-gather of the records (`world` slots of
+ *    `slot`, counts[r] valid in slot r) the records of ids in [id_lo, id_hi) (this rank's share) are sorted stably
+ *    by (id, visit index); merged_out (id_hi - id_lo uint32, host) = records per id of the share.
+ *  shp_dsegpoints_emit: as shp_segpoints_emit, for the ids this rank answers for: ids complete here (their points
+ *    from the local rows) and straddlers of its share (from the merged records); every other id has no points.  The
+ *    context's next calls must be its emissions. */
+int shp_dsegpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                             int64_t ncols, int64_t row0, int64_t img_rows, uint32_t max_seg_id, int64_t null_val,
+                             int64_t tile_size, const uint32_t *d_hist, uint32_t *lh_out, uint32_t *pts_out,
+                             void **d_rec_out, int64_t *n_rec_out);
+int shp_dsegpoints_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, int world, const uint32_t *counts,
+                             uint32_t id_lo, uint32_t id_hi, uint32_t *merged_out, int64_t *n_merged_out);
+int shp_dsegpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *offs_out, void *pts_out, int64_t cap,
+                        int64_t *npts_out);
+
 /* The spatial statistics split by rows over the ranks (the data path of
  * distributed.calcPerSegmentSpatialStatsDistributed), modelled on shp_dstats_local_dev / _merge_dev.
  *  shp_dspatial_local_dev: this rank's rows [row0, row0 + nrows) of an img_rows-row raster in place (d_seg,

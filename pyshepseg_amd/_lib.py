@@ -142,6 +142,13 @@ _SIGS = {
                                            _c.c_int64, _c.c_int64, _c.POINTER(_c.c_int64)]),
     'shp_segpoints_emit': (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_int64,
                                       _c.POINTER(_c.c_int64)]),
+    'shp_dsegpoints_build_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                            _c.c_uint32, _c.c_int64, _c.c_int64, _vp, _vp, _vp, _c.POINTER(_vp),
+                                            _c.POINTER(_c.c_int64)]),
+    'shp_dsegpoints_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_uint32, _c.c_uint32, _vp,
+                                            _c.POINTER(_c.c_int64)]),
+    'shp_dsegpoints_emit': (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp, _c.c_int64,
+                                       _c.POINTER(_c.c_int64)]),
     'shp_comm_unique_id': (_c.c_int, [_vp]),
     'shp_comm_create': (_c.c_int, [_vp, _c.c_int, _c.c_int, _vp, _c.POINTER(_vp)]),
     'shp_comm_destroy': (None, [_vp]),

@@ -15,6 +15,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "subset.h"
 #include "spatial.h"
 #include "segpoints.h"
+#include "dsegpoints.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -96,7 +97,10 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->chtail, &ctx->mergeto, &ctx->tcount, &ctx->toff, &ctx->tfill, &ctx->tlist,
                  &ctx->tsorted, &ctx->small, &ctx->cen, &ctx->fit_x, &ctx->fit_lab, &ctx->fit_part, &ctx->fit_lb,
                  &ctx->big, &ctx->srclist, &ctx->tgtlist, &ctx->bigbits, &ctx->singles, &ctx->dbg, &ctx->snap,
-                 &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage};
+                 &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage,
+                 &ctx->dpts_lh, &ctx->dpts_cls, &ctx->dpts_spos, &ctx->dpts_rec, &ctx->dpts_moff, &ctx->dpts_eoff,
+                 &ctx->dpts_cnt, &ctx->dpts_kpos, &ctx->dpts_mrec, &ctx->dpts_key, &ctx->dpts_idx, &ctx->dpts_k0,
+                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix};
     *out = ctx;
     return SHP_OK;
 }
@@ -137,6 +141,7 @@ static int enter(shp_ctx *ctx)
     if (!ctx) return SHP_ERR_ARG;
     ctx->err.clear();
     ctx->pts.valid = false;             // (shp_segpoints_emit keeps it)
+    ctx->dpts.stage = 0;                // (shp_dsegpoints_merge_dev / _emit move it on)
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (ctx->prof_used) {                       // events of an earlier (synchronised) call
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1365,6 +1370,62 @@ API int shp_segpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t
         SHP_FAIL(ctx, SHP_ERR_ARG, "id range %u..%u outside 0..%llu", id_lo, id_hi,
                  (unsigned long long)ctx->pts.S + 1ull);
     return run_segpoints_emit(ctx, id_lo, id_hi, offs_out, pts_out, cap, npts_out);
+}
+
+// ---- the point lists of row shards (dsegpoints.h) ------------------------------------------------------------
+API int shp_dsegpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                                 int64_t ncols, int64_t row0, int64_t img_rows, uint32_t max_seg_id, int64_t null_val,
+                                 int64_t tile_size, const uint32_t *d_hist, uint32_t *lh_out, uint32_t *pts_out,
+                                 void **d_rec_out, int64_t *n_rec_out)
+{
+    CHK(enter(ctx));
+    if (!d_hist || !lh_out || !pts_out || !d_rec_out || !n_rec_out || dtype_size(dtype) == 0 || nrows < 0 ||
+        ncols < 0 || row0 < 0 || (nrows > 0 && (!d_seg || !d_band)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (tile_size < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "tile_size must be positive (got %lld)", (long long)tile_size);
+    if (row0 + nrows > img_rows || img_rows >= 0xffffffffll || ncols >= 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "rows %lld..%lld outside the image's %lld rows", (long long)row0,
+                 (long long)(row0 + nrows), (long long)img_rows);
+    // per rank: the own rows stay below 2^32 pixels, the whole raster need not
+    if ((uint64_t)nrows * (uint64_t)ncols >= 0xffffffffull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "shard too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    const uint32_t ts = tile_size > 0xffffffffll ? 0xffffffffu : (uint32_t)tile_size;
+    return run_dsegpoints_build(ctx, d_seg, d_band, dtype, (uint32_t)nrows, (uint32_t)ncols, (uint32_t)row0,
+                                (uint32_t)img_rows, max_seg_id, null_val, ts, d_hist, lh_out, pts_out, d_rec_out,
+                                n_rec_out);
+}
+
+API int shp_dsegpoints_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, int world, const uint32_t *counts,
+                                 uint32_t id_lo, uint32_t id_hi, uint32_t *merged_out, int64_t *n_merged_out)
+{
+    const int stage = ctx ? ctx->dpts.stage : 0;
+    CHK(enter(ctx));
+    if (!counts || !n_merged_out || slot < 0 || world < 1 || (slot > 0 && !d_recs) ||
+        (uint64_t)slot * (uint64_t)world >= 0xffffffffull || (id_hi > id_lo && !merged_out))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no local point lists: shp_dsegpoints_build_dev must come first");
+    ctx->dpts.stage = 1;
+    if (id_lo > id_hi || (uint64_t)id_hi > (uint64_t)ctx->pts.S + 1u)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %u..%u outside 0..%llu", id_lo, id_hi,
+                 (unsigned long long)ctx->pts.S + 1ull);
+    for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
+    return run_dsegpoints_merge(ctx, (const unsigned long long *)d_recs, (uint32_t)slot, (uint32_t)world, counts,
+                                id_lo, id_hi, merged_out, n_merged_out);
+}
+
+API int shp_dsegpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *offs_out, void *pts_out,
+                            int64_t cap, int64_t *npts_out)
+{
+    const int stage = ctx ? ctx->dpts.stage : 0;
+    CHK(enter(ctx));
+    if (!offs_out || !npts_out || (cap > 0 && !pts_out) || cap < 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no merged point lists: shp_dsegpoints_merge_dev must come first");
+    ctx->dpts.stage = 2;
+    if (id_lo > id_hi || (uint64_t)id_hi > (uint64_t)ctx->pts.S + 1u)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id range %u..%u outside 0..%llu", id_lo, id_hi,
+                 (unsigned long long)ctx->pts.S + 1ull);
+    return run_dsegpoints_emit(ctx, id_lo, id_hi, offs_out, pts_out, cap, npts_out);
 }
 
 // the multi-GPU split with everything left in device memory (spatial.h: run_dspatial_local / run_dspatial_merge)

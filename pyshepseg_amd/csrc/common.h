@@ -45,6 +45,14 @@ struct SegPointsState {
     bool valid = false;
 };
 
+// what shp_dsegpoints_build_dev leaves for shp_dsegpoints_merge_dev (stage 1), and that for
+// shp_dsegpoints_emit (stage 2) (dsegpoints.h); any other call of the context resets stage to 0
+struct DSegPointsState {
+    int stage = 0;
+    uint32_t row0 = 0, nrec = 0, npts_local = 0, id_lo = 0, id_hi = 0, nmerged = 0, npts_emit = 0;
+    unsigned long long max_visit = 0;       // largest visit index of the whole raster
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -57,8 +65,11 @@ struct shp_ctx {
     DevBuf img, clus, lab, seg, aux, aux2, stack, scan_tmp, sort_k0, sort_k1, sort_v1, sort_hist,
         pix, segsz, origsz, off, ssum, chnext, chtail, mergeto, tcount, toff, tfill, tlist, tsorted,
         small, cen, fit_x, fit_lab, fit_part, fit_lb, big, srclist, tgtlist, bigbits, singles, dbg, snap,
-        pts_runs, pts_off, pts_offs, pts_stage;
+        pts_runs, pts_off, pts_offs, pts_stage,
+        dpts_lh, dpts_cls, dpts_spos, dpts_rec, dpts_moff, dpts_eoff, dpts_cnt, dpts_kpos, dpts_mrec, dpts_key,
+        dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix;
     SegPointsState pts;
+    DSegPointsState dpts;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)
     int fit_path = 0;               // last k-means fit: 0 the fast (Lloyd) path, 1 the reference's Elkan path
     double *h_fit = nullptr;        // pinned, grow-only: the centred k-means sample

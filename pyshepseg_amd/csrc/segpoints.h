@@ -27,25 +27,38 @@
 #define PTS_TILE 4096u          // visit indices per workgroup: 4 wavefronts x 16 rows of 64
 #define PTS_ROWS 16u
 
+// The rows seg / band hold: nrows x ncols pixels, the whole raster or a slice of it (dsegpoints.h: a rank's rows
+// [row0, row0 + nrows) of a taller raster).  Tile rows (bands) are th rows of the WHOLE raster, so a slice's first
+// band may be cut short: it holds h0 rows (th for the whole raster), every later band th rows but the last.
 struct PtsGeom {
     const uint32_t *seg;
     const void *band;
     int dtype;
     uint32_t nrows, ncols, S;
-    uint32_t th, tw;            // tile height / width: min(tileSize, nrows), min(tileSize, ncols)
+    uint32_t th, tw;            // tile height / width: min(tileSize, raster rows), min(tileSize, ncols)
     long long null_val;
+    uint32_t h0;                // rows of the first band
 };
 
 // visit index i (< nrows * ncols) -> raster position; *row_start: i is the first pixel of a tile row.  Tile rows
-// (bands of th image rows) are visited one after the other; inside a band the tiles (all tw wide but the last),
-// inside a tile its rows.  Every earlier band is full, and so is every earlier tile of a band.
+// (bands of th image rows; the first of h0) are visited one after the other; inside a band the tiles (all tw wide
+// but the last), inside a tile its rows.  Every earlier band is full, and so is every earlier tile of a band.  The
+// order is the raster's visit order restricted to the rows held.
 __device__ __forceinline__ uint32_t pts_visit_pos(const PtsGeom &g, uint32_t i, bool *row_start)
 {
-    const uint32_t bandsz = g.th * g.ncols;
-    const uint32_t tr = i / bandsz;
-    uint32_t rem = i - tr * bandsz;
-    const uint32_t y0 = tr * g.th;
-    const uint32_t h = min(g.th, g.nrows - y0);
+    const uint32_t first = g.h0 * g.ncols;
+    uint32_t rem, y0, h;
+    if (i < first) {
+        rem = i;
+        y0 = 0u;
+        h = g.h0;
+    } else {
+        const uint32_t bandsz = g.th * g.ncols;
+        const uint32_t tr = (i - first) / bandsz;
+        rem = i - first - tr * bandsz;
+        y0 = g.h0 + tr * g.th;
+        h = min(g.th, g.nrows - y0);
+    }
     const uint32_t tilesz = h * g.tw;
     const uint32_t tc = rem / tilesz;
     rem -= tc * tilesz;
@@ -213,8 +226,21 @@ __global__ __launch_bounds__(256) void k_pts_expand(const uint32_t *__restrict__
 static inline PtsGeom pts_geom(const uint32_t *d_seg, const void *d_band, int dtype, uint32_t nrows, uint32_t ncols,
                                uint32_t S, int64_t null_val, uint32_t tile_size)
 {
-    return PtsGeom{d_seg, d_band, dtype, nrows, ncols, S, tile_size < nrows ? tile_size : nrows,
-                   tile_size < ncols ? tile_size : ncols, (long long)null_val};
+    const uint32_t th = tile_size < nrows ? tile_size : nrows;
+    return PtsGeom{d_seg, d_band, dtype, nrows, ncols, S, th, tile_size < ncols ? tile_size : ncols,
+                   (long long)null_val, th};
+}
+
+// rows [row0, row0 + nrows) of an img_rows-row raster: the bands stay those of the whole raster
+static inline PtsGeom pts_geom_slice(const uint32_t *d_seg, const void *d_band, int dtype, uint32_t row0,
+                                     uint32_t nrows, uint32_t img_rows, uint32_t ncols, uint32_t S, int64_t null_val,
+                                     uint32_t tile_size)
+{
+    PtsGeom g = pts_geom(d_seg, d_band, dtype, img_rows, ncols, S, null_val, tile_size);
+    g.nrows = nrows;
+    const uint32_t left = g.th ? g.th - row0 % g.th : 0u;     // rows of row0's band from row0 on
+    g.h0 = left < nrows ? left : nrows;
+    return g;
 }
 
 // counts_out (host, S + 1 entries): valid points per id (k_spatial_sums without the coordinate sums)
@@ -239,10 +265,15 @@ static int run_segpoints_count(shp_ctx *ctx, const uint32_t *d_seg, const void *
 // The sorted runs of the whole raster, left in the context for run_segpoints_emit: run table in ctx->pts_runs,
 // sorted run order in ctx->pix, sorted ids in sort_k0 / sort_k1, first point of every sorted run in ctx->sort_v1,
 // per-id first points (S + 2) in ctx->pts_off.  The band stays where the caller keeps it (emit reads it).
-static int run_segpoints_build(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, uint32_t nrows,
-                               uint32_t ncols, uint32_t S, int64_t null_val, uint32_t tile_size, int64_t *npts_out)
+// run_segpoints_build_geom: the same for the rows of any geometry (a slice: pts_geom_slice; the points' runs then
+// come in the whole raster's visit order restricted to the slice).
+static int run_segpoints_build_geom(shp_ctx *ctx, const PtsGeom &g, int64_t null_val, int64_t *npts_out)
 {
     hipStream_t st = ctx->stream;
+    const uint32_t *d_seg = g.seg;
+    const void *d_band = g.band;
+    const int dtype = g.dtype;
+    const uint32_t nrows = g.nrows, ncols = g.ncols, S = g.S;
     const uint32_t n = nrows * ncols;
     const size_t ns = (size_t)S + 1;
     SegPointsState &ps = ctx->pts;
@@ -261,7 +292,6 @@ static int run_segpoints_build(shp_ctx *ctx, const uint32_t *d_seg, const void *
     ArrFn cf{cnt};
     CHK(scan_exclusive(ctx, cf, (uint32_t)ns, poff, poff + ns, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 1));
     // the runs in visit order
-    const PtsGeom g = pts_geom(d_seg, d_band, dtype, nrows, ncols, S, null_val, tile_size);
     const uint32_t nblk = (n + PTS_TILE - 1) / PTS_TILE;
     uint32_t m = 0;
     if (n) {
@@ -307,6 +337,13 @@ static int run_segpoints_build(shp_ctx *ctx, const uint32_t *d_seg, const void *
     ps.valid = true;
     *npts_out = npts;
     return 0;
+}
+
+static int run_segpoints_build(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, uint32_t nrows,
+                               uint32_t ncols, uint32_t S, int64_t null_val, uint32_t tile_size, int64_t *npts_out)
+{
+    return run_segpoints_build_geom(ctx, pts_geom(d_seg, d_band, dtype, nrows, ncols, S, null_val, tile_size),
+                                    null_val, npts_out);
 }
 
 // ids [lo, hi) of the last build: offs_out (host, hi - lo + 1 int64) and the records (host, at most cap of them)

@@ -69,6 +69,7 @@ recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six nu
   spatialOnDevice (optional): calcPerSegmentSpatialStatsDistributed.
 """
 import collections
+import contextlib
 import ctypes
 import sys
 import json
@@ -589,9 +590,22 @@ def calcPerSegmentStatsDistributed(engine, comm, hist, imgbandnum, statsSelectio
 
 
 def calcPerSegmentSpatialStatsDistributed(engine, comm, hist, imgbandnum, colTypes, userFunc, userParam,
-                                          missingStatsValue=-9999, imgNullVal=None, info=None):
-    """Per-segment spatial statistics (tilingstats.calcPerSegmentSpatialStats with its built-in user functions)
-    of one image band against the label raster that runDistributed left sharded by rows over the ranks.  As in
+                                          missingStatsValue=-9999, imgNullVal=None, info=None,
+                                          tileSize=tiling.TILESIZE, batchPoints=None):
+    """Per-segment spatial statistics (tilingstats.calcPerSegmentSpatialStats) of one image band against the
+    label raster that runDistributed left sharded by rows over the ranks.
+
+    A user function (tilingstats.spatialUserFunc, or @jit / @njit) is called once per segment with at least one
+    point, with the same ``pts`` as on one GPU: its points in the visit order of ``tileSize`` x ``tileSize``
+    tiles of the WHOLE raster.  A segment whose pixels all lie on one rank is called there; a segment with
+    pixels on several ranks (a straddler) is called by the rank whose id share (idRange) holds its id, after
+    its points have travelled as records.  Each rank makes its calls in ascending id order, in batches of at
+    most ``batchPoints`` points (tilingstats.iterSegmentPoints); the ranks call at the same time.  An
+    exception of the function on one rank is re-raised there; the other ranks raise PyShepSegStatsError
+    naming that rank.  ``info`` receives 'path' = 'points', 'straddlers', 'points_exchanged' (of all ranks)
+    and 'calls' (this rank's).
+
+    The built-in user functions run as reductions on the device instead.  As in
     calcPerSegmentStatsDistributed, ``hist`` (DistResult.hist) plays the part of segSize: segments complete on a
     rank are finished there, the straddlers' partial sums travel as packed records and every rank reduces those
     of its id share (idRange).  Edge pixels and the variogram also read rows of the neighbouring ranks (halo
@@ -606,8 +620,16 @@ def calcPerSegmentSpatialStatsDistributed(engine, comm, hist, imgbandnum, colTyp
     if not hasattr(engine, 'spatialOnDevice'):
         raise tilingstats.PyShepSegStatsError("the distributed spatial statistics need a device engine (HipEngine)")
     dcomm = comm if getattr(comm, 'onDevice', False) else _comm.HostStagedDev(comm, engine.c)
+    if not isinstance(userFunc, tilingstats._BuiltinSpatialFunc) and tilingstats._isUserFunc(userFunc):
+        pinfo = {}
+        (ic, fc, nStrad, haloRows) = engine.spatialOnDevice(dcomm, hist, imgbandnum, colTypes, userFunc, userParam,
+                                                            missingStatsValue, imgNullVal, tileSize=tileSize,
+                                                            batchPoints=batchPoints, info=pinfo)
+        if info is not None:
+            info.update(pinfo)
+        return ic, fc
     (ic, fc, nStrad, haloRows) = engine.spatialOnDevice(dcomm, hist, imgbandnum, colTypes, userFunc, userParam,
-                                                        missingStatsValue, imgNullVal)
+                                                        missingStatsValue, imgNullVal, tileSize=tileSize)
     if info is not None:
         info.update(straddlers=nStrad, halo_rows=haloRows, path='device')
     return ic, fc
@@ -741,7 +763,8 @@ _DTYPE_SIZE = {0: 1, 1: 2, 2: 2, 3: 4, 4: 4}
 
 
 def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange, hist, colTypes, userFunc, userParam,
-                       missing=-9999, imgNullVal=None, fetch=True):
+                       missing=-9999, imgNullVal=None, fetch=True, tileSize=tiling.TILESIZE, batchPoints=None,
+                       info=None):
     """The device-resident data path of calcPerSegmentSpatialStatsDistributed for ONE rank: output rows rowRange =
     (outLo, outHi) of an nRows x nCols raster (nRows None: the largest outHi of the ranks), labels d_seg (uint32)
     and band d_band (dtypeCode; -1 on a rank without rows: the other ranks' code) in the HBM of context ``c``;
@@ -749,7 +772,9 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
     ('dev', address, length).  Halo rows (spatialHaloPlan) travel in one all-gather of labels and one of band
     values; shp_dspatial_local_dev -> all-gather of the straddlers' records -> shp_dspatial_merge_dev by id share
     -> all-reduce of the column block.  Every error that depends on a rank's data is all-gathered first, so all
-    ranks raise it.  Returns (ic, fc, straddling segments, halo rows of all ranks); fetch=False: ic = fc = None."""
+    ranks raise it.  Returns (ic, fc, straddling segments, halo rows of all ranks); fetch=False: ic = fc = None.
+    A user function (tilingstats._isUserFunc) takes the point-list path instead (_userFuncSpatialStats:
+    ``tileSize``, ``batchPoints``; ``info`` receives its figures; no halo rows)."""
     from . import tilingstats
     Err = tilingstats.PyShepSegStatsError
     L = c._L
@@ -759,20 +784,25 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
     nInt = sum(1 for t in colTypes if t == tilingstats.GFT_Integer)
     nFloat = sum(1 for t in colTypes if t == tilingstats.GFT_Real)
     func = getattr(userFunc, 'funcId', None) if isinstance(userFunc, tilingstats._BuiltinSpatialFunc) else None
+    isUser = func is None and tilingstats._isUserFunc(userFunc)
     err = None
-    if func is None:
-        err = ("only the built-in user functions (userFuncMeanCoord, userFuncNumEdgePixels, userFuncVariogram) are "
-               "supported on the GPU")
+    if func is None and not isUser:
+        err = ("userFunc must be one of the built-in user functions (userFuncMeanCoord, userFuncNumEdgePixels, "
+               "userFuncVariogram), or a function decorated with tilingstats.spatialUserFunc (or @jit / @njit)")
     elif imgNullVal is None:
         err = "NoData value must be set on imgfile"
     elif nInt + nFloat != len(colTypes) or not colTypes:
         err = "column types must be GFT_Integer or GFT_Real, one or more of them"
     elif func == 2 and not (1.0 <= params[0] <= 255.0):
         err = "variogram maxDist must be 1..255 (got %g)" % params[0]
-    ctrl = comm.allgather_obj((int(rowRange[0]), int(rowRange[1]), int(dtypeCode), err))
+    elif isUser and int(tileSize) < 1:
+        err = "tileSize must be positive"
+    ctrl = comm.allgather_obj((int(rowRange[0]), int(rowRange[1]), int(dtypeCode), err, isUser))
     errs = [x[3] for x in ctrl if x[3]]
     if errs:
         raise Err(errs[0])
+    if len({x[4] for x in ctrl}) != 1:
+        raise Err("the ranks pass different kinds of user function (built-in on some, user-defined on others)")
     ranges = [(x[0], x[1]) for x in ctrl]
     codes = {x[2] for x in ctrl if x[2] >= 0}
     if len(codes) != 1:
@@ -781,6 +811,10 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
     isz = _DTYPE_SIZE[dtypeCode]
     if nRows is None:
         nRows = max(b for (a, b) in ranges)
+    if isUser:
+        return _userFuncSpatialStats(c, comm, d_seg, d_band, dtypeCode, int(nRows), nCols, rowRange, hist, nInt,
+                                     nFloat, userFunc, userParam, missing, imgNullVal, fetch, int(tileSize),
+                                     batchPoints, info)
     (above, below) = {0: (0, 0), 1: (1, 1), 2: (0, int(params[0]))}[func]
     plan = spatialHaloPlan(ranges, comm.rank, nRows, above, below)     # (raises alike on every rank)
     (lo, hi) = (int(rowRange[0]), int(rowRange[1]))
@@ -871,6 +905,177 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
             tiling._devRelease(c, p, sz)
     tot = comm.allgather_obj((int(nIds.value), ha + hb))
     return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
+
+
+SEGPOINT_RECORD_BYTES = 24         # a straddler's point as it travels: visit index, id, x, y, value bits
+
+
+def userFuncRowPlan(hist, localLabels, localPoints, share, merged, pointless):
+    """Which rows of the columns one rank answers for in the user-function path of deviceSpatialStats (host only).
+    hist: the global histogram (S + 1); localLabels / localPoints: labelled pixels / points (non-nodata pixels)
+    of every id on this rank; share = (idLo, idHi), this rank's id share (idRange); merged: points of every id
+    of the share that reached this rank as records (idHi - idLo); pointless: ids that straddle ranks and have no
+    point on some rank that reported them (every rank's list together).
+    A row belongs to the rank that holds all of the id's pixels (complete: local count == hist) or, for ids that
+    no rank holds completely -- straddlers, and ids without pixels -- to the owner of the id's share.  So every
+    row has exactly one owner, which the column all-reduce needs.  Returns (emit, owned, straddlers): emit
+    (int64, S + 1) = the points this rank hands the function for every id (an id with emit > 0 is called here,
+    once), owned (bool, S + 1) = the rows it writes, straddlers = the straddling ids of its share."""
+    hist = numpy.asarray(hist, dtype=numpy.int64)
+    lh = numpy.asarray(localLabels, dtype=numpy.int64)
+    lp = numpy.asarray(localPoints, dtype=numpy.int64)
+    merged = numpy.asarray(merged, dtype=numpy.int64)
+    (lo, hi) = (int(share[0]), int(share[1]))
+    complete = (lh == hist) & (hist > 0)
+    complete[:1] = False
+    emit = numpy.where(complete, lp, 0)
+    owned = complete.copy()
+    nStrad = 0
+    if hi > lo:
+        strad = (merged > 0) | numpy.isin(numpy.arange(lo, hi), numpy.asarray(pointless, dtype=numpy.int64))
+        owned[lo:hi] |= (hist[lo:hi] == 0) | strad
+        emit[lo:hi] += merged
+        nStrad = int(numpy.count_nonzero(strad))
+    emit[:1] = 0
+    return emit, owned, nStrad
+
+
+def clearUnownedRows(intcols, floatcols, owned):
+    """The missing-value fill of the user-function path: runUserFunc left missingStatsValue in every row it did
+    not call for (row 0 zero); the rows this rank does not own become zero, so that the ranks' column blocks
+    add up to the one-GPU columns (each row written by one rank, every 32-bit half with one non-zero
+    contributor)."""
+    intcols[:, ~owned] = 0
+    floatcols[:, ~owned] = 0
+    return intcols, floatcols
+
+
+def userFuncErrorOf(gathered):
+    """The error every rank raises after the user-function calls: gathered = every rank's None or (exception
+    type name, message).  Returns None or the message for the ranks whose own calls did not fail."""
+    for (r, g) in enumerate(gathered):
+        if g is not None:
+            return "the spatial user function raised %s on rank %d: %s" % (g[0], r, g[1])
+    return None
+
+
+def _userFuncSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange, hist, nInt, nFloat,
+                          userFunc, userParam, missing, imgNullVal, fetch, tileSize, batchPoints, info):
+    """The user-function path of deviceSpatialStats (after its control exchange): shp_dsegpoints_build_dev over
+    the own rows -> all-gather of the straddlers' point records -> shp_dsegpoints_merge_dev of this rank's id
+    share -> tilingstats.runUserFunc over this rank's batches (ids complete here and straddlers of the share, in
+    ascending id order) -> all-reduce of the column block.  The point lists live in a context of their own
+    (each of its calls needs the previous one's workspace); copies, collectives and pinned buffers use ``c``."""
+    from . import tilingstats
+    Err = tilingstats.PyShepSegStatsError
+    L = c._L
+    (lo, hi) = (int(rowRange[0]), int(rowRange[1]))
+    h = max(hi - lo, 0)
+    toFree = []
+
+    def alloc(nbytes):
+        p = tiling._devAlloc(c, nbytes)
+        toFree.append((p, nbytes))
+        return p
+    pc = None
+    try:
+        if isinstance(hist, tuple):
+            (d_hist, ns) = (ctypes.c_void_p(hist[1]), int(hist[2]))
+            h32 = numpy.empty(ns, dtype=numpy.uint32)
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(h32), d_hist, ns * 4))
+        else:
+            h32 = numpy.ascontiguousarray(hist, dtype=numpy.uint32)
+            ns = len(h32)
+            d_hist = alloc(ns * 4)
+            c.check(L.shp_dev_upload(c.handle, d_hist, _lib.ptr(h32), ns * 4))
+        S = ns - 1
+        pc = _lib.Context(device=c.device)
+        PL = pc._L
+        (lh, lp) = (numpy.zeros(ns, dtype=numpy.uint32), numpy.zeros(ns, dtype=numpy.uint32))
+        (pRec, nRec) = (ctypes.c_void_p(), ctypes.c_int64(0))
+        pc.check(PL.shp_dsegpoints_build_dev(
+            pc.handle, ctypes.c_void_p(d_seg if h else None), ctypes.c_void_p(d_band if h else None), dtypeCode, h,
+            nCols, lo if h else 0, nRows, S, int(imgNullVal), tileSize, d_hist, _lib.ptr(lh), _lib.ptr(lp),
+            ctypes.byref(pRec), ctypes.byref(nRec)))
+        # ---- the histogram's checks and the straddlers without points, of every rank
+        hist64 = h32.astype(numpy.int64)
+        strad = (lh > 0) & (lh.astype(numpy.int64) < hist64)
+        over = int(numpy.count_nonzero(lh.astype(numpy.int64) > hist64))
+        pointless = numpy.flatnonzero(strad & (lp == 0)).astype(numpy.uint32)
+        got = comm.allgather_obj((int(nRec.value), over, int(lh.sum(dtype=numpy.int64)), pointless))
+        (overAll, px, hpx) = (sum(g[1] for g in got), sum(g[2] for g in got), int(hist64[1:].sum()))
+        if overAll or px != hpx:
+            raise Err("the segment histogram does not match the label raster (%d ids with more pixels on one rank "
+                      "than the histogram says; %d labelled pixels, %d in the histogram)" % (overAll, px, hpx))
+        counts = [g[0] for g in got]
+        slot = max(counts)
+        (idLo, idHi) = idRange(comm.rank, comm.world, S)
+        d_all = None
+        if slot > 0:
+            nb = slot * SEGPOINT_RECORD_BYTES
+            d_send = alloc(nb)
+            d_all = alloc(comm.world * nb)
+            if nRec.value:
+                c.check(L.shp_dev_copy(c.handle, d_send, pRec, nRec.value * SEGPOINT_RECORD_BYTES))
+            comm.allgather_dev(d_send.value, d_all.value, nb)
+        merged = numpy.zeros(max(idHi - idLo, 1), dtype=numpy.uint32)
+        nMerged = ctypes.c_int64(0)
+        cnts = numpy.array(counts, dtype=numpy.uint32)
+        pc.check(PL.shp_dsegpoints_merge_dev(pc.handle, d_all, slot, comm.world, _lib.ptr(cnts), idLo, idHi,
+                                             _lib.ptr(merged), ctypes.byref(nMerged)))
+        merged = merged[:idHi - idLo]
+        allPointless = numpy.concatenate([numpy.asarray(g[3], dtype=numpy.int64) for g in got])
+        (ecnt, owned, nStradMine) = userFuncRowPlan(hist64, lh, lp, (idLo, idHi), merged, allPointless)
+        # ---- this rank's calls, batch by batch (the ids complete here, the straddlers of the share)
+        batches = tilingstats.planPointBatches(ecnt, tilingstats.POINTS_BATCH if batchPoints is None else batchPoints)
+        cum = numpy.concatenate([[0], numpy.cumsum(ecnt, dtype=numpy.int64)])
+        cap = max([int(cum[b] - cum[a]) for (a, b) in batches] + [1])
+        hostBufs = [tilingstats._PinnedBuffer(c, cap * tilingstats.SEGPOINT_DTYPE.itemsize)
+                    for _k in range(min(2, len(batches)))]
+
+        def emit(a, b, offs, buf, n):
+            pc.check(PL.shp_dsegpoints_emit(pc.handle, a, b, _lib.ptr(offs), buf, cap, ctypes.byref(n)))
+            if n.value != int(cum[b] - cum[a]):
+                raise Err("internal: ids %d..%d emitted %d points, %d planned" % (a, b, n.value, int(cum[b] - cum[a])))
+        failed = None
+        try:
+            with contextlib.closing(tilingstats.emitPointBatches(batches, hostBufs, emit)) as it:
+                (ic, fc) = tilingstats.runUserFunc(it, ns, userFunc, userParam, imgNullVal, nInt, nFloat, missing)
+        except Exception as e:      # (every rank learns of it before anyone leaves the collectives)
+            failed = e
+        errs = comm.allgather_obj(None if failed is None else (type(failed).__name__, str(failed)))
+        if failed is not None:
+            raise failed
+        msg = userFuncErrorOf(errs)
+        if msg is not None:
+            raise Err(msg)
+        clearUnownedRows(ic, fc, owned)
+        # ---- the column block: the ranks' rows add up
+        if comm.world > 1:
+            colWords = ((nInt * 8 + nFloat * 4) * ns + 7) // 8
+            block = numpy.zeros(colWords * 8, dtype=numpy.uint8)
+            block[:ic.nbytes] = ic.reshape(-1).view(numpy.uint8)
+            block[ic.nbytes:ic.nbytes + fc.nbytes] = fc.reshape(-1).view(numpy.uint8)
+            d_cols = alloc(colWords * 8)
+            c.check(L.shp_dev_upload(c.handle, d_cols, _lib.ptr(block), block.nbytes))
+            comm.allreduce_dev_i64(d_cols.value, colWords)
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(block), d_cols, block.nbytes))
+            ic = block[:ic.nbytes].view(numpy.int64).reshape(nInt, ns).copy()
+            fc = block[ic.nbytes:ic.nbytes + fc.nbytes].view(numpy.float32).reshape(nFloat, ns).copy()
+    finally:
+        for (p, sz) in toFree:
+            tiling._devRelease(c, p, sz)
+        if pc is not None:
+            pc.close()
+    # the job's figures: the ranks' id shares partition the straddlers
+    tot = comm.allgather_obj((nStradMine, int(nRec.value)))
+    nStrad = int(sum(t[0] for t in tot))
+    if info is not None:
+        info.update(path='points', straddlers=nStrad, points_exchanged=int(sum(t[1] for t in tot)),
+                    calls=int(numpy.count_nonzero(ecnt)))
+    if not fetch:
+        (ic, fc) = (None, None)
+    return ic, fc, nStrad, 0
 
 
 # ------------------------------------------------------------------------------------------
@@ -1136,13 +1341,15 @@ class HipEngine(object):
                            self._bandPtr(imgbandnum), _lib.SHP_DTYPES[self.ras.dtype], self.outHi - self.outLo,
                            self.nCols, hist, fast, nInt, nFloat, missing, imgNullVal)
 
-    def spatialOnDevice(self, comm, hist, imgbandnum, colTypes, userFunc, userParam, missing, imgNullVal):
+    def spatialOnDevice(self, comm, hist, imgbandnum, colTypes, userFunc, userParam, missing, imgNullVal,
+                        tileSize=tiling.TILESIZE, batchPoints=None, info=None):
         """calcPerSegmentSpatialStatsDistributed's path for this rank's output rows (deviceSpatialStats)."""
         held = self.ras is not None and self.outHi > self.outLo
         d_out = (self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut)) if held else 0
         return deviceSpatialStats(self.c, comm, d_out, self._bandPtr(imgbandnum) if held else 0,
                                   _lib.SHP_DTYPES[self.ras.dtype] if self.ras is not None else -1, None, self.nCols,
-                                  (self.outLo, self.outHi), hist, colTypes, userFunc, userParam, missing, imgNullVal)
+                                  (self.outLo, self.outHi), hist, colTypes, userFunc, userParam, missing, imgNullVal,
+                                  tileSize=tileSize, batchPoints=batchPoints, info=info)
 
     def localOutput(self):
         out = numpy.empty((self.outHi - self.outLo, self.nCols), dtype=numpy.uint32)

@@ -731,27 +731,36 @@ def iterSegmentPoints(seg, band, imgNullVal, tileSize=TILESIZE, maxSegId=None, b
         if npts.value != int(cum[-1]):
             raise PyShepSegStatsError("internal: %d points sorted, %d counted" % (npts.value, int(cum[-1])))
 
-        def emit(b):
-            (lo, hi) = batches[b]
-            offs = numpy.empty(hi - lo + 1, dtype=numpy.int64)
-            n = ctypes.c_int64(0)
-            c.check(L.shp_segpoints_emit(c.handle, lo, hi, _lib.ptr(offs), hostBufs[b % 2].p, cap,
-                                         ctypes.byref(n)))
-            return (offs, n.value)
-
-        with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
-            nxt = pool.submit(emit, 0) if batches else None
-            for b in range(len(batches)):
-                (offs, n) = nxt.result()
-                nxt = pool.submit(emit, b + 1) if b + 1 < len(batches) else None
-                pts = hostBufs[b % 2].points(n)
-                offs.flags.writeable = False
-                (lo, hi) = batches[b]
-                yield (numpy.arange(lo, hi, dtype=shepseg.SegIdType), offs, pts)
-            # (leaving the block waits for an emission still running: its buffer is freed below)
+        def emit(lo, hi, offs, buf, n):
+            c.check(L.shp_segpoints_emit(c.handle, lo, hi, _lib.ptr(offs), buf, cap, ctypes.byref(n)))
+        yield from emitPointBatches(batches, hostBufs, emit)       # (closing this closes that: its thread ends first)
     finally:
         for p in devBufs:
             L.shp_dev_free(c.handle, p)
+
+
+def emitPointBatches(batches, hostBufs, emit):
+    """The double-buffered emission of iterSegmentPoints: batch b + 1 is emitted (in a worker thread) into one
+    of the two pinned hostBufs while the caller works on batch b.  ``emit(lo, hi, offs, bufPtr, n)`` fills the
+    points of ids [lo, hi) and their offsets (offs: hi - lo + 1 int64) and sets the ctypes int64 ``n`` to their
+    number.  Yields (ids, offsets, pts) for the (lo, hi) ranges of ``batches``, in order."""
+    def one(b):
+        (lo, hi) = batches[b]
+        offs = numpy.empty(hi - lo + 1, dtype=numpy.int64)
+        n = ctypes.c_int64(0)
+        emit(lo, hi, offs, hostBufs[b % 2].p, n)
+        return (offs, n.value)
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=1) as pool:
+        nxt = pool.submit(one, 0) if batches else None
+        for b in range(len(batches)):
+            (offs, n) = nxt.result()
+            nxt = pool.submit(one, b + 1) if b + 1 < len(batches) else None
+            pts = hostBufs[b % 2].points(n)
+            offs.flags.writeable = False
+            (lo, hi) = batches[b]
+            yield (numpy.arange(lo, hi, dtype=shepseg.SegIdType), offs, pts)
+        # (leaving the block waits for an emission still running: its buffer is freed by its owner)
 
 
 def convertPtsInto2DArray(pts, imgNullVal):
