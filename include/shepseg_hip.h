@@ -373,6 +373,28 @@ int shp_subset_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t img_rows,
                           int tile_size, uint32_t max_seg_id, uint32_t *d_out, uint32_t *orig_out,
                           uint32_t *hist_out, int64_t cap, uint32_t *n_new_out);
 
+/* The subset recode split by rows over the ranks (the data path of distributed.deviceSubset /
+ * subsetImageDistributed).  A rank holds rows [row0, row0 + nrows) of the label raster in place (d_seg, row
+ * pitch ncols, fewer than 2^32 pixels), hence the window rows [a, b) = [max(0, row0 - tly), min(ys, row0 + nrows
+ * - tly)) (empty when b <= a); d_mask (optional) holds (b - a) * xs bytes, the mask rows of those window rows.
+ * Keys are positions in the WHOLE window's visiting order (tile_size tiles), so they compare across ranks.
+ *  shp_dsubset_local_dev: first-seen key of every id in the held rows; the ids present are packed as
+ *    *n_pairs_out keys followed by as many ids (uint32) at *d_pairs_out in the context's workspace, valid until
+ *    its next call.  *bad_out = 1 when a held pixel has an id above max_seg_id (such ids are left out; the
+ *    caller decides, after a collective, whether to raise).
+ *  shp_dsubset_merge_dev: after the all-gather of the pairs -- `world` slots of 2 * slot words, slot r holds
+ *    counts[r] keys then counts[r] ids -- the minimum key of every id gives its new id, the same on every rank.
+ *    The held window rows are recoded into d_out ((b - a) * xs uint32) and their new ids counted into d_hist
+ *    (cap uint32, device, zeroed first); orig_out (host, cap rows) = old id per new id (row 0 = 0);
+ *    *n_new_out = m.  Summing d_hist over the ranks gives shp_subset_recode's hist_out. */
+int shp_dsubset_local_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t row0,
+                          uint32_t max_seg_id, int64_t tlx, int64_t tly, int64_t xs, int64_t ys, int tile_size,
+                          const uint8_t *d_mask, void **d_pairs_out, int64_t *n_pairs_out, int *bad_out);
+int shp_dsubset_merge_dev(shp_ctx *ctx, const void *d_pairs, int64_t slot, int world, const uint32_t *counts,
+                          const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t row0, uint32_t max_seg_id,
+                          int64_t tlx, int64_t tly, int64_t xs, int64_t ys, int tile_size, const uint8_t *d_mask,
+                          uint32_t *d_out, uint32_t *d_hist, uint32_t *orig_out, int64_t cap, uint32_t *n_new_out);
+
 /* ---- spatial statistics --------------------------------------------------------------
  * replaces the tile loop of tilingstats.calcPerSegmentSpatialStatsTiled (tilingstats.py:1262-1390)
  * for the reference's built-in user functions, func = 0 userFuncMeanCoord (:1098-1142; params =

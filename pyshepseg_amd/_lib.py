@@ -126,6 +126,12 @@ _SIGS = {
     'shp_subset_recode_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
                                          _c.c_int64, _c.c_int64, _vp, _c.c_int, _c.c_uint32, _vp, _vp,
                                          _vp, _c.c_int64, _vp]),
+    'shp_dsubset_local_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int64,
+                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _vp, _c.POINTER(_vp),
+                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int)]),
+    'shp_dsubset_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _vp, _c.c_int64, _c.c_int64,
+                                         _c.c_int64, _c.c_uint32, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64,
+                                         _c.c_int, _vp, _vp, _vp, _vp, _c.c_int64, _vp]),
     'shp_spatialstats': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32,
                                     _c.c_int64, _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp,
                                     _vp]),

@@ -1240,6 +1240,58 @@ API int shp_subset_recode(shp_ctx *ctx, const uint32_t *seg, int64_t img_rows, i
     return 0;
 }
 
+// the recode of a row-sharded window (subset.h: run_dsubset_local / run_dsubset_merge): this rank's rows
+// [row0, row0 + nrows) in place, the window rows they hold and the matching mask rows
+static int dsubset_geom(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t row0,
+                        uint32_t max_seg_id, int64_t tlx, int64_t tly, int64_t xs, int64_t ys, int tile_size,
+                        const uint8_t *d_mask, SubsetGeom *g)
+{
+    if (nrows < 0 || ncols < 0 || row0 < 0 || tlx < 0 || tly < 0 || xs < 0 || ys < 0 || tile_size < 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (tlx + xs > ncols) SHP_FAIL(ctx, SHP_ERR_ARG, "Requested subset is not within input image");
+    if ((uint64_t)xs * (uint64_t)ys >= 0xffffffffull || ncols >= 0xffffffffll || row0 + nrows >= 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "subset too large");
+    if ((uint64_t)nrows * (uint64_t)ncols >= 0xffffffffull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "shard too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    // window rows held: [a, b) = [max(0, row0 - tly), min(ys, row0 + nrows - tly)), empty if b <= a
+    const int64_t a = std::min(std::max<int64_t>(0, row0 - tly), ys);
+    const int64_t b = std::max(a, std::min(ys, row0 + nrows - tly));
+    if (b > a && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *g = SubsetGeom{d_seg, d_mask, (uint32_t)ncols, (uint32_t)tlx, (uint32_t)tly, (uint32_t)xs, (uint32_t)ys,
+                    (uint32_t)tile_size, (uint32_t)row0, (uint32_t)a, (uint32_t)(b - a)};
+    return 0;
+}
+
+API int shp_dsubset_local_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t row0,
+                              uint32_t max_seg_id, int64_t tlx, int64_t tly, int64_t xs, int64_t ys, int tile_size,
+                              const uint8_t *d_mask, void **d_pairs_out, int64_t *n_pairs_out, int *bad_out)
+{
+    CHK(enter(ctx));
+    if (!d_pairs_out || !n_pairs_out || !bad_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    SubsetGeom g;
+    CHK(dsubset_geom(ctx, d_seg, nrows, ncols, row0, max_seg_id, tlx, tly, xs, ys, tile_size, d_mask, &g));
+    return run_dsubset_local(ctx, g, max_seg_id, d_pairs_out, n_pairs_out, bad_out);
+}
+
+API int shp_dsubset_merge_dev(shp_ctx *ctx, const void *d_pairs, int64_t slot, int world, const uint32_t *counts,
+                              const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t row0, uint32_t max_seg_id,
+                              int64_t tlx, int64_t tly, int64_t xs, int64_t ys, int tile_size, const uint8_t *d_mask,
+                              uint32_t *d_out, uint32_t *d_hist, uint32_t *orig_out, int64_t cap,
+                              uint32_t *n_new_out)
+{
+    CHK(enter(ctx));
+    if (!counts || !d_hist || !orig_out || !n_new_out || cap < 1 || slot < 0 || world < 1 ||
+        (slot > 0 && !d_pairs) || (uint64_t)slot * (uint64_t)world >= 0x7fffffffull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
+    SubsetGeom g;
+    CHK(dsubset_geom(ctx, d_seg, nrows, ncols, row0, max_seg_id, tlx, tly, xs, ys, tile_size, d_mask, &g));
+    if (g.nr > 0 && !d_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_dsubset_merge(ctx, (const uint32_t *)d_pairs, (uint32_t)slot, (uint32_t)world, counts, g, max_seg_id,
+                             d_out, d_hist, orig_out, cap, n_new_out);
+}
+
 // ---- spatial statistics ------------------------------------------------------------
 static int spatial_check(shp_ctx *ctx, int dtype, int64_t nrows, int64_t ncols, int func,
                          const double *params, int nint, int nflt)

@@ -23,12 +23,14 @@ class PyShepSegSubsetError(Exception):
 class SubsetResult(object):
     """segimg: recoded window (newYsize, newXsize) uint32; origSegIds[new id] = old id (row 0 = 0);
     hist[new id] = pixel count (the output 'Histogram' column); columns: the input RAT columns
-    gathered to the new ids (plus origSegIdColName when asked for)."""
+    gathered to the new ids (plus origSegIdColName when asked for).  From
+    distributed.subsetImageDistributed: segimg holds window rows [rows[0], rows[1]) only."""
     def __init__(self):
         self.segimg = None
         self.origSegIds = None
         self.hist = None
         self.columns = {}
+        self.rows = None        # subsetImageDistributed: (a, b), the window rows of segimg
 
 
 def _load(x):
@@ -53,14 +55,8 @@ def subsetImage(inname, outname, tlx, tly, newXsize, newYsize, outformat=None, c
     if seg.ndim != 2:
         raise PyShepSegSubsetError("input must be a single-band label raster")
     (tlx, tly, newXsize, newYsize) = (int(tlx), int(tly), int(newXsize), int(newYsize))
-    if (tlx + newXsize) > seg.shape[1] or (tly + newYsize) > seg.shape[0] or tlx < 0 or tly < 0:
-        raise PyShepSegSubsetError('Requested subset is not within input image')
-    mask = None
-    if maskImage is not None:
-        mask = numpy.asarray(_load(maskImage))
-        if mask.shape != (newYsize, newXsize):
-            raise PyShepSegSubsetError('mask should match requested subset size if supplied')
-        mask = numpy.ascontiguousarray(mask != 0, dtype=numpy.uint8)
+    checkWindow(seg.shape[0], seg.shape[1], tlx, tly, newXsize, newYsize)
+    mask = loadMask(maskImage, newXsize, newYsize)
     if tileSize is None:
         tileSize = tiling.TILESIZE
     # only the window is needed on the device
@@ -85,20 +81,51 @@ def subsetImage(inname, outname, tlx, tly, newXsize, newYsize, outformat=None, c
     res.segimg = out
     res.origSegIds = orig[:n + 1].copy()
     res.hist = hist[:n + 1].copy()
+    res.columns = recodeColumns(res.origSegIds, res.hist, ratColumns, origSegIdColName)
+    if outname is not None:
+        checkOutname(outname)
+        numpy.save(outname, out)
+    return res
+
+
+def checkWindow(nRows, nCols, tlx, tly, newXsize, newYsize):
+    "the window must lie inside the nRows x nCols label raster (subset.py:86-88)"
+    if (tlx + newXsize) > nCols or (tly + newYsize) > nRows or tlx < 0 or tly < 0:
+        raise PyShepSegSubsetError('Requested subset is not within input image')
+
+
+def loadMask(maskImage, newXsize, newYsize):
+    """maskImage (None, an array or a .npy path) as contiguous uint8 0 / 1 of the window's shape, or None
+    (subset.py:121-123)"""
+    if maskImage is None:
+        return None
+    mask = numpy.asarray(_load(maskImage))
+    if mask.shape != (newYsize, newXsize):
+        raise PyShepSegSubsetError('mask should match requested subset size if supplied')
+    return numpy.ascontiguousarray(mask != 0, dtype=numpy.uint8)
+
+
+def checkOutname(outname):
+    if not (isinstance(outname, str) and outname.endswith('.npy')):
+        raise PyShepSegSubsetError("GDAL is not available here: outname must be None or a .npy path")
+
+
+def recodeColumns(origSegIds, hist, ratColumns, origSegIdColName):
+    """The output RAT: every input column gathered to the new ids (copySubsettedSegmentsToNew,
+    subset.py:232-266; row 0 = 0), 'Histogram' (:196-205) and origSegIdColName (:207-226).
+    origSegIds[new id] = old id with at least one new id; returns a dict name -> array."""
+    columns = {}
+    maxId = int(origSegIds.max())
     if ratColumns:
         for name, col in ratColumns.items():
             col = numpy.asarray(col)
             if col.shape[0] <= maxId:
                 raise PyShepSegSubsetError("RAT column %r has %d rows, segment id %d needs more"
                                            % (name, col.shape[0], maxId))
-            new = col[res.origSegIds]
+            new = col[origSegIds]
             new[0] = 0
-            res.columns[name] = new
-    res.columns['Histogram'] = res.hist.astype(numpy.float64)          # subset.py:196-205
+            columns[name] = new
+    columns['Histogram'] = hist.astype(numpy.float64)
     if origSegIdColName is not None:
-        res.columns[origSegIdColName] = res.origSegIds.astype(numpy.int32)     # subset.py:207-226
-    if outname is not None:
-        if not (isinstance(outname, str) and outname.endswith('.npy')):
-            raise PyShepSegSubsetError("GDAL is not available here: outname must be None or a .npy path")
-        numpy.save(outname, out)
-    return res
+        columns[origSegIdColName] = origSegIds.astype(numpy.int32)
+    return columns
