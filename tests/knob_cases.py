@@ -5,6 +5,7 @@ child process (tests/knob_worker.py): the library reads these knobs once per pro
 is the GPU side of a case, expected() the oracle's; both return dicts of arrays compared exactly."""
 import numpy as np
 
+import segtable_cases
 from seg_cases import (STATS_SEL, cut_components, fixed_centres, many_sources_one_target, oracle_tiled,
                        stats_band, synth_tile, uniform_region)
 
@@ -16,7 +17,8 @@ CLUMP = ('clump_cut4', 'clump_cut8', 'clump_uniform')
 # (name, environment of the child, cases that reach the code the setting changes)
 MATRIX = [
     ('scan_two_launch', {'SHEPSEG_SCAN_ONE': '0'},
-     ('tile', 'tiled4', 'stats_sort_int32', 'stats_sort_uint8', 'subset')),
+     ('tile', 'tiled4', 'stats_sort_int32', 'stats_sort_uint8', 'subset', 'tables')),
+    ('csr_pixel_sort', {'SHEPSEG_CSR_RUNS': '0'}, ('tables',)),
     ('sort_wide', {'SHEPSEG_SORT_WIDE': '1'}, tuple('stats_sort_' + d for d in STATS_DTYPES)),
     ('small_no_lists', {'SHEPSEG_SMALL_LISTS': '0'}, SMALL),
     ('small_one_level_barrier', {'SHEPSEG_SMALL_BAR2': '0'}, SMALL),
@@ -34,6 +36,36 @@ MATRIX = [
     ('tile_order_rowmajor', {'SHEPSEG_TILE_ORDER': 'rowmajor'}, TILED),
     ('fill_max_1', {'SHEPSEG_FILL_MAX': '1'}, TILED),
 ]
+
+TABLES_CASE = ('ids_65537', 'uint16', 3)       # (segtable_cases generator, dtype, nb): S >= 65 536
+
+
+def device_tables(seg, img, max_seg_id):
+    """spectra (buildSegmentSpectra), the raw CSR of shp_segment_locations (offsets of ids 0 .. S + 1,
+    pixel indices grouped by id, the null segment first) and makeSegSize of one raster, on the device"""
+    from pyshepseg_amd import _lib, shepseg
+    seg = np.ascontiguousarray(seg, dtype=np.uint32)
+    (nr, nc) = seg.shape
+    off = np.zeros(max_seg_id + 2, dtype=np.uint32)
+    pix = np.empty(seg.size, dtype=np.uint32)
+    c = _lib.ctx()
+    c.check(c._L.shp_segment_locations(c.handle, _lib.ptr(seg), nr, nc, max_seg_id, _lib.ptr(off), _lib.ptr(pix)))
+    out = {'off': off, 'pix': pix, 'size': shepseg.makeSegSize(seg)}
+    if img is not None:
+        out['spectra'] = shepseg.buildSegmentSpectra(seg, img, max_seg_id)
+    return out
+
+
+def expected_tables(seg, img, max_seg_id, oracle):
+    """the same tables by the oracle and numpy: a stable argsort groups the pixels"""
+    cnt = np.bincount(seg.ravel(), minlength=max_seg_id + 1)
+    out = {'off': np.r_[0, np.cumsum(cnt)].astype(np.uint32),
+           'pix': np.argsort(seg.ravel(), kind='stable').astype(np.uint32),
+           'size': np.bincount(seg.ravel()).astype(np.uint32)}
+    if img is not None:
+        out['spectra'] = oracle.build_segment_spectra(seg, img, max_seg_id)
+    return out
+
 
 TILED_ARGS = dict(seed=7, nb=4, nr=900, nc=1100, tile=384, ov=96, ms=40, workers=4)
 
@@ -106,6 +138,8 @@ def run_case(name, oracle, tmpdir):
         cl = uniform_region() if name == 'clump_uniform' else cut_components()
         seg, nxt = shepseg.clump(cl, 0, fourConnected=name != 'clump_cut8')
         return {'seg': seg, 'next': np.array([nxt])}
+    if name == 'tables':
+        return device_tables(*segtable_cases.make(*TABLES_CASE))
     raise KeyError(name)
 
 
@@ -136,6 +170,8 @@ def expected(name, oracle):
         cl = uniform_region() if name == 'clump_uniform' else cut_components()
         seg, nxt = oracle.clump(cl, 0, name != 'clump_cut8', 1)
         return {'seg': seg, 'next': np.array([nxt])}
+    if name == 'tables':
+        return expected_tables(*segtable_cases.make(*TABLES_CASE), oracle)
     raise KeyError(name)
 
 

@@ -122,7 +122,8 @@ def test_device_fit_equals_reference_on_ties(ties, shepseg):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('n,nb,k', [(20000, 6, 60), (5000, 1, 12), (9000, 10, 30), (700, 3, 300), (130000, 4, 25),
-                                    (3000, 70, 5), (64, 2, 64), (4000, 8, 65)])
+                                    (3000, 70, 5), (64, 2, 64), (4000, 8, 65),
+                                    (6000, 5, 40), (5000, 11, 20), (4000, 12, 33)])
 def test_device_elkan_path_equals_oracle(n, nb, k, shepseg, oracle, monkeypatch):
     """SHEPSEG_FIT_ALGO=elkan on integer samples with a few hundred distinct rows (ties, empty
     clusters): the device's Elkan path against the oracle's, bit for bit; and without the override the
@@ -170,6 +171,24 @@ def test_device_fast_path_equals_elkan_when_guard_is_quiet(seed, shepseg, oracle
     km_e = shepseg._fit(xs, init)
     assert km_e.n_iter_ == ne and np.array_equal(km_e.labels_, le)
     assert np.array_equal(km_e.cluster_centers_.view(np.uint64), ce.view(np.uint64))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nb', range(1, 13))
+def test_device_fast_path_every_band_count(nb, shepseg, oracle):
+    """the fast path's E-step k_fit_assign<NB> in every form (NB 1..8, 10, 12 and the run-time form at nb 9
+    and 11) decides the labels: distinct sample rows shifted by 0.375 as the initial centres (no cluster
+    starts empty, no integer midpoint ties), so the guard stays quiet and the fit never leaves the fast
+    path; iterations, labels and centres are the reference algorithm's bit for bit"""
+    img = oracle.synthimg(60, nb, 300, 300)
+    xs = shepseg._sample_rows(img, 20, None)
+    u = np.unique(xs, axis=0)
+    init = u[np.linspace(0, len(u) - 1, 16).astype(np.int64)].astype(np.float64) + 0.375
+    km = shepseg._fit(xs, init)
+    assert km.fit_path_ == 'lloyd'
+    ce, le, ne = oracle.kmeans_fit(xs.astype(np.float64), init, algorithm='elkan')
+    assert km.n_iter_ == ne and np.array_equal(km.labels_, le)
+    assert np.array_equal(km.cluster_centers_.view(np.uint64), ce.view(np.uint64))
 
 
 @pytest.mark.gpu

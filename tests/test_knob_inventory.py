@@ -11,7 +11,6 @@ from conftest import ROOT
 TESTED_ELSEWHERE = {
     'SHEPSEG_STATS_PATCH': 'tests/test_gpu_stats.py::test_stats_patch_path_dtypes',
     'SHEPSEG_CLUSTER_MAP': 'tests/test_gpu_tiling.py::test_knobs_off_paths_match',
-    'SHEPSEG_CSR_RUNS': 'tests/test_gpu_tiling.py::test_knobs_off_paths_match',
     'SHEPSEG_STREAM_INPUT': 'tests/test_gpu_tiling.py::test_streamed_input_and_output_match_the_per_tile_path',
     'SHEPSEG_ELK_TABLE': 'tests/test_fit_elkan.py',
     'SHEPSEG_ELK_UNFUSED': 'tests/test_fit_elkan.py',
