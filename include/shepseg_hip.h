@@ -269,6 +269,13 @@ int shp_renumber_dev(shp_ctx *ctx, uint32_t *d_raster, int64_t npix, uint32_t st
  * clipped to the ov_w x ov_h layer.  Asynchronous, ordered behind the tile's output write. */
 int shp_overview_window_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t pitch, int xout, int yout,
                             int w, int h, int level, uint32_t *d_ov, int ov_w, int ov_h);
+/* overview layers of a row-sharded label raster (distributed.writeOutputDistributed): nrects rectangles of
+ * six int64 each, {src0, rowStep, colStep, nrows, ncols, dst0}, host memory; pixel (r, c) of rectangle k is
+ * d_raster[src0 + r * rowStep + c * colStep] and goes to d_packed[dst0 + r * ncols + c].  The rectangles are
+ * non-empty and packed back to back (dst0 of the first 0, the last one ending at npacked); every index read
+ * must lie in [0, npix), which is checked before the launch.  Synchronous. */
+int shp_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
+                           int nrects, uint32_t *d_packed, int64_t npacked);
 /* the band statistics the reference derives from the segment histogram (utils.estimateStatsFromHisto,
  * utils.py:47-95), evaluated as numpy evaluates them there (int64 sums, float64 pairwise sum for the
  * variance, float64 comparison for the median): out[0..5] = minimum, maximum, mean, standard deviation,

@@ -952,6 +952,40 @@ API int shp_overview_window_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t 
     return 0;
 }
 
+// overview rectangles of a row-sharded raster, every level in one launch (k_overview_rects); the table is
+// checked here, on the host, so that no rectangle reads outside the npix pixels of d_raster.  Synchronous.
+API int shp_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
+                               int nrects, uint32_t *d_packed, int64_t npacked)
+{
+    CHK(enter(ctx));
+    if (npix < 0 || nrects < 0 || npacked < 0 || (nrects > 0 && !rects) || (npacked > 0 && (!d_raster || !d_packed)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    int64_t at = 0;
+    for (int k = 0; k < nrects; k++) {
+        const int64_t *q = rects + 6 * (size_t)k;
+        const int64_t src0 = q[0], rs = q[1], cs = q[2], nr = q[3], nc = q[4];
+        if (nr < 1 || nc < 1 || rs < 0 || cs < 0 || src0 < 0 || q[5] != at || nr > npacked || nc > npacked)
+            SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangle %d is malformed", k);
+        int64_t room = npix - 1 - src0;             // the last pixel read, src0 + (nr - 1) rs + (nc - 1) cs, < npix
+        if (room < 0 || (rs > 0 && nr - 1 > room / rs))
+            SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangle %d reads past the raster", k);
+        room -= (nr - 1) * rs;
+        if (cs > 0 && nc - 1 > room / cs) SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangle %d reads past the raster", k);
+        if (nr * nc > npacked - at) SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangles overrun the packed buffer");
+        at += nr * nc;
+    }
+    if (at != npacked) SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangles fill %lld of %lld packed pixels",
+                                (long long)at, (long long)npacked);
+    if (npacked == 0) return 0;
+    CHK(buf_ensure(ctx, ctx->tlist, (size_t)nrects * 48));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->tlist.p, rects, (size_t)nrects * 48, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_overview_rects, dim3(grid_for((size_t)npacked, 256)), dim3(256), 0, ctx->stream, d_raster,
+                       bp<int64_t>(ctx->tlist), (uint32_t)nrects, (uint64_t)npacked, d_packed);
+    KCHK(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 // histogram of a device label raster: hist_out[0..max_seg_id], hist_out[0] = 0 (tiling.py:1915-1963).
 // ncols > 0 (npix a multiple of it): the raster's row length, which lets the pixels of a segment
 // be combined per 2-D patch before they reach the global counters; 0 = unknown (1-D runs).

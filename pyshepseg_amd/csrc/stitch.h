@@ -909,3 +909,26 @@ __global__ __launch_bounds__(256) void k_overview_window(const uint32_t *__restr
     if (dr >= ovh || dc >= ovw) return;
     ov[(size_t)dr * ovw + dc] = ras[(size_t)(yout + o + r * lvl) * pitch + xout + o + c * lvl];
 }
+
+// The same sampling for the overview layers of a row-sharded raster (distributed.writeOutputDistributed):
+// every rectangle a rank owns, of every level, in one launch.  Rectangle k is six int64 words
+// {src0, rowStep, colStep, nrows, ncols, dst0}: pixel (r, c) of it is ras[src0 + r * rowStep + c * colStep]
+// (rowStep = lvl * pitch, colStep = lvl: k_overview_window's formula from the rectangle's first pixel on) and
+// goes to packed[dst0 + r * ncols + c].  The rectangles are packed back to back in table order (dst0 ascending,
+// none empty; the host checks every index against the raster), so a thread finds its rectangle by bisection.
+__global__ __launch_bounds__(256) void k_overview_rects(const uint32_t *__restrict__ ras,
+                                                        const int64_t *__restrict__ rects, uint32_t nrects,
+                                                        uint64_t npacked, uint32_t *__restrict__ packed)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= npacked) return;
+    uint32_t lo = 0u, hi = nrects;                  // rects[lo].dst0 <= i < rects[hi].dst0 (npacked for nrects)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) / 2u;
+        if ((uint64_t)rects[6 * (size_t)mid + 5] <= i) lo = mid; else hi = mid;
+    }
+    const int64_t *q = rects + 6 * (size_t)lo;
+    const uint64_t k = i - (uint64_t)q[5];
+    const uint64_t r = k / (uint64_t)q[4], c = k - r * (uint64_t)q[4];
+    packed[i] = ras[(uint64_t)q[0] + r * (uint64_t)q[1] + c * (uint64_t)q[2]];
+}

@@ -68,6 +68,9 @@ recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six nu
   localStats, gatherFlagged, statsOfPairs (optional statsOnDevice): calcPerSegmentStatsDistributed.
   spatialOnDevice (optional): calcPerSegmentSpatialStatsDistributed.
   subsetOnDevice (optional): subsetImageDistributed.
+  outputRows(y0, y1) -> image rows [y0, y1) of the kept output (inside outRows), uint32, on the host;
+      overviewRects(table, npacked) -> the pixels of a table of overview rectangles (overviewTable), packed:
+      writeOutputDistributed, after finish.
 """
 import collections
 import contextlib
@@ -403,7 +406,8 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
     stitchMode ('sequential', 'parallel', or 'parallel->sequential' when part of the parallel form
     had to be redone -- chainStepsRedone says how many tiles, from the first one whose ids the
     provisional numbering cannot express; argument / SHEPSEG_STITCH: None = parallel when
-    comm.world > 1)."""
+    comm.world > 1).  nRows, nCols, tileInfo and overlapSize describe the grid for the output stage
+    (writeOutputDistributed)."""
     _t = [time.time()]
     _marks = []
 
@@ -520,6 +524,7 @@ def runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegment
     res.outRows = (outLo, outHi)
     res.numTileRows, res.numTileCols = tileInfo.nrows, tileInfo.ncols
     res.hasEmptySegments = bool((hist[1:] == 0).any())
+    (res.nRows, res.nCols, res.tileInfo, res.overlapSize) = (nRows, nCols, tileInfo, overlapSize)    # (the output stage)
     return res
 
 
@@ -1056,20 +1061,26 @@ def subsetImageDistributed(engine, comm, result, tlx, tly, newXsize, newYsize, o
     return res
 
 
+def _stepOnAllRanks(comm, outname, fn, Err):
+    """fn() on this rank, then an all-gather of what failed (a collective: every rank calls it): the first
+    rank's error is raised as Err on every rank, so none is left waiting in a later collective"""
+    err = None
+    try:
+        fn()
+    except Exception as e:      # noqa: B902  (raised below, on every rank)
+        err = '%s: %s' % (type(e).__name__, e)
+    errs = [(r, x) for (r, x) in enumerate(comm.allgather_obj(err)) if x]
+    if errs:
+        raise Err("writing %s failed on rank %d: %s" % (outname, errs[0][0], errs[0][1]))
+
+
 def _writeRows(comm, outname, rows, a, shape):
     """rank 0 creates the .npy file, then every rank writes its rows; a collective before and after (built from
     allgather_obj), errors raised on every rank"""
     from . import subset
 
     def step(fn):
-        err = None
-        try:
-            fn()
-        except Exception as e:      # noqa: B902  (raised below, on every rank)
-            err = '%s: %s' % (type(e).__name__, e)
-        errs = [(r, x) for (r, x) in enumerate(comm.allgather_obj(err)) if x]
-        if errs:
-            raise subset.PyShepSegSubsetError("writing %s failed on rank %d: %s" % (outname, errs[0][0], errs[0][1]))
+        _stepOnAllRanks(comm, outname, fn, subset.PyShepSegSubsetError)
 
     def create():
         if comm.rank == 0:
@@ -1085,6 +1096,226 @@ def _writeRows(comm, outname, rows, a, shape):
             del f
     step(create)
     step(write)
+
+
+# ------------------------------------------------------------------------------------------
+# file to file: the slice reader, the overview ownership plan, the output stage
+# ------------------------------------------------------------------------------------------
+def readSlice(src, bandNumbers, yLo, yHi):
+    """Rows [yLo, yHi) of the 1-based bands ``bandNumbers`` of a tiling._open_source source, as one
+    C-contiguous (len(bandNumbers), yHi - yLo, nCols) array in a pixel type of the library, converted as
+    _lib.as_image converts (int8 -> int16, 64-bit -> uint32 or int32 by the values of these rows; TypeError
+    for anything else).  Reads those rows only (src.readRowsInto)."""
+    bands = [int(b) - 1 for b in bandNumbers]
+    out = numpy.empty((len(bands), int(yHi) - int(yLo), src.RasterXSize), dtype=src.dtype)
+    if out.size:
+        src.readRowsInto(bands, int(yLo), int(yHi), out)
+    return _lib.as_image(out)[0]
+
+
+def _overviewBlock(tileInfo, overlapSize, lvl, col, row, ovw, ovh):
+    """(x0, y0, x1, y1, sx, sy): the block k_overview_window writes for a tile at one level -- layer pixels
+    [x0, x1) x [y0, y1), pixel (x0 + c, y0 + r) sampling raster pixel (sx + c lvl, sy + r lvl) -- or None when
+    the tile's trimmed window is no larger than lvl / 2 in one direction (the kernel writes nothing)."""
+    (xpos, ypos, xs, ys) = tileInfo.getTile(col, row)
+    (top, bottom, left, right, xout, yout) = tiling.trimmedWindow(tileInfo, col, row, xpos, ypos, xs, ys, overlapSize)
+    (w, h, o) = (right - left, bottom - top, lvl // 2)
+    nsr = (h - o + lvl - 1) // lvl if h > o else 0
+    nsc = (w - o + lvl - 1) // lvl if w > o else 0
+    (x0, y0) = (xout // lvl, yout // lvl)
+    (x1, y1) = (min(x0 + nsc, ovw), min(y0 + nsr, ovh))
+    if x1 <= x0 or y1 <= y0:
+        return None
+    return (x0, y0, x1, y1, xout + o, yout + o)
+
+
+def overviewPlan(tileInfo, overlapSize, lvl, tiles):
+    """The part of each tile's overview block that the tile owns at level ``lvl``: one entry per (col, row) of
+    ``tiles``, (x0, y0, x1, y1, sx, sy) -- layer pixels [x0, x1) x [y0, y1), pixel (x0 + c, y0 + r) sampling
+    raster pixel (sx + c lvl, sy + r lvl) -- or None when it owns nothing.
+
+    The one-GPU driver writes the blocks tile by tile in row-major (chain) order, a later block over an earlier
+    one; a tile owns a pixel when it is the last tile whose block covers it, so ranks that write their tiles'
+    owned parts at the same time make the same layer.  Tiles of one tile column share xout and the window
+    width, tiles of one tile row share yout and the window height, so what a tile owns is its block clipped at
+    the first column of the next non-empty block to its right (same tile row) and at the first row of the next
+    non-empty block below it (same tile column); a block is empty when its window is no larger than lvl / 2."""
+    (ncols, nrows) = (tileInfo.ncols, tileInfo.nrows)
+    nCols = max(x + xs for (x, _y, xs, _ys) in tileInfo.tiles.values())
+    nRows = max(y + ys for (_x, y, _xs, ys) in tileInfo.tiles.values())
+    (ovw, ovh) = ((nCols + lvl - 1) // lvl, (nRows + lvl - 1) // lvl)
+    memo = {}
+
+    def block(c, r):
+        if (c, r) not in memo:
+            memo[(c, r)] = _overviewBlock(tileInfo, overlapSize, lvl, c, r, ovw, ovh)
+        return memo[(c, r)]
+    out = []
+    for (col, row) in tiles:
+        b = block(col, row)
+        if b is None:
+            out.append(None)
+            continue
+        (x0, y0, x1, y1, sx, sy) = b
+        for c in range(col + 1, ncols):
+            nb = block(c, row)
+            if nb is not None:
+                x1 = min(x1, nb[0])
+                break
+        for r in range(row + 1, nrows):
+            nb = block(col, r)
+            if nb is not None:
+                y1 = min(y1, nb[1])
+                break
+        out.append((x0, y0, x1, y1, sx, sy) if x1 > x0 and y1 > y0 else None)
+    return out
+
+
+def checkNpyOutfile(outfile):
+    """The output the multi-rank driver writes: a .npy path whose directory exists and is writable (every rank
+    must see it).  Raises tiling.PyShepSegTilingError; creates nothing."""
+    Err = tiling.PyShepSegTilingError
+    if not isinstance(outfile, str) or not outfile.endswith('.npy'):
+        raise Err("the multi-rank driver writes a .npy file that every rank can write (got %r); GDAL formats "
+                  "and outfile=None are not supported" % (outfile,))
+    d = os.path.dirname(os.path.abspath(outfile))
+    if not os.path.isdir(d) or not os.access(d, os.W_OK):
+        raise Err("cannot write %r: %s is not a writable directory" % (outfile, d))
+
+
+class _NpyPatchWriter(tiling._NpyRowWriter):
+    """An existing (nRows, nCols) uint32 .npy file (made by _NpyRowWriter) opened for pwrite by any rank."""
+    def __init__(self, path, nrows, ncols):
+        with open(path, 'rb') as f:
+            version = numpy.lib.format.read_magic(f)
+            (shape, fortran, dtype) = numpy.lib.format._read_array_header(f, version)
+            self.offset = f.tell()
+        if shape != (nrows, ncols) or fortran or dtype != numpy.dtype(numpy.uint32):
+            raise tiling.PyShepSegTilingError("%s holds %s %s, not (%d, %d) uint32" % (path, shape, dtype, nrows, ncols))
+        (self.nrows, self.ncols) = (nrows, ncols)
+        self.fd = os.open(path, os.O_WRONLY)
+
+    def writeRect(self, y0, x0, v):
+        """v (h x w) at rows [y0, y0 + h), columns [x0, x0 + w): whole rows in one pwrite, else row by row"""
+        (h, w) = v.shape
+        if x0 == 0 and w == self.ncols:
+            return self.writeRows(y0, y0 + h, v)
+        for r in range(h):
+            mv = memoryview(numpy.ascontiguousarray(v[r])).cast('B')
+            pos = self.offset + ((y0 + r) * self.ncols + x0) * 4
+            done = 0
+            while done < len(mv):
+                done += os.pwrite(self.fd, mv[done:], pos + done)
+
+
+def _mosaicPieces(dres):
+    """What this rank writes of the mosaic: [(y0, y1, x0, x1)] -- its output rows in one piece when it holds
+    whole tile rows (no other rank writes them), else its tiles' trimmed windows (ranks share output rows)"""
+    (t0, t1) = dres.tileRange
+    (lo, hi) = dres.outRows
+    ti = dres.tileInfo
+    if t1 <= t0 or hi <= lo:
+        return []
+    if t0 % ti.ncols == 0 and t1 % ti.ncols == 0:
+        return [(lo, hi, 0, dres.nCols)]
+    out = []
+    for t in range(t0, t1):
+        (col, row) = (t % ti.ncols, t // ti.ncols)
+        (top, bottom, left, right, xout, yout) = tiling.trimmedWindow(ti, col, row, *ti.getTile(col, row),
+                                                                      dres.overlapSize)
+        if bottom > top and right > left:
+            out.append((yout, yout + bottom - top, xout, xout + right - left))
+    return out
+
+
+def overviewTable(dres, levels):
+    """This rank's overview rectangles of every level, for engine.overviewRects: (table int64 (n, 6) rows
+    {src0, rowStep, colStep, nrows, ncols, dst0} relative to the output rows the engine holds (image row
+    outRows[0] first), [(level, x0, y0, x1, y1)] in the same order, packed pixel count)"""
+    (t0, t1) = dres.tileRange
+    ti = dres.tileInfo
+    tiles = [(t % ti.ncols, t // ti.ncols) for t in range(t0, t1)]
+    (lo, nCols) = (dres.outRows[0], dres.nCols)
+    (rows, where, at) = ([], [], 0)
+    for lvl in levels:
+        for p in overviewPlan(ti, dres.overlapSize, lvl, tiles):
+            if p is None:
+                continue
+            (x0, y0, x1, y1, sx, sy) = p
+            rows.append(((sy - lo) * nCols + sx, lvl * nCols, lvl, y1 - y0, x1 - x0, at))
+            where.append((lvl, x0, y0, x1, y1))
+            at += (y1 - y0) * (x1 - x0)
+    return numpy.array(rows, dtype=numpy.int64).reshape(-1, 6), where, at
+
+
+def writeOutputDistributed(engine, comm, dres, outfile, writeHistogram=True, timings=None):
+    """The output stage of a multi-rank run, after runDistributed(engine, comm, ...) returned ``dres`` (every id
+    final; the engine kept its output rows: outputRows, overviewRects).  Writes what the one-GPU driver writes
+    for a .npy ``outfile`` (tiling.doTiledShepherdSegmentation): the mosaic, ``<base>_hist.npy`` (writeHistogram,
+    rank 0) and ``<base>_ov<lvl>.npy`` for each level of tiling.overviewLevels -- rank 0 creates every file,
+    zero-filled at full size, then each rank writes its own pixels with pwrite: its output rows in one piece
+    when it holds whole tile rows, else its tiles' trimmed windows (SHEPSEG_SHARD=tiles: ranks share rows), and
+    the overview pixels its tiles own (overviewPlan), sampled on the engine in one call.  Errors are raised on
+    every rank.  ``timings`` (a tiling.Timers, optional) gets 'writing' and 'overviews'.  Returns the band
+    statistics (tiling.estimateStatsFromHisto), the same on every rank."""
+    Err = tiling.PyShepSegTilingError
+    checkNpyOutfile(outfile)
+    timings = timings if timings is not None else tiling.Timers()
+    (nRows, nCols) = (dres.nRows, dres.nCols)
+    base = outfile[:-4]
+    layers = [(int(lvl), base + '_ov%d.npy' % lvl, ((nRows + lvl - 1) // lvl, (nCols + lvl - 1) // lvl))
+              for lvl in tiling.overviewLevels(nCols, nRows)]
+
+    def create():
+        if comm.rank == 0:
+            for (path, shape) in [(outfile, (nRows, nCols))] + [(p, s) for (_l, p, s) in layers]:
+                tiling._NpyRowWriter(path, *shape).close()
+            if writeHistogram:
+                numpy.save(base + '_hist.npy', dres.hist)
+    _stepOnAllRanks(comm, outfile, create, Err)
+
+    def mosaic():
+        pieces = _mosaicPieces(dres)
+        if not pieces:
+            return
+        block = max(1, tiling.STREAM_BLOCK_ROWS)
+        w = _NpyPatchWriter(outfile, nRows, nCols)
+        try:
+            (lo, hi) = dres.outRows
+            for y in range(lo, hi, block):
+                y1 = min(hi, y + block)
+                rows = None
+                for (a, b, x0, x1) in pieces:
+                    (ra, rb) = (max(a, y), min(b, y1))
+                    if ra < rb:
+                        if rows is None:
+                            rows = engine.outputRows(y, y1)
+                        w.writeRect(ra, x0, rows[ra - y:rb - y, x0:x1])
+        finally:
+            w.close()
+    with timings.interval('writing'):
+        _stepOnAllRanks(comm, outfile, mosaic, Err)
+
+    def overviews():
+        (table, where, npacked) = overviewTable(dres, [lvl for (lvl, _p, _s) in layers])
+        if not where:
+            return
+        packed = engine.overviewRects(table, npacked)
+        files = {lvl: _NpyPatchWriter(path, *shape) for (lvl, path, shape) in layers}
+        try:
+            for (q, (lvl, x0, y0, x1, y1)) in zip(table, where):
+                n = int(q[3] * q[4])
+                files[lvl].writeRect(y0, x0, packed[q[5]:q[5] + n].reshape(y1 - y0, x1 - x0))
+        finally:
+            for f in files.values():
+                f.close()
+    if layers:
+        with timings.interval('overviews'):
+            _stepOnAllRanks(comm, base + '_ov*.npy', overviews, Err)
+    hist = dres.hist
+    if dres.hasEmptySegments and comm.rank == 0:
+        tiling._warnEmptySegments(hist, dres.overlapSize)
+    return tiling.estimateStatsFromHisto(hist) if hist.sum() > 0 else []
 
 
 SEGPOINT_RECORD_BYTES = 24         # a straddler's point as it travels: visit index, id, x, y, value bits
@@ -1543,6 +1774,32 @@ class HipEngine(object):
         self.c.check(self.L.shp_dev_download(self.c.handle, _lib.ptr(out), self._lastOut, out.nbytes))
         return out
 
+    def outputRows(self, y0, y1):
+        """image rows [y0, y1) of the kept output (inside outRows), to the host"""
+        out = numpy.empty((y1 - y0, self.nCols), dtype=numpy.uint32)
+        if out.size:
+            d = self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut)
+            self.c.check(self.L.shp_dev_download(self.c.handle, _lib.ptr(out),
+                                                 ctypes.c_void_p(d + (y0 - self.outLo) * self.nCols * 4), out.nbytes))
+        return out
+
+    def overviewRects(self, table, npacked):
+        """the overview rectangles of a writeOutputDistributed table sampled from the kept output in one launch
+        (shp_overview_rects_dev), downloaded once: uint32 (npacked,)"""
+        out = numpy.empty(npacked, dtype=numpy.uint32)
+        if npacked == 0:
+            return out
+        table = numpy.ascontiguousarray(table, dtype=numpy.int64)
+        d = tiling._devAlloc(self.c, npacked * 4)
+        try:
+            self.c.check(self.L.shp_overview_rects_dev(self.c.handle, self._lastOut,
+                                                       (self.outHi - self.outLo) * self.nCols, _lib.ptr(table),
+                                                       table.shape[0], d, npacked))
+            self.c.check(self.L.shp_dev_download(self.c.handle, _lib.ptr(out), d, out.nbytes))
+        finally:
+            tiling._devRelease(self.c, d, npacked * 4)
+        return out
+
     def finish(self):
         for t in self.threads:
             t.join()
@@ -1557,6 +1814,188 @@ class HipEngine(object):
 
     def releaseOutput(self):
         tiling._devRelease(self.c, self.bufs.d_out, self.bufs.nbOut)
+
+
+class _FileSliceEngine(HipEngine):
+    """HipEngine whose makeSlice uploads rows [yLo, yHi) of the selected bands of a raster source (readSlice).
+    The rows are read in setup, before any collective of runDistributed; what fails there (a 64-bit band
+    outside the 32-bit range, a read error) is all-gathered and raised alike on every rank.  The output is
+    always kept: writeOutputDistributed reads it; release() frees what the run left on the device."""
+
+    def __init__(self, comm, src, bandNumbers, nullVal, numWorkers):
+        HipEngine.__init__(self, self._upload, numWorkers=numWorkers, keepOutput=True)
+        (self.comm, self.src, self.bandNumbers, self.nullVal) = (comm, src, bandNumbers, nullVal)
+        (self._host, self._finished) = (None, False)
+        (self.threads, self.forceExit) = ([], None)
+
+    def _upload(self, yLo, yHi):
+        with self.timings.interval('reading'):
+            ras = tiling.DeviceRaster.fromArray(self._host, self.nullVal)
+        self._host = None
+        return ras
+
+    def setup(self, tileInfo, jobs, total, yLo, yHi, outLo, outHi, nCols, overlapSize):
+        err = None
+        with self.timings.interval('reading'):
+            try:
+                if yHi > yLo:
+                    self._host = readSlice(self.src, self.bandNumbers, yLo, yHi)
+            except Exception as e:      # noqa: B902  (raised below, on every rank)
+                err = e
+        _raiseOnAllRanks(self.comm, err)
+        HipEngine.setup(self, tileInfo, jobs, total, yLo, yHi, outLo, outHi, nCols, overlapSize)
+
+    def finish(self):
+        HipEngine.finish(self)
+        self._finished = True
+
+    def release(self):
+        """Free every device block of the run: after a failure too (the workers are stopped first, and a buffer a
+        worker may still write is leaked rather than reused, as in tiling.doTiledShepherdSegmentation)."""
+        if self.forceExit is not None:
+            self.forceExit.set()
+        stuck = False
+        for t in self.threads:
+            t.join(timeout=None if self._finished else 120.0)
+            stuck = stuck or t.is_alive()
+        if getattr(self, 'c', None) is not None:
+            self.L.shp_sync(self.c.handle)
+        if stuck:
+            sys.stderr.write("pyshepseg_amd: a worker did not stop after a failure; its device buffers are leaked "
+                             "rather than reused\n")
+            return
+        if self._finished:
+            if getattr(self, '_lastOut', None) is not None:
+                self.releaseOutput()
+                self._lastOut = None
+        elif getattr(self, 'bufs', None) is not None:
+            for (d, nbytes) in self.recvDev:
+                tiling._devRelease(self.c, d, nbytes)
+            self.recvDev = []
+            if getattr(self, 'd_bases', None) is not None:
+                tiling._devRelease(self.c, self.d_bases, self.nbBases)
+                self.d_bases = None
+            self.bufs.free()            # (a failed run: freed, not recycled)
+        self.bufs = None
+        if self.ras is not None:
+            self.ras.free()
+            self.ras = None
+        self._sliceKey = None
+
+
+_SAME_TYPE_ERRORS = (TypeError, ValueError, IndexError, OSError, tiling.PyShepSegTilingError,
+                     _lib.ShepsegHipError)
+
+
+def _raiseOnAllRanks(comm, err):
+    """All-gather this rank's exception (or None); the first rank's is raised on every rank, with its type when
+    that is one of _SAME_TYPE_ERRORS (else as tiling.PyShepSegTilingError)."""
+    got = comm.allgather_obj(None if err is None else (type(err).__name__, str(err)))
+    bad = [(r, x) for (r, x) in enumerate(got) if x is not None]
+    if not bad:
+        return
+    (r, (name, msg)) = bad[0]
+    if err is not None and r == comm.rank:
+        raise err
+    types = {t.__name__: t for t in _SAME_TYPE_ERRORS}
+    typ = types.get(name, tiling.PyShepSegTilingError)
+    raise typ(msg if name in types else '%s: %s' % (name, msg))
+
+
+def doTiledShepherdSegmentationDistributed(infile, outfile, comm=None, tileSize=tiling.DFLT_TILESIZE,
+        overlapSize=tiling.DFLT_OVERLAPSIZE, minSegmentSize=50, numClusters=60, bandNumbers=None,
+        subsamplePcnt=None, maxSpectralDiff='auto', imgNullVal=None, fixedKMeansInit=False,
+        fourConnected=True, verbose=False, simpleTileRecode=False, spectDistPcntile=50, kmeansObj=None,
+        writeHistogram=True, concurrencyCfg=None, stitchMode=None, keepOutput=False):
+    """tiling.doTiledShepherdSegmentation from a raster file to a .npy file over the ranks of ``comm``: every
+    rank calls it with the same arguments.  Each rank reads the rows its tiles need (readSlice) into its own
+    GPU, runDistributed segments and stitches them, writeOutputDistributed writes the mosaic, the histogram
+    and the overview layers -- the files the one-GPU driver writes, bit for bit.
+
+    ``infile``: a numpy array, a .npy path or a GDAL-readable path (not a DeviceRaster); ``outfile``: a .npy
+    path on a filesystem every rank sees (anything else raises tiling.PyShepSegTilingError on every rank before
+    any collective, and creates nothing).  The segmentation keywords and their defaults are those of
+    tiling.doTiledShepherdSegmentation; concurrencyCfg.numWorkers sizes the HipEngine; ``stitchMode`` as in
+    runDistributed.  ``comm`` None: comm.fromEnvironment(), closed before returning (a communicator passed in
+    stays open).  Argument errors (outfile, odd overlap, band numbers, pixel type) are raised alike on every
+    rank.
+
+    Returns a tiling.TiledSegmentationResult, the same on every rank: the fields of the one-GPU .npy path
+    (segimg and overviews None: the layers are in the files), plus rowRange, outRows, tileRange, stitchMode and
+    chainStepsRedone of the DistResult.  keepOutput=True: the raster slice and the labels stay on this rank's
+    GPU, ``result.engine`` and ``result.dist`` (the DistResult) are set for calcPerSegmentStatsDistributed,
+    calcPerSegmentSpatialStatsDistributed and subsetImageDistributed -- whose ``imgbandnum`` is the 1-based
+    position of the band in ``bandNumbers`` when bands were selected -- and the caller frees them with
+    result.engine.release().  keepOutput=False: every device block of the call is released, also on failure."""
+    from . import comm as _comm
+    Err = tiling.PyShepSegTilingError
+    checkNpyOutfile(outfile)
+    if isinstance(infile, tiling.DeviceRaster):
+        raise Err("the multi-rank driver reads a numpy array, a .npy path or a GDAL raster, not a DeviceRaster "
+                  "(it lives on one GPU)")
+    if concurrencyCfg is None:
+        concurrencyCfg = tiling.SegmentationConcurrencyConfig()
+    numWorkers = 1
+    if concurrencyCfg.concurrencyType != tiling.CONC_NONE:
+        numWorkers = max(1, int(concurrencyCfg.numWorkers))
+    ownComm = comm is None
+    if ownComm:
+        comm = _comm.fromEnvironment()
+    engine = None
+    ok = False
+    try:
+        timings = tiling.Timers()
+        with timings.interval('walltime'):
+            # ---- arguments: checked on every rank, the first rank's error raised on all of them
+            err = src = None
+            try:
+                if (overlapSize % 2) != 0:
+                    raise Err("Overlap size must be an even number")
+                src = tiling._open_source(infile)
+                nBandsAll = src.shape[0]
+                if bandNumbers is None:
+                    bandNumbers = list(range(1, nBandsAll + 1))
+                bandNumbers = [int(b) for b in bandNumbers]
+                if not bandNumbers or any(b < 1 or b > nBandsAll for b in bandNumbers):
+                    raise Err("band numbers %s out of range 1..%d" % (bandNumbers, nBandsAll))
+                _lib.as_image(numpy.zeros((1, 1, 1), dtype=src.dtype))        # (the pixel types as_image takes)
+                if imgNullVal is None:
+                    imgNullVal = (src.bandNull(bandNumbers) if isinstance(src, tiling._GdalSource)
+                                  else src.nullVal)
+            except Exception as e:      # noqa: B902  (raised below, on every rank)
+                err = e
+            _raiseOnAllRanks(comm, err)
+            (nRows, nCols) = (src.RasterYSize, src.RasterXSize)
+            engine = _FileSliceEngine(comm, src, bandNumbers, imgNullVal, numWorkers)
+            dres = runDistributed(engine, comm, nRows, nCols, tileSize, overlapSize, minSegmentSize=minSegmentSize,
+                                  numClusters=numClusters, subsamplePcnt=subsamplePcnt,
+                                  maxSpectralDiff=maxSpectralDiff, imgNullVal=imgNullVal,
+                                  fixedKMeansInit=fixedKMeansInit, fourConnected=fourConnected,
+                                  simpleTileRecode=simpleTileRecode, spectDistPcntile=spectDistPcntile,
+                                  kmeansObj=kmeansObj, stitchMode=stitchMode)
+            if verbose and comm.rank == 0:
+                print("KMeans of whole raster", dres.kmeans.n_clusters, "clusters; maxSpectralDiff",
+                      dres.maxSpectralDiff)
+                print("Found {} tiles, with {} rows and {} cols".format(
+                    dres.numTileRows * dres.numTileCols, dres.numTileRows, dres.numTileCols))
+            bandStatistics = writeOutputDistributed(engine, comm, dres, outfile, writeHistogram, timings=timings)
+        for (name, pairs) in engine.timings.pairs.items():
+            timings.pairs.setdefault(name, []).extend(pairs)
+        result = tiling.TiledSegmentationResult()
+        for k in ('maxSegId', 'hist', 'kmeans', 'maxSpectralDiff', 'subsamplePcnt', 'numTileRows', 'numTileCols',
+                  'hasEmptySegments', 'rowRange', 'outRows', 'tileRange', 'stitchMode', 'chainStepsRedone'):
+            setattr(result, k, getattr(dres, k))
+        (result.bandStatistics, result.timings) = (bandStatistics, timings)
+        (result.segimg, result.overviews) = (None, None)
+        if keepOutput:
+            (result.engine, result.dist) = (engine, dres)
+        ok = True
+        return result
+    finally:
+        if engine is not None and not (ok and keepOutput):
+            engine.release()
+        if ownComm:
+            comm.close()
 
 
 # ------------------------------------------------------------------------------------------
