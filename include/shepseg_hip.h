@@ -506,6 +506,25 @@ int shp_dspatial_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_ba
 int shp_dspatial_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, int world, const uint32_t *counts,
                            uint32_t max_seg_id, int func, const double *params, int64_t missing, int nint, int nflt,
                            uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_ids_out);
+/* The variogram (func 2) adds squares as integers; a (segment, bin) pair whose float64 sum in the reference's
+ * order may differ from that (a square or the total at 2^53 or beyond) is flagged and recomputed.
+ *  shp_spatial_vario_redo_count: the pairs the last shp_spatialstats(_dev) call recomputed.
+ *  shp_dspatial_vario_pairs: the flagged pairs (s * maxd + bin, ascending) of the last local or merge call
+ *    (*n_out; copied into out when cap >= *n_out).
+ *  shp_dspatial_vario_redo_dev: the reference's sums of the pairs (the union over the ranks, ascending) over the
+ *    own rows and the rows_dn halo rows below them, continuing from sum / cnt (host arrays, in and out): the
+ *    ranks run it one after the other from the top of the image.
+ *  shp_dspatial_vario_store_dev: before the column block is summed over the ranks, one rank stores the pairs'
+ *    entries (write = 1: (float)sqrt(sum / cnt)) and every other rank zeroes them (write = 0). */
+int shp_spatial_vario_redo_count(shp_ctx *ctx, int64_t *n_out);
+int shp_dspatial_vario_pairs(shp_ctx *ctx, uint64_t *out, int64_t cap, int64_t *n_out);
+int shp_dspatial_vario_redo_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                                int64_t ncols, const uint32_t *d_seg_dn, const void *d_band_dn, int64_t rows_dn,
+                                uint32_t max_seg_id, int64_t null_val, int maxd, const uint64_t *pairs, int64_t np,
+                                double *sum, uint32_t *cnt);
+int shp_dspatial_vario_store_dev(shp_ctx *ctx, const uint64_t *pairs, int64_t np, const double *sum,
+                                 const uint32_t *cnt, int maxd, uint32_t max_seg_id, int nint, int nflt,
+                                 void *d_cols, int write);
 
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a

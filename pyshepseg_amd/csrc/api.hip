@@ -100,7 +100,7 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage,
                  &ctx->dpts_lh, &ctx->dpts_cls, &ctx->dpts_spos, &ctx->dpts_rec, &ctx->dpts_moff, &ctx->dpts_eoff,
                  &ctx->dpts_cnt, &ctx->dpts_kpos, &ctx->dpts_mrec, &ctx->dpts_key, &ctx->dpts_idx, &ctx->dpts_k0,
-                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix};
+                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo};
     *out = ctx;
     return SHP_OK;
 }
@@ -1565,6 +1565,64 @@ API int shp_dspatial_merge_dev(shp_ctx *ctx, const void *d_recs, int64_t slot, i
     for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
     return run_dspatial_merge(ctx, (const unsigned long long *)d_recs, (uint32_t)slot, (uint32_t)world, counts, max_seg_id,
                               func, params, missing, nint, nflt, id_lo, id_hi, d_cols, n_ids_out);
+}
+
+// the (segment, bin) pairs the last built-in variogram recomputed in the reference's order (one GPU)
+API int shp_spatial_vario_redo_count(shp_ctx *ctx, int64_t *n_out)
+{
+    CHK(enter(ctx));
+    if (!n_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *n_out = ctx->vario_redo;
+    return 0;
+}
+
+// the flagged pairs (s * maxd + bin, ascending) of the last shp_dspatial_local_dev / shp_dspatial_merge_dev call:
+// *n_out of them, copied into out when cap holds them all
+API int shp_dspatial_vario_pairs(shp_ctx *ctx, uint64_t *out, int64_t cap, int64_t *n_out)
+{
+    CHK(enter(ctx));
+    if (!n_out || cap < 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    *n_out = (int64_t)ctx->vario_pairs.size();
+    if (out && cap >= *n_out && *n_out) memcpy(out, ctx->vario_pairs.data(), (size_t)*n_out * 8);
+    return 0;
+}
+
+// The variogram's pairs (ascending, all ids <= max_seg_id) again over the own rows nrows x ncols, the halo of
+// rows_dn rows below them holding the partners there; sum / cnt (host, np each) carry the rows above in and the
+// rows up to the end of the own rows out.
+API int shp_dspatial_vario_redo_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
+                                    int64_t ncols, const uint32_t *d_seg_dn, const void *d_band_dn, int64_t rows_dn,
+                                    uint32_t max_seg_id, int64_t null_val, int maxd, const uint64_t *pairs,
+                                    int64_t np, double *sum, uint32_t *cnt)
+{
+    CHK(enter(ctx));
+    if (dtype_size(dtype) == 0 || nrows < 0 || ncols < 0 || rows_dn < 0 || np < 0 || np >= 0x7fffffffll ||
+        maxd < 1 || maxd > 255 || (nrows > 0 && (!d_seg || !d_band)) || (rows_dn > 0 && (!d_seg_dn || !d_band_dn)) ||
+        (np > 0 && (!pairs || !sum || !cnt)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if ((uint64_t)nrows * (uint64_t)ncols >= 0xffffffffull || (uint64_t)rows_dn * (uint64_t)ncols >= 0xffffffffull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "shard too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    for (int64_t j = 0; j < np; j++)
+        if (pairs[j] / (uint64_t)maxd > max_seg_id) SHP_FAIL(ctx, SHP_ERR_ARG, "pair %lld beyond max_seg_id", (long long)j);
+    SpatialWin w{d_seg, nullptr, d_seg_dn, d_band, nullptr, d_band_dn, dtype, (uint32_t)ncols, (uint32_t)nrows, 0u,
+                 (uint32_t)rows_dn, max_seg_id, (long long)null_val, 0ull};
+    return spatial_vario_redo(ctx, w, (uint32_t)maxd, (const unsigned long long *)pairs, (uint32_t)np, sum, cnt);
+}
+
+// the pairs' variogram entries of the column block d_cols (nint int64 columns, then nflt float32 columns of
+// max_seg_id + 1 ids): (float)sqrt(sum / cnt) where write, else 0
+API int shp_dspatial_vario_store_dev(shp_ctx *ctx, const uint64_t *pairs, int64_t np, const double *sum,
+                                     const uint32_t *cnt, int maxd, uint32_t max_seg_id, int nint, int nflt,
+                                     void *d_cols, int write)
+{
+    CHK(enter(ctx));
+    if (np < 0 || np >= 0x7fffffffll || maxd < 1 || maxd > 255 || nint < 0 || nflt < 0 || !d_cols ||
+        (np > 0 && (!pairs || !sum || !cnt)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    const size_t ns = (size_t)max_seg_id + 1;
+    return spatial_vario_store(ctx, (const unsigned long long *)pairs, (uint32_t)np, sum, cnt, (uint32_t)maxd, ns,
+                               nflt, (float *)((long long *)d_cols + (size_t)nint * ns), write);
 }
 
 // Grow the context's workspace for tiles of up to npix pixels now (the buffers are grow-only and

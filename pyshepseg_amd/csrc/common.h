@@ -67,10 +67,13 @@ struct shp_ctx {
         small, cen, fit_x, fit_lab, fit_part, fit_lb, big, srclist, tgtlist, bigbits, singles, dbg, snap,
         pts_runs, pts_off, pts_offs, pts_stage,
         dpts_lh, dpts_cls, dpts_spos, dpts_rec, dpts_moff, dpts_eoff, dpts_cnt, dpts_kpos, dpts_mrec, dpts_key,
-        dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix;
+        dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix,
+        vflag, vlist, vredo;
     SegPointsState pts;
     DSegPointsState dpts;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)
+    int64_t vario_redo = 0;         // last built-in variogram: (segment, bin) pairs recomputed in the reference's order
+    std::vector<unsigned long long> vario_pairs;  // last multi-GPU variogram step: its flagged pairs
     int fit_path = 0;               // last k-means fit: 0 the fast (Lloyd) path, 1 the reference's Elkan path
     double *h_fit = nullptr;        // pinned, grow-only: the centred k-means sample
     size_t h_fit_cap = 0;

@@ -13,11 +13,18 @@
 //                      exactly that, the box border being made of such pixels;
 //   variogram          for every pixel the (yo, xo) in 1..maxDist pairs inside the same segment,
 //                      binned by floor(sqrt(yo^2 + xo^2)): integer count and integer sum of squared
-//                      differences per (segment, bin) -- exact, so sqrt(sum / count) is the
-//                      reference's value bit for bit.
+//                      differences per (segment, bin).  The reference adds (double)(int64)(d*d) into a
+//                      float64 sum in the order (row, column, yo, xo), the square wrapping negative
+//                      once |d| > 3037000499.  That sum equals the integer sum only while every term
+//                      and the total stay below 2^53 (every partial sum is then exact); where either
+//                      fails the (segment, bin) pair is flagged (vario_add: no wrapped uint64 is
+//                      trusted) and k_spatial_wredo adds its terms again, one wavefront per pair, in
+//                      the reference's order and arithmetic.  sqrt(sum / count) is then the
+//                      reference's value bit for bit (ctx->vario_redo: the pairs recomputed).
 // userFunc outputs land as the reference stores them: intArr int32 -> int64 column, floatArr
 // float64 -> float32 column; unset entries and segments without a valid pixel hold `missing`.
 #pragma once
+#include <algorithm>
 #include "common.h"
 
 struct SpatialGeom {
@@ -87,10 +94,32 @@ __global__ __launch_bounds__(256) void k_spatial_edges(SpatialGeom g, int four, 
     if (len) atomicAdd(&edges[key], len);
 }
 
+#define VARIO_EXACT (1ull << 53)
+
+// Bit i of vflag: the integer sum of (segment, bin) i may differ from the reference's float64 sum.  The thread
+// that sets the bit first counts it in *nflag.
+__device__ __forceinline__ void vario_flag(uint32_t *vflag, uint32_t *nflag, size_t i)
+{
+    const uint32_t bit = 1u << (i & 31u);
+    if (!(atomicOr(&vflag[i >> 5], bit) & bit)) atomicAdd(nflag, 1u);
+}
+
+// One thread's c pairs of (segment, bin) i, their squares summing to acc; big: one square is >= 2^53 (acc may
+// then have wrapped).  Every other square is below 2^53, so acc < 2^62 does not wrap, and while the running
+// total of i stays below 2^53 old + acc is exact: the add that first takes it to 2^53 or beyond sees that, and
+// every earlier add saw an exact total below 2^53.  A total below 2^53 is never flagged.
+__device__ __forceinline__ void vario_add(uint32_t *vcnt, unsigned long long *vsum, uint32_t *vflag, uint32_t *nflag,
+                                          size_t i, uint32_t c, unsigned long long acc, bool big)
+{
+    atomicAdd(&vcnt[i], c);
+    const unsigned long long old = atomicAdd(&vsum[i], acc);
+    if (big || acc >= VARIO_EXACT || old + acc >= VARIO_EXACT) vario_flag(vflag, nflag, i);
+}
+
 // offs: noffs packed (bin << 16 | yo << 8 | xo) sorted by bin (1-based), yo, xo
 __global__ __launch_bounds__(256) void k_spatial_vario(SpatialGeom g, const uint32_t *__restrict__ offs,
                                                        uint32_t noffs, uint32_t maxd, uint32_t *vcnt,
-                                                       unsigned long long *vsum)
+                                                       unsigned long long *vsum, uint32_t *vflag, uint32_t *nflag)
 {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= g.nrows * g.ncols) return;
@@ -100,15 +129,13 @@ __global__ __launch_bounds__(256) void k_spatial_vario(SpatialGeom g, const uint
     const long long v = ld_px(g.band, g.dtype, p);
     uint32_t bin = 0, c = 0;
     unsigned long long acc = 0;
+    bool big = false;
     for (uint32_t i = 0; i <= noffs; i++) {
         const uint32_t o = i < noffs ? offs[i] : 0xFFFFFFFFu;
         const uint32_t b = o >> 16;
         if (b != bin) {
-            if (c) {
-                atomicAdd(&vcnt[(size_t)s * maxd + (bin - 1u)], c);
-                atomicAdd(&vsum[(size_t)s * maxd + (bin - 1u)], acc);
-            }
-            bin = b; c = 0; acc = 0;
+            if (c) vario_add(vcnt, vsum, vflag, nflag, (size_t)s * maxd + (bin - 1u), c, acc, big);
+            bin = b; c = 0; acc = 0; big = false;
             if (i == noffs) break;
         }
         const uint32_t yo = (o >> 8) & 255u, xo = o & 255u;
@@ -116,8 +143,10 @@ __global__ __launch_bounds__(256) void k_spatial_vario(SpatialGeom g, const uint
             const uint32_t q = p + yo * g.ncols + xo;
             if (spatial_member(g, q) == s) {
                 const unsigned long long d = (unsigned long long)(v - ld_px(g.band, g.dtype, q));
+                const unsigned long long t = d * d;   // |d| < 2^32: exact in uint64
                 c++;
-                acc += d * d;                 // (unsigned: the square of a 32-bit difference may wrap)
+                acc += t;
+                big |= t >= VARIO_EXACT;
             }
         }
     }
@@ -191,68 +220,6 @@ static int spatial_upload_params(shp_ctx *ctx, const double *params, const std::
     return 0;
 }
 
-// d_seg / d_band: device rasters (nrows x ncols).  Outputs are HOST arrays.
-static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
-                            uint32_t nrows, uint32_t ncols, uint32_t S, int64_t null_val, int func,
-                            const double *params, int64_t missing, int nint, int nflt,
-                            int64_t *intcols_out, float *fltcols_out)
-{
-    hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
-    const uint32_t n = nrows * ncols;
-    uint32_t maxd = 0;
-    std::vector<uint32_t> offs;
-    if (func == 2) {
-        if (!(params[0] >= 1.0 && params[0] <= 255.0))
-            SHP_FAIL(ctx, SHP_ERR_ARG, "variogram maxDist must be 1..255 (got %g)", params[0]);
-        maxd = (uint32_t)params[0];
-        offs = spatial_vario_offsets(maxd);
-    }
-    const size_t vrows = func == 2 ? ns * maxd : 1;
-    CHK(buf_ensure(ctx, ctx->segsz, ns * 4));                                   // cnt
-    CHK(buf_ensure(ctx, ctx->origsz, ns * 4));                                  // edges
-    CHK(buf_ensure(ctx, ctx->aux, ns * 16));                                    // sumx | sumy
-    CHK(buf_ensure(ctx, ctx->aux2, vrows * 12 + 64));                           // vsum | vcnt
-    CHK(buf_ensure(ctx, ctx->small, 4096 + offs.size() * 4));
-    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
-    if (offs.size() * 4 + 64 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "maxDist too large");
-    uint32_t *cnt = bp<uint32_t>(ctx->segsz), *edges = bp<uint32_t>(ctx->origsz);
-    unsigned long long *sumx = (unsigned long long *)ctx->aux.p, *sumy = sumx + ns;
-    unsigned long long *vsum = (unsigned long long *)ctx->aux2.p;
-    uint32_t *vcnt = (uint32_t *)(vsum + vrows);
-    double *d_prm = (double *)ctx->small.p;
-    uint32_t *d_offs = bp<uint32_t>(ctx->small) + 64;
-    long long *d_int = (long long *)ctx->ssum.p;
-    float *d_flt = (float *)(d_int + (size_t)nint * ns);
-    CHK(spatial_upload_params(ctx, params, offs, d_prm, d_offs));
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, ns * 4, st));
-    SpatialGeom g{d_seg, d_band, dtype, nrows, ncols, S, (long long)null_val};
-    const unsigned grid = grid_for(n, 256);
-    if (func == 0) {
-        HIPCHK(ctx, hipMemsetAsync(sumx, 0, ns * 16, st));
-        if (n) hipLaunchKernelGGL(k_spatial_sums, dim3(grid), dim3(256), 0, st, g, cnt, sumx, sumy);
-    } else {
-        if (n) hipLaunchKernelGGL(k_spatial_sums, dim3(grid), dim3(256), 0, st, g, cnt,
-                                  (unsigned long long *)nullptr, (unsigned long long *)nullptr);
-        if (func == 1) {
-            HIPCHK(ctx, hipMemsetAsync(edges, 0, ns * 4, st));
-            if (n) hipLaunchKernelGGL(k_spatial_edges, dim3(grid), dim3(256), 0, st, g, params[0] != 0.0, edges);
-        } else {
-            HIPCHK(ctx, hipMemsetAsync(vsum, 0, vrows * 12, st));
-            if (n) hipLaunchKernelGGL(k_spatial_vario, dim3(grid), dim3(256), 0, st, g, d_offs,
-                                      (uint32_t)offs.size(), maxd, vcnt, vsum);
-        }
-    }
-    KCHK(ctx);
-    hipLaunchKernelGGL(k_spatial_finish, dim3(grid_for(ns, 256)), dim3(256), 0, st, func, S, cnt, sumx, sumy,
-                       edges, vcnt, vsum, maxd, d_prm, (long long)missing, nint, nflt, d_int, d_flt);
-    KCHK(ctx);
-    if (nint) HIPCHK(ctx, hipMemcpyAsync(intcols_out, d_int, (size_t)nint * ns * 8, hipMemcpyDeviceToHost, st));
-    if (nflt) HIPCHK(ctx, hipMemcpyAsync(fltcols_out, d_flt, (size_t)nflt * ns * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    return 0;
-}
-
 // ---- multi-GPU split, device-resident (pyshepseg_amd/distributed.py: deviceSpatialStats) ------------------
 // A rank holds rows [row0, row0 + h) of the label raster and of the band.  Edges and the variogram look past a
 // pixel's own row, so they also read `ha` halo rows just above row0 and `hb` just below row0 + h -- other ranks'
@@ -261,7 +228,10 @@ static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
 // neighbour outside the window is outside the image.  Only the rank's own pixels are accumulated: each pixel,
 // and each variogram pair (by its upper pixel), is counted by exactly one rank, and every accumulator is an
 // integer sum (uint32 / uint64, wrapping as on one GPU), so the ranks' partial sums add up to the one-GPU sums
-// bit for bit and k_spatial_finish's arithmetic (spatial_finish_row) gives the same columns.
+// bit for bit and k_spatial_finish's arithmetic (spatial_finish_row) gives the same columns.  The variogram's
+// flagged pairs (the ranks' flags and those of the merged partial sums, all-gathered) are recomputed in the
+// reference's order rank after rank, each rank continuing over its own rows from the sums the ranks above it
+// left (spatial_vario_redo), and stored by one rank (spatial_vario_store) before the columns are added up.
 struct SpatialWin {
     const uint32_t *seg, *seg_up, *seg_dn;
     const void *band, *band_up, *band_dn;
@@ -333,7 +303,7 @@ __global__ __launch_bounds__(256) void k_spatial_wedges(SpatialWin w, int four, 
 // k_spatial_vario over the own rows; the partners (yo rows below) may lie in the halo below
 __global__ __launch_bounds__(256) void k_spatial_wvario(SpatialWin w, const uint32_t *__restrict__ offs,
                                                         uint32_t noffs, uint32_t maxd, uint32_t *vcnt,
-                                                        unsigned long long *vsum)
+                                                        unsigned long long *vsum, uint32_t *vflag, uint32_t *nflag)
 {
     WIN_PIXEL(w)
     if (!inb) return;
@@ -343,15 +313,13 @@ __global__ __launch_bounds__(256) void k_spatial_wvario(SpatialWin w, const uint
     const long long wend = (long long)w.h + (long long)w.hb;
     uint32_t bin = 0, c = 0;
     unsigned long long acc = 0;
+    bool big = false;
     for (uint32_t i = 0; i <= noffs; i++) {
         const uint32_t o = i < noffs ? offs[i] : 0xFFFFFFFFu;
         const uint32_t b = o >> 16;
         if (b != bin) {
-            if (c) {
-                atomicAdd(&vcnt[(size_t)s * maxd + (bin - 1u)], c);
-                atomicAdd(&vsum[(size_t)s * maxd + (bin - 1u)], acc);
-            }
-            bin = b; c = 0; acc = 0;
+            if (c) vario_add(vcnt, vsum, vflag, nflag, (size_t)s * maxd + (bin - 1u), c, acc, big);
+            bin = b; c = 0; acc = 0; big = false;
             if (i == noffs) break;
         }
         const uint32_t yo = (o >> 8) & 255u, xo = o & 255u;
@@ -360,12 +328,206 @@ __global__ __launch_bounds__(256) void k_spatial_wvario(SpatialWin w, const uint
             const long long u = rq < (long long)w.h ? ld_px(w.band, w.dtype, p + (size_t)yo * w.ncols + xo)
                                                     : ld_px(w.band_dn, w.dtype, (size_t)(rq - (long long)w.h) * w.ncols + col + xo);
             const unsigned long long d = (unsigned long long)(v - u);
+            const unsigned long long t = d * d;   // |d| < 2^32: exact in uint64
             c++;
-            acc += d * d;                 // (unsigned: the square of a 32-bit difference may wrap)
+            acc += t;
+            big |= t >= VARIO_EXACT;
         }
     }
 }
+
+// the bounding box of every id's pixels in the own rows: bmin[2 s] / bmin[2 s + 1] = first row / column,
+// bmax[2 s] / bmax[2 s + 1] = last row / column (bmin cleared to all ones, bmax to 0)
+__global__ __launch_bounds__(256) void k_spatial_wbbox(SpatialWin w, uint32_t *bmin, uint32_t *bmax)
+{
+    WIN_PIXEL(w)
+    const uint32_t s = inb ? win_member(w, row, col) : 0u;
+    const uint32_t len = spatial_runlen(s, col, inb);
+    if (len) {
+        atomicMin(&bmin[2 * (size_t)s], row);
+        atomicMax(&bmax[2 * (size_t)s], row);
+        atomicMin(&bmin[2 * (size_t)s + 1], col);
+        atomicMax(&bmax[2 * (size_t)s + 1], col + len - 1u);
+    }
+}
 #undef WIN_PIXEL
+
+// The reference's sum of flagged (segment, bin) pairs over the own rows, one wavefront per pair pr = s * maxd +
+// bin (bin 0-based), continuing from sum[j] / cnt[j] (what the rows above the own rows added).  The wavefront
+// walks the (pixel, offset) elements of the segment's bounding box in the reference's order -- the box's pixels
+// in raster order, for each the bin's offsets offs[bstart[bin] ..) in (yo, xo) order -- 64 at a time, one per
+// lane; the terms of the lanes that hold a pair, (double)(int64)(d * d) as numba forms them, are then added in
+// lane order by every lane alike.
+__global__ __launch_bounds__(64) void k_spatial_wredo(SpatialWin w, const uint32_t *__restrict__ offs,
+                                                      const uint32_t *__restrict__ bstart, uint32_t maxd,
+                                                      const unsigned long long *__restrict__ pairs, uint32_t npairs,
+                                                      const uint32_t *__restrict__ bmin,
+                                                      const uint32_t *__restrict__ bmax, double *sum, uint32_t *cnt)
+{
+    const uint32_t j = blockIdx.x;
+    if (j >= npairs) return;
+    const unsigned long long pr = pairs[j];
+    const unsigned long long s = pr / maxd;
+    const uint32_t bin = (uint32_t)(pr - s * maxd);
+    if (s == 0u || s > w.S) return;
+    const uint32_t r0 = bmin[2 * s], c0 = bmin[2 * s + 1], r1 = bmax[2 * s], c1 = bmax[2 * s + 1];
+    if (r0 > r1) return;                                  // no pixel of s in the own rows
+    const uint32_t o0 = bstart[bin], nb = bstart[bin + 1u] - o0;
+    const unsigned long long bw = (unsigned long long)(c1 - c0) + 1ull;
+    const unsigned long long ne = ((unsigned long long)(r1 - r0) + 1ull) * bw * nb;
+    const long long wend = (long long)w.h + (long long)w.hb;
+    const unsigned lane = lane_id();
+    double acc = sum[j];
+    uint32_t c = cnt[j];
+    for (unsigned long long base = 0; base < ne; base += 64u) {
+        const unsigned long long e = base + lane;
+        double t = 0.0;
+        bool pair = false;
+        if (e < ne) {
+            const unsigned long long px = e / nb, br = px / bw;
+            const uint32_t k = (uint32_t)(e - px * nb);
+            const uint32_t row = r0 + (uint32_t)br, col = c0 + (uint32_t)(px - br * bw);
+            if (win_member(w, row, col) == (uint32_t)s) {
+                const uint32_t o = offs[o0 + k];
+                const uint32_t yo = (o >> 8) & 255u, xo = o & 255u;
+                const long long rq = (long long)row + yo;
+                if (rq < wend && col + xo < w.ncols && win_member(w, rq, col + xo) == (uint32_t)s) {
+                    const long long v = ld_px(w.band, w.dtype, (size_t)row * w.ncols + col);
+                    const long long u = rq < (long long)w.h
+                                            ? ld_px(w.band, w.dtype, (size_t)rq * w.ncols + col + xo)
+                                            : ld_px(w.band_dn, w.dtype, (size_t)(rq - (long long)w.h) * w.ncols + col + xo);
+                    const unsigned long long d = (unsigned long long)(v - u);
+                    t = (double)(long long)(d * d);
+                    pair = true;
+                }
+            }
+        }
+        unsigned long long m = __ballot(pair);
+        c += (uint32_t)__popcll(m);
+        const unsigned long long tb = (unsigned long long)__double_as_longlong(t);
+        const int tlo = (int)(uint32_t)tb, thi = (int)(uint32_t)(tb >> 32);
+        while (m) {
+            const int l = __builtin_ctzll(m);
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane(tlo, l);
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(thi, l);
+            acc += __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+            m &= m - 1ull;
+        }
+    }
+    if (lane == 0u) {
+        sum[j] = acc;
+        cnt[j] = c;
+    }
+}
+
+// the flagged pairs of vflag (nwords words) as pair indices base + bit, appended at *n
+__global__ __launch_bounds__(256) void k_vario_flag_list(const uint32_t *__restrict__ vflag, size_t nwords,
+                                                         unsigned long long base, unsigned long long *list, uint32_t *n)
+{
+    const size_t wi = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (wi >= nwords) return;
+    uint32_t m = vflag[wi];
+    if (m == 0u) return;
+    uint32_t k = atomicAdd(n, (uint32_t)__popc(m));
+    while (m) {
+        list[k++] = base + (unsigned long long)wi * 32ull + (unsigned long long)__builtin_ctz(m);
+        m &= m - 1u;
+    }
+}
+
+// column `bin` of id s for every pair: (float)sqrt(sum / cnt) (write), else 0 (a rank that only adds zeros)
+__global__ __launch_bounds__(256) void k_vario_store(const unsigned long long *__restrict__ pairs, uint32_t npairs,
+                                                     uint32_t maxd, const double *__restrict__ sum,
+                                                     const uint32_t *__restrict__ cnt, size_t ns, int nflt,
+                                                     float *fltcols, int write)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= npairs) return;
+    const unsigned long long pr = pairs[j];
+    const unsigned long long s = pr / maxd, bin = pr - s * maxd;
+    if (s >= ns || bin >= (unsigned long long)(nflt > 0 ? nflt : 0)) return;
+    fltcols[bin * ns + s] = (write && cnt[j]) ? (float)sqrt(sum[j] / (double)cnt[j]) : 0.0f;
+}
+
+// the flagged pairs of nwords flag words, their indices offset by base, downloaded into list (*n of them)
+static int vario_flag_download(shp_ctx *ctx, const uint32_t *vflag, size_t nwords, unsigned long long base,
+                               uint32_t *d_n, std::vector<unsigned long long> &list)
+{
+    hipStream_t st = ctx->stream;
+    uint32_t nf = 0;
+    CHK(read_u32(ctx, d_n, &nf));
+    list.assign(nf, 0ull);
+    if (nf == 0u) return 0;
+    CHK(buf_ensure(ctx, ctx->vlist, (size_t)nf * 8 + 64));
+    uint32_t *d_k = d_n + 1;
+    HIPCHK(ctx, hipMemsetAsync(d_k, 0, 4, st));
+    hipLaunchKernelGGL(k_vario_flag_list, dim3(grid_for(nwords, 256)), dim3(256), 0, st, vflag, nwords, base,
+                       (unsigned long long *)ctx->vlist.p, d_k);
+    KCHK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(list.data(), ctx->vlist.p, (size_t)nf * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    std::sort(list.begin(), list.end());
+    return 0;
+}
+
+// Recomputes the pairs (s * maxd + bin, ascending) over the own rows of w, sum / cnt carrying what the rows above
+// them added (zeros for the first rows of the image).  Host arrays in and out.
+static int spatial_vario_redo(shp_ctx *ctx, const SpatialWin &w, uint32_t maxd, const unsigned long long *pairs,
+                              uint32_t np, double *sum, uint32_t *cnt)
+{
+    hipStream_t st = ctx->stream;
+    if (np == 0u || w.h == 0u || w.ncols == 0u) return 0;
+    const std::vector<uint32_t> offs = spatial_vario_offsets(maxd);
+    std::vector<uint32_t> bstart(maxd + 1u, 0u);
+    for (uint32_t b = 0, i = 0; b <= maxd; b++) {
+        while (i < offs.size() && (offs[i] >> 16) < b + 1u) i++;
+        bstart[b] = i;
+    }
+    const size_t ns = (size_t)w.S + 1;
+    const size_t nbb = 2 * ns * 4;
+    const size_t o_pairs = 2 * nbb, o_sum = o_pairs + (size_t)np * 8, o_cnt = o_sum + (size_t)np * 8;
+    const size_t o_offs = o_cnt + (((size_t)np * 4 + 15) & ~(size_t)15), o_bst = o_offs + offs.size() * 4;
+    CHK(buf_ensure(ctx, ctx->vredo, o_bst + bstart.size() * 4 + 64));
+    char *base = (char *)ctx->vredo.p;
+    uint32_t *bmin = (uint32_t *)base, *bmax = (uint32_t *)(base + nbb);
+    HIPCHK(ctx, hipMemsetAsync(bmin, 0xFF, nbb, st));
+    HIPCHK(ctx, hipMemsetAsync(bmax, 0, nbb, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_pairs, pairs, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_sum, sum, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_cnt, cnt, (size_t)np * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_offs, offs.data(), offs.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_bst, bstart.data(), bstart.size() * 4, hipMemcpyHostToDevice, st));
+    const size_t n = (size_t)w.h * w.ncols;
+    hipLaunchKernelGGL(k_spatial_wbbox, dim3(grid_for(n, 256)), dim3(256), 0, st, w, bmin, bmax);
+    hipLaunchKernelGGL(k_spatial_wredo, dim3(np), dim3(64), 0, st, w, (const uint32_t *)(base + o_offs),
+                       (const uint32_t *)(base + o_bst), maxd, (const unsigned long long *)(base + o_pairs), np,
+                       bmin, bmax, (double *)(base + o_sum), (uint32_t *)(base + o_cnt));
+    KCHK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(sum, base + o_sum, (size_t)np * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(cnt, base + o_cnt, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// the pairs' variogram columns in fltcols (ns ids per column): their values (write), or zeros
+static int spatial_vario_store(shp_ctx *ctx, const unsigned long long *pairs, uint32_t np, const double *sum,
+                               const uint32_t *cnt, uint32_t maxd, size_t ns, int nflt, float *fltcols, int write)
+{
+    hipStream_t st = ctx->stream;
+    if (np == 0u || nflt <= 0) return 0;
+    const size_t o_sum = (size_t)np * 8, o_cnt = o_sum + (size_t)np * 8;
+    CHK(buf_ensure(ctx, ctx->vlist, o_cnt + (size_t)np * 4 + 64));
+    char *base = (char *)ctx->vlist.p;
+    HIPCHK(ctx, hipMemcpyAsync(base, pairs, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_sum, sum, (size_t)np * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_cnt, cnt, (size_t)np * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_vario_store, dim3(grid_for(np, 256)), dim3(256), 0, st,
+                       (const unsigned long long *)base, np, maxd, (const double *)(base + o_sum),
+                       (const uint32_t *)(base + o_cnt), ns, nflt, fltcols, write);
+    KCHK(ctx);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
 
 // Every id judged against the global histogram gh (the reference's segSize): complete here (local label count
 // == global) -> its finished row goes into cols; ids nobody holds (global 0, row 0 among them) -> their
@@ -447,12 +609,93 @@ __global__ __launch_bounds__(256) void k_dspatial_pack(
     }
 }
 
+// d_seg / d_band: device rasters (nrows x ncols).  Outputs are HOST arrays.
+static int run_spatialstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
+                            uint32_t nrows, uint32_t ncols, uint32_t S, int64_t null_val, int func,
+                            const double *params, int64_t missing, int nint, int nflt,
+                            int64_t *intcols_out, float *fltcols_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    const uint32_t n = nrows * ncols;
+    uint32_t maxd = 0;
+    std::vector<uint32_t> offs;
+    if (func == 2) {
+        if (!(params[0] >= 1.0 && params[0] <= 255.0))
+            SHP_FAIL(ctx, SHP_ERR_ARG, "variogram maxDist must be 1..255 (got %g)", params[0]);
+        maxd = (uint32_t)params[0];
+        offs = spatial_vario_offsets(maxd);
+    }
+    const size_t vrows = func == 2 ? ns * maxd : 1;
+    CHK(buf_ensure(ctx, ctx->segsz, ns * 4));                                   // cnt
+    CHK(buf_ensure(ctx, ctx->origsz, ns * 4));                                  // edges
+    CHK(buf_ensure(ctx, ctx->aux, ns * 16));                                    // sumx | sumy
+    CHK(buf_ensure(ctx, ctx->aux2, vrows * 12 + 64));                           // vsum | vcnt
+    CHK(buf_ensure(ctx, ctx->small, 4096 + offs.size() * 4));
+    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
+    if (offs.size() * 4 + 64 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "maxDist too large");
+    uint32_t *cnt = bp<uint32_t>(ctx->segsz), *edges = bp<uint32_t>(ctx->origsz);
+    unsigned long long *sumx = (unsigned long long *)ctx->aux.p, *sumy = sumx + ns;
+    unsigned long long *vsum = (unsigned long long *)ctx->aux2.p;
+    uint32_t *vcnt = (uint32_t *)(vsum + vrows);
+    double *d_prm = (double *)ctx->small.p;
+    uint32_t *d_offs = bp<uint32_t>(ctx->small) + 64;
+    long long *d_int = (long long *)ctx->ssum.p;
+    float *d_flt = (float *)(d_int + (size_t)nint * ns);
+    const size_t fwords = (vrows + 31) / 32;
+    CHK(buf_ensure(ctx, ctx->vflag, func == 2 ? fwords * 4 + 64 : 64));
+    uint32_t *vflag = bp<uint32_t>(ctx->vflag), *nflag = vflag + fwords;     // flags | count | list position
+    ctx->vario_redo = 0;
+    CHK(spatial_upload_params(ctx, params, offs, d_prm, d_offs));
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, ns * 4, st));
+    SpatialGeom g{d_seg, d_band, dtype, nrows, ncols, S, (long long)null_val};
+    const unsigned grid = grid_for(n, 256);
+    if (func == 0) {
+        HIPCHK(ctx, hipMemsetAsync(sumx, 0, ns * 16, st));
+        if (n) hipLaunchKernelGGL(k_spatial_sums, dim3(grid), dim3(256), 0, st, g, cnt, sumx, sumy);
+    } else {
+        if (n) hipLaunchKernelGGL(k_spatial_sums, dim3(grid), dim3(256), 0, st, g, cnt,
+                                  (unsigned long long *)nullptr, (unsigned long long *)nullptr);
+        if (func == 1) {
+            HIPCHK(ctx, hipMemsetAsync(edges, 0, ns * 4, st));
+            if (n) hipLaunchKernelGGL(k_spatial_edges, dim3(grid), dim3(256), 0, st, g, params[0] != 0.0, edges);
+        } else {
+            HIPCHK(ctx, hipMemsetAsync(vsum, 0, vrows * 12, st));
+            HIPCHK(ctx, hipMemsetAsync(vflag, 0, fwords * 4 + 8, st));
+            if (n) hipLaunchKernelGGL(k_spatial_vario, dim3(grid), dim3(256), 0, st, g, d_offs,
+                                      (uint32_t)offs.size(), maxd, vcnt, vsum, vflag, nflag);
+        }
+    }
+    KCHK(ctx);
+    hipLaunchKernelGGL(k_spatial_finish, dim3(grid_for(ns, 256)), dim3(256), 0, st, func, S, cnt, sumx, sumy,
+                       edges, vcnt, vsum, maxd, d_prm, (long long)missing, nint, nflt, d_int, d_flt);
+    KCHK(ctx);
+    if (func == 2) {        // the flagged pairs again, in the reference's order, over the whole raster
+        std::vector<unsigned long long> pairs;
+        CHK(vario_flag_download(ctx, vflag, fwords, 0ull, nflag, pairs));
+        const uint32_t np = (uint32_t)pairs.size();
+        std::vector<double> vs(np, 0.0);
+        std::vector<uint32_t> vc(np, 0u);
+        const SpatialWin w{d_seg, nullptr, nullptr, d_band, nullptr, nullptr, dtype, ncols, nrows, 0u, 0u, S,
+                           (long long)null_val, 0ull};
+        CHK(spatial_vario_redo(ctx, w, maxd, pairs.data(), np, vs.data(), vc.data()));
+        CHK(spatial_vario_store(ctx, pairs.data(), np, vs.data(), vc.data(), maxd, ns, nflt, d_flt, 1));
+        ctx->vario_redo = (int64_t)np;
+    }
+    if (nint) HIPCHK(ctx, hipMemcpyAsync(intcols_out, d_int, (size_t)nint * ns * 8, hipMemcpyDeviceToHost, st));
+    if (nflt) HIPCHK(ctx, hipMemcpyAsync(fltcols_out, d_flt, (size_t)nflt * ns * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
 // the accumulators of one call: per id (local part) or per id of the share (merge)
 struct SpatialAcc {
     uint32_t *cnt, *edges, *vcnt;
     unsigned long long *sumx, *sumy, *vsum;
     double *prm;
     uint32_t *offs;
+    uint32_t *vflag, *nflag;        // the variogram's flags (vario_flag), fwords words, and their count
+    size_t fwords;
 };
 
 // cnt, edges, sumx | sumy, vsum | vcnt for `rows` ids, the parameters and the variogram's offsets
@@ -467,6 +710,10 @@ static int spatial_acc(shp_ctx *ctx, int func, size_t rows, uint32_t maxd, const
     CHK(buf_ensure(ctx, ctx->aux, rows * 16));
     CHK(buf_ensure(ctx, ctx->aux2, vrows * 12 + 64));
     CHK(buf_ensure(ctx, ctx->small, 4096 + offs.size() * 4));
+    a->fwords = func == 2 ? (vrows + 31) / 32 : 0;
+    CHK(buf_ensure(ctx, ctx->vflag, a->fwords * 4 + 64));
+    a->vflag = bp<uint32_t>(ctx->vflag);
+    a->nflag = a->vflag + a->fwords;
     a->cnt = bp<uint32_t>(ctx->segsz);
     a->edges = bp<uint32_t>(ctx->origsz);
     a->sumx = (unsigned long long *)ctx->aux.p;
@@ -480,15 +727,18 @@ static int spatial_acc(shp_ctx *ctx, int func, size_t rows, uint32_t maxd, const
     if (func == 0) HIPCHK(ctx, hipMemsetAsync(a->sumx, 0, rows * 16, st));
     if (func == 1) HIPCHK(ctx, hipMemsetAsync(a->edges, 0, rows * 4, st));
     if (func == 2) HIPCHK(ctx, hipMemsetAsync(a->vsum, 0, vrows * 12, st));
+    HIPCHK(ctx, hipMemsetAsync(a->vflag, 0, a->fwords * 4 + 8, st));
     return 0;
 }
 
 // Rank-local part: accumulate over the own rows, classify every id, pack the straddlers' records (a scan over
 // the ids places them: no atomic per id) into the context's workspace.  checks[0..2] = ctr of k_dspatial_classify.
+// The variogram's flagged pairs of the own rows (s * maxd + bin, ascending) go to ctx->vario_pairs.
 static int run_dspatial_local(shp_ctx *ctx, const SpatialWin &w, int func, const double *params, int64_t missing,
                               int nint, int nflt, const uint32_t *d_hist, int keep_unheld, void *d_cols,
                               void **d_rec, int64_t *n_rec, int64_t *rec_words, int64_t *checks)
 {
+    ctx->vario_pairs.clear();
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)w.S + 1;
     const size_t n = (size_t)w.h * w.ncols;
@@ -516,7 +766,7 @@ static int run_dspatial_local(shp_ctx *ctx, const SpatialWin &w, int func, const
             hipLaunchKernelGGL(k_spatial_wedges, dim3(grid), dim3(256), 0, st, w, params[0] != 0.0, a.edges);
         if (func == 2)
             hipLaunchKernelGGL(k_spatial_wvario, dim3(grid), dim3(256), 0, st, w, a.offs, (uint32_t)offs.size(), maxd,
-                               a.vcnt, a.vsum);
+                               a.vcnt, a.vsum, a.vflag, a.nflag);
         KCHK(ctx);
     }
     long long *cint = (long long *)d_cols;
@@ -537,6 +787,7 @@ static int run_dspatial_local(shp_ctx *ctx, const SpatialWin &w, int func, const
                            a.cnt, a.sumx, a.sumy, a.edges, a.vcnt, a.vsum, maxd, W,
                            (unsigned long long *)ctx->tlist.p);
     KCHK(ctx);
+    if (func == 2) CHK(vario_flag_download(ctx, a.vflag, a.fwords, 0ull, a.nflag, ctx->vario_pairs));
     *d_rec = ctx->tlist.p;
     *n_rec = (int64_t)nr;
     *rec_words = (int64_t)W;
@@ -567,7 +818,11 @@ __global__ __launch_bounds__(256) void k_dspatial_scatter(
     else if (func == 0) atomicAdd(wd == 2 ? &a.sumx[i] : &a.sumy[i], v);
     else if (func == 1) atomicAdd(&a.edges[i], (uint32_t)v);
     else if (wd < 2u + maxd) atomicAdd(&a.vcnt[i * maxd + (wd - 2u)], (uint32_t)v);
-    else atomicAdd(&a.vsum[i * maxd + (wd - 2u - maxd)], v);
+    else {          // the ranks' partial sums: flagged where they add up to 2^53 or more (see vario_add)
+        const size_t j = i * maxd + (wd - 2u - maxd);
+        const unsigned long long old = atomicAdd(&a.vsum[j], v);
+        if (v >= VARIO_EXACT || old + v >= VARIO_EXACT) vario_flag(a.vflag, a.nflag, j);
+    }
 }
 
 __global__ __launch_bounds__(256) void k_dspatial_finish_share(int func, uint32_t S, uint32_t id_lo, uint32_t nshare,
@@ -590,6 +845,7 @@ static int run_dspatial_merge(shp_ctx *ctx, const unsigned long long *d_rec, uin
 {
     hipStream_t st = ctx->stream;
     *n_ids = 0;
+    ctx->vario_pairs.clear();
     if ((size_t)slot * world == 0 || id_lo >= id_hi) return 0;
     const uint32_t maxd = func == 2 ? (uint32_t)params[0] : 0u;
     const uint32_t W = dspatial_rec_words(func, maxd);
@@ -615,5 +871,7 @@ static int run_dspatial_merge(shp_ctx *ctx, const unsigned long long *d_rec, uin
     uint32_t ids = 0;
     CHK(read_u32(ctx, d_n, &ids));
     *n_ids = (int64_t)ids;
+    if (func == 2) CHK(vario_flag_download(ctx, a.vflag, a.fwords, (unsigned long long)id_lo * maxd, a.nflag,
+                                           ctx->vario_pairs));
     return 0;
 }

@@ -875,6 +875,7 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
             nCols, halo['segUp'], halo['bandUp'], ha, halo['segDn'], halo['bandDn'], hb, lo if h else 0, nRows, S,
             int(imgNullVal), func, _lib.ptr(params), int(missing), nInt, nFloat, d_hist, int(comm.rank == 0), d_cols,
             ctypes.byref(pRec), ctypes.byref(nRec), ctypes.byref(W), _lib.ptr(checks)))
+        flagged = [_varioPairs(c)] if func == 2 else []
         got = comm.allgather_obj((int(nRec.value), [int(x) for x in checks]))
         over = sum(g[1][0] for g in got)
         (px, hpx) = (sum(g[1][1] for g in got), got[0][1][2])
@@ -896,6 +897,14 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
             c.check(L.shp_dspatial_merge_dev(c.handle, d_all, recSlot, comm.world, _lib.ptr(cnts), S, func,
                                              _lib.ptr(params), int(missing), nInt, nFloat, idLo, idHi, d_cols,
                                              ctypes.byref(nIds)))
+            if func == 2:
+                flagged.append(_varioPairs(c))
+        if func == 2:
+            nRedo = _varioRedo(c, comm, ranges, flagged, d_seg if h else None, d_band if h else None, dtypeCode, h, nCols,
+                               halo['segDn'], halo['bandDn'], hb, S, imgNullVal, int(params[0]), nInt, nFloat,
+                               d_cols)
+            if info is not None:
+                info['varioRecomputed'] = nRedo
         if comm.world > 1:
             comm.allreduce_dev_i64(d_cols.value, colWords)
         (ic, fc) = (None, None)
@@ -911,6 +920,41 @@ def deviceSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRange
             tiling._devRelease(c, p, sz)
     tot = comm.allgather_obj((int(nIds.value), ha + hb))
     return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
+
+
+def _varioPairs(c):
+    """The flagged variogram pairs (s * maxDist + bin) of the context's last local or merge step (uint64)."""
+    n = ctypes.c_int64(0)
+    c.check(c._L.shp_dspatial_vario_pairs(c.handle, None, 0, ctypes.byref(n)))
+    out = numpy.zeros(n.value, dtype=numpy.uint64)
+    if n.value:
+        c.check(c._L.shp_dspatial_vario_pairs(c.handle, _lib.ptr(out), n.value, ctypes.byref(n)))
+    return out
+
+
+def _varioRedo(c, comm, ranges, flagged, d_seg, d_band, dtypeCode, h, nCols, segDn, bandDn, hb, S, imgNullVal, maxDist,
+               nInt, nFloat, d_cols):
+    """The variogram pairs flagged on any rank (the union of ``flagged``, every rank's local and merge flags),
+    recomputed in the reference's order: rank after rank from the top of the image (``ranges``: every rank's
+    output rows), each continuing the sums and counts over its own rows; rank 0 stores the pairs' entries into d_cols and the others zero them, so that the
+    sum of the column blocks holds them.  Returns the number of pairs."""
+    mine = numpy.concatenate(flagged) if flagged else numpy.zeros(0, dtype=numpy.uint64)
+    pairs = numpy.unique(numpy.concatenate(comm.allgather_obj(mine)).astype(numpy.uint64))
+    n = len(pairs)
+    if n == 0:
+        return 0
+    (sums, cnts) = (numpy.zeros(n, dtype=numpy.float64), numpy.zeros(n, dtype=numpy.uint32))
+    for r in sorted(range(comm.world), key=lambda k: (ranges[k][0], k)):
+        if r == comm.rank and h:
+            c.check(c._L.shp_dspatial_vario_redo_dev(
+                c.handle, ctypes.c_void_p(d_seg), ctypes.c_void_p(d_band), dtypeCode, h, nCols, segDn, bandDn, hb,
+                S, int(imgNullVal), maxDist, _lib.ptr(pairs), n, _lib.ptr(sums), _lib.ptr(cnts)))
+        if comm.world > 1:
+            (sums, cnts) = comm.allgather_obj((sums, cnts) if r == comm.rank else None)[r]
+            (sums, cnts) = (numpy.ascontiguousarray(sums), numpy.ascontiguousarray(cnts))
+    c.check(c._L.shp_dspatial_vario_store_dev(c.handle, _lib.ptr(pairs), n, _lib.ptr(sums), _lib.ptr(cnts),
+                                              maxDist, S, nInt, nFloat, d_cols, int(comm.rank == 0)))
+    return n
 
 
 def subsetHeldRows(rowRange, tly, ys):

@@ -847,6 +847,16 @@ def calcPerSegmentSpatialStats(seg, band, colTypes, userFunc, userParam, imgNull
     return intcols[:nInt], floatcols[:nFloat]
 
 
+def variogramRecomputed():
+    """The (segment, bin) pairs the calling thread's last built-in variogram recomputed in the reference's
+    float64 order, because a squared difference or a bin's integer sum reached 2^53 (wide 32-bit imagery, or very
+    large segments): 0 when the integer sums were the reference's sums already."""
+    c = _lib.ctx()
+    n = ctypes.c_int64(0)
+    c.check(c._L.shp_spatial_vario_redo_count(c.handle, ctypes.byref(n)))
+    return int(n.value)
+
+
 def calcPerSegmentSpatialStatsTiled(imgfile, imgbandnum, segfile, colNamesAndTypes, userFunc,
         userParam=None, missingStatsValue=-9999, imgNullVal=None, tileSize=TILESIZE):
     """

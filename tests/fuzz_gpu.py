@@ -224,6 +224,12 @@ def more_case(rng, kind, tmpdir):
     band = make_image(rng, dtype, 1, nr, nc)[0]
     nullv = int(band.flat[int(rng.integers(0, band.size))])
     if kind == 'spatial':
+        if np.dtype(dtype).itemsize == 4 and rng.random() < 0.5:     # wide 32-bit values: squares past 2^53
+            info = np.iinfo(dtype)
+            span = int(rng.choice([10 ** 8, 10 ** 9, 1 << 32]))
+            lo = max(int(info.min), -(span // 2)) if info.min < 0 else 0
+            band = rng.integers(lo, min(int(info.max), lo + span), size=band.shape, endpoint=True).astype(dtype)
+            nullv = int(band.flat[int(rng.integers(0, band.size))])
         ts = tilingstats
         R, I = ts.GFT_Real, ts.GFT_Integer
         which = int(rng.integers(0, 3))

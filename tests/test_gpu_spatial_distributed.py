@@ -10,6 +10,7 @@ import pytest
 from conftest import ROOT
 
 import dist_cases
+import spatial_cases as sc
 import spatial_dist_helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -37,10 +38,39 @@ SHARDS = {1: [(0, 61)], 2: [(0, 29), (29, 61)], 3: [(0, 25), (25, 27), (27, 61)]
 @pytest.mark.parametrize('world,dtype,nullv', [(1, np.uint16, 65535), (2, np.uint8, 0), (3, np.int16, -7),
                                                (4, np.uint32, 4000), (4, np.uint16, 3)])
 def test_spatial_split_matches_one_gpu(world, dtype, nullv, oracle):
+    _check_split(world, dtype, nullv, None, oracle)
+
+
+@pytest.mark.parametrize('world,dtype,nullv,span', [(2, np.int32, -2 ** 31, 'full'), (3, np.uint32, 2 ** 32 - 1, 'mid'),
+                                                    (4, np.int32, 7, 'mid'), (4, np.uint32, 0, 'full')])
+def test_spatial_split_wide_values(world, dtype, nullv, span, oracle):
+    """32-bit values whose squared differences pass 2^53 (mid) or wrap the reference's int64 square (full): the
+    flagged variogram pairs, straddlers among them, are recomputed rank after rank"""
+    _check_split(world, dtype, nullv, span, oracle)
+
+
+@pytest.mark.parametrize('world', [2, 3, 4])
+def test_spatial_split_chain_across_shards(world, oracle):
+    """spatial_cases' order-sensitive chain (+2^62, small terms lost under its ulp, then about -2^62) down rows
+    5..47, across every shard boundary: only the ranks' recomputes carried on in row order give the reference's
+    value"""
+    _check_split(world, np.uint32, 4000, 'chain', oracle)
+
+
+def _check_split(world, dtype, nullv, span, oracle):
     from pyshepseg_amd import distributed, tilingstats as ts, _lib
     rng = np.random.default_rng(world * 100 + np.dtype(dtype).itemsize)
     (nr, nc) = (61, 83)
     (seg, band, S) = H.blockRaster(rng, nr, nc, dtype, nullv)
+    if span == 'chain':
+        sc.plant_chain(seg, band, 5, 20, int(seg.max()) + 1)
+        S = int(seg.max()) + 3
+    elif span is not None:          # the same nodata pixels, values over the span
+        info = np.iinfo(dtype)
+        (lo, hi) = (int(info.min), int(info.max)) if span == 'full' else (max(int(info.min), -10 ** 9), 10 ** 9)
+        wide = rng.integers(lo, hi, size=band.shape, endpoint=True, dtype=np.int64)
+        wide[wide == nullv] = nullv + 1 if nullv < hi else nullv - 1
+        band = np.where(band == nullv, nullv, wide).astype(dtype)
     hist = np.bincount(seg.ravel(), minlength=S + 1).astype(np.uint32)
     hist[0] = 0
     cases = _cases()
@@ -49,9 +79,10 @@ def test_spatial_split_matches_one_gpu(world, dtype, nullv, oracle):
     def work(c, comm, d_seg, d_band, rr):
         out = []
         for (_name, fn, prm, types, _exact) in cases:
+            info = {}
             res = distributed.deviceSpatialStats(c, comm, d_seg, d_band, _lib.SHP_DTYPES[np.dtype(dtype)], nr, nc, rr,
-                                                 hist, types, fn, prm, -9999, nullv)
-            out.append(res)
+                                                 hist, types, fn, prm, -9999, nullv, info=info)
+            out.append(res + (info.get('varioRecomputed'),))
         return out
     (results, errors) = H.runShards(seg, band, ranges, work)
     assert not any(errors), errors
@@ -63,11 +94,15 @@ def test_spatial_split_matches_one_gpu(world, dtype, nullv, oracle):
     assert world == 1 or len(strad) > 10
     for (k, (name, fn, prm, types, exact)) in enumerate(cases):
         (wi, wf) = ts.calcPerSegmentSpatialStats(seg, band, types, fn, prm, nullv, maxSegId=S)
+        oneRedo = ts.variogramRecomputed() if name == 'variogram' else None
         nInt = sum(1 for t in types if t == ts.GFT_Integer)
         (oi, of) = oracle.spatialstats(seg, band, name, prm, nullv, nInt, len(types) - nInt, max_seg_id=S)
         for r in range(world):
-            (ic, fc, nStrad, halo) = results[r][k]
+            (ic, fc, nStrad, halo, nRedo) = results[r][k]
             assert nStrad == len(strad), (name, prm, r)
+            if name == 'variogram':
+                assert nRedo == oneRedo, (prm, r)
+                assert (nRedo > 0) == (span is not None), (prm, r)
             assert np.array_equal(ic, wi), (name, prm, r)
             assert np.array_equal(fc.view(np.uint32), wf.view(np.uint32)), (name, prm, r)
             assert np.array_equal(ic, oi), (name, prm, r)
