@@ -333,6 +333,23 @@ int shp_gather_flagged_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_ba
                            int64_t npix, uint32_t max_seg_id, const uint8_t *flags, int64_t cap,
                            uint32_t *seg_out, int64_t *val_out, int64_t *count_out);
 
+/* Several bands of one image against the same label raster in one pass over the labels (the reference loops
+ * calcPerSegmentStatsTiled over the bands, cmdline/tiling.py:238-251).  d_bands: nbands device pointers, the bands'
+ * planes of the row block, all of pixel type dtype; has_null / null_val: one entry per band.  stats_sel: the bands'
+ * selections one after the other (nstats_per_band[b] rows for band b), built as for ONE call: the column array
+ * index runs through all bands.  intcols_out / floatcols_out: all bands' columns, (#int stats) x (max_seg_id+1)
+ * int64 and (#float stats) x (max_seg_id+1) float32.  Every column has the bits shp_segstats2d_dev gives for its
+ * band alone. */
+int shp_segstats2d_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_bands, int dtype, int nbands,
+                             int64_t nrows, int64_t ncols, uint32_t max_seg_id, const int *has_null,
+                             const int64_t *null_val, const uint32_t *stats_sel, const int *nstats_per_band,
+                             int64_t missing, int64_t *intcols_out, float *floatcols_out);
+/* shp_gather_flagged_dev for several bands: the ids once (seg_out), and val_out = nbands rows of cap int64 values,
+ * every band's in the order of seg_out. */
+int shp_gather_flagged_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_bands, int dtype,
+                                 int nbands, int64_t npix, uint32_t max_seg_id, const uint8_t *flags, int64_t cap,
+                                 uint32_t *seg_out, int64_t *val_out, int64_t *count_out);
+
 /* The same split with everything left in device memory (the data path of calcPerSegmentStatsDistributed
  * under RCCL; the reference has no counterpart: its per-segment dictionaries live in one process,
  * tilingstats.py:466-553).

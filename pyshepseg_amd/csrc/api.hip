@@ -1175,6 +1175,36 @@ API int shp_gather_flagged_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *
                               seg_out, val_out, count_out);
 }
 
+// several bands of one image against the same labels in one pass (segstats.h: run_segstats_bands)
+API int shp_segstats2d_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_bands, int dtype, int nbands,
+                                 int64_t nrows, int64_t ncols, uint32_t max_seg_id, const int *has_null,
+                                 const int64_t *null_val, const uint32_t *stats_sel, const int *nstats_per_band,
+                                 int64_t missing, int64_t *intcols_out, float *floatcols_out)
+{
+    CHK(enter(ctx));
+    if (!d_seg || !d_bands || !has_null || !null_val || !stats_sel || !nstats_per_band || nbands < 1 ||
+        dtype_size(dtype) == 0 || nrows < 0 || ncols < 0)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0xffffffffll || ncols > 0xffffffffll || nrows * ncols >= 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "raster too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    return run_segstats_bands(ctx, d_seg, d_bands, dtype, nbands, (uint32_t)nrows, (uint32_t)ncols, max_seg_id, has_null,
+                              null_val, stats_sel, nstats_per_band, missing, intcols_out, floatcols_out);
+}
+
+API int shp_gather_flagged_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_bands, int dtype,
+                                     int nbands, int64_t npix, uint32_t max_seg_id, const uint8_t *flags, int64_t cap,
+                                     uint32_t *seg_out, int64_t *val_out, int64_t *count_out)
+{
+    CHK(enter(ctx));
+    if (!d_seg || !d_bands || nbands < 1 || !flags || !count_out || dtype_size(dtype) == 0 || cap < 0 ||
+        (cap > 0 && (!seg_out || !val_out)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (npix < 0 || npix >= 0xffffffffll || cap >= 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "raster too large (%lld px)", (long long)npix);
+    return run_gather_flagged_bands(ctx, d_seg, d_bands, dtype, nbands, (uint32_t)npix, max_seg_id, flags, (uint32_t)cap,
+                                    seg_out, val_out, count_out);
+}
+
 // the multi-GPU split with everything left in device memory (segstats.h: run_dstats_local / run_dstats_merge)
 API int shp_dstats_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
                              int64_t ncols, uint32_t max_seg_id, int has_null, int64_t null_val,

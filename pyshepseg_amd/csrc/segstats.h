@@ -524,6 +524,50 @@ static int segstats_download(shp_ctx *ctx, void *intcols_out, const void *d_int,
     return 0;
 }
 
+// The two sorts and the reducers over n (segment key, biased value) pairs in ctx->aux2 / ctx->aux: by value (payload:
+// segment key), then stably by segment key (payload: value); then a thread per segment (k_seg_stats), a wavefront per
+// long one (k_seg_stats_big).  only != nullptr: only the rows of flagged segments are written.
+static int segstats_sort_reduce(shp_ctx *ctx, uint32_t n, uint32_t S, int valbits, long long bias, const uint32_t *d_sel,
+                                int nstats, int64_t missing, long long *d_int, float *d_flt, const uint8_t *only)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    uint32_t *kval = bp<uint32_t>(ctx->aux), *kseg = bp<uint32_t>(ctx->aux2);
+    uint32_t *cnt = bp<uint32_t>(ctx->segsz), *off = bp<uint32_t>(ctx->off);
+    // sort by value (payload: segment key), then stably by segment key (payload: value)
+    uint32_t *k1 = nullptr, *v1 = nullptr, *k2 = nullptr, *v2 = nullptr;
+    CHK(sort_pairs(ctx, kval, kseg, n, valbits, &k1, &v1, true));            // k1 = values, v1 = seg keys
+    // the second sort reads the first one's result where it lies unless its own first pass would
+    // write into the same ping-pong buffers (that depends on the two pass counts' parities)
+    const uint32_t *in_seg = v1, *in_val = k1;
+    {
+        const int passes2 = (bits_for(S) + 7) / 8;
+        const uint32_t *out_k = bp<uint32_t>(ctx->sort_k0);
+        const uint32_t *out_v = (passes2 & 1) ? bp<uint32_t>(ctx->pix) : bp<uint32_t>(ctx->sort_v1);
+        if (n && (k1 == out_k || k1 == out_v || v1 == out_k || v1 == out_v)) {
+            HIPCHK(ctx, hipMemcpyAsync(kval, k1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(ctx, hipMemcpyAsync(kseg, v1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+            in_seg = kseg; in_val = kval;
+        }
+    }
+    CHK(sort_pairs(ctx, in_seg, in_val, n, bits_for(S), &k2, &v2, true));    // k2 = seg keys, v2 = values
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, ns * 4, st));
+    if (n) {
+        hipLaunchKernelGGL(k_run_count, dim3(grid_for(n, 256)), dim3(256), 0, st, k2, n, cnt, 0u, 0); KCHK(ctx);
+    }
+    ArrFn cf{cnt};
+    CHK(scan_exclusive(ctx, cf, (uint32_t)ns, off, nullptr, bp<uint32_t>(ctx->scan_tmp)));
+    // (the list of long segments: in the first sort's key buffer, free by now)
+    uint32_t *biglist = kval;
+    HIPCHK(ctx, hipMemsetAsync(biglist, 0, 4, st));
+    hipLaunchKernelGGL(k_seg_stats, dim3(grid_for(ns, 256)), dim3(256), 0, st, v2, off, cnt, S, bias, d_sel,
+                       nstats, (long long)missing, d_int, d_flt, biglist, only); KCHK(ctx);
+    hipLaunchKernelGGL(k_seg_stats_big, dim3(512), dim3(256), 0, st, v2, off, cnt, S, bias, d_sel, nstats,
+                       (long long)missing, d_int, d_flt, biglist); KCHK(ctx);      // (only flagged ones got onto the list)
+    return 0;
+}
+
 static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
                         uint32_t n, uint32_t S, int has_null, int64_t null_val,
                         const uint32_t *sel_host, int nstats, int64_t missing,
@@ -556,7 +600,6 @@ static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band,
     CHK(buf_ensure(ctx, ctx->small, 4096 + (size_t)nstats * 20));
     CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
     uint32_t *kval = bp<uint32_t>(ctx->aux), *kseg = bp<uint32_t>(ctx->aux2);
-    uint32_t *cnt = bp<uint32_t>(ctx->segsz), *off = bp<uint32_t>(ctx->off);
     uint32_t *d_sel = bp<uint32_t>(ctx->small) + 256;
     long long *d_int = (long long *)ctx->ssum.p;
     float *d_flt = (float *)(d_int + (size_t)nint * ns);
@@ -601,40 +644,328 @@ static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band,
         if (dev_int) { *dev_int = d_int; *dev_flt = d_flt; return 0; }
         return segstats_download(ctx, intcols_out, d_int, (size_t)nint * ns * 8, fltcols_out, d_flt, (size_t)nflt * ns * 4);
     }
-    n = nsort;
-    // sort by value (payload: segment key), then stably by segment key (payload: value)
-    uint32_t *k1 = nullptr, *v1 = nullptr, *k2 = nullptr, *v2 = nullptr;
-    CHK(sort_pairs(ctx, kval, kseg, n, valbits, &k1, &v1, true));            // k1 = values, v1 = seg keys
-    // the second sort reads the first one's result where it lies unless its own first pass would
-    // write into the same ping-pong buffers (that depends on the two pass counts' parities)
-    const uint32_t *in_seg = v1, *in_val = k1;
-    {
-        const int passes2 = (bits_for(S) + 7) / 8;
-        const uint32_t *out_k = bp<uint32_t>(ctx->sort_k0);
-        const uint32_t *out_v = (passes2 & 1) ? bp<uint32_t>(ctx->pix) : bp<uint32_t>(ctx->sort_v1);
-        if (n && (k1 == out_k || k1 == out_v || v1 == out_k || v1 == out_v)) {
-            HIPCHK(ctx, hipMemcpyAsync(kval, k1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-            HIPCHK(ctx, hipMemcpyAsync(kseg, v1, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-            in_seg = kseg; in_val = kval;
-        }
-    }
-    CHK(sort_pairs(ctx, in_seg, in_val, n, bits_for(S), &k2, &v2, true));    // k2 = seg keys, v2 = values
-    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
-    HIPCHK(ctx, hipMemsetAsync(cnt, 0, ns * 4, st));
-    if (n) {
-        hipLaunchKernelGGL(k_run_count, dim3(grid_for(n, 256)), dim3(256), 0, st, k2, n, cnt, 0u, 0); KCHK(ctx);
-    }
-    ArrFn cf{cnt};
-    CHK(scan_exclusive(ctx, cf, (uint32_t)ns, off, nullptr, bp<uint32_t>(ctx->scan_tmp)));
-    // (the list of long segments: in the first sort's key buffer, free by now)
-    uint32_t *biglist = kval;
-    HIPCHK(ctx, hipMemsetAsync(biglist, 0, 4, st));
-    hipLaunchKernelGGL(k_seg_stats, dim3(grid_for(ns, 256)), dim3(256), 0, st, v2, off, cnt, S, bias, d_sel,
-                       nstats, (long long)missing, d_int, d_flt, biglist, only); KCHK(ctx);
-    hipLaunchKernelGGL(k_seg_stats_big, dim3(512), dim3(256), 0, st, v2, off, cnt, S, bias, d_sel, nstats,
-                       (long long)missing, d_int, d_flt, biglist); KCHK(ctx);      // (only flagged ones got onto the list)
+    CHK(segstats_sort_reduce(ctx, nsort, S, valbits, bias, d_sel, nstats, missing, d_int, d_flt, only));
     prof_end(ctx, ps);
     if (dev_int) { *dev_int = d_int; *dev_flt = d_flt; return 0; }
+    return segstats_download(ctx, intcols_out, d_int, (size_t)nint * ns * 8, fltcols_out, d_flt, (size_t)nflt * ns * 4);
+}
+
+// ---- several bands in one pass over the labels ------------------------------------------------------------------
+// The bands of one image share the label raster, and most of the work above depends on the labels alone: the label
+// totals (k_label_hist_patch), the slot table of a patch, which labels are complete in it, and which pixels are left
+// over for the sorts.  k_stats_patch_bands does that part once per patch and then takes the bands one after the other
+// through the same LDS arrays; what is left over is ONE list of (label, pixel position), from which each band
+// gathers its values for the two sorts.
+// A label is complete in a patch when all its pixels lie there and they are at most SPP_MAXRUN -- ALL pixels, where
+// k_stats_patch asks that of the valid ones: the valid count differs from band to band, the pixel count does not,
+// and a label's row has the same bits on either path (a run is a run).
+struct StatsBand {                  // one entry of the device table, 32 bytes
+    const void *band;               // the band's plane of the row block (device memory)
+    long long null_val;
+    int has_null;
+    int sel_first, nstats;          // its rows of the combined selection
+    int pad;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_stats_patch_bands(
+    const uint32_t *__restrict__ seg, const StatsBand *__restrict__ bands, int nbands, uint32_t nrows, uint32_t ncols,
+    uint32_t S, long long bias, const uint32_t *__restrict__ tot, const uint32_t *__restrict__ sel, long long missing,
+    long long *__restrict__ intcols, float *__restrict__ fltcols, uint8_t *__restrict__ flagged,
+    uint32_t *__restrict__ left_seg, uint32_t *__restrict__ left_pos, uint32_t *left_count)
+{
+    // (the same LDS as k_stats_patch, byte for byte: the arrays are reused from band to band.  cnt[]: bit 31 = the
+    //  label is complete here; the two 15-bit halves below it are the run's fill counter, bands taking them in turn,
+    //  so that a band's counter can be cleared while nobody reads it -- during the next band)
+    __shared__ uint32_t key[SPP_SLOTS], cnt[SPP_SLOTS];
+    __shared__ uint16_t offs[SPP_SLOTS];
+    __shared__ uint32_t runs[SPP_H * SPP_W + SPP_MAXDIST];
+    __shared__ uint32_t s_ndist, s_left, s_leftbase, s_wsum[4], s_nc;
+    __shared__ uint16_t clist[SPP_SLOTS];
+    for (uint32_t i = threadIdx.x; i < SPP_SLOTS; i += 256u) { key[i] = SPP_EMPTY; cnt[i] = 0u; }
+    if (threadIdx.x == 0) { s_ndist = 0u; s_left = 0u; s_nc = 0u; }
+    __syncthreads();
+    const uint32_t x0 = blockIdx.x * SPP_W, y0 = blockIdx.y * SPP_H;
+    constexpr bool narrow = DT != SHP_I32 && DT != SHP_U32;         // biased values below 2^16
+    // this thread's pixels: pixel k is patch pixel k * 256 + threadIdx.x, through every phase and band
+    // (a band's values are loaded when its turn comes, not with the labels: holding the first band's through the
+    //  label phases, or the next band's through the statistics of the one at hand, takes the kernel past the 72
+    //  VGPRs of seven wavefronts per SIMD -- 28 to 36 bytes of scratch per lane in the compiler's report)
+    uint32_t pslot[SPP_PPT];
+    {
+        uint32_t ps[SPP_PPT];
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            const uint32_t pl = k * 256u + threadIdx.x;
+            const uint32_t y = y0 + pl / SPP_W, x = x0 + (pl % SPP_W);
+            ps[k] = 0u;
+            if (y < nrows && x < ncols) {
+                const uint32_t sg = seg[(size_t)y * ncols + x];
+                if (sg <= S) ps[k] = sg;
+            }
+        }
+        // ---- slots and pixel counts ----
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            pslot[k] = SPP_SLOTS;
+            if (ps[k] == 0u) continue;
+            uint32_t h = (ps[k] * 2654435761u) >> 22;
+            for (uint32_t probe = 0; probe < SPP_SLOTS; probe++) {
+                const uint32_t kk = key[h];
+                if (kk == ps[k]) { pslot[k] = h; break; }
+                if (kk == SPP_EMPTY) {
+                    const uint32_t old = atomicCAS(&key[h], SPP_EMPTY, ps[k]);
+                    if (old == SPP_EMPTY) { atomicAdd(&s_ndist, 1u); pslot[k] = h; break; }
+                    if (old == ps[k]) { pslot[k] = h; break; }
+                }
+                h = (h + 1u) & (SPP_SLOTS - 1u);
+            }
+            if (pslot[k] < SPP_SLOTS) atomicAdd(&cnt[pslot[k]], 1u);
+        }
+        __syncthreads();
+        const bool crowded = s_ndist > SPP_MAXDIST;          // (a pixel may then have found no slot at all)
+        // ---- which labels are complete here; run offsets by a scan of their pixel counts (a band's run is at most
+        //      that long, and one unused entry behind every run keeps runs of equal length off the same banks) ----
+        uint32_t mine[4], msum = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; q++) {
+            const uint32_t sl = threadIdx.x * 4u + q;
+            const uint32_t kk = key[sl], c = cnt[sl];
+            uint32_t nv = 0;
+            if (kk != SPP_EMPTY) {
+                const bool complete = !crowded && c == tot[kk] && c <= SPP_MAXRUN;
+                if (complete) { nv = c + 1u; clist[atomicAdd(&s_nc, 1u)] = (uint16_t)sl; }
+                else flagged[kk] = 1;
+                cnt[sl] = complete ? 0x80000000u : 0u;
+            }
+            mine[q] = nv;
+            msum += nv;
+        }
+        uint32_t incl = msum;                                  // inclusive scan over the workgroup's 256 threads
+        const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(incl, d, 64);
+            if ((int)lane >= d) incl += o;
+        }
+        if (lane == 63) s_wsum[wv] = incl;
+        __syncthreads();
+        uint32_t base = incl - msum;
+        for (unsigned w2 = 0; w2 < wv; w2++) base += s_wsum[w2];
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; q++) { offs[threadIdx.x * 4u + q] = (uint16_t)base; base += mine[q]; }
+        // ---- the pixels of every other label, nodata or not in whichever band: (label, position) into the list ----
+        // (pslot[k] becomes 0x80000000 | the pixel's place among the patch's left-over ones)
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            if (ps[k] == 0u) continue;
+            if (pslot[k] < SPP_SLOTS && (cnt[pslot[k]] & 0x80000000u)) continue;
+            if (pslot[k] >= SPP_SLOTS) flagged[ps[k]] = 1;     // (crowded: no slot, so nobody flagged its label above)
+            pslot[k] = 0x80000000u | atomicAdd(&s_left, 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && s_left) s_leftbase = atomicAdd(left_count, s_left);
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++)
+            if (pslot[k] & 0x80000000u) {
+                const uint32_t pl = k * 256u + threadIdx.x;
+                const uint32_t li = s_leftbase + (pslot[k] & 0x7FFFFFFFu);
+                left_seg[li] = ps[k];
+                left_pos[li] = (y0 + pl / SPP_W) * ncols + x0 + (pl % SPP_W);
+            }
+    }
+    // from here on pslot[k] < SPP_SLOTS says: a pixel of a label that is complete in this patch
+    const size_t ns = (size_t)S + 1;
+    const uint32_t nc = s_nc;
+    for (int b = 0; b < nbands; b++) {
+        const void *__restrict__ band = bands[b].band;
+        const bool has_null = bands[b].has_null != 0;
+        const long long null_val = bands[b].null_val;
+        const uint32_t sh = (b & 1) ? 15u : 0u;                 // this band's half of cnt[]
+        // ---- this band's values of complete labels into their runs ----
+        // rpos[k]: the place in the label's run; 0xFFFFFFFF: not a member of a run
+        uint32_t pv[SPP_PPT], rpos[SPP_PPT];
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            const uint32_t pl = k * 256u + threadIdx.x;
+            rpos[k] = 0xFFFFFFFFu;
+            pv[k] = 0u;
+            if (pslot[k] < SPP_SLOTS) {                         // (inside the raster, then)
+                const size_t p = (size_t)(y0 + pl / SPP_W) * ncols + x0 + (pl % SPP_W);
+                const long long v = ld_t<DT>(band, p);
+                pv[k] = (uint32_t)(v - bias);
+                if (!(has_null && v == null_val)) rpos[k] = 0u;
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            if (rpos[k] == 0xFFFFFFFFu) continue;
+            const uint32_t sl = pslot[k];
+            rpos[k] = (atomicAdd(&cnt[sl], 1u << sh) >> sh) & 0x7FFFu;
+            runs[offs[sl] + rpos[k]] = narrow ? (pv[k] << 6) | rpos[k] : pv[k];
+        }
+        __syncthreads();
+        // (the other half of cnt[] served the band before: nobody reads it now)
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; q++) atomicAnd(&cnt[threadIdx.x * 4u + q], 0x80000000u | (0x7FFFu << sh));
+        // ---- the runs sorted by RANK, as in k_stats_patch ----
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++) {
+            if (rpos[k] == 0xFFFFFFFFu) continue;
+            const uint32_t sl = pslot[k];
+            const uint32_t n = (cnt[sl] >> sh) & 0x7FFFu, o = offs[sl];
+            const uint32_t v = pv[k];
+            uint32_t r = 0;
+            const uint32_t *q = &runs[o];
+            if (narrow) {
+                const uint32_t me = (v << 6) | rpos[k];
+                uint32_t j = 0;
+                for (; j + 8u <= n; j += 8u) {
+#pragma unroll
+                    for (uint32_t u = 0; u < 8u; u++) r += q[j + u] < me ? 1u : 0u;
+                }
+                for (; j < n; j++) r += q[j] < me ? 1u : 0u;
+            } else {
+                const uint32_t rp = rpos[k];
+                for (uint32_t j = 0; j < n; j++) {
+                    const uint32_t w = q[j];
+                    r += (w < v || (w == v && j < rp)) ? 1u : 0u;
+                }
+            }
+            rpos[k] = o + r;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = 0; k < SPP_PPT; k++)
+            if (rpos[k] != 0xFFFFFFFFu) runs[rpos[k]] = pv[k];
+        __syncthreads();
+        // ---- a thread per complete label, this band's statistics into this band's columns ----
+        const uint32_t *bsel = sel + (size_t)bands[b].sel_first * 5;
+        const int bnstats = bands[b].nstats;
+        for (uint32_t ci = threadIdx.x; ci < nc; ci += 256u) {
+            const uint32_t sl = clist[ci];
+            const uint32_t n = (cnt[sl] >> sh) & 0x7FFFu;
+            seg_stats_of_run(key[sl], n, &runs[offs[sl]], bias, bsel, bnstats, missing, intcols, fltcols, ns);
+        }
+        __syncthreads();                                        // (the next band overwrites runs[])
+    }
+}
+
+// a band's (segment key, biased value) pairs of the left-over pixels; nodata pixels get key 0 as in k_stats_keys
+__global__ __launch_bounds__(256) void k_stats_left_keys(const uint32_t *__restrict__ left_seg,
+                                                         const uint32_t *__restrict__ left_pos,
+                                                         const void *__restrict__ band, int dtype, uint32_t n,
+                                                         int has_null, long long null_val, long long bias,
+                                                         uint32_t *__restrict__ kseg, uint32_t *__restrict__ kval)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const long long v = ld_px(band, dtype, left_pos[i]);
+    kseg[i] = (has_null && v == null_val) ? 0u : left_seg[i];
+    kval[i] = (uint32_t)(v - bias);
+}
+
+// d_seg, bands_host[b] (device pointers): a row block of nrows x ncols pixels.  sel_host: the combined selection, nstats_per_band[b] consecutive rows for band b, column array indices
+// running through all bands; the outputs are HOST arrays of all bands' columns.
+static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *const *bands_host, int dtype, int nbands,
+                              uint32_t nrows, uint32_t ncols, uint32_t S, const int *has_null, const int64_t *null_val,
+                              const uint32_t *sel_host, const int *nstats_per_band, int64_t missing,
+                              int64_t *intcols_out, float *fltcols_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    const uint32_t n = nrows * ncols;
+    int nstats = 0;
+    for (int b = 0; b < nbands; b++) {
+        if (nstats_per_band[b] < 1 || !bands_host[b]) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry %d: no statistics or no band", b);
+        nstats += nstats_per_band[b];
+    }
+    int nint = 0, nflt = 0;
+    for (int i = 0; i < nstats; i++) {
+        const uint32_t stat = sel_host[i * 5 + 1], ctype = sel_host[i * 5 + 2];
+        if (stat > 7u || ctype > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
+        if (sel_host[i * 5 + 3] != (uint32_t)(ctype == 0 ? nint : nflt))
+            SHP_FAIL(ctx, SHP_ERR_ARG, "statsSelection entry %d: column array index does not run through the bands", i);
+        if (ctype == 0) nint++; else nflt++;
+    }
+    const size_t sel_bytes = ((size_t)nstats * 20 + 31) & ~(size_t)31, tab_bytes = (size_t)nbands * sizeof(StatsBand);
+    if (sel_bytes + tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many statistics");
+    long long bias = 0;
+    int valbits = 32;
+    switch (dtype) {
+    case SHP_U8: valbits = 8; break;
+    case SHP_U16: valbits = 16; break;
+    case SHP_I16: valbits = 16; bias = -32768; break;
+    case SHP_I32: bias = -2147483648ll; break;
+    default: break;
+    }
+    CHK(buf_ensure(ctx, ctx->aux, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->aux2, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->segsz, (ns + 1) * 4));
+    CHK(buf_ensure(ctx, ctx->off, (ns + 1) * 4 + 16));
+    CHK(buf_ensure(ctx, ctx->small, 4096 + sel_bytes + tab_bytes));
+    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
+    uint32_t *kval = bp<uint32_t>(ctx->aux), *kseg = bp<uint32_t>(ctx->aux2);
+    uint32_t *d_sel = bp<uint32_t>(ctx->small) + 256;
+    StatsBand *d_tab = (StatsBand *)(bp<uint8_t>(ctx->small) + 1024 + sel_bytes);
+    long long *d_int = (long long *)ctx->ssum.p;
+    float *d_flt = (float *)(d_int + (size_t)nint * ns);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    uint8_t *pin = (uint8_t *)(ctx->h_pinned + 16);
+    memcpy(pin, sel_host, (size_t)nstats * 20);
+    StatsBand *tab = (StatsBand *)(pin + sel_bytes);
+    for (int b = 0, first = 0; b < nbands; first += nstats_per_band[b], b++)
+        tab[b] = StatsBand{bands_host[b], (long long)(has_null[b] ? null_val[b] : 0), has_null[b] ? 1 : 0, first,
+                           nstats_per_band[b], 0};
+    HIPCHK(ctx, hipMemcpyAsync(d_sel, pin, sel_bytes + tab_bytes, hipMemcpyHostToDevice, st));
+    const int ps = prof_begin(ctx, PROF_SEGSTATS);
+    // (SHEPSEG_STATS_PATCH as in run_segstats)
+    const int patch_env = getenv("SHEPSEG_STATS_PATCH") ? atoi(getenv("SHEPSEG_STATS_PATCH")) : -1;
+    const bool patches = n && patch_env != 0 &&
+                         (patch_env == 1 || (uint64_t)n <= (uint64_t)SPP_MAXRUN * ((uint64_t)S + 1));
+    if (patches) {
+        CHK(buf_ensure(ctx, ctx->tcount, (ns + 1) * 4));
+        CHK(buf_ensure(ctx, ctx->mergeto, ns + 64));
+        CHK(buf_ensure(ctx, ctx->tlist, (size_t)n * 4));
+        CHK(buf_ensure(ctx, ctx->tsorted, (size_t)n * 4));
+        uint32_t *tot = bp<uint32_t>(ctx->tcount);
+        uint8_t *flagged = bp<uint8_t>(ctx->mergeto);
+        uint32_t *left_seg = bp<uint32_t>(ctx->tlist), *left_pos = bp<uint32_t>(ctx->tsorted);
+        uint32_t *d_left = bp<uint32_t>(ctx->small);      // (word 0; the selection sits behind word 256)
+        HIPCHK(ctx, hipMemsetAsync(tot, 0, ns * 4, st));
+        HIPCHK(ctx, hipMemsetAsync(flagged, 0, ns, st));
+        HIPCHK(ctx, hipMemsetAsync(d_left, 0, 4, st));
+        const dim3 grid(grid_for(ncols, SPP_W), grid_for(nrows, SPP_H));
+        hipLaunchKernelGGL(k_label_hist_patch, grid, dim3(256), 0, st, d_seg, nrows, ncols, S, tot); KCHK(ctx);
+        hipLaunchKernelGGL(k_stats_prefill, dim3(grid_for(ns, 256)), dim3(256), 0, st, S, bias, d_sel, nstats,
+                           (long long)missing, d_int, d_flt); KCHK(ctx);
+        DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_stats_patch_bands<DT>, grid, dim3(256), 0, st, d_seg, d_tab, nbands, nrows,
+                                                 ncols, S, bias, tot, d_sel, (long long)missing, d_int, d_flt, flagged,
+                                                 left_seg, left_pos, d_left));
+        KCHK(ctx);
+        uint32_t nleft = 0;
+        CHK(read_u32(ctx, d_left, &nleft));
+        if (nleft > n) SHP_FAIL(ctx, SHP_ERR_STATE, "%u left-over pixels of %u", nleft, n);
+        for (int b = 0, first = 0; nleft && b < nbands; first += nstats_per_band[b], b++) {
+            hipLaunchKernelGGL(k_stats_left_keys, dim3(grid_for(nleft, 256)), dim3(256), 0, st, left_seg, left_pos,
+                               bands_host[b], dtype, nleft, has_null[b] ? 1 : 0, (long long)(has_null[b] ? null_val[b] : 0), bias, kseg,
+                               kval); KCHK(ctx);
+            CHK(segstats_sort_reduce(ctx, nleft, S, valbits, bias, d_sel + (size_t)first * 5, nstats_per_band[b], missing,
+                                     d_int, d_flt, flagged));
+        }
+    } else {
+        for (int b = 0, first = 0; b < nbands; first += nstats_per_band[b], b++) {
+            if (n) {
+                hipLaunchKernelGGL(k_stats_keys, dim3(grid_for(n, 256)), dim3(256), 0, st, d_seg, bands_host[b], dtype, n, S,
+                                   has_null[b] ? 1 : 0, (long long)(has_null[b] ? null_val[b] : 0), bias, kseg, kval);
+                KCHK(ctx);
+            }
+            CHK(segstats_sort_reduce(ctx, n, S, valbits, bias, d_sel + (size_t)first * 5, nstats_per_band[b], missing,
+                                     d_int, d_flt, nullptr));
+        }
+    }
+    prof_end(ctx, ps);
     return segstats_download(ctx, intcols_out, d_int, (size_t)nint * ns * 8, fltcols_out, d_flt, (size_t)nflt * ns * 4);
 }
 
@@ -706,6 +1037,88 @@ static int run_gather_flagged(shp_ctx *ctx, const uint32_t *d_seg, const void *d
     if (take) {
         HIPCHK(ctx, hipMemcpyAsync(seg_out, ctx->aux.p, (size_t)take * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(val_out, ctx->aux2.p, (size_t)take * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+    }
+    *count_out = (int64_t)cnt;
+    return 0;
+}
+
+// The same for several bands of one image: the ids once, and every band's values in the SAME order (the order itself
+// is again arbitrary) -- out_val: nbands rows of cap values.
+__global__ __launch_bounds__(256) void k_gather_flagged_bands(const uint32_t *__restrict__ seg,
+                                                              const StatsBand *__restrict__ bands, int nbands, int dtype,
+                                                              uint32_t n, uint32_t S, const uint8_t *__restrict__ flags,
+                                                              uint32_t *__restrict__ out_seg,
+                                                              long long *__restrict__ out_val, uint32_t cap,
+                                                              uint32_t *count)
+{
+    __shared__ uint32_t s_buf[4096];
+    __shared__ uint32_t s_cnt, s_base;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const unsigned lane = lane_id();
+    for (uint32_t it = 0; it < 16u; it++) {
+        const uint32_t p = blockIdx.x * 4096u + it * 256u + threadIdx.x;
+        bool take = false;
+        if (p < n) {
+            const uint32_t sg = seg[p];
+            take = sg != 0u && sg <= S && flags[sg] != 0;
+        }
+        const unsigned long long m = __ballot(take);
+        if (m != 0ull) {
+            uint32_t wbase = 0;
+            if (lane == 0) wbase = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
+            wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+            if (take) s_buf[wbase + (uint32_t)__popcll(m & lanemask_lt())] = p;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_cnt ? atomicAdd(count, s_cnt) : 0u;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < s_cnt; i += 256u) {
+        const uint32_t o = s_base + i;
+        if (o < cap) {
+            const uint32_t p = s_buf[i];
+            out_seg[o] = seg[p];
+            for (int b = 0; b < nbands; b++) out_val[(size_t)b * cap + o] = ld_px(bands[b].band, dtype, p);
+        }
+    }
+}
+
+static int run_gather_flagged_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *const *bands_host, int dtype,
+                                    int nbands, uint32_t n, uint32_t S, const uint8_t *flags_host, uint32_t cap,
+                                    uint32_t *seg_out, int64_t *val_out, int64_t *count_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    const size_t tab_bytes = (size_t)nbands * sizeof(StatsBand);
+    if (tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many bands");
+    CHK(buf_ensure(ctx, ctx->small, 64 + tab_bytes + ns + 64));
+    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->aux2, (size_t)cap * 8 * nbands + 64));
+    uint32_t *d_count = bp<uint32_t>(ctx->small);
+    StatsBand *d_tab = (StatsBand *)(bp<uint8_t>(ctx->small) + 64);
+    uint8_t *d_flags = bp<uint8_t>(ctx->small) + 64 + tab_bytes;
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    StatsBand *tab = (StatsBand *)(ctx->h_pinned + 16);
+    for (int b = 0; b < nbands; b++) {
+        if (!bands_host[b]) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry %d: no band", b);
+        tab[b] = StatsBand{bands_host[b], 0, 0, 0, 0, 0};
+    }
+    HIPCHK(ctx, hipMemcpyAsync(d_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(d_flags, flags_host, ns, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(d_count, 0, 4, st));
+    if (n) {
+        hipLaunchKernelGGL(k_gather_flagged_bands, dim3(grid_for(n, 4096)), dim3(256), 0, st, d_seg, d_tab, nbands, dtype,
+                           n, S, d_flags, bp<uint32_t>(ctx->aux), (long long *)ctx->aux2.p, cap, d_count);
+        KCHK(ctx);
+    }
+    uint32_t cnt = 0;
+    CHK(read_u32(ctx, d_count, &cnt));
+    if (cnt && cap) {
+        const uint32_t take = cnt < cap ? cnt : cap;
+        HIPCHK(ctx, hipMemcpyAsync(seg_out, ctx->aux.p, (size_t)take * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(val_out, ctx->aux2.p, (size_t)cap * 8 * nbands, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
     }
     *count_out = (int64_t)cnt;

@@ -513,6 +513,333 @@ def _countSegments(src, chunkPixels):
     return out
 
 
+# ------------------------------------------------------------------------------------------
+# several bands against the same segmentation in one pass over the labels
+# ------------------------------------------------------------------------------------------
+def makeBandStatsSelection(bandSelections):
+    """The combined fast selection of ``bandSelections``, a list of (imgbandnum, statsSelection):
+    returns (fast, bandOfStat, numIntCols, numFloatCols), ``fast`` as makeFastStatsSelection gives it
+    for the statsSelections one after the other (the global column index and the per-type column
+    array index run through all entries), ``bandOfStat[i]`` the index of the bandSelections entry
+    that statistic i belongs to.  Column names must be unique over all entries and every
+    statsSelection non-empty."""
+    bandSelections = list(bandSelections)
+    if len(bandSelections) == 0:
+        raise PyShepSegStatsError("bandSelections must hold one or more (imgbandnum, statsSelection)")
+    flat = []
+    bandOfStat = []
+    names = set()
+    for (k, entry) in enumerate(bandSelections):
+        if len(entry) != 2:
+            raise PyShepSegStatsError("bandSelections entry {} is not (imgbandnum, statsSelection)".format(k))
+        statsSelection = list(entry[1])
+        if len(statsSelection) == 0:
+            raise PyShepSegStatsError("bandSelections entry {} (band {}) selects no statistic".format(k, entry[0]))
+        for sel in statsSelection:
+            if sel[0] in names:
+                raise PyShepSegStatsError("Column name '{}' is used more than once".format(sel[0]))
+            names.add(sel[0])
+            flat.append(sel)
+            bandOfStat.append(k)
+    (fast, nInt, nFloat) = makeFastStatsSelection(list(range(len(flat))), flat)
+    return (fast, numpy.array(bandOfStat, dtype=numpy.intp), nInt, nFloat)
+
+
+class _BandsChunkSource(_ChunkSource):
+    """_ChunkSource for several planes of one image: a row block is the labels and one device pointer
+    per plane.  bands: host planes (arrays / memmaps), or devBands: device addresses of whole planes."""
+    def __init__(self, c, seg, bands, devSeg=None, devBands=None, bandDtype=None, shape=None):
+        _ChunkSource.__init__(self, c, seg, None, devSeg=devSeg, devBand=None, bandDtype=bandDtype, shape=shape)
+        (self.bands, self.devBands) = (bands, devBands)
+        self.nplanes = len(bands if devBands is None else devBands)
+
+    def chunk(self, y0, y1):
+        n = (y1 - y0) * self.ncols
+        isz = self.bandDtype.itemsize
+        if self.devSeg is not None:
+            return (ctypes.c_void_p(self.devSeg + 4 * y0 * self.ncols),
+                    [ctypes.c_void_p(p + isz * y0 * self.ncols) for p in self.devBands])
+        s = numpy.ascontiguousarray(self.seg[y0:y1], dtype=shepseg.SegIdType)
+        ds = self._buf(0, n * 4)
+        self.c.check(self.c._L.shp_dev_upload(self.c.handle, ds, _lib.ptr(s), s.nbytes))
+        dbs = []
+        for (k, band) in enumerate(self.bands):
+            b = numpy.ascontiguousarray(band[y0:y1], dtype=self.bandDtype)
+            db = self._buf(3 + k, n * isz)
+            self.c.check(self.c._L.shp_dev_upload(self.c.handle, db, _lib.ptr(b), b.nbytes))
+            dbs.append(db)
+        return (ds, dbs)
+
+    def scratch(self, i, nbytes):
+        return self._buf(1 + i, nbytes)             # (buffers 1 and 2; the planes' start at 3)
+
+
+def _streamStatsBands(src, planeOfEntry, segSize, bandSelections, fast, bandOfStat, numIntCols, numFloatCols,
+                      nullVals, missingStatsValue, attrTbl, timings, chunkPixels):
+    """_streamStats for several bands (bandSelections entry k reads plane planeOfEntry[k] of src with the
+    null value nullVals[k]).  Per row block the labels go up and are renumbered once, all entries'
+    statistics come out of one library call (shp_segstats2d_bands_dev), the complete / unfinished split
+    -- a property of the labels -- is made once; the unfinished segments' pixels are set aside as ids
+    once and one value array per plane, in one order, and reduced per entry at the end."""
+    c = src.c
+    L = c._L
+    (nrows, ncols) = (src.nrows, src.ncols)
+    S = len(segSize) - 1
+    dt = _lib.SHP_DTYPES[src.bandDtype]
+    nEntries = len(bandSelections)
+    fast = numpy.ascontiguousarray(fast, dtype=numpy.uint32)
+    perBand = numpy.ascontiguousarray(numpy.bincount(bandOfStat, minlength=nEntries), dtype=numpy.int32)
+    hasNull = numpy.ascontiguousarray([int(v is not None) for v in nullVals], dtype=numpy.int32)
+    nullArr = numpy.ascontiguousarray([0 if v is None else int(v) for v in nullVals], dtype=numpy.int64)
+    emptyInt = numpy.full(numIntCols, int(missingStatsValue), dtype=numpy.int64)
+    emptyFloat = numpy.full(numFloatCols, float(missingStatsValue), dtype=numpy.float32)
+    for sel in fast:
+        if sel[STATSEL_STATID] == STATID_PIXCOUNT:
+            emptyInt[sel[STATSEL_COLARRAYINDEX]] = 0
+    pagedRat = createPagedRat()
+    written = set()
+
+    def flush():
+        written.update(pid for (pid, pg) in pagedRat.items() if pg.pageComplete())
+        writeCompletePages(pagedRat, attrTbl, fast)
+
+    def pointers(planes, which):
+        arr = (ctypes.c_void_p * len(which))()
+        for (k, p) in enumerate(which):
+            arr[k] = planes[p].value
+        return arr
+
+    rowsPerChunk = max(1, min(nrows, int(chunkPixels) // max(ncols, 1)))
+    allPlanes = list(range(src.nplanes))
+    carryIds = []
+    carryVals = []
+    for y0 in range(0, nrows, rowsPerChunk):
+        y1 = min(nrows, y0 + rowsPerChunk)
+        n = (y1 - y0) * ncols
+        with timings.interval('reading'):
+            (dseg, dplanes) = src.chunk(y0, y1)
+        with timings.interval('accumulation'):
+            cap = min(S, n) + 1
+            drec = src.scratch(0, n * 4)
+            orig = numpy.zeros(cap, dtype=numpy.uint32)
+            lhist = numpy.zeros(cap, dtype=numpy.uint32)
+            nnew = ctypes.c_uint32(0)
+            c.check(L.shp_subset_recode_dev(c.handle, dseg, y1 - y0, ncols, 0, 0, ncols, y1 - y0, None,
+                                            1 << 30, S, drec, _lib.ptr(orig), _lib.ptr(lhist), cap,
+                                            ctypes.byref(nnew)))
+            m = nnew.value
+            if m == 0:
+                continue
+            ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
+            fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
+            c.check(L.shp_segstats2d_bands_dev(c.handle, drec, pointers(dplanes, planeOfEntry), dt, nEntries,
+                                               y1 - y0, ncols, m, _lib.ptr(hasNull), _lib.ptr(nullArr),
+                                               _lib.ptr(fast), _lib.ptr(perBand), int(missingStatsValue),
+                                               _lib.ptr(ic), _lib.ptr(fc)))
+        with timings.interval('statscompletion'):
+            ids = orig[1:m + 1].astype(numpy.int64)
+            done = lhist[1:m + 1] == segSize[ids]
+            sel = numpy.flatnonzero(done)
+            _pageRows(pagedRat, ids[sel], ic[:numIntCols, 1:][:, sel], fc[:numFloatCols, 1:][:, sel],
+                      segSize, numIntCols, numFloatCols, (emptyInt, emptyFloat))
+            rest = numpy.flatnonzero(~done)
+            if len(rest):
+                flags = numpy.zeros(m + 1, dtype=numpy.uint8)
+                flags[rest + 1] = 1
+                npairs = int(lhist[1:m + 1][rest].sum())
+                so = numpy.empty(npairs, dtype=numpy.uint32)
+                vo = numpy.empty((src.nplanes, npairs), dtype=numpy.int64)
+                cnt = ctypes.c_int64(0)
+                c.check(L.shp_gather_flagged_bands_dev(c.handle, drec, pointers(dplanes, allPlanes), dt,
+                                                       src.nplanes, n, m, _lib.ptr(flags), npairs, _lib.ptr(so),
+                                                       _lib.ptr(vo), ctypes.byref(cnt)))
+                if cnt.value != npairs:
+                    raise PyShepSegStatsError("internal: %d pixels of unfinished segments, expected %d"
+                                              % (cnt.value, npairs))
+                carryIds.append(orig[so])
+                carryVals.append(vo.astype(src.bandDtype))
+        with timings.interval('writing'):
+            flush()
+    if carryIds:
+        # the segments that straddle block boundaries: all their pixels are here now
+        with timings.interval('statscompletion'):
+            allIds = numpy.concatenate(carryIds)
+            allVals = numpy.concatenate(carryVals, axis=1)
+            (uids, compact) = numpy.unique(allIds, return_inverse=True)
+            counts = numpy.bincount(compact, minlength=len(uids))
+            if not numpy.array_equal(counts, segSize[uids]):
+                raise PyShepSegStatsError('Not all pixels found during processing')     # tilingstats.py:211
+            m = len(uids)
+            ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
+            fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
+            seg1 = numpy.ascontiguousarray(compact + 1, dtype=numpy.uint32)
+            for (k, (_bandnum, statsSelection)) in enumerate(bandSelections):
+                # (the one-band entry point numbers its columns from 0: the entry's own fast selection)
+                (bfast, bInt, bFloat) = makeFastStatsSelection(list(range(len(statsSelection))), statsSelection)
+                bic = numpy.zeros((max(bInt, 1), m + 1), dtype=numpy.int64)
+                bfc = numpy.zeros((max(bFloat, 1), m + 1), dtype=numpy.float32)
+                vals = numpy.ascontiguousarray(allVals[planeOfEntry[k]])
+                c.check(L.shp_segstats(c.handle, _lib.ptr(seg1), _lib.ptr(vals), dt, len(seg1), m,
+                                       int(hasNull[k]), int(nullArr[k]), _lib.ptr(bfast), len(bfast),
+                                       int(missingStatsValue), _lib.ptr(bic), _lib.ptr(bfc)))
+                for (own, comb) in zip(bfast, fast[bandOfStat == k]):
+                    if own[STATSEL_COLTYPE] == STAT_DTYPE_INT:
+                        ic[comb[STATSEL_COLARRAYINDEX]] = bic[own[STATSEL_COLARRAYINDEX]]
+                    else:
+                        fc[comb[STATSEL_COLARRAYINDEX]] = bfc[own[STATSEL_COLARRAYINDEX]]
+            _pageRows(pagedRat, uids.astype(numpy.int64), ic[:numIntCols, 1:], fc[:numFloatCols, 1:], segSize,
+                      numIntCols, numFloatCols, (emptyInt, emptyFloat))
+    # pages no block touched hold only ids without pixels
+    with timings.interval('writing'):
+        for pageId in range(0, S + 1, RAT_PAGE_SIZE):
+            if pageId in written or pageId in pagedRat:
+                continue
+            if (segSize[max(pageId, 1):pageId + RAT_PAGE_SIZE] != 0).any():
+                raise PyShepSegStatsError('Not all pixels found during processing')      # tilingstats.py:211
+            numSeg = min(RAT_PAGE_SIZE, S + 1 - pageId)
+            page = pagedRat[pageId] = RatPage(numIntCols, numFloatCols, pageId, numSeg)
+            first = 1 if pageId == shepseg.SEGNULLVAL else 0
+            page.intcols[:, first:] = emptyInt[:, None]
+            page.floatcols[:, first:] = emptyFloat[:, None]
+            page.complete[:] = True
+        flush()
+    if len(pagedRat) > 0:
+        raise PyShepSegStatsError('Not all pixels found during processing')              # tilingstats.py:211
+
+
+def _entryNullVals(imgNullVal, nEntries, default):
+    """One null value per bandSelections entry: imgNullVal is one value for all, a list with one entry
+    each, or None (then default[k])."""
+    if imgNullVal is None:
+        return list(default)
+    if isinstance(imgNullVal, (list, tuple, numpy.ndarray)):
+        if len(imgNullVal) != nEntries:
+            raise PyShepSegStatsError("imgNullVal has %d entries, bandSelections %d" % (len(imgNullVal), nEntries))
+        return [default[k] if v is None else v for (k, v) in enumerate(imgNullVal)]
+    return [imgNullVal] * nEntries
+
+
+def calcPerSegmentStatsTiledBands(imgfile, bandSelections, segfile, missingStatsValue=-9999,
+        imgNullVal=None, segSize=None, chunkPixels=None):
+    """
+    calcPerSegmentStatsTiled for several bands of imgfile in one pass over the segment raster:
+    ``bandSelections`` is a list of (imgbandnum, statsSelection), each statsSelection as
+    calcPerSegmentStatsTiled takes it; a band may appear in more than one entry, column names must be
+    unique over the whole call.  ``imgNullVal`` is one value for all entries or a list with one per
+    entry (GDAL files: each band's own nodata value when not given); a pixel that is null in one
+    band still counts in the others.  Everything else -- the raster forms accepted, ``segSize``,
+    ``chunkPixels``, the errors -- is as for calcPerSegmentStatsTiled, and every column is
+    bit-identical to what that function returns for the entry's band and selection on its own.
+
+    The label raster is read, uploaded, renumbered and histogrammed once per row block instead of once
+    per band, and the patches' label tables are built once (csrc/segstats.h, k_stats_patch_bands).
+    """
+    timings = Timers()
+    from . import tiling as _tiling
+    (fast, bandOfStat, nInt, nFloat) = makeBandStatsSelection(bandSelections)    # (the checks: before anything is read)
+    bandSelections = [(int(b), list(s)) for (b, s) in bandSelections]
+    flatSelection = [sel for (_b, s) in bandSelections for sel in s]
+    bandNums = [b for (b, _s) in bandSelections]
+    planes = sorted(set(bandNums))                        # a band listed twice is read once
+    planeOfEntry = [planes.index(b) for b in bandNums]
+    nEntries = len(bandSelections)
+    c = _lib.ctx()
+    gdalSeg = None
+    if chunkPixels is None:
+        chunkPixels = STATS_CHUNK_PIXELS
+    with timings.interval('reading'):
+        if isinstance(imgfile, _tiling.DeviceRaster) and getattr(segfile, 'outDev', None):
+            (dptr, nrows, ncols, _nbytes) = segfile.outDev
+            (nb, ir, ic_) = imgfile.shape
+            if (ir, ic_) != (nrows, ncols):
+                raise PyShepSegStatsError("Images are different sizes")
+            for b in bandNums:
+                if not (1 <= b <= nb):
+                    raise PyShepSegStatsError("band %d not in image" % b)
+            nullVals = _entryNullVals(imgNullVal, nEntries, [imgfile.nullVal] * nEntries)
+            if segSize is None:
+                segSize = getattr(segfile, 'hist', None)
+            devBands = [imgfile.ptr + (b - 1) * nrows * ncols * imgfile.dtype.itemsize for b in planes]
+            src = _BandsChunkSource(c, None, None, devSeg=dptr, devBands=devBands, bandDtype=imgfile.dtype,
+                                    shape=(nrows, ncols))
+            maxSegId = int(segfile.maxSegId)
+        else:
+            seg = _loadArray(segfile)
+            img = _loadArray(imgfile)
+            if seg is None or img is None:
+                (seg, imgs, nodata, gdalSeg, segSize) = _readGdalBands(imgfile, planes, segfile)
+                nullVals = _entryNullVals(imgNullVal, nEntries, [nodata[p] for p in planeOfEntry])
+            else:
+                if img.ndim == 3:
+                    for b in bandNums:
+                        if not (1 <= b <= img.shape[0]):
+                            raise PyShepSegStatsError("band %d not in image" % b)
+                    imgs = [img[b - 1] for b in planes]
+                else:
+                    imgs = [img for _b in planes]             # (a single plane stands for any band, as _loadArray has it)
+                nullVals = _entryNullVals(imgNullVal, nEntries, [None] * nEntries)
+            if imgs[0].dtype.kind == 'f':
+                raise PyShepSegStatsError("Float image types not supported")        # tilingstats.py:450-452
+            if imgs[0].shape != seg.shape:
+                raise PyShepSegStatsError("Images are different sizes")             # tilingstats.py:453-455
+            bdt = imgs[0].dtype
+            if bdt not in _lib.SHP_DTYPES:
+                bdt = _lib.as_image(numpy.zeros((1, 1, 1), dtype=bdt))[0].dtype
+            src = _BandsChunkSource(c, seg, imgs, bandDtype=bdt, shape=seg.shape)
+            maxSegId = None
+    try:
+        if segSize is None:
+            with timings.interval('reading'):
+                segSize = _countSegments(src, chunkPixels)
+        segSize = numpy.ascontiguousarray(segSize).astype(numpy.int64)
+        if maxSegId is not None and len(segSize) < maxSegId + 1:
+            raise PyShepSegStatsError("segSize has %d rows, segment id %d needs more" % (len(segSize), maxSegId))
+        if gdalSeg is not None:
+            attrTbl = _GdalRat(gdalSeg, flatSelection, fast)
+        else:
+            attrTbl = MemoryRat(len(segSize), [int(f[STATSEL_COLTYPE]) for f in fast])
+        _streamStatsBands(src, planeOfEntry, segSize, bandSelections, fast, bandOfStat, nInt, nFloat, nullVals,
+                          missingStatsValue, attrTbl, timings, chunkPixels)
+    finally:
+        src.close()
+    rtn = TiledStatsResult()
+    rtn.timings = timings
+    if isinstance(attrTbl, MemoryRat):
+        rtn.columns = {sel[0]: attrTbl.columns[i] for (i, sel) in enumerate(flatSelection)}
+        rtn.pagesWritten = attrTbl.pagesWritten
+    else:
+        attrTbl.flush()
+        rtn.columns = None
+    return rtn
+
+
+def _readGdalBands(imgfile, bandnums, segfile):
+    """_readGdal for several bands of imgfile: (seg, bands, each band's nodata value, segment dataset, segSize)."""
+    try:
+        from osgeo import gdal
+    except ImportError:
+        raise PyShepSegStatsError("GDAL (osgeo) is not importable here: pass numpy arrays or "
+                                  ".npy paths")
+    gdal.UseExceptions()
+    segds = segfile if isinstance(segfile, gdal.Dataset) else gdal.Open(segfile, gdal.GA_Update)
+    imgds = gdal.Open(imgfile)
+    if (segds.RasterXSize != imgds.RasterXSize) or (segds.RasterYSize != imgds.RasterYSize):
+        raise PyShepSegStatsError("Images are different sizes")
+    if segds.GetGeoTransform() != imgds.GetGeoTransform():
+        raise PyShepSegStatsError("Images have different spatial extents or pixel sizes")
+    for b in bandnums:
+        if not (1 <= b <= imgds.RasterCount):
+            raise PyShepSegStatsError("band %d not in image" % b)
+    imgbands = [imgds.GetRasterBand(b) for b in bandnums]
+    attrTbl = segds.GetRasterBand(1).GetDefaultRAT()
+    names = [attrTbl.GetNameOfCol(i) for i in range(attrTbl.GetColumnCount())]
+    if 'Histogram' not in names:
+        raise PyShepSegStatsError("Histogram column must exist before calculating per-segment stats")
+    segSize = attrTbl.ReadAsArray(names.index('Histogram')).astype(numpy.uint32)
+    return (segds.GetRasterBand(1).ReadAsArray(), [b.ReadAsArray() for b in imgbands],
+            [b.GetNoDataValue() for b in imgbands], segds, segSize)
+
+
 class _GdalRat(object):
     """The segfile's GDAL attribute table behind the WriteArray interface writeCompletePages uses;
     creates the requested columns like the reference's createStatColumns (tilingstats.py:682-720):
