@@ -1218,8 +1218,7 @@ API int shp_dstats_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_
         SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
     if (nrows > 0xffffffffll || ncols > 0xffffffffll || nrows * ncols >= 0xffffffffll)
         SHP_FAIL(ctx, SHP_ERR_ARG, "raster too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
-    for (int i = 0; i < nstats; i++)
-        if (stats_sel[i * 5 + 1] > 7u || stats_sel[i * 5 + 2] > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
+    CHK(stats_sel_check(ctx, stats_sel, nstats));
     uint32_t *ps = nullptr;
     long long *pv = nullptr;
     CHK(run_dstats_local(ctx, d_seg, d_band, dtype, (uint32_t)nrows, (uint32_t)ncols, max_seg_id, has_null, null_val,
@@ -1238,8 +1237,7 @@ API int shp_dstats_merge_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const int
     if (!stats_sel || !counts || !d_cols || !n_merged_out || !n_ids_out || nstats < 1 || dtype_size(dtype) == 0 || slot < 0 || world < 1 ||
         slot >= 0xffffffffll || (slot > 0 && (!d_pair_seg || !d_pair_val)))
         SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
-    for (int i = 0; i < nstats; i++)
-        if (stats_sel[i * 5 + 1] > 7u || stats_sel[i * 5 + 2] > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
+    CHK(stats_sel_check(ctx, stats_sel, nstats));
     for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
     return run_dstats_merge(ctx, d_pair_seg, (const long long *)d_pair_val, (uint32_t)slot, (uint32_t)world, counts, dtype,
                             max_seg_id, has_null, null_val, stats_sel, nstats, missing, id_lo, id_hi, d_cols, n_merged_out, n_ids_out);

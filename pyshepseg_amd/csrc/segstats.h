@@ -317,6 +317,56 @@ __global__ __launch_bounds__(256) void k_stats_prefill(uint32_t S, long long bia
     seg_stats_of_run(s, 0u, nullptr, bias, sel, nstats, missing, intcols, fltcols, ns);
 }
 
+// ---- the phases k_stats_patch and k_stats_patch_bands have in common (the LDS arrays are the kernels') ----
+// (the slot probe/insert of a label is the same text in both kernels too, and stays there: as a function -- returning
+//  the slot, or setting it through a reference -- it compiled to other instructions in all ten instantiations,
+//  LABNOTES 2026-10-16)
+
+// offs[slot] = the sum of the run lengths of the slots before it: mine[] are those of this thread's four slots
+// (threadIdx.x * 4 ..), msum their sum.  Holds a workgroup barrier; the caller places one before offs[] is read.
+__device__ __forceinline__ void spp_scan_offsets(const uint32_t (&mine)[4], uint32_t msum, uint32_t *s_wsum, uint16_t *offs)
+{
+    uint32_t incl = msum;                                  // inclusive scan over the workgroup's 256 threads
+    const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d, 64);
+        if ((int)lane >= d) incl += o;
+    }
+    if (lane == 63) s_wsum[wv] = incl;
+    __syncthreads();
+    uint32_t base = incl - msum;
+    for (unsigned w2 = 0; w2 < wv; w2++) base += s_wsum[w2];
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; q++) { offs[threadIdx.x * 4u + q] = (uint16_t)base; base += mine[q]; }
+}
+
+// The rank of value v, stored at place rp of the run q[0..n): how many of the run's values come before it (smaller,
+// or equal and stored earlier).
+template <bool narrow>
+__device__ __forceinline__ uint32_t spp_rank_in_run(const uint32_t *q, uint32_t n, uint32_t v, uint32_t rp)
+{
+    uint32_t r = 0;
+    if (narrow) {
+        // 8/16-bit bands: the run holds value << 6 | position (positions < SPP_MAXRUN = 64), and "smaller, or equal
+        // and stored earlier" is ONE unsigned compare -- this loop is n iterations for each of the n values, a third
+        // of the kernel's instructions: plain offsets from one base, so that a value costs a compare and an add
+        const uint32_t me = (v << 6) | rp;
+        uint32_t j = 0;
+        for (; j + 8u <= n; j += 8u) {
+#pragma unroll
+            for (uint32_t u = 0; u < 8u; u++) r += q[j + u] < me ? 1u : 0u;
+        }
+        for (; j < n; j++) r += q[j] < me ? 1u : 0u;
+    } else {
+        for (uint32_t j = 0; j < n; j++) {
+            const uint32_t w = q[j];
+            r += (w < v || (w == v && j < rp)) ? 1u : 0u;
+        }
+    }
+    return r;
+}
+
 // (eight workgroups per CU -- 64 VGPRs, 20 KiB of LDS -- is worth more here than any unrolling: 23.4 ms at five,
 //  21.5 at eight on C5 with the same instructions)
 // (DT: the band's pixel type at compile time -- eight loads issued together instead of eight trips through a
@@ -403,19 +453,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
         mine[q] = nv;
         msum += nv;
     }
-    uint32_t incl = msum;                                  // inclusive scan over the workgroup's 256 threads
-    const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += o;
-    }
-    if (lane == 63) s_wsum[wv] = incl;
-    __syncthreads();
-    uint32_t base = incl - msum;
-    for (unsigned w2 = 0; w2 < wv; w2++) base += s_wsum[w2];
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; q++) { offs[threadIdx.x * 4u + q] = (uint16_t)base; base += mine[q]; }
+    spp_scan_offsets(mine, msum, s_wsum, offs);
     __syncthreads();
     // ---- values of complete labels into their runs, the rest into the list ----
     // (a run's first lane probing and adding for the run -- one atomic per run instead of one per pixel -- was built
@@ -457,28 +495,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
         if (rpos[k] == 0xFFFFFFFFu) continue;
         const uint32_t sl = pslot[k];
         const uint32_t n = (cnt[sl] >> 16) & 0x7FFFu, o = offs[sl];
-        const uint32_t v = pv[k];
-        uint32_t r = 0;
-        const uint32_t *q = &runs[o];
-        if (narrow) {
-            // 8/16-bit bands: the run holds value << 6 | position (positions < SPP_MAXRUN = 64), and "smaller, or equal
-            // and stored earlier" is ONE unsigned compare -- this loop is n iterations for each of the n values, a third
-            // of the kernel's instructions: plain offsets from one base, so that a value costs a compare and an add
-            const uint32_t me = (v << 6) | rpos[k];
-            uint32_t j = 0;
-            for (; j + 8u <= n; j += 8u) {
-#pragma unroll
-                for (uint32_t u = 0; u < 8u; u++) r += q[j + u] < me ? 1u : 0u;
-            }
-            for (; j < n; j++) r += q[j] < me ? 1u : 0u;
-        } else {
-            const uint32_t rp = rpos[k];
-            for (uint32_t j = 0; j < n; j++) {
-                const uint32_t w = q[j];
-                r += (w < v || (w == v && j < rp)) ? 1u : 0u;
-            }
-        }
-        rpos[k] = o + r;
+        rpos[k] = o + spp_rank_in_run<narrow>(&runs[o], n, pv[k], rpos[k]);
     }
     __syncthreads();
 #pragma unroll
@@ -568,6 +585,62 @@ static int segstats_sort_reduce(shp_ctx *ctx, uint32_t n, uint32_t S, int valbit
     return 0;
 }
 
+// ---- what the drivers below do alike ----
+// A selection as the host hands it over, five words per statistic: statistic id and column type are checked, the
+// integer and the float columns counted.  index_runs: the column array indices must number the columns of each
+// type 0, 1, 2 .. in the order of the entries (the several-band form: its bands' columns lie side by side).
+static int stats_sel_check(shp_ctx *ctx, const uint32_t *sel_host, int nstats, int *nint_out = nullptr,
+                           int *nflt_out = nullptr, bool index_runs = false)
+{
+    int nint = 0, nflt = 0;
+    for (int i = 0; i < nstats; i++) {
+        const uint32_t stat = sel_host[i * 5 + 1], ctype = sel_host[i * 5 + 2];
+        if (stat > 7u || ctype > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
+        if (index_runs && sel_host[i * 5 + 3] != (uint32_t)(ctype == 0 ? nint : nflt))
+            SHP_FAIL(ctx, SHP_ERR_ARG, "statsSelection entry %d: column array index does not run through the bands", i);
+        if (ctype == 0) nint++; else nflt++;
+    }
+    if (nint_out) *nint_out = nint;
+    if (nflt_out) *nflt_out = nflt;
+    return 0;
+}
+
+// value - bias is the unsigned sort key of a pixel value, valbits wide
+static void stats_value_range(int dtype, long long *bias, int *valbits)
+{
+    *bias = 0;
+    *valbits = 32;
+    switch (dtype) {
+    case SHP_U8: *valbits = 8; break;
+    case SHP_U16: *valbits = 16; break;
+    case SHP_I16: *valbits = 16; *bias = -32768; break;
+    case SHP_I32: *bias = -2147483648ll; break;
+    default: break;
+    }
+}
+
+// Patch by patch, or everything through the sorts?  SHEPSEG_STATS_PATCH=0: never; =1: whenever the raster's shape
+// is known; default: when the average segment has at most SPP_MAXRUN pixels.
+static bool stats_use_patches(uint32_t n, uint32_t S, bool shape_known)
+{
+    const int patch_env = getenv("SHEPSEG_STATS_PATCH") ? atoi(getenv("SHEPSEG_STATS_PATCH")) : -1;
+    return n && shape_known && patch_env != 0 &&
+           (patch_env == 1 || (uint64_t)n <= (uint64_t)SPP_MAXRUN * ((uint64_t)S + 1));
+}
+
+// the workspace of a statistics run over n pixels and ns rows: sort keys, run counts and offsets, the small buffer
+// (left-over count | selection | what else the caller keeps there), the columns
+static int stats_workspace(shp_ctx *ctx, uint32_t n, size_t ns, size_t small_bytes, int nint, int nflt)
+{
+    CHK(buf_ensure(ctx, ctx->aux, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->aux2, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->segsz, (ns + 1) * 4));
+    CHK(buf_ensure(ctx, ctx->off, (ns + 1) * 4 + 16));
+    CHK(buf_ensure(ctx, ctx->small, small_bytes));
+    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
+    return 0;
+}
+
 static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
                         uint32_t n, uint32_t S, int has_null, int64_t null_val,
                         const uint32_t *sel_host, int nstats, int64_t missing,
@@ -578,27 +651,12 @@ static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band,
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)S + 1;
     int nint = 0, nflt = 0;
-    for (int i = 0; i < nstats; i++) {
-        const uint32_t stat = sel_host[i * 5 + 1], ctype = sel_host[i * 5 + 2];
-        if (stat > 7u || ctype > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
-        if (ctype == 0) nint++; else nflt++;
-    }
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt));
     if ((size_t)nstats * 20 + 64 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many statistics");
-    long long bias = 0;
-    int valbits = 32;
-    switch (dtype) {
-    case SHP_U8: valbits = 8; break;
-    case SHP_U16: valbits = 16; break;
-    case SHP_I16: valbits = 16; bias = -32768; break;
-    case SHP_I32: bias = -2147483648ll; break;
-    default: break;
-    }
-    CHK(buf_ensure(ctx, ctx->aux, (size_t)n * 4));
-    CHK(buf_ensure(ctx, ctx->aux2, (size_t)n * 4));
-    CHK(buf_ensure(ctx, ctx->segsz, (ns + 1) * 4));
-    CHK(buf_ensure(ctx, ctx->off, (ns + 1) * 4 + 16));
-    CHK(buf_ensure(ctx, ctx->small, 4096 + (size_t)nstats * 20));
-    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
+    long long bias;
+    int valbits;
+    stats_value_range(dtype, &bias, &valbits);
+    CHK(stats_workspace(ctx, n, ns, 4096 + (size_t)nstats * 20, nint, nflt));
     uint32_t *kval = bp<uint32_t>(ctx->aux), *kseg = bp<uint32_t>(ctx->aux2);
     uint32_t *d_sel = bp<uint32_t>(ctx->small) + 256;
     long long *d_int = (long long *)ctx->ssum.p;
@@ -608,11 +666,7 @@ static int run_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band,
     memcpy(pin, sel_host, (size_t)nstats * 20);
     HIPCHK(ctx, hipMemcpyAsync(d_sel, pin, (size_t)nstats * 20, hipMemcpyHostToDevice, st));
     const int ps = prof_begin(ctx, PROF_SEGSTATS);      // device time of the kernels (keys .. statistics)
-    // (SHEPSEG_STATS_PATCH=0: never; =1: whenever the shape is known; default: when the average segment has
-    //  at most SPP_MAXRUN pixels)
-    const int patch_env = getenv("SHEPSEG_STATS_PATCH") ? atoi(getenv("SHEPSEG_STATS_PATCH")) : -1;
-    const bool patches = n && nrows && ncols && (uint64_t)nrows * ncols == n && patch_env != 0 &&
-                         (patch_env == 1 || (uint64_t)n <= (uint64_t)SPP_MAXRUN * ((uint64_t)S + 1));
+    const bool patches = stats_use_patches(n, S, nrows && ncols && (uint64_t)nrows * ncols == n);
     const uint8_t *only = nullptr;
     uint32_t nsort = n;                                   // pairs that go through the sorts
     if (patches) {
@@ -741,19 +795,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
             mine[q] = nv;
             msum += nv;
         }
-        uint32_t incl = msum;                                  // inclusive scan over the workgroup's 256 threads
-        const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, 64);
-            if ((int)lane >= d) incl += o;
-        }
-        if (lane == 63) s_wsum[wv] = incl;
-        __syncthreads();
-        uint32_t base = incl - msum;
-        for (unsigned w2 = 0; w2 < wv; w2++) base += s_wsum[w2];
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; q++) { offs[threadIdx.x * 4u + q] = (uint16_t)base; base += mine[q]; }
+        spp_scan_offsets(mine, msum, s_wsum, offs);
         // ---- the pixels of every other label, nodata or not in whichever band: (label, position) into the list ----
         // (pslot[k] becomes 0x80000000 | the pixel's place among the patch's left-over ones)
 #pragma unroll
@@ -815,25 +857,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
             if (rpos[k] == 0xFFFFFFFFu) continue;
             const uint32_t sl = pslot[k];
             const uint32_t n = (cnt[sl] >> sh) & 0x7FFFu, o = offs[sl];
-            const uint32_t v = pv[k];
-            uint32_t r = 0;
-            const uint32_t *q = &runs[o];
-            if (narrow) {
-                const uint32_t me = (v << 6) | rpos[k];
-                uint32_t j = 0;
-                for (; j + 8u <= n; j += 8u) {
-#pragma unroll
-                    for (uint32_t u = 0; u < 8u; u++) r += q[j + u] < me ? 1u : 0u;
-                }
-                for (; j < n; j++) r += q[j] < me ? 1u : 0u;
-            } else {
-                const uint32_t rp = rpos[k];
-                for (uint32_t j = 0; j < n; j++) {
-                    const uint32_t w = q[j];
-                    r += (w < v || (w == v && j < rp)) ? 1u : 0u;
-                }
-            }
-            rpos[k] = o + r;
+            rpos[k] = o + spp_rank_in_run<narrow>(&runs[o], n, pv[k], rpos[k]);
         }
         __syncthreads();
 #pragma unroll
@@ -882,30 +906,13 @@ static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *c
         nstats += nstats_per_band[b];
     }
     int nint = 0, nflt = 0;
-    for (int i = 0; i < nstats; i++) {
-        const uint32_t stat = sel_host[i * 5 + 1], ctype = sel_host[i * 5 + 2];
-        if (stat > 7u || ctype > 1u) SHP_FAIL(ctx, SHP_ERR_ARG, "bad statsSelection entry %d", i);
-        if (sel_host[i * 5 + 3] != (uint32_t)(ctype == 0 ? nint : nflt))
-            SHP_FAIL(ctx, SHP_ERR_ARG, "statsSelection entry %d: column array index does not run through the bands", i);
-        if (ctype == 0) nint++; else nflt++;
-    }
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt, true));
     const size_t sel_bytes = ((size_t)nstats * 20 + 31) & ~(size_t)31, tab_bytes = (size_t)nbands * sizeof(StatsBand);
     if (sel_bytes + tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many statistics");
-    long long bias = 0;
-    int valbits = 32;
-    switch (dtype) {
-    case SHP_U8: valbits = 8; break;
-    case SHP_U16: valbits = 16; break;
-    case SHP_I16: valbits = 16; bias = -32768; break;
-    case SHP_I32: bias = -2147483648ll; break;
-    default: break;
-    }
-    CHK(buf_ensure(ctx, ctx->aux, (size_t)n * 4));
-    CHK(buf_ensure(ctx, ctx->aux2, (size_t)n * 4));
-    CHK(buf_ensure(ctx, ctx->segsz, (ns + 1) * 4));
-    CHK(buf_ensure(ctx, ctx->off, (ns + 1) * 4 + 16));
-    CHK(buf_ensure(ctx, ctx->small, 4096 + sel_bytes + tab_bytes));
-    CHK(buf_ensure(ctx, ctx->ssum, ((size_t)nint * 8 + (size_t)nflt * 4) * ns + 64));
+    long long bias;
+    int valbits;
+    stats_value_range(dtype, &bias, &valbits);
+    CHK(stats_workspace(ctx, n, ns, 4096 + sel_bytes + tab_bytes, nint, nflt));
     uint32_t *kval = bp<uint32_t>(ctx->aux), *kseg = bp<uint32_t>(ctx->aux2);
     uint32_t *d_sel = bp<uint32_t>(ctx->small) + 256;
     StatsBand *d_tab = (StatsBand *)(bp<uint8_t>(ctx->small) + 1024 + sel_bytes);
@@ -920,10 +927,7 @@ static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *c
                            nstats_per_band[b], 0};
     HIPCHK(ctx, hipMemcpyAsync(d_sel, pin, sel_bytes + tab_bytes, hipMemcpyHostToDevice, st));
     const int ps = prof_begin(ctx, PROF_SEGSTATS);
-    // (SHEPSEG_STATS_PATCH as in run_segstats)
-    const int patch_env = getenv("SHEPSEG_STATS_PATCH") ? atoi(getenv("SHEPSEG_STATS_PATCH")) : -1;
-    const bool patches = n && patch_env != 0 &&
-                         (patch_env == 1 || (uint64_t)n <= (uint64_t)SPP_MAXRUN * ((uint64_t)S + 1));
+    const bool patches = stats_use_patches(n, S, true);
     if (patches) {
         CHK(buf_ensure(ctx, ctx->tcount, (ns + 1) * 4));
         CHK(buf_ensure(ctx, ctx->mergeto, ns + 64));
@@ -972,17 +976,13 @@ static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *c
 // ---- multi-GPU split: the pixels of segments that straddle a rank boundary ------------------
 // (seg id, band value) of every pixel whose segment is flagged, compacted (any order) with one
 // global atomic per 4096 pixels.  count may exceed cap: only the first cap pairs are stored.
-__global__ __launch_bounds__(256) void k_gather_flagged(const uint32_t *__restrict__ seg,
-                                                        const void *__restrict__ band, int dtype,
-                                                        uint32_t n, uint32_t S,
-                                                        const uint8_t *__restrict__ flags,
-                                                        uint32_t *__restrict__ out_seg,
-                                                        long long *__restrict__ out_val,
-                                                        uint32_t cap, uint32_t *count)
+// The workgroup's 4096 pixels: the positions of those whose segment is flagged, compacted into s_buf (*s_cnt of them),
+// and room for them reserved in the output from *s_base on, with one global atomic.
+__device__ __forceinline__ void gather_flagged_positions(const uint32_t *__restrict__ seg, uint32_t n, uint32_t S,
+                                                         const uint8_t *__restrict__ flags, uint32_t *count,
+                                                         uint32_t *s_buf, uint32_t *s_cnt, uint32_t *s_base)
 {
-    __shared__ uint32_t s_buf[4096];
-    __shared__ uint32_t s_cnt, s_base;
-    if (threadIdx.x == 0) s_cnt = 0;
+    if (threadIdx.x == 0) *s_cnt = 0;
     __syncthreads();
     const unsigned lane = lane_id();
     for (uint32_t it = 0; it < 16u; it++) {
@@ -995,14 +995,27 @@ __global__ __launch_bounds__(256) void k_gather_flagged(const uint32_t *__restri
         const unsigned long long m = __ballot(take);
         if (m != 0ull) {
             uint32_t wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
+            if (lane == 0) wbase = atomicAdd(s_cnt, (uint32_t)__popcll(m));
             wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
             if (take) s_buf[wbase + (uint32_t)__popcll(m & lanemask_lt())] = p;
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) s_base = s_cnt ? atomicAdd(count, s_cnt) : 0u;
+    if (threadIdx.x == 0) *s_base = *s_cnt ? atomicAdd(count, *s_cnt) : 0u;
     __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_gather_flagged(const uint32_t *__restrict__ seg,
+                                                        const void *__restrict__ band, int dtype,
+                                                        uint32_t n, uint32_t S,
+                                                        const uint8_t *__restrict__ flags,
+                                                        uint32_t *__restrict__ out_seg,
+                                                        long long *__restrict__ out_val,
+                                                        uint32_t cap, uint32_t *count)
+{
+    __shared__ uint32_t s_buf[4096];
+    __shared__ uint32_t s_cnt, s_base;
+    gather_flagged_positions(seg, n, S, flags, count, s_buf, &s_cnt, &s_base);
     for (uint32_t i = threadIdx.x; i < s_cnt; i += 256u) {
         const uint32_t o = s_base + i;
         if (o < cap) {
@@ -1013,34 +1026,53 @@ __global__ __launch_bounds__(256) void k_gather_flagged(const uint32_t *__restri
     }
 }
 
-static int run_gather_flagged(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
-                              uint32_t n, uint32_t S, const uint8_t *flags_host, uint32_t cap,
-                              uint32_t *seg_out, int64_t *val_out, int64_t *count_out)
+// The two gather drivers' device side: ctx->small = the count (word 0) | tab_bytes for the caller's band table (from
+// byte 64) | the flags, uploaded here; ctx->aux = the ids, ctx->aux2 = val_rows rows of cap values.
+static int gather_flagged_begin(shp_ctx *ctx, uint32_t S, const uint8_t *flags_host, uint32_t cap, int val_rows,
+                                size_t tab_bytes, uint8_t **d_flags)
+{
+    const size_t ns = (size_t)S + 1;
+    CHK(buf_ensure(ctx, ctx->small, 64 + tab_bytes + ns + 64));
+    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->aux2, (size_t)cap * 8 * val_rows + 64));
+    *d_flags = bp<uint8_t>(ctx->small) + 64 + tab_bytes;
+    HIPCHK(ctx, hipMemcpyAsync(*d_flags, flags_host, ns, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->small.p, 0, 4, ctx->stream));
+    return 0;
+}
+
+// ... and the way back: the count, and the first min(count, cap) pairs (of several rows of values all cap columns
+// travel: the rows lie cap apart)
+static int gather_flagged_end(shp_ctx *ctx, uint32_t cap, int val_rows, uint32_t *seg_out, int64_t *val_out,
+                              int64_t *count_out)
 {
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
-    CHK(buf_ensure(ctx, ctx->small, ns + 64));
-    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
-    CHK(buf_ensure(ctx, ctx->aux2, (size_t)cap * 8 + 64));
-    uint8_t *d_flags = bp<uint8_t>(ctx->small) + 64;
-    uint32_t *d_count = bp<uint32_t>(ctx->small);
-    HIPCHK(ctx, hipMemcpyAsync(d_flags, flags_host, ns, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(d_count, 0, 4, st));
-    if (n) {
-        hipLaunchKernelGGL(k_gather_flagged, dim3(grid_for(n, 4096)), dim3(256), 0, st, d_seg, d_band, dtype,
-                           n, S, d_flags, bp<uint32_t>(ctx->aux), (long long *)ctx->aux2.p, cap, d_count);
-        KCHK(ctx);
-    }
     uint32_t cnt = 0;
-    CHK(read_u32(ctx, d_count, &cnt));
+    CHK(read_u32(ctx, bp<uint32_t>(ctx->small), &cnt));
     const uint32_t take = cnt < cap ? cnt : cap;
     if (take) {
+        const size_t nval = val_rows == 1 ? (size_t)take : (size_t)cap * val_rows;
         HIPCHK(ctx, hipMemcpyAsync(seg_out, ctx->aux.p, (size_t)take * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(val_out, ctx->aux2.p, (size_t)take * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(val_out, ctx->aux2.p, nval * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
     }
     *count_out = (int64_t)cnt;
     return 0;
+}
+
+static int run_gather_flagged(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
+                              uint32_t n, uint32_t S, const uint8_t *flags_host, uint32_t cap,
+                              uint32_t *seg_out, int64_t *val_out, int64_t *count_out)
+{
+    uint8_t *d_flags = nullptr;
+    CHK(gather_flagged_begin(ctx, S, flags_host, cap, 1, 0, &d_flags));
+    uint32_t *d_count = bp<uint32_t>(ctx->small);
+    if (n) {
+        hipLaunchKernelGGL(k_gather_flagged, dim3(grid_for(n, 4096)), dim3(256), 0, ctx->stream, d_seg, d_band, dtype,
+                           n, S, d_flags, bp<uint32_t>(ctx->aux), (long long *)ctx->aux2.p, cap, d_count);
+        KCHK(ctx);
+    }
+    return gather_flagged_end(ctx, cap, 1, seg_out, val_out, count_out);
 }
 
 // The same for several bands of one image: the ids once, and every band's values in the SAME order (the order itself
@@ -1054,27 +1086,7 @@ __global__ __launch_bounds__(256) void k_gather_flagged_bands(const uint32_t *__
 {
     __shared__ uint32_t s_buf[4096];
     __shared__ uint32_t s_cnt, s_base;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    const unsigned lane = lane_id();
-    for (uint32_t it = 0; it < 16u; it++) {
-        const uint32_t p = blockIdx.x * 4096u + it * 256u + threadIdx.x;
-        bool take = false;
-        if (p < n) {
-            const uint32_t sg = seg[p];
-            take = sg != 0u && sg <= S && flags[sg] != 0;
-        }
-        const unsigned long long m = __ballot(take);
-        if (m != 0ull) {
-            uint32_t wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
-            wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-            if (take) s_buf[wbase + (uint32_t)__popcll(m & lanemask_lt())] = p;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) s_base = s_cnt ? atomicAdd(count, s_cnt) : 0u;
-    __syncthreads();
+    gather_flagged_positions(seg, n, S, flags, count, s_buf, &s_cnt, &s_base);
     for (uint32_t i = threadIdx.x; i < s_cnt; i += 256u) {
         const uint32_t o = s_base + i;
         if (o < cap) {
@@ -1090,15 +1102,12 @@ static int run_gather_flagged_bands(shp_ctx *ctx, const uint32_t *d_seg, const v
                                     uint32_t *seg_out, int64_t *val_out, int64_t *count_out)
 {
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
     const size_t tab_bytes = (size_t)nbands * sizeof(StatsBand);
     if (tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many bands");
-    CHK(buf_ensure(ctx, ctx->small, 64 + tab_bytes + ns + 64));
-    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
-    CHK(buf_ensure(ctx, ctx->aux2, (size_t)cap * 8 * nbands + 64));
+    uint8_t *d_flags = nullptr;
+    CHK(gather_flagged_begin(ctx, S, flags_host, cap, nbands, tab_bytes, &d_flags));
     uint32_t *d_count = bp<uint32_t>(ctx->small);
     StatsBand *d_tab = (StatsBand *)(bp<uint8_t>(ctx->small) + 64);
-    uint8_t *d_flags = bp<uint8_t>(ctx->small) + 64 + tab_bytes;
     HIPCHK(ctx, hipStreamSynchronize(st));
     StatsBand *tab = (StatsBand *)(ctx->h_pinned + 16);
     for (int b = 0; b < nbands; b++) {
@@ -1106,23 +1115,12 @@ static int run_gather_flagged_bands(shp_ctx *ctx, const uint32_t *d_seg, const v
         tab[b] = StatsBand{bands_host[b], 0, 0, 0, 0, 0};
     }
     HIPCHK(ctx, hipMemcpyAsync(d_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemcpyAsync(d_flags, flags_host, ns, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(d_count, 0, 4, st));
     if (n) {
         hipLaunchKernelGGL(k_gather_flagged_bands, dim3(grid_for(n, 4096)), dim3(256), 0, st, d_seg, d_tab, nbands, dtype,
                            n, S, d_flags, bp<uint32_t>(ctx->aux), (long long *)ctx->aux2.p, cap, d_count);
         KCHK(ctx);
     }
-    uint32_t cnt = 0;
-    CHK(read_u32(ctx, d_count, &cnt));
-    if (cnt && cap) {
-        const uint32_t take = cnt < cap ? cnt : cap;
-        HIPCHK(ctx, hipMemcpyAsync(seg_out, ctx->aux.p, (size_t)take * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(val_out, ctx->aux2.p, (size_t)cap * 8 * nbands, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    }
-    *count_out = (int64_t)cnt;
-    return 0;
+    return gather_flagged_end(ctx, cap, nbands, seg_out, val_out, count_out);
 }
 
 // ---- multi-GPU split, device-resident (pyshepseg_amd/distributed.py) ---------------------------
@@ -1174,7 +1172,7 @@ static int run_dstats_local(shp_ctx *ctx, const uint32_t *d_seg, const void *d_b
     const size_t ns = (size_t)S + 1;
     const uint32_t n = nrows * ncols;
     int nint = 0, nflt = 0;
-    for (int i = 0; i < nstats; i++) { if (sel_host[i * 5 + 2] == 0) nint++; else nflt++; }
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt));
     long long *di = nullptr;
     float *df = nullptr;
     CHK(run_segstats(ctx, d_seg, d_band, dtype, n, S, has_null, null_val, sel_host, nstats, missing, nullptr, nullptr,
@@ -1272,7 +1270,7 @@ static int run_dstats_merge(shp_ctx *ctx, const uint32_t *d_pseg, const long lon
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)S + 1;
     int nint = 0, nflt = 0;
-    for (int i = 0; i < nstats; i++) { if (sel_host[i * 5 + 2] == 0) nint++; else nflt++; }
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt));
     *n_merged = 0;
     *n_ids = 0;
     const size_t total = (size_t)slot * world;

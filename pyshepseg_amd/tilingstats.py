@@ -250,11 +250,13 @@ def _pageRows(pagedRat, segIds, intRows, floatRows, segSize, numIntCols, numFloa
 
 
 class _ChunkSource(object):
-    """Row blocks of (label raster, image band) as device pointers: resident rasters are addressed
-    in place, host arrays / memmaps go up block by block into two reusable device buffers."""
-    def __init__(self, c, seg, band, devSeg=None, devBand=None, bandDtype=None, shape=None):
+    """Row blocks of (label raster, image planes) as device pointers: resident rasters are addressed in
+    place, host arrays / memmaps go up block by block into reusable device buffers.  planes: host planes
+    (arrays / memmaps), or devPlanes: device addresses of whole planes."""
+    def __init__(self, c, seg, planes, devSeg=None, devPlanes=None, bandDtype=None, shape=None):
         self.c = c
-        (self.seg, self.band, self.devSeg, self.devBand) = (seg, band, devSeg, devBand)
+        (self.seg, self.planes, self.devSeg, self.devPlanes) = (seg, planes, devSeg, devPlanes)
+        self.nplanes = len(planes if devPlanes is None else devPlanes)
         (self.nrows, self.ncols) = shape
         self.bandDtype = numpy.dtype(bandDtype)
         self.bufs = []
@@ -271,20 +273,25 @@ class _ChunkSource(object):
         return self.bufs[i][0]
 
     def chunk(self, y0, y1):
+        """(labels, [one pointer per plane]) of rows y0..y1"""
         n = (y1 - y0) * self.ncols
+        isz = self.bandDtype.itemsize
         if self.devSeg is not None:
             return (ctypes.c_void_p(self.devSeg + 4 * y0 * self.ncols),
-                    ctypes.c_void_p(self.devBand + self.bandDtype.itemsize * y0 * self.ncols))
+                    [ctypes.c_void_p(p + isz * y0 * self.ncols) for p in self.devPlanes])
         s = numpy.ascontiguousarray(self.seg[y0:y1], dtype=shepseg.SegIdType)
-        b = numpy.ascontiguousarray(self.band[y0:y1], dtype=self.bandDtype)
         ds = self._buf(0, n * 4)
-        db = self._buf(1, n * self.bandDtype.itemsize)
         self.c.check(self.c._L.shp_dev_upload(self.c.handle, ds, _lib.ptr(s), s.nbytes))
-        self.c.check(self.c._L.shp_dev_upload(self.c.handle, db, _lib.ptr(b), b.nbytes))
-        return (ds, db)
+        dbs = []
+        for (k, plane) in enumerate(self.planes):
+            b = numpy.ascontiguousarray(plane[y0:y1], dtype=self.bandDtype)
+            db = self._buf(3 + k, n * isz)
+            self.c.check(self.c._L.shp_dev_upload(self.c.handle, db, _lib.ptr(b), b.nbytes))
+            dbs.append(db)
+        return (ds, dbs)
 
     def scratch(self, i, nbytes):
-        return self._buf(2 + i, nbytes)
+        return self._buf(1 + i, nbytes)             # (buffers 1 and 2; the planes' start at 3)
 
     def close(self):
         for (p, _n) in self.bufs:
@@ -296,20 +303,30 @@ class _ChunkSource(object):
 STATS_CHUNK_PIXELS = 1 << 28        # pixels per streamed block (the kernels index a block with 32 bits)
 
 
-def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, imgNullVal,
-                 missingStatsValue, attrTbl, timings, chunkPixels):
-    """The tile loop of calcPerSegmentStatsTiled (tilingstats.py:183-206) over row blocks.  Per block:
-    the labels are renumbered 1..m in first-seen order on the device (shp_subset_recode_dev, which
-    also counts their pixels), the block's statistics are computed for those m ids, the ids whose
-    block count equals segSize are complete (checkSegComplete, :518-553) and go to their RAT page;
-    the (id, value) pairs of the others are set aside and reduced once at the end."""
+def _streamStats(src, entries, segSize, statsSelection_fast, missingStatsValue, attrTbl, timings, chunkPixels):
+    """The tile loop of calcPerSegmentStatsTiled (tilingstats.py:183-206) over row blocks, for one band or several:
+    ``entries`` is a list of (plane of src, null value, statsSelection), ``statsSelection_fast`` the combined fast
+    selection of their statsSelections one after the other.  Per block: the labels are renumbered 1..m in first-seen
+    order on the device (the subset module's recode, which also counts their pixels), all entries' statistics are computed
+    for those m ids, the ids whose block count equals segSize are complete (checkSegComplete, :518-553) and go to
+    their RAT page -- a property of the labels, established once; the pixels of the others are set aside as ids once
+    and one value array per plane, in one order, and reduced per entry at the end.
+    One entry goes through the one-band library calls (k_stats_patch), several through the bands calls
+    (k_stats_patch_bands): csrc/segstats.h has why these are two kernels."""
     c = src.c
     L = c._L
     (nrows, ncols) = (src.nrows, src.ncols)
     S = len(segSize) - 1
     dt = _lib.SHP_DTYPES[src.bandDtype]
-    nstats = len(statsSelection_fast)
+    nEntries = len(entries)
     fast = numpy.ascontiguousarray(statsSelection_fast, dtype=numpy.uint32)
+    numIntCols = int((fast[:, STATSEL_COLTYPE] == STAT_DTYPE_INT).sum())
+    numFloatCols = len(fast) - numIntCols
+    planeOfEntry = [e[0] for e in entries]
+    perBand = numpy.ascontiguousarray([len(e[2]) for e in entries], dtype=numpy.int32)
+    bandOfStat = numpy.repeat(numpy.arange(nEntries), perBand)
+    hasNull = numpy.ascontiguousarray([int(e[1] is not None) for e in entries], dtype=numpy.int32)
+    nullArr = numpy.ascontiguousarray([0 if e[1] is None else int(e[1]) for e in entries], dtype=numpy.int64)
     # statistics of a segment without pixels (see _pageRows)
     emptyInt = numpy.full(numIntCols, int(missingStatsValue), dtype=numpy.int64)
     emptyFloat = numpy.full(numFloatCols, float(missingStatsValue), dtype=numpy.float32)
@@ -323,16 +340,50 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
         written.update(pid for (pid, pg) in pagedRat.items() if pg.pageComplete())
         writeCompletePages(pagedRat, attrTbl, fast)
 
+    def pointers(planes, which):
+        arr = (ctypes.c_void_p * len(which))()
+        for (k, p) in enumerate(which):
+            arr[k] = planes[p].value
+        return arr
+
+    def blockStats(drec, dplanes, blockRows, m, ic, fc):
+        """the statistics of all entries for the block's ids 1..m"""
+        if nEntries == 1:
+            # (the block's shape goes along: with small segments the library works patch by patch)
+            c.check(L.shp_segstats2d_dev(c.handle, drec, dplanes[planeOfEntry[0]], dt, blockRows, ncols, m,
+                                         int(hasNull[0]), int(nullArr[0]), _lib.ptr(fast), len(fast),
+                                         int(missingStatsValue), _lib.ptr(ic), _lib.ptr(fc)))
+        else:
+            c.check(L.shp_segstats2d_bands_dev(c.handle, drec, pointers(dplanes, planeOfEntry), dt, nEntries,
+                                               blockRows, ncols, m, _lib.ptr(hasNull), _lib.ptr(nullArr),
+                                               _lib.ptr(fast), _lib.ptr(perBand), int(missingStatsValue),
+                                               _lib.ptr(ic), _lib.ptr(fc)))
+
+    def gatherFlagged(drec, dplanes, n, m, flags, npairs):
+        """(ids, values[plane]) of the npairs pixels of the block whose id is flagged"""
+        so = numpy.empty(npairs, dtype=numpy.uint32)
+        vo = numpy.empty((src.nplanes, npairs), dtype=numpy.int64)
+        cnt = ctypes.c_int64(0)
+        if nEntries == 1:                                   # (one entry reads one plane)
+            c.check(L.shp_gather_flagged_dev(c.handle, drec, dplanes[0], dt, n, m, _lib.ptr(flags), npairs,
+                                             _lib.ptr(so), _lib.ptr(vo), ctypes.byref(cnt)))
+        else:
+            c.check(L.shp_gather_flagged_bands_dev(c.handle, drec, pointers(dplanes, range(src.nplanes)), dt,
+                                                   src.nplanes, n, m, _lib.ptr(flags), npairs, _lib.ptr(so),
+                                                   _lib.ptr(vo), ctypes.byref(cnt)))
+        if cnt.value != npairs:
+            raise PyShepSegStatsError("internal: %d pixels of unfinished segments, expected %d"
+                                      % (cnt.value, npairs))
+        return (so, vo)
+
     rowsPerChunk = max(1, min(nrows, int(chunkPixels) // max(ncols, 1)))
     carryIds = []
     carryVals = []
-    nullFlag = int(imgNullVal is not None)
-    nullV = 0 if imgNullVal is None else int(imgNullVal)
     for y0 in range(0, nrows, rowsPerChunk):
         y1 = min(nrows, y0 + rowsPerChunk)
         n = (y1 - y0) * ncols
         with timings.interval('reading'):
-            (dseg, dband) = src.chunk(y0, y1)
+            (dseg, dplanes) = src.chunk(y0, y1)
         with timings.interval('accumulation'):
             cap = min(S, n) + 1
             drec = src.scratch(0, n * 4)
@@ -347,10 +398,7 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
                 continue
             ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
             fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
-            # (the block's shape goes along: with small segments the library works patch by patch)
-            c.check(L.shp_segstats2d_dev(c.handle, drec, dband, dt, y1 - y0, ncols, m, nullFlag, nullV,
-                                         _lib.ptr(fast), nstats, int(missingStatsValue), _lib.ptr(ic),
-                                         _lib.ptr(fc)))
+            blockStats(drec, dplanes, y1 - y0, m, ic, fc)
         with timings.interval('statscompletion'):
             ids = orig[1:m + 1].astype(numpy.int64)
             done = lhist[1:m + 1] == segSize[ids]
@@ -361,15 +409,7 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
             if len(rest):
                 flags = numpy.zeros(m + 1, dtype=numpy.uint8)
                 flags[rest + 1] = 1
-                npairs = int(lhist[1:m + 1][rest].sum())
-                so = numpy.empty(npairs, dtype=numpy.uint32)
-                vo = numpy.empty(npairs, dtype=numpy.int64)
-                cnt = ctypes.c_int64(0)
-                c.check(L.shp_gather_flagged_dev(c.handle, drec, dband, dt, n, m, _lib.ptr(flags), npairs,
-                                                 _lib.ptr(so), _lib.ptr(vo), ctypes.byref(cnt)))
-                if cnt.value != npairs:
-                    raise PyShepSegStatsError("internal: %d pixels of unfinished segments, expected %d"
-                                              % (cnt.value, npairs))
+                (so, vo) = gatherFlagged(drec, dplanes, n, m, flags, int(lhist[1:m + 1][rest].sum()))
                 carryIds.append(orig[so])
                 carryVals.append(vo.astype(src.bandDtype))
         with timings.interval('writing'):
@@ -378,7 +418,7 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
         # the segments that straddle block boundaries: all their pixels are here now
         with timings.interval('statscompletion'):
             allIds = numpy.concatenate(carryIds)
-            allVals = numpy.concatenate(carryVals)
+            allVals = numpy.concatenate(carryVals, axis=1)
             (uids, compact) = numpy.unique(allIds, return_inverse=True)
             counts = numpy.bincount(compact, minlength=len(uids))
             if not numpy.array_equal(counts, segSize[uids]):
@@ -387,9 +427,21 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
             ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
             fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
             seg1 = numpy.ascontiguousarray(compact + 1, dtype=numpy.uint32)
-            c.check(L.shp_segstats(c.handle, _lib.ptr(seg1), _lib.ptr(allVals), dt, len(seg1), m, nullFlag,
-                                   nullV, _lib.ptr(fast), nstats, int(missingStatsValue), _lib.ptr(ic),
-                                   _lib.ptr(fc)))
+            for (k, (plane, _nullVal, statsSelection)) in enumerate(entries):
+                # (shp_segstats numbers its columns from 0: the entry's own fast selection; with one entry that
+                #  is the combined one)
+                (bfast, bInt, bFloat) = makeFastStatsSelection(list(range(len(statsSelection))), statsSelection)
+                bic = numpy.zeros((max(bInt, 1), m + 1), dtype=numpy.int64)
+                bfc = numpy.zeros((max(bFloat, 1), m + 1), dtype=numpy.float32)
+                vals = numpy.ascontiguousarray(allVals[plane])
+                c.check(L.shp_segstats(c.handle, _lib.ptr(seg1), _lib.ptr(vals), dt, len(seg1), m,
+                                       int(hasNull[k]), int(nullArr[k]), _lib.ptr(bfast), len(bfast),
+                                       int(missingStatsValue), _lib.ptr(bic), _lib.ptr(bfc)))
+                for (own, comb) in zip(bfast, fast[bandOfStat == k]):
+                    if own[STATSEL_COLTYPE] == STAT_DTYPE_INT:
+                        ic[comb[STATSEL_COLARRAYINDEX]] = bic[own[STATSEL_COLARRAYINDEX]]
+                    else:
+                        fc[comb[STATSEL_COLARRAYINDEX]] = bfc[own[STATSEL_COLARRAYINDEX]]
             _pageRows(pagedRat, uids.astype(numpy.int64), ic[:numIntCols, 1:], fc[:numFloatCols, 1:], segSize,
                       numIntCols, numFloatCols, (emptyInt, emptyFloat))
     # pages no block touched hold only ids without pixels
@@ -410,6 +462,91 @@ def _streamStats(src, segSize, statsSelection_fast, numIntCols, numFloatCols, im
         raise PyShepSegStatsError('Not all pixels found during processing')              # tilingstats.py:211
 
 
+def _planeNumbers(bandSelections):
+    """The band numbers whose planes a call reads, ascending: a band listed twice is read once."""
+    return sorted(set(b for (b, _s) in bandSelections))
+
+
+def _tiledStats(imgfile, hostPlanes, segfile, bandSelections, statsSelection_fast, nullVals, missingStatsValue,
+                segSize, chunkPixels):
+    """What calcPerSegmentStatsTiled and calcPerSegmentStatsTiledBands share: the rasters resolved to a block
+    source (a device raster with resident labels; arrays / .npy; GDAL files), segSize, the attribute table, the
+    streaming loop, the result.  bandSelections: a list of (imgbandnum, statsSelection), statsSelection_fast their
+    combined fast selection (None: built here with makeFastStatsSelection, once the rasters are open).
+    hostPlanes: the 2-D planes of _planeNumbers(bandSelections) when the caller found imgfile to be an array or a
+    .npy path, else None.  nullVals(default): the null value of every entry, given
+    every entry's default (the raster's / its band's own nodata value, None on arrays)."""
+    timings = Timers()
+    from . import tiling as _tiling
+    flatSelection = [sel for (_b, s) in bandSelections for sel in s]
+    bandNums = [b for (b, _s) in bandSelections]
+    planes = _planeNumbers(bandSelections)
+    planeOfEntry = [planes.index(b) for b in bandNums]
+    c = _lib.ctx()
+    gdalSeg = None
+    if chunkPixels is None:
+        chunkPixels = STATS_CHUNK_PIXELS
+    with timings.interval('reading'):
+        if isinstance(imgfile, _tiling.DeviceRaster) and getattr(segfile, 'outDev', None):
+            (dptr, nrows, ncols, _nbytes) = segfile.outDev
+            (nb, ir, ic_) = imgfile.shape
+            if (ir, ic_) != (nrows, ncols):
+                raise PyShepSegStatsError("Images are different sizes")
+            for b in bandNums:
+                if not (1 <= b <= nb):
+                    raise PyShepSegStatsError("band %d not in image" % b)
+            nullVals = nullVals([imgfile.nullVal] * len(bandNums))
+            if segSize is None:
+                segSize = getattr(segfile, 'hist', None)
+            devPlanes = [imgfile.ptr + (b - 1) * nrows * ncols * imgfile.dtype.itemsize for b in planes]
+            src = _ChunkSource(c, None, None, devSeg=dptr, devPlanes=devPlanes, bandDtype=imgfile.dtype,
+                               shape=(nrows, ncols))
+            maxSegId = int(segfile.maxSegId)
+        else:
+            seg = _loadArray(segfile)
+            if seg is None or hostPlanes is None:
+                (seg, hostPlanes, nodata, gdalSeg, segSize) = _readGdalBands(imgfile, planes, segfile)
+                nullVals = nullVals([nodata[p] for p in planeOfEntry])
+            else:
+                nullVals = nullVals([None] * len(bandNums))
+            if hostPlanes[0].dtype.kind == 'f':
+                raise PyShepSegStatsError("Float image types not supported")        # tilingstats.py:450-452
+            if hostPlanes[0].shape != seg.shape:
+                raise PyShepSegStatsError("Images are different sizes")             # tilingstats.py:453-455
+            bdt = hostPlanes[0].dtype
+            if bdt not in _lib.SHP_DTYPES:
+                bdt = _lib.as_image(numpy.zeros((1, 1, 1), dtype=bdt))[0].dtype
+            src = _ChunkSource(c, seg, hostPlanes, bandDtype=bdt, shape=seg.shape)
+            maxSegId = None
+    try:
+        if segSize is None:
+            with timings.interval('reading'):
+                segSize = _countSegments(src, chunkPixels)
+        segSize = numpy.ascontiguousarray(segSize).astype(numpy.int64)
+        if maxSegId is not None and len(segSize) < maxSegId + 1:
+            raise PyShepSegStatsError("segSize has %d rows, segment id %d needs more" % (len(segSize), maxSegId))
+        fast = statsSelection_fast
+        if fast is None:
+            fast = makeFastStatsSelection(list(range(len(flatSelection))), flatSelection)[0]
+        if gdalSeg is not None:
+            attrTbl = _GdalRat(gdalSeg, flatSelection, fast)
+        else:
+            attrTbl = MemoryRat(len(segSize), [int(f[STATSEL_COLTYPE]) for f in fast])
+        entries = [(planeOfEntry[k], nullVals[k], s) for (k, (_b, s)) in enumerate(bandSelections)]
+        _streamStats(src, entries, segSize, fast, missingStatsValue, attrTbl, timings, chunkPixels)
+    finally:
+        src.close()
+    rtn = TiledStatsResult()
+    rtn.timings = timings
+    if isinstance(attrTbl, MemoryRat):
+        rtn.columns = {sel[0]: attrTbl.columns[i] for (i, sel) in enumerate(flatSelection)}
+        rtn.pagesWritten = attrTbl.pagesWritten
+    else:
+        attrTbl.flush()
+        rtn.columns = None
+    return rtn
+
+
 def calcPerSegmentStatsTiled(imgfile, imgbandnum, segfile, statsSelection,
         missingStatsValue=-9999, imgNullVal=None, segSize=None, chunkPixels=None):
     """
@@ -428,67 +565,12 @@ def calcPerSegmentStatsTiled(imgfile, imgbandnum, segfile, statsSelection,
     here otherwise.  Both rasters may already live in HBM: ``imgfile`` a ``tiling.DeviceRaster``
     and ``segfile`` the result of ``doTiledShepherdSegmentation(..., outfile=tiling._KEEP_ON_DEVICE)``.
     """
-    timings = Timers()
-    from . import tiling as _tiling
-    c = _lib.ctx()
-    gdalSeg = None
-    if chunkPixels is None:
-        chunkPixels = STATS_CHUNK_PIXELS
-    with timings.interval('reading'):
-        if isinstance(imgfile, _tiling.DeviceRaster) and getattr(segfile, 'outDev', None):
-            (dptr, nrows, ncols, _nbytes) = segfile.outDev
-            (nb, ir, ic_) = imgfile.shape
-            if (ir, ic_) != (nrows, ncols):
-                raise PyShepSegStatsError("Images are different sizes")
-            if not (1 <= imgbandnum <= nb):
-                raise PyShepSegStatsError("band %d not in image" % imgbandnum)
-            if imgNullVal is None:
-                imgNullVal = imgfile.nullVal
-            if segSize is None:
-                segSize = getattr(segfile, 'hist', None)
-            band = imgfile.ptr + (imgbandnum - 1) * nrows * ncols * imgfile.dtype.itemsize
-            src = _ChunkSource(c, None, None, devSeg=dptr, devBand=band, bandDtype=imgfile.dtype,
-                               shape=(nrows, ncols))
-            maxSegId = int(segfile.maxSegId)
-        else:
-            seg = _loadArray(segfile)
-            img = _loadArray(imgfile, imgbandnum)
-            if seg is None or img is None:
-                (seg, img, imgNullVal, gdalSeg, segSize) = _readGdal(imgfile, imgbandnum, segfile, imgNullVal)
-            if img.dtype.kind == 'f':
-                raise PyShepSegStatsError("Float image types not supported")        # tilingstats.py:450-452
-            if img.shape != seg.shape:
-                raise PyShepSegStatsError("Images are different sizes")             # tilingstats.py:453-455
-            bdt = img.dtype
-            if bdt not in _lib.SHP_DTYPES:
-                bdt = _lib.as_image(numpy.zeros((1, 1, 1), dtype=img.dtype))[0].dtype
-            src = _ChunkSource(c, seg, img, bandDtype=bdt, shape=seg.shape)
-            maxSegId = None
-    try:
-        if segSize is None:
-            with timings.interval('reading'):
-                segSize = _countSegments(src, chunkPixels)
-        segSize = numpy.ascontiguousarray(segSize).astype(numpy.int64)
-        if maxSegId is not None and len(segSize) < maxSegId + 1:
-            raise PyShepSegStatsError("segSize has %d rows, segment id %d needs more" % (len(segSize), maxSegId))
-        (fast, nInt, nFloat) = makeFastStatsSelection(list(range(len(statsSelection))), statsSelection)
-        if gdalSeg is not None:
-            attrTbl = _GdalRat(gdalSeg, statsSelection, fast)
-        else:
-            attrTbl = MemoryRat(len(segSize), [int(f[STATSEL_COLTYPE]) for f in fast])
-        _streamStats(src, segSize, fast, nInt, nFloat, imgNullVal, missingStatsValue, attrTbl, timings,
-                     chunkPixels)
-    finally:
-        src.close()
-    rtn = TiledStatsResult()
-    rtn.timings = timings
-    if isinstance(attrTbl, MemoryRat):
-        rtn.columns = {sel[0]: attrTbl.columns[i] for (i, sel) in enumerate(statsSelection)}
-        rtn.pagesWritten = attrTbl.pagesWritten
-    else:
-        attrTbl.flush()
-        rtn.columns = None
-    return rtn
+    # (the selection may name a column twice or be empty -- makeBandStatsSelection refuses both, so it is not used
+    #  here -- and the plane of an array is whatever _loadArray picks for imgbandnum)
+    img = _loadArray(imgfile, imgbandnum)
+    return _tiledStats(imgfile, None if img is None else [img], segfile, [(imgbandnum, statsSelection)], None,
+                       lambda default: [default[0] if imgNullVal is None else imgNullVal],
+                       missingStatsValue, segSize, chunkPixels)
 
 
 def _countSegments(src, chunkPixels):
@@ -545,168 +627,6 @@ def makeBandStatsSelection(bandSelections):
     return (fast, numpy.array(bandOfStat, dtype=numpy.intp), nInt, nFloat)
 
 
-class _BandsChunkSource(_ChunkSource):
-    """_ChunkSource for several planes of one image: a row block is the labels and one device pointer
-    per plane.  bands: host planes (arrays / memmaps), or devBands: device addresses of whole planes."""
-    def __init__(self, c, seg, bands, devSeg=None, devBands=None, bandDtype=None, shape=None):
-        _ChunkSource.__init__(self, c, seg, None, devSeg=devSeg, devBand=None, bandDtype=bandDtype, shape=shape)
-        (self.bands, self.devBands) = (bands, devBands)
-        self.nplanes = len(bands if devBands is None else devBands)
-
-    def chunk(self, y0, y1):
-        n = (y1 - y0) * self.ncols
-        isz = self.bandDtype.itemsize
-        if self.devSeg is not None:
-            return (ctypes.c_void_p(self.devSeg + 4 * y0 * self.ncols),
-                    [ctypes.c_void_p(p + isz * y0 * self.ncols) for p in self.devBands])
-        s = numpy.ascontiguousarray(self.seg[y0:y1], dtype=shepseg.SegIdType)
-        ds = self._buf(0, n * 4)
-        self.c.check(self.c._L.shp_dev_upload(self.c.handle, ds, _lib.ptr(s), s.nbytes))
-        dbs = []
-        for (k, band) in enumerate(self.bands):
-            b = numpy.ascontiguousarray(band[y0:y1], dtype=self.bandDtype)
-            db = self._buf(3 + k, n * isz)
-            self.c.check(self.c._L.shp_dev_upload(self.c.handle, db, _lib.ptr(b), b.nbytes))
-            dbs.append(db)
-        return (ds, dbs)
-
-    def scratch(self, i, nbytes):
-        return self._buf(1 + i, nbytes)             # (buffers 1 and 2; the planes' start at 3)
-
-
-def _streamStatsBands(src, planeOfEntry, segSize, bandSelections, fast, bandOfStat, numIntCols, numFloatCols,
-                      nullVals, missingStatsValue, attrTbl, timings, chunkPixels):
-    """_streamStats for several bands (bandSelections entry k reads plane planeOfEntry[k] of src with the
-    null value nullVals[k]).  Per row block the labels go up and are renumbered once, all entries'
-    statistics come out of one library call (shp_segstats2d_bands_dev), the complete / unfinished split
-    -- a property of the labels -- is made once; the unfinished segments' pixels are set aside as ids
-    once and one value array per plane, in one order, and reduced per entry at the end."""
-    c = src.c
-    L = c._L
-    (nrows, ncols) = (src.nrows, src.ncols)
-    S = len(segSize) - 1
-    dt = _lib.SHP_DTYPES[src.bandDtype]
-    nEntries = len(bandSelections)
-    fast = numpy.ascontiguousarray(fast, dtype=numpy.uint32)
-    perBand = numpy.ascontiguousarray(numpy.bincount(bandOfStat, minlength=nEntries), dtype=numpy.int32)
-    hasNull = numpy.ascontiguousarray([int(v is not None) for v in nullVals], dtype=numpy.int32)
-    nullArr = numpy.ascontiguousarray([0 if v is None else int(v) for v in nullVals], dtype=numpy.int64)
-    emptyInt = numpy.full(numIntCols, int(missingStatsValue), dtype=numpy.int64)
-    emptyFloat = numpy.full(numFloatCols, float(missingStatsValue), dtype=numpy.float32)
-    for sel in fast:
-        if sel[STATSEL_STATID] == STATID_PIXCOUNT:
-            emptyInt[sel[STATSEL_COLARRAYINDEX]] = 0
-    pagedRat = createPagedRat()
-    written = set()
-
-    def flush():
-        written.update(pid for (pid, pg) in pagedRat.items() if pg.pageComplete())
-        writeCompletePages(pagedRat, attrTbl, fast)
-
-    def pointers(planes, which):
-        arr = (ctypes.c_void_p * len(which))()
-        for (k, p) in enumerate(which):
-            arr[k] = planes[p].value
-        return arr
-
-    rowsPerChunk = max(1, min(nrows, int(chunkPixels) // max(ncols, 1)))
-    allPlanes = list(range(src.nplanes))
-    carryIds = []
-    carryVals = []
-    for y0 in range(0, nrows, rowsPerChunk):
-        y1 = min(nrows, y0 + rowsPerChunk)
-        n = (y1 - y0) * ncols
-        with timings.interval('reading'):
-            (dseg, dplanes) = src.chunk(y0, y1)
-        with timings.interval('accumulation'):
-            cap = min(S, n) + 1
-            drec = src.scratch(0, n * 4)
-            orig = numpy.zeros(cap, dtype=numpy.uint32)
-            lhist = numpy.zeros(cap, dtype=numpy.uint32)
-            nnew = ctypes.c_uint32(0)
-            c.check(L.shp_subset_recode_dev(c.handle, dseg, y1 - y0, ncols, 0, 0, ncols, y1 - y0, None,
-                                            1 << 30, S, drec, _lib.ptr(orig), _lib.ptr(lhist), cap,
-                                            ctypes.byref(nnew)))
-            m = nnew.value
-            if m == 0:
-                continue
-            ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
-            fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
-            c.check(L.shp_segstats2d_bands_dev(c.handle, drec, pointers(dplanes, planeOfEntry), dt, nEntries,
-                                               y1 - y0, ncols, m, _lib.ptr(hasNull), _lib.ptr(nullArr),
-                                               _lib.ptr(fast), _lib.ptr(perBand), int(missingStatsValue),
-                                               _lib.ptr(ic), _lib.ptr(fc)))
-        with timings.interval('statscompletion'):
-            ids = orig[1:m + 1].astype(numpy.int64)
-            done = lhist[1:m + 1] == segSize[ids]
-            sel = numpy.flatnonzero(done)
-            _pageRows(pagedRat, ids[sel], ic[:numIntCols, 1:][:, sel], fc[:numFloatCols, 1:][:, sel],
-                      segSize, numIntCols, numFloatCols, (emptyInt, emptyFloat))
-            rest = numpy.flatnonzero(~done)
-            if len(rest):
-                flags = numpy.zeros(m + 1, dtype=numpy.uint8)
-                flags[rest + 1] = 1
-                npairs = int(lhist[1:m + 1][rest].sum())
-                so = numpy.empty(npairs, dtype=numpy.uint32)
-                vo = numpy.empty((src.nplanes, npairs), dtype=numpy.int64)
-                cnt = ctypes.c_int64(0)
-                c.check(L.shp_gather_flagged_bands_dev(c.handle, drec, pointers(dplanes, allPlanes), dt,
-                                                       src.nplanes, n, m, _lib.ptr(flags), npairs, _lib.ptr(so),
-                                                       _lib.ptr(vo), ctypes.byref(cnt)))
-                if cnt.value != npairs:
-                    raise PyShepSegStatsError("internal: %d pixels of unfinished segments, expected %d"
-                                              % (cnt.value, npairs))
-                carryIds.append(orig[so])
-                carryVals.append(vo.astype(src.bandDtype))
-        with timings.interval('writing'):
-            flush()
-    if carryIds:
-        # the segments that straddle block boundaries: all their pixels are here now
-        with timings.interval('statscompletion'):
-            allIds = numpy.concatenate(carryIds)
-            allVals = numpy.concatenate(carryVals, axis=1)
-            (uids, compact) = numpy.unique(allIds, return_inverse=True)
-            counts = numpy.bincount(compact, minlength=len(uids))
-            if not numpy.array_equal(counts, segSize[uids]):
-                raise PyShepSegStatsError('Not all pixels found during processing')     # tilingstats.py:211
-            m = len(uids)
-            ic = numpy.zeros((max(numIntCols, 1), m + 1), dtype=numpy.int64)
-            fc = numpy.zeros((max(numFloatCols, 1), m + 1), dtype=numpy.float32)
-            seg1 = numpy.ascontiguousarray(compact + 1, dtype=numpy.uint32)
-            for (k, (_bandnum, statsSelection)) in enumerate(bandSelections):
-                # (the one-band entry point numbers its columns from 0: the entry's own fast selection)
-                (bfast, bInt, bFloat) = makeFastStatsSelection(list(range(len(statsSelection))), statsSelection)
-                bic = numpy.zeros((max(bInt, 1), m + 1), dtype=numpy.int64)
-                bfc = numpy.zeros((max(bFloat, 1), m + 1), dtype=numpy.float32)
-                vals = numpy.ascontiguousarray(allVals[planeOfEntry[k]])
-                c.check(L.shp_segstats(c.handle, _lib.ptr(seg1), _lib.ptr(vals), dt, len(seg1), m,
-                                       int(hasNull[k]), int(nullArr[k]), _lib.ptr(bfast), len(bfast),
-                                       int(missingStatsValue), _lib.ptr(bic), _lib.ptr(bfc)))
-                for (own, comb) in zip(bfast, fast[bandOfStat == k]):
-                    if own[STATSEL_COLTYPE] == STAT_DTYPE_INT:
-                        ic[comb[STATSEL_COLARRAYINDEX]] = bic[own[STATSEL_COLARRAYINDEX]]
-                    else:
-                        fc[comb[STATSEL_COLARRAYINDEX]] = bfc[own[STATSEL_COLARRAYINDEX]]
-            _pageRows(pagedRat, uids.astype(numpy.int64), ic[:numIntCols, 1:], fc[:numFloatCols, 1:], segSize,
-                      numIntCols, numFloatCols, (emptyInt, emptyFloat))
-    # pages no block touched hold only ids without pixels
-    with timings.interval('writing'):
-        for pageId in range(0, S + 1, RAT_PAGE_SIZE):
-            if pageId in written or pageId in pagedRat:
-                continue
-            if (segSize[max(pageId, 1):pageId + RAT_PAGE_SIZE] != 0).any():
-                raise PyShepSegStatsError('Not all pixels found during processing')      # tilingstats.py:211
-            numSeg = min(RAT_PAGE_SIZE, S + 1 - pageId)
-            page = pagedRat[pageId] = RatPage(numIntCols, numFloatCols, pageId, numSeg)
-            first = 1 if pageId == shepseg.SEGNULLVAL else 0
-            page.intcols[:, first:] = emptyInt[:, None]
-            page.floatcols[:, first:] = emptyFloat[:, None]
-            page.complete[:] = True
-        flush()
-    if len(pagedRat) > 0:
-        raise PyShepSegStatsError('Not all pixels found during processing')              # tilingstats.py:211
-
-
 def _entryNullVals(imgNullVal, nEntries, default):
     """One null value per bandSelections entry: imgNullVal is one value for all, a list with one entry
     each, or None (then default[k])."""
@@ -734,87 +654,26 @@ def calcPerSegmentStatsTiledBands(imgfile, bandSelections, segfile, missingStats
     The label raster is read, uploaded, renumbered and histogrammed once per row block instead of once
     per band, and the patches' label tables are built once (csrc/segstats.h, k_stats_patch_bands).
     """
-    timings = Timers()
-    from . import tiling as _tiling
-    (fast, bandOfStat, nInt, nFloat) = makeBandStatsSelection(bandSelections)    # (the checks: before anything is read)
+    (fast, _bandOfStat, _nInt, _nFloat) = makeBandStatsSelection(bandSelections)    # (the checks: before anything is read)
     bandSelections = [(int(b), list(s)) for (b, s) in bandSelections]
-    flatSelection = [sel for (_b, s) in bandSelections for sel in s]
-    bandNums = [b for (b, _s) in bandSelections]
-    planes = sorted(set(bandNums))                        # a band listed twice is read once
-    planeOfEntry = [planes.index(b) for b in bandNums]
-    nEntries = len(bandSelections)
-    c = _lib.ctx()
-    gdalSeg = None
-    if chunkPixels is None:
-        chunkPixels = STATS_CHUNK_PIXELS
-    with timings.interval('reading'):
-        if isinstance(imgfile, _tiling.DeviceRaster) and getattr(segfile, 'outDev', None):
-            (dptr, nrows, ncols, _nbytes) = segfile.outDev
-            (nb, ir, ic_) = imgfile.shape
-            if (ir, ic_) != (nrows, ncols):
-                raise PyShepSegStatsError("Images are different sizes")
-            for b in bandNums:
-                if not (1 <= b <= nb):
+    img = _loadArray(imgfile)
+    hostPlanes = None
+    if img is not None:
+        if img.ndim == 3:
+            for (b, _s) in bandSelections:
+                if not (1 <= b <= img.shape[0]):
                     raise PyShepSegStatsError("band %d not in image" % b)
-            nullVals = _entryNullVals(imgNullVal, nEntries, [imgfile.nullVal] * nEntries)
-            if segSize is None:
-                segSize = getattr(segfile, 'hist', None)
-            devBands = [imgfile.ptr + (b - 1) * nrows * ncols * imgfile.dtype.itemsize for b in planes]
-            src = _BandsChunkSource(c, None, None, devSeg=dptr, devBands=devBands, bandDtype=imgfile.dtype,
-                                    shape=(nrows, ncols))
-            maxSegId = int(segfile.maxSegId)
+            hostPlanes = [img[b - 1] for b in _planeNumbers(bandSelections)]
         else:
-            seg = _loadArray(segfile)
-            img = _loadArray(imgfile)
-            if seg is None or img is None:
-                (seg, imgs, nodata, gdalSeg, segSize) = _readGdalBands(imgfile, planes, segfile)
-                nullVals = _entryNullVals(imgNullVal, nEntries, [nodata[p] for p in planeOfEntry])
-            else:
-                if img.ndim == 3:
-                    for b in bandNums:
-                        if not (1 <= b <= img.shape[0]):
-                            raise PyShepSegStatsError("band %d not in image" % b)
-                    imgs = [img[b - 1] for b in planes]
-                else:
-                    imgs = [img for _b in planes]             # (a single plane stands for any band, as _loadArray has it)
-                nullVals = _entryNullVals(imgNullVal, nEntries, [None] * nEntries)
-            if imgs[0].dtype.kind == 'f':
-                raise PyShepSegStatsError("Float image types not supported")        # tilingstats.py:450-452
-            if imgs[0].shape != seg.shape:
-                raise PyShepSegStatsError("Images are different sizes")             # tilingstats.py:453-455
-            bdt = imgs[0].dtype
-            if bdt not in _lib.SHP_DTYPES:
-                bdt = _lib.as_image(numpy.zeros((1, 1, 1), dtype=bdt))[0].dtype
-            src = _BandsChunkSource(c, seg, imgs, bandDtype=bdt, shape=seg.shape)
-            maxSegId = None
-    try:
-        if segSize is None:
-            with timings.interval('reading'):
-                segSize = _countSegments(src, chunkPixels)
-        segSize = numpy.ascontiguousarray(segSize).astype(numpy.int64)
-        if maxSegId is not None and len(segSize) < maxSegId + 1:
-            raise PyShepSegStatsError("segSize has %d rows, segment id %d needs more" % (len(segSize), maxSegId))
-        if gdalSeg is not None:
-            attrTbl = _GdalRat(gdalSeg, flatSelection, fast)
-        else:
-            attrTbl = MemoryRat(len(segSize), [int(f[STATSEL_COLTYPE]) for f in fast])
-        _streamStatsBands(src, planeOfEntry, segSize, bandSelections, fast, bandOfStat, nInt, nFloat, nullVals,
-                          missingStatsValue, attrTbl, timings, chunkPixels)
-    finally:
-        src.close()
-    rtn = TiledStatsResult()
-    rtn.timings = timings
-    if isinstance(attrTbl, MemoryRat):
-        rtn.columns = {sel[0]: attrTbl.columns[i] for (i, sel) in enumerate(flatSelection)}
-        rtn.pagesWritten = attrTbl.pagesWritten
-    else:
-        attrTbl.flush()
-        rtn.columns = None
-    return rtn
+            hostPlanes = [img for _b in _planeNumbers(bandSelections)]     # (a single plane stands for any band, as _loadArray has it)
+    return _tiledStats(imgfile, hostPlanes, segfile, bandSelections, fast,
+                       lambda default: _entryNullVals(imgNullVal, len(bandSelections), default),
+                       missingStatsValue, segSize, chunkPixels)
 
 
 def _readGdalBands(imgfile, bandnums, segfile):
-    """_readGdal for several bands of imgfile: (seg, bands, each band's nodata value, segment dataset, segSize)."""
+    """The reference's doImageAlignmentChecks + Histogram column read (tilingstats.py:151-166, :409-461) for the
+    bands bandnums of imgfile; returns (seg, bands, each band's nodata value, segment dataset, segSize)."""
     try:
         from osgeo import gdal
     except ImportError:
@@ -865,32 +724,6 @@ class _GdalRat(object):
 
     def flush(self):
         self.segds.FlushCache()
-
-
-def _readGdal(imgfile, imgbandnum, segfile, imgNullVal):
-    """The reference's doImageAlignmentChecks + Histogram column read (tilingstats.py:151-166,
-    :409-461); returns (seg, band, nodata, segment dataset, segSize)."""
-    try:
-        from osgeo import gdal
-    except ImportError:
-        raise PyShepSegStatsError("GDAL (osgeo) is not importable here: pass numpy arrays or "
-                                  ".npy paths")
-    gdal.UseExceptions()
-    segds = segfile if isinstance(segfile, gdal.Dataset) else gdal.Open(segfile, gdal.GA_Update)
-    imgds = gdal.Open(imgfile)
-    if (segds.RasterXSize != imgds.RasterXSize) or (segds.RasterYSize != imgds.RasterYSize):
-        raise PyShepSegStatsError("Images are different sizes")
-    if segds.GetGeoTransform() != imgds.GetGeoTransform():
-        raise PyShepSegStatsError("Images have different spatial extents or pixel sizes")
-    imgband = imgds.GetRasterBand(imgbandnum)
-    if imgNullVal is None:
-        imgNullVal = imgband.GetNoDataValue()
-    attrTbl = segds.GetRasterBand(1).GetDefaultRAT()
-    names = [attrTbl.GetNameOfCol(i) for i in range(attrTbl.GetColumnCount())]
-    if 'Histogram' not in names:
-        raise PyShepSegStatsError("Histogram column must exist before calculating per-segment stats")
-    segSize = attrTbl.ReadAsArray(names.index('Histogram')).astype(numpy.uint32)
-    return (segds.GetRasterBand(1).ReadAsArray(), imgband.ReadAsArray(), imgNullVal, segds, segSize)
 
 
 # ------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """The GDAL-facing branches of pyshepseg_amd (tiling._GdalSource, _createGdalOutput, _finishGdalOutput;
-tilingstats._readGdal, _GdalRat), executed against the in-memory ``osgeo`` stand-in of tests/fake_osgeo
+tilingstats._readGdalBands, _GdalRat), executed against the in-memory ``osgeo`` stand-in of tests/fake_osgeo
 and compared with what the reference issues (tiling.py:961-975, :1343-1404; tilingstats.py:151-166,
 :409-461, :682-764).  No GPU: these run wherever the tests run.  The end-to-end runs through the same
 branches are in test_gpu_gdal_double.py."""
@@ -96,12 +96,12 @@ def test_gdal_rat_and_alignment_checks(gdal):
     make_image(gdal, 'img.kea', img, 0)
     make_image(gdal, 'seg.kea', seg[None], 0)
     with pytest.raises(ts.PyShepSegStatsError, match='Histogram column must exist'):
-        ts._readGdal('img.kea', 1, 'seg.kea', None)
+        ts._readGdalBands('img.kea', [1], 'seg.kea')
     rat = gdal.REGISTRY['seg.kea'].GetRasterBand(1).GetDefaultRAT()
     rat.SetRowCount(4)
     rat.CreateColumn('Histogram', gdal.GFT_Real, gdal.GFU_PixelCount)
     rat.WriteArray(np.array([1, 2, 1, 2], dtype=np.float64), 0)
-    (s, b, nullv, segds, segSize) = ts._readGdal('img.kea', 1, 'seg.kea', None)
+    (s, (b,), (nullv,), segds, segSize) = ts._readGdalBands('img.kea', [1], 'seg.kea')
     assert np.array_equal(s, seg) and np.array_equal(b, img[0]) and nullv == 0 and segds.path == 'seg.kea'
     assert segSize.dtype == np.uint32 and segSize.tolist() == [1, 2, 1, 2]
     sel = [('mn', 'min'), ('avg', 'mean'), ('sd', 'stddev'), ('p', 'percentile', 50)]
@@ -116,7 +116,7 @@ def test_gdal_rat_and_alignment_checks(gdal):
     assert rat.GetColumnCount() == 5
     make_image(gdal, 'small.kea', img[:, :1], 0)
     with pytest.raises(ts.PyShepSegStatsError, match='different sizes'):
-        ts._readGdal('small.kea', 1, 'seg.kea', None)
+        ts._readGdalBands('small.kea', [1], 'seg.kea')
     make_image(gdal, 'shifted.kea', img, 0, gt=(1.0, 30.0, 0.0, 2.0, 0.0, -30.0))
     with pytest.raises(ts.PyShepSegStatsError, match='different spatial extents'):
-        ts._readGdal('shifted.kea', 1, 'seg.kea', None)
+        ts._readGdalBands('shifted.kea', [1], 'seg.kea')

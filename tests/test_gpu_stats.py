@@ -119,6 +119,53 @@ def test_stats_errors():
                                         [('m', 'mean')])
 
 
+def _small_case():
+    seg = (np.arange(40)[:, None] // 4 * 8 + np.arange(64)[None, :] // 8 + 1).astype(np.uint32)
+    img = (np.arange(3 * 40 * 64).reshape(3, 40, 64) * 7 % 251).astype(np.uint16)
+    return seg, img
+
+
+def test_stats_column_named_twice():
+    """calcPerSegmentStatsTiled takes a statsSelection that names a column twice (the several-band function refuses
+    it): both statistics are computed, and ``columns`` keeps the later one under the name"""
+    from pyshepseg_amd import tilingstats as ts
+    seg, img = _small_case()
+    want = ts.calcPerSegmentStatsTiled(img, 2, seg, [('lo', 'min'), ('hi', 'max')])
+    got = ts.calcPerSegmentStatsTiled(img, 2, seg, [('a', 'min'), ('a', 'max')])
+    assert list(got.columns) == ['a'] and np.array_equal(got.columns['a'], want.columns['hi'])
+    assert got.pagesWritten == want.pagesWritten
+    with pytest.raises(ts.PyShepSegStatsError, match="Column name 'a' is used more than once"):
+        ts.calcPerSegmentStatsTiledBands(img, [(2, [('a', 'min'), ('a', 'max')])], seg)
+
+
+def test_stats_empty_selection():
+    """an empty statsSelection is not refused by calcPerSegmentStatsTiled itself (the several-band function does
+    that): it reaches the library, which takes no call without a statistic"""
+    from pyshepseg_amd import tilingstats as ts, _lib
+    seg, img = _small_case()
+    with pytest.raises(_lib.ShepsegHipError, match='bad argument'):
+        ts.calcPerSegmentStatsTiled(img, 1, seg, [])
+    with pytest.raises(ts.PyShepSegStatsError, match='selects no statistic'):
+        ts.calcPerSegmentStatsTiledBands(img, [(1, [])], seg)
+
+
+def test_stats_band_number_on_host_arrays():
+    """host arrays: a 2-D image stands for any band number; a band number past the end of a 3-D image is numpy's
+    IndexError, not a PyShepSegStatsError (the several-band function raises 'band %d not in image')"""
+    from pyshepseg_amd import tilingstats as ts
+    seg, img = _small_case()
+    sel = [('m', 'mean'), ('md', 'median'), ('n', 'pixcount')]
+    want = ts.calcPerSegmentStatsTiled(img, 2, seg, sel)
+    got = ts.calcPerSegmentStatsTiled(img[1], 3, seg, sel)
+    for name in ('m', 'md', 'n'):
+        assert got.columns[name].dtype == want.columns[name].dtype
+        assert np.array_equal(got.columns[name].view(np.uint8), want.columns[name].view(np.uint8)), name
+    with pytest.raises(IndexError):
+        ts.calcPerSegmentStatsTiled(img, 4, seg, sel)
+    with pytest.raises(ts.PyShepSegStatsError, match='band 4 not in image'):
+        ts.calcPerSegmentStatsTiledBands(img, [(4, sel)], seg)
+
+
 def _spatial_cases(g):
     from pyshepseg_amd import tilingstats as ts
     R, I = ts.GFT_Real, ts.GFT_Integer

@@ -210,6 +210,8 @@ def test_bands_counts_the_labels_once(oracle, monkeypatch):
     bandSelections = [(b + 1, [('m%d' % b, 'mean'), ('n%d' % b, 'pixcount')]) for b in range(4)]
     got = ts.calcPerSegmentStatsTiledBands(img, bandSelections, seg)
     assert len(calls) == 1
+    ts.calcPerSegmentStatsTiled(img, 2, seg, bandSelections[1][1])          # (the one-band call: the same code)
+    assert len(calls) == 2
     monkeypatch.setattr(ts, '_countSegments', real)
     check_against_single_and_oracle(oracle, img, seg, bandSelections, [None] * 4, got)
 
