@@ -376,6 +376,41 @@ int shp_dstats_merge_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const int64_t
                          const uint32_t *stats_sel, int nstats, int64_t missing, uint32_t id_lo, uint32_t id_hi,
                          void *d_cols, int64_t *n_merged_out, int64_t *n_ids_out);
 
+/* The device-resident split for several bands in one call (the data path of
+ * calcPerSegmentStatsDistributedBands): they replace one shp_dstats_local_dev / shp_dstats_merge_dev pair PER
+ * ENTRY, and do what depends on the labels alone once.  A "band" is an entry of the caller's list (a plane, a null
+ * value, nstats_per_band[b] rows of stats_sel, built as for shp_segstats2d_bands_dev), a "plane" a distinct image
+ * band; plane_of_band[b] < nplanes names the plane entry b reads.
+ *  shp_dstats_local_bands_dev replaces nbands calls of shp_dstats_local_dev: the statistics of all entries in one
+ *    pass over the labels (as shp_segstats2d_bands_dev), ONE local histogram, ONE classification that keeps or
+ *    clears the rows of all entries' columns in d_cols, ONE gather of the straddlers' pixels: *d_pair_seg_out =
+ *    *n_pairs_out uint32 ids, *d_pair_val_out = nplanes rows of raw pixel values IN THE PLANES' PIXEL TYPE,
+ *    *pair_row_bytes_out bytes apart (a multiple of 16), every row in the order of the ids; both in the context's
+ *    workspace, valid until its next call.  Null values are not applied to the pairs: they belong to the entries
+ *    and are applied at the merge.  Unlike shp_dstats_local_dev it refuses a histogram that cannot belong to these
+ *    labels: ids with MORE pixels in these rows than d_hist gives them fail with SHP_ERR_ARG, the message naming
+ *    their number (the one-band call clears their rows silently).  nrows * ncols may be 0 (d_seg is not read).
+ *  shp_dstats_merge_bands_dev replaces nbands calls of shp_dstats_merge_dev: d_pair_seg = `world` slots of `slot`
+ *    ids, d_pair_val = `world` blocks of nplanes rows of values, slot_row_bytes apart on every rank; the pairs with
+ *    id_lo <= id < id_hi are picked once, all planes' values with them, reduced per entry and their rows written
+ *    into d_cols.
+ *  4 + nplanes * itemsize bytes per straddler pixel travel, against 12 * nbands with the one-band pair.  Summing
+ *  d_cols over the ranks as above gives the columns of shp_segstats2d_bands_dev, each with the bits
+ *  shp_dstats_local_dev / _merge_dev give for its entry alone. */
+int shp_dstats_local_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_planes, int nplanes,
+                               const int *plane_of_band, int dtype, int nbands, int64_t nrows, int64_t ncols,
+                               uint32_t max_seg_id, const int *has_null, const int64_t *null_val,
+                               const uint32_t *stats_sel, const int *nstats_per_band, int64_t missing,
+                               const uint32_t *d_hist, int keep_unheld, void *d_cols, void **d_pair_seg_out,
+                               void **d_pair_val_out, int64_t *pair_row_bytes_out, int64_t *n_pairs_out,
+                               int64_t *n_straddlers_out);
+int shp_dstats_merge_bands_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const void *d_pair_val, int64_t slot,
+                               int64_t slot_row_bytes, int world, const uint32_t *counts, int dtype, int nbands,
+                               int nplanes, const int *plane_of_band, uint32_t max_seg_id, const int *has_null,
+                               const int64_t *null_val, const uint32_t *stats_sel, const int *nstats_per_band,
+                               int64_t missing, uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_merged_out,
+                               int64_t *n_ids_out);
+
 /* ---- subset --------------------------------------------------------------------------
  * replaces the tile loop of subset.subsetImage (subset.py:124-166) and its njit kernel
  * processSubsetTile (subset.py:366-425): the window (tlx, tly, xs, ys) of a label raster is

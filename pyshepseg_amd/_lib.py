@@ -190,6 +190,13 @@ _SIGS = {
     'shp_dstats_merge_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int, _c.c_uint32, _c.c_int,
                                         _c.c_int64, _vp, _c.c_int, _c.c_int64, _c.c_uint32, _c.c_uint32, _vp,
                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    'shp_dstats_local_bands_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64,
+                                              _c.c_uint32, _vp, _vp, _vp, _vp, _c.c_int64, _vp, _c.c_int, _vp,
+                                              _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_c.c_int64),
+                                              _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
+    'shp_dstats_merge_bands_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int, _vp, _c.c_int, _c.c_int,
+                                              _c.c_int, _vp, _c.c_uint32, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_uint32,
+                                              _c.c_uint32, _vp, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     'shp_spatial_vario_redo_count': (_c.c_int, [_vp, _c.POINTER(_c.c_int64)]),
     'shp_dspatial_vario_pairs': (_c.c_int, [_vp, _vp, _c.c_int64, _c.POINTER(_c.c_int64)]),
     'shp_dspatial_vario_redo_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _vp, _c.c_int64,

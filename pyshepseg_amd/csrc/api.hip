@@ -1243,6 +1243,52 @@ API int shp_dstats_merge_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const int
                             max_seg_id, has_null, null_val, stats_sel, nstats, missing, id_lo, id_hi, d_cols, n_merged_out, n_ids_out);
 }
 
+// the same for several bands in one call (segstats.h: run_dstats_local_bands / run_dstats_merge_bands)
+API int shp_dstats_local_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_planes, int nplanes,
+                                   const int *plane_of_band, int dtype, int nbands, int64_t nrows, int64_t ncols,
+                                   uint32_t max_seg_id, const int *has_null, const int64_t *null_val,
+                                   const uint32_t *stats_sel, const int *nstats_per_band, int64_t missing,
+                                   const uint32_t *d_hist, int keep_unheld, void *d_cols, void **d_pair_seg_out,
+                                   void **d_pair_val_out, int64_t *pair_row_bytes_out, int64_t *n_pairs_out,
+                                   int64_t *n_straddlers_out)
+{
+    CHK(enter(ctx));
+    if (!d_planes || !plane_of_band || !has_null || !null_val || !stats_sel || !nstats_per_band || !d_hist || !d_cols ||
+        !d_pair_seg_out || !d_pair_val_out || !pair_row_bytes_out || !n_pairs_out || !n_straddlers_out || nbands < 1 ||
+        nplanes < 1 || nplanes > nbands || dtype_size(dtype) == 0 || nrows < 0 || ncols < 0)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0xffffffffll || ncols > 0xffffffffll || nrows * ncols >= 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "raster too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
+    if (!d_seg && nrows * ncols > 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    for (int p = 0; p < nplanes; p++) if (!d_planes[p]) SHP_FAIL(ctx, SHP_ERR_ARG, "plane %d: no band", p);
+    uint32_t *ps = nullptr;
+    void *pv = nullptr;
+    CHK(run_dstats_local_bands(ctx, d_seg, d_planes, nplanes, plane_of_band, dtype, nbands, (uint32_t)nrows, (uint32_t)ncols,
+                               max_seg_id, has_null, null_val, stats_sel, nstats_per_band, missing, d_hist, keep_unheld,
+                               d_cols, &ps, &pv, pair_row_bytes_out, n_pairs_out, n_straddlers_out));
+    *d_pair_seg_out = ps;
+    *d_pair_val_out = pv;
+    return 0;
+}
+
+API int shp_dstats_merge_bands_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const void *d_pair_val, int64_t slot,
+                                   int64_t slot_row_bytes, int world, const uint32_t *counts, int dtype, int nbands,
+                                   int nplanes, const int *plane_of_band, uint32_t max_seg_id, const int *has_null,
+                                   const int64_t *null_val, const uint32_t *stats_sel, const int *nstats_per_band,
+                                   int64_t missing, uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_merged_out,
+                                   int64_t *n_ids_out)
+{
+    CHK(enter(ctx));
+    if (!plane_of_band || !has_null || !null_val || !stats_sel || !nstats_per_band || !counts || !d_cols || !n_merged_out ||
+        !n_ids_out || nbands < 1 || nplanes < 1 || nplanes > nbands || dtype_size(dtype) == 0 || slot < 0 || world < 1 ||
+        slot >= 0xffffffffll || slot_row_bytes < 0 || (slot > 0 && (!d_pair_seg || !d_pair_val)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    for (int r = 0; r < world; r++) if ((int64_t)counts[r] > slot) SHP_FAIL(ctx, SHP_ERR_ARG, "counts[%d] exceeds the slot", r);
+    return run_dstats_merge_bands(ctx, d_pair_seg, d_pair_val, (uint32_t)slot, (size_t)slot_row_bytes, (uint32_t)world, counts,
+                                  dtype, nbands, nplanes, plane_of_band, max_seg_id, has_null, null_val, stats_sel,
+                                  nstats_per_band, missing, id_lo, id_hi, d_cols, n_merged_out, n_ids_out);
+}
+
 // ---- subset ---------------------------------------------------------------------
 static int subset_check(shp_ctx *ctx, int64_t img_rows, int64_t img_cols, int64_t tlx, int64_t tly,
                         int64_t xs, int64_t ys, int tile_size)

@@ -892,10 +892,14 @@ __global__ __launch_bounds__(256) void k_stats_left_keys(const uint32_t *__restr
 
 // d_seg, bands_host[b] (device pointers): a row block of nrows x ncols pixels.  sel_host: the combined selection, nstats_per_band[b] consecutive rows for band b, column array indices
 // running through all bands; the outputs are HOST arrays of all bands' columns.
+// dev_int / dev_flt given: the columns stay in the context's workspace (ctx->ssum), nothing is copied to the host.
+// allow_patches false: everything goes through the sorts whatever SHEPSEG_STATS_PATCH says (a 1 x m list of pairs
+// has no patches worth the name).
 static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *const *bands_host, int dtype, int nbands,
                               uint32_t nrows, uint32_t ncols, uint32_t S, const int *has_null, const int64_t *null_val,
                               const uint32_t *sel_host, const int *nstats_per_band, int64_t missing,
-                              int64_t *intcols_out, float *fltcols_out)
+                              int64_t *intcols_out, float *fltcols_out, long long **dev_int = nullptr,
+                              float **dev_flt = nullptr, bool allow_patches = true)
 {
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)S + 1;
@@ -927,7 +931,7 @@ static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *c
                            nstats_per_band[b], 0};
     HIPCHK(ctx, hipMemcpyAsync(d_sel, pin, sel_bytes + tab_bytes, hipMemcpyHostToDevice, st));
     const int ps = prof_begin(ctx, PROF_SEGSTATS);
-    const bool patches = stats_use_patches(n, S, true);
+    const bool patches = stats_use_patches(n, S, allow_patches);
     if (patches) {
         CHK(buf_ensure(ctx, ctx->tcount, (ns + 1) * 4));
         CHK(buf_ensure(ctx, ctx->mergeto, ns + 64));
@@ -970,6 +974,7 @@ static int run_segstats_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *c
         }
     }
     prof_end(ctx, ps);
+    if (dev_int) { *dev_int = d_int; *dev_flt = d_flt; return 0; }
     return segstats_download(ctx, intcols_out, d_int, (size_t)nint * ns * 8, fltcols_out, d_flt, (size_t)nflt * ns * 4);
 }
 
@@ -1293,6 +1298,242 @@ static int run_dstats_merge(shp_ctx *ctx, const uint32_t *d_pseg, const long lon
     float *df = nullptr;
     CHK(run_segstats(ctx, bp<uint32_t>(ctx->lab), ctx->img.p, dtype, m, S, has_null, null_val, sel_host, nstats, missing,
                      nullptr, nullptr, 0, 0, &di, &df));
+    CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
+    uint32_t *present = bp<uint32_t>(ctx->chnext);
+    HIPCHK(ctx, hipMemsetAsync(present, 0, ns * 4, st));
+    hipLaunchKernelGGL(k_label_hist, dim3(grid_for(m, 256)), dim3(256), 0, st, bp<uint32_t>(ctx->lab), m, S, present); KCHK(ctx);
+    HIPCHK(ctx, hipMemsetAsync(d_n, 0, 4, st));
+    hipLaunchKernelGGL(k_dstats_take, dim3(grid_for(ns, 256)), dim3(256), 0, st, present, S, nint, nflt, di, df,
+                       (long long *)d_cols, (float *)((long long *)d_cols + (size_t)nint * ns), d_n); KCHK(ctx);
+    uint32_t ids = 0;
+    CHK(read_u32(ctx, d_n, &ids));
+    *n_ids = (int64_t)ids;
+    return 0;
+}
+
+// ---- the same split for several bands in one call (distributed.calcPerSegmentStatsDistributedBands) ---------------
+// "band" = an entry of the caller's bandSelections (a plane, a null value, some statistics), "plane" = a distinct
+// image band; plane_of_band[e] says which plane entry e reads.  Everything that depends on the labels alone -- the
+// local label histogram, the classification against the global one, the straddlers' ids on the wire, the pick of
+// this rank's id share, the `present` histogram -- is done once instead of once per entry, and the straddlers'
+// values travel in the planes' own pixel type: 4 + nplanes * itemsize bytes per straddler pixel.
+// Values travel RAW, nulls included: a null value belongs to an entry, and two entries may read one plane with
+// different ones, so it is applied where the statistics are computed (k_stats_keys at the merge).
+
+// rows of values lie this many bytes apart (16-byte aligned, so that every plane's row can be copied and read
+// with wide accesses whatever the count)
+static inline size_t dstats_row_bytes(size_t count, int dtype) { return (count * dtype_size(dtype) + 15) & ~(size_t)15; }
+
+// ids whose local count EXCEEDS the global histogram: k_dstats_classify would take them for complete nowhere and
+// straddling nowhere and clear their rows silently -- the sign of a histogram that belongs to other labels
+__global__ __launch_bounds__(256) void k_dstats_stale(const uint32_t *__restrict__ lh, const uint32_t *__restrict__ gh,
+                                                      uint32_t S, unsigned long long *counter)
+{
+    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
+    const bool over = id != 0 && id <= (size_t)S && lh[id] > gh[id];
+    const unsigned long long m = __ballot(over);
+    if (m != 0ull && lane_id() == 0) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// k_gather_flagged_bands with the values left in the planes' pixel type T (only its width matters: nothing is
+// computed here): the id once, and row b of out_val = plane b's raw values, rows row_bytes apart.
+template <typename T>
+__global__ __launch_bounds__(256) void k_gather_flagged_planes(const uint32_t *__restrict__ seg,
+                                                               const StatsBand *__restrict__ planes, int nplanes,
+                                                               uint32_t n, uint32_t S, const uint8_t *__restrict__ flags,
+                                                               uint32_t *__restrict__ out_seg,
+                                                               uint8_t *__restrict__ out_val, size_t row_bytes,
+                                                               uint32_t cap, uint32_t *count)
+{
+    __shared__ uint32_t s_buf[4096];
+    __shared__ uint32_t s_cnt, s_base;
+    gather_flagged_positions(seg, n, S, flags, count, s_buf, &s_cnt, &s_base);
+    for (uint32_t i = threadIdx.x; i < s_cnt; i += 256u) {
+        const uint32_t o = s_base + i;
+        if (o < cap) {
+            const uint32_t p = s_buf[i];
+            out_seg[o] = seg[p];
+            for (int b = 0; b < nplanes; b++)
+                ((T *)(out_val + (size_t)b * row_bytes))[o] = ((const T *)planes[b].band)[p];
+        }
+    }
+}
+
+// Local part.  planes_host: nplanes device pointers (this rank's rows of the distinct planes).  The pairs end up in
+// ctx->aux (cap ids) and ctx->aux2 (nplanes rows of cap values of the pixel type, dstats_row_bytes(cap) apart): both
+// hold run_segstats_bands' sort keys until the statistics are done, so they are sized for the pairs only AFTER the
+// classify kernel has read the columns out of ctx->ssum into d_cols (nothing between the statistics and that kernel
+// touches ssum, aux or aux2), and the pairs stay valid until the context's next call.
+static int run_dstats_local_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *const *planes_host, int nplanes,
+                                  const int *plane_of_band, int dtype, int nbands, uint32_t nrows, uint32_t ncols,
+                                  uint32_t S, const int *has_null, const int64_t *null_val, const uint32_t *sel_host,
+                                  const int *nstats_per_band, int64_t missing, const uint32_t *d_hist, int keep_unheld,
+                                  void *d_cols, uint32_t **d_pair_seg, void **d_pair_val, int64_t *pair_row_bytes,
+                                  int64_t *n_pairs, int64_t *n_strad)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    const uint32_t n = nrows * ncols;
+    int nstats = 0;
+    std::vector<const void *> bands((size_t)nbands);
+    for (int b = 0; b < nbands; b++) {
+        if (plane_of_band[b] < 0 || plane_of_band[b] >= nplanes) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry %d: no such plane", b);
+        bands[(size_t)b] = planes_host[plane_of_band[b]];
+        nstats += nstats_per_band[b] > 0 ? nstats_per_band[b] : 0;
+    }
+    const size_t tab_bytes = (size_t)nplanes * sizeof(StatsBand);
+    if (tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many bands");
+    long long *di = nullptr;
+    float *df = nullptr;
+    CHK(run_segstats_bands(ctx, d_seg, bands.data(), dtype, nbands, nrows, ncols, S, has_null, null_val, sel_host,
+                           nstats_per_band, missing, nullptr, nullptr, &di, &df));
+    int nint = 0, nflt = 0;
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt, true));
+    // the local label histogram (all pixels of a label, valid or not) | counters, the planes' table, flags
+    CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->chtail, 64 + tab_bytes + ns + 64));
+    uint32_t *lh = bp<uint32_t>(ctx->chnext);
+    unsigned long long *ctr = (unsigned long long *)bp<uint8_t>(ctx->chtail);     // [0] pixels [1] segments [2] stale ids
+    StatsBand *d_tab = (StatsBand *)(bp<uint8_t>(ctx->chtail) + 64);
+    uint8_t *flags = bp<uint8_t>(ctx->chtail) + 64 + tab_bytes;
+    HIPCHK(ctx, hipMemsetAsync(lh, 0, ns * 4, st));
+    HIPCHK(ctx, hipMemsetAsync(ctr, 0, 64, st));
+    if (n) { hipLaunchKernelGGL(k_label_hist, dim3(grid_for(n, 256)), dim3(256), 0, st, d_seg, n, S, lh); KCHK(ctx); }
+    hipLaunchKernelGGL(k_dstats_stale, dim3(grid_for(ns, 256)), dim3(256), 0, st, lh, d_hist, S, ctr + 2); KCHK(ctx);
+    hipLaunchKernelGGL(k_dstats_classify, dim3(grid_for(ns, 256)), dim3(256), 0, st, lh, d_hist, S, keep_unheld, nint, nflt,
+                       di, df, (long long *)d_cols, (float *)((long long *)d_cols + (size_t)nint * ns), flags, ctr); KCHK(ctx);
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(h, ctr, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (h[2] != 0ull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "%llu segment ids have more pixels in these rows than the histogram gives them in the "
+                 "whole raster: the histogram does not belong to these labels", h[2]);
+    if (h[0] >= 0xffffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "too many straddling pixels (%llu)", h[0]);
+    const uint32_t cap = (uint32_t)h[0];
+    const size_t row_bytes = dstats_row_bytes(cap, dtype);
+    // (the statistics are done with aux / aux2, and the columns have left ssum: see above)
+    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->aux2, (size_t)nplanes * row_bytes + 64));
+    uint32_t *d_count = (uint32_t *)(ctr + 4);
+    if (n && cap) {
+        StatsBand *tab = (StatsBand *)(ctx->h_pinned + 16);
+        for (int b = 0; b < nplanes; b++) tab[b] = StatsBand{planes_host[b], 0, 0, 0, 0, 0};
+        HIPCHK(ctx, hipMemcpyAsync(d_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
+        uint8_t *out_val = bp<uint8_t>(ctx->aux2);
+        const dim3 grid(grid_for(n, 4096));
+        switch (dtype_size(dtype)) {
+        case 1: hipLaunchKernelGGL(k_gather_flagged_planes<uint8_t>, grid, dim3(256), 0, st, d_seg, d_tab, nplanes, n, S, flags,
+                                   bp<uint32_t>(ctx->aux), out_val, row_bytes, cap, d_count); break;
+        case 2: hipLaunchKernelGGL(k_gather_flagged_planes<uint16_t>, grid, dim3(256), 0, st, d_seg, d_tab, nplanes, n, S, flags,
+                                   bp<uint32_t>(ctx->aux), out_val, row_bytes, cap, d_count); break;
+        default: hipLaunchKernelGGL(k_gather_flagged_planes<uint32_t>, grid, dim3(256), 0, st, d_seg, d_tab, nplanes, n, S, flags,
+                                    bp<uint32_t>(ctx->aux), out_val, row_bytes, cap, d_count); break;
+        }
+        KCHK(ctx);
+        uint32_t got = 0;
+        CHK(read_u32(ctx, d_count, &got));
+        if (got != cap) SHP_FAIL(ctx, SHP_ERR_STATE, "straddler gather found %u pixels, the histogram says %u", got, cap);
+    }
+    *d_pair_seg = bp<uint32_t>(ctx->aux);
+    *d_pair_val = ctx->aux2.p;
+    *pair_row_bytes = (int64_t)row_bytes;
+    *n_pairs = (int64_t)cap;
+    *n_strad = (int64_t)h[1];
+    return 0;
+}
+
+// Merge part.  pseg: `world` slots of `slot` ids; pval: `world` blocks of nplanes rows, rows slot_row_bytes apart
+// (the same on every rank), counts[r] pairs valid in slot r.  A pair whose id lies in [id_lo, id_hi) takes ONE
+// output position (ballot + one atomic per wavefront) and its id and all planes' values go there, so that the planes
+// stay aligned with the ids; out_val: nplanes rows, out_row_bytes apart.
+template <typename T>
+__global__ __launch_bounds__(256) void k_dstats_pick_planes(const uint32_t *__restrict__ pseg,
+                                                            const uint8_t *__restrict__ pval, uint32_t slot,
+                                                            uint32_t world, size_t slot_row_bytes, int nplanes,
+                                                            const uint32_t *__restrict__ counts, uint32_t id_lo,
+                                                            uint32_t id_hi, uint32_t *__restrict__ out_seg,
+                                                            uint8_t *__restrict__ out_val, size_t out_row_bytes,
+                                                            uint32_t *count)
+{
+    const size_t q = (size_t)blockIdx.x * 256u + threadIdx.x;
+    bool take = false;
+    uint32_t sg = 0, r = 0, e = 0;
+    if (q < (size_t)slot * world) {
+        r = (uint32_t)(q / slot);
+        e = (uint32_t)(q - (size_t)r * slot);
+        if (e < counts[r]) { sg = pseg[q]; take = sg >= id_lo && sg < id_hi; }
+    }
+    const unsigned long long m = __ballot(take);
+    if (m == 0ull) return;
+    uint32_t base = 0;
+    if (lane_id() == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (take) {
+        const uint32_t o = base + (uint32_t)__popcll(m & lanemask_lt());
+        out_seg[o] = sg;
+        const uint8_t *src = pval + (size_t)r * (size_t)nplanes * slot_row_bytes;
+        for (int b = 0; b < nplanes; b++)
+            ((T *)(out_val + (size_t)b * out_row_bytes))[o] = ((const T *)(src + (size_t)b * slot_row_bytes))[e];
+    }
+}
+
+static int run_dstats_merge_bands(shp_ctx *ctx, const uint32_t *d_pseg, const void *d_pval, uint32_t slot,
+                                  size_t slot_row_bytes, uint32_t world, const uint32_t *counts_host, int dtype,
+                                  int nbands, int nplanes, const int *plane_of_band, uint32_t S, const int *has_null,
+                                  const int64_t *null_val, const uint32_t *sel_host, const int *nstats_per_band,
+                                  int64_t missing, uint32_t id_lo, uint32_t id_hi, void *d_cols, int64_t *n_merged,
+                                  int64_t *n_ids)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    int nstats = 0;
+    for (int b = 0; b < nbands; b++) {
+        if (plane_of_band[b] < 0 || plane_of_band[b] >= nplanes) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry %d: no such plane", b);
+        if (nstats_per_band[b] < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry %d: no statistics", b);
+        nstats += nstats_per_band[b];
+    }
+    int nint = 0, nflt = 0;
+    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt, true));
+    *n_merged = 0;
+    *n_ids = 0;
+    const size_t total = (size_t)slot * world;
+    if (total == 0 || id_lo >= id_hi) return 0;
+    if (total >= 0xffffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "too many gathered pairs");
+    if (slot_row_bytes < (size_t)slot * dtype_size(dtype)) SHP_FAIL(ctx, SHP_ERR_ARG, "the values' rows overlap");
+    const size_t out_row_bytes = dstats_row_bytes(total, dtype);
+    CHK(buf_ensure(ctx, ctx->lab, total * 4 + 64));
+    CHK(buf_ensure(ctx, ctx->img, (size_t)nplanes * out_row_bytes + 64));
+    CHK(buf_ensure(ctx, ctx->chtail, (size_t)world * 4 + 128));
+    uint32_t *d_counts = bp<uint32_t>(ctx->chtail) + 16, *d_n = bp<uint32_t>(ctx->chtail);
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipMemcpyAsync(d_counts, counts_host, (size_t)world * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(d_n, 0, 4, st));
+    {
+        const dim3 grid(grid_for(total, 256));
+        uint32_t *out_seg = bp<uint32_t>(ctx->lab);
+        uint8_t *out_val = bp<uint8_t>(ctx->img);
+        const uint8_t *pval = (const uint8_t *)d_pval;
+        switch (dtype_size(dtype)) {
+        case 1: hipLaunchKernelGGL(k_dstats_pick_planes<uint8_t>, grid, dim3(256), 0, st, d_pseg, pval, slot, world,
+                                   slot_row_bytes, nplanes, d_counts, id_lo, id_hi, out_seg, out_val, out_row_bytes, d_n); break;
+        case 2: hipLaunchKernelGGL(k_dstats_pick_planes<uint16_t>, grid, dim3(256), 0, st, d_pseg, pval, slot, world,
+                                   slot_row_bytes, nplanes, d_counts, id_lo, id_hi, out_seg, out_val, out_row_bytes, d_n); break;
+        default: hipLaunchKernelGGL(k_dstats_pick_planes<uint32_t>, grid, dim3(256), 0, st, d_pseg, pval, slot, world,
+                                    slot_row_bytes, nplanes, d_counts, id_lo, id_hi, out_seg, out_val, out_row_bytes, d_n); break;
+        }
+        KCHK(ctx);
+    }
+    uint32_t m = 0;
+    CHK(read_u32(ctx, d_n, &m));
+    *n_merged = (int64_t)m;
+    if (m == 0) return 0;
+    if ((size_t)m > total) SHP_FAIL(ctx, SHP_ERR_STATE, "%u pairs picked of %zu", m, total);
+    std::vector<const void *> bands((size_t)nbands);
+    for (int b = 0; b < nbands; b++) bands[(size_t)b] = bp<uint8_t>(ctx->img) + (size_t)plane_of_band[b] * out_row_bytes;
+    long long *di = nullptr;
+    float *df = nullptr;
+    CHK(run_segstats_bands(ctx, bp<uint32_t>(ctx->lab), bands.data(), dtype, nbands, 1u, m, S, has_null, null_val, sel_host,
+                           nstats_per_band, missing, nullptr, nullptr, &di, &df, false));
     CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
     uint32_t *present = bp<uint32_t>(ctx->chnext);
     HIPCHK(ctx, hipMemsetAsync(present, 0, ns * 4, st));

@@ -710,6 +710,252 @@ def deviceStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, hist, fast, nIn
     return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
 
 
+def _engineBandCount(engine):
+    """How many image bands the engine holds (``numBands``, or the whole image ``img`` of a host engine); None when
+    this rank cannot tell (a device engine without rows)."""
+    nb = getattr(engine, 'numBands', None)
+    if nb is None and getattr(engine, 'img', None) is not None:
+        nb = engine.img.shape[0]
+    return nb
+
+
+def _placeEntryColumns(ic, fc, bic, bfc, bfast, combined):
+    """The columns of ONE entry, numbered from 0 by its own fast selection ``bfast``, into the rows of the combined
+    selection's columns (``combined``: the entry's rows of it)."""
+    from . import tilingstats
+    for (own, comb) in zip(bfast, combined):
+        if own[tilingstats.STATSEL_COLTYPE] == tilingstats.STAT_DTYPE_INT:
+            ic[comb[tilingstats.STATSEL_COLARRAYINDEX]] = bic[own[tilingstats.STATSEL_COLARRAYINDEX]]
+        else:
+            fc[comb[tilingstats.STATSEL_COLARRAYINDEX]] = bfc[own[tilingstats.STATSEL_COLARRAYINDEX]]
+
+
+def calcPerSegmentStatsDistributedBands(engine, comm, hist, bandSelections, missingStatsValue=-9999,
+                                        imgNullVal=None, info=None):
+    """calcPerSegmentStatsDistributed for several bands in one call, as tilingstats.calcPerSegmentStatsTiledBands
+    is to calcPerSegmentStatsTiled: ``bandSelections`` is a list of (imgbandnum, statsSelection); a band may be
+    named by several entries, column names are unique over the call, ``imgNullVal`` is one value for all entries
+    or a list with one per entry (None: no null value).  The columns lie in the order of the entries.  Bad
+    arguments raise tilingstats.PyShepSegStatsError before any collective, alike on every rank.
+
+    What depends on the labels alone happens once instead of once per entry: the local histogram and the
+    classification of every id against ``hist``, the straddlers' ids on the wire (each distinct band's values
+    travel beside them, once), the pick of this rank's id share, and ONE all-reduce of all columns.  Under RCCL
+    with a device engine nothing crosses the host (shp_dstats_local_bands_dev -> all-gather of the ids and of the
+    values in the bands' pixel type -> shp_dstats_merge_bands_dev -> ncclAllReduce); on the other transports the
+    engine's localStatsBands / gatherFlaggedBands / statsOfPairsBands do the work, or, on an engine without them,
+    its one-band methods entry by entry.  One entry takes the route of calcPerSegmentStatsDistributed.  A ``hist``
+    that gives an id FEWER pixels than a rank holds of it raises on every rank.
+
+    ``info`` (a dict, optional) receives 'straddlers', 'straddler_pixels', 'path', 'bands' (distinct bands read)
+    and 'exchange_bytes' (the straddlers' ids and values all ranks put on the wire, without padding: on the device
+    path straddler_pixels * (4 + bands * itemsize)).  Returns (intcols int64 (nInt, maxSegId+1), floatcols float32
+    (nFloat, maxSegId+1), statsSelection_fast) on every rank, every column bit-identical to the column
+    calcPerSegmentStatsDistributed returns for its entry alone."""
+    from . import tilingstats
+    Err = tilingstats.PyShepSegStatsError
+    (fast, bandOfStat, nInt, nFloat) = tilingstats.makeBandStatsSelection(bandSelections)
+    bandSelections = [(int(b), list(sel)) for (b, sel) in bandSelections]
+    nEntries = len(bandSelections)
+    nullVals = tilingstats._entryNullVals(imgNullVal, nEntries, [None] * nEntries)
+    nBands = _engineBandCount(engine)
+    for (b, _sel) in bandSelections:
+        if b < 1 or (nBands is not None and b > nBands):
+            raise Err("band %d not in image" % b)
+    if nEntries == 1:
+        oneInfo = {}
+        (ic, fc, fast1) = calcPerSegmentStatsDistributed(engine, comm, hist, bandSelections[0][0], bandSelections[0][1],
+                                                         missingStatsValue, nullVals[0], oneInfo)
+        if info is not None:
+            info.update(oneInfo, bands=1, exchange_bytes=12 * oneInfo['straddler_pixels'])
+        return ic, fc, fast1
+    planes = tilingstats._planeNumbers(bandSelections)
+    planeOfEntry = [planes.index(b) for (b, _sel) in bandSelections]
+    perBand = numpy.ascontiguousarray([len(sel) for (_b, sel) in bandSelections], dtype=numpy.int32)
+    if getattr(comm, 'onDevice', False) and hasattr(engine, 'statsBandsOnDevice'):
+        (ic, fc, nStrad, nPix, nBytes) = engine.statsBandsOnDevice(comm, hist, planes, planeOfEntry, fast, perBand, nullVals,
+                                                                  nInt, nFloat, missingStatsValue)
+        if info is not None:
+            info.update(straddlers=nStrad, straddler_pixels=nPix, path='device', bands=len(planes), exchange_bytes=nBytes)
+        return ic, fc, fast
+    ownFast = [tilingstats.makeFastStatsSelection(list(range(len(sel))), sel) for (_b, sel) in bandSelections]
+    hist = numpy.asarray(hist).astype(numpy.int64)
+    S = len(hist) - 1
+    # ---- the labels' part, once: who is complete here, who straddles
+    lh = numpy.asarray(engine.histogram(S)).astype(numpy.int64)
+    lh[0] = 0
+    nStale = int((lh[1:] > hist[1:]).sum())
+    _raiseOnAllRanks(comm, None if nStale == 0 else Err(
+        "%d segment ids have more pixels in this rank's rows than the histogram gives them in the whole raster: "
+        "the histogram does not belong to these labels" % nStale))
+    complete = (lh == hist) & (lh > 0)
+    strad = (lh > 0) & (lh < hist)
+    if hasattr(engine, 'localStatsBands'):
+        (ic, fc) = engine.localStatsBands([b for (b, _sel) in bandSelections], S, fast, perBand, nInt, nFloat,
+                                          missingStatsValue, nullVals)
+    else:
+        ic = numpy.zeros((nInt, S + 1), dtype=numpy.int64)
+        fc = numpy.zeros((nFloat, S + 1), dtype=numpy.float32)
+        for (k, (b, _sel)) in enumerate(bandSelections):
+            (bfast, bInt, bFloat) = ownFast[k]
+            (bic, bfc) = engine.localStats(b, S, bfast, bInt, bFloat, missingStatsValue, nullVals[k])
+            _placeEntryColumns(ic, fc, bic, bfc, bfast, fast[bandOfStat == k])
+    keep = complete.copy()
+    if comm.rank == 0:
+        keep |= (hist == 0)                 # ids nobody holds (and row 0): "missing" rows, once
+    ic[:, ~keep] = 0
+    fc[:, ~keep] = 0
+    # ---- the straddlers' pixels: the ids once, one value array per distinct band
+    flags = strad.astype(numpy.uint8)
+    count = int(lh[strad].sum())
+    if hasattr(engine, 'gatherFlaggedBands'):
+        (pairIds, pairVals) = engine.gatherFlaggedBands(planes, S, flags, count)
+        pairVals = [pairVals[p] for p in range(len(planes))]
+    else:
+        # gatherFlagged promises no order, so a plane's values are matched to the ids of ITS call: both sorted by id
+        # (a segment's statistics do not depend on the order of its pixels)
+        (pairIds, pairVals) = (None, [])
+        for b in planes:
+            (ids_b, vals_b) = engine.gatherFlagged(b, S, flags, count)
+            order = numpy.argsort(ids_b, kind='stable')
+            ids_b = numpy.asarray(ids_b)[order]
+            if pairIds is None:
+                pairIds = ids_b
+            elif not numpy.array_equal(pairIds, ids_b):
+                raise Err("internal: the straddlers' pixels of band %d are not those of band %d" % (b, planes[0]))
+            pairVals.append(numpy.asarray(vals_b)[order])
+    allPairs = comm.allgather_arrays([pairIds] + pairVals)
+    segs = numpy.concatenate([p[0] for p in allPairs])
+    vals = [numpy.concatenate([p[1 + k] for p in allPairs]) for k in range(len(planes))]
+    nBytes = int(segs.nbytes + sum(v.nbytes for v in vals))
+    # ---- this rank's share of the straddlers: picked once
+    (lo, hi) = idRange(comm.rank, comm.world, S)
+    mine = (segs >= lo) & (segs < hi)
+    if mine.any():
+        (ids, compact) = numpy.unique(segs[mine], return_inverse=True)
+        seg1 = (compact + 1).astype(numpy.uint32)
+        myVals = [numpy.ascontiguousarray(v[mine]) for v in vals]
+        if hasattr(engine, 'statsOfPairsBands'):
+            (ic2, fc2) = engine.statsOfPairsBands(seg1, myVals, len(ids), planeOfEntry, fast, perBand, nInt, nFloat,
+                                                  missingStatsValue, nullVals)
+        else:
+            ic2 = numpy.zeros((nInt, len(ids) + 1), dtype=numpy.int64)
+            fc2 = numpy.zeros((nFloat, len(ids) + 1), dtype=numpy.float32)
+            for k in range(nEntries):
+                (bfast, bInt, bFloat) = ownFast[k]
+                (bic, bfc) = engine.statsOfPairs(seg1, myVals[planeOfEntry[k]], len(ids), bfast, bInt, bFloat,
+                                                 missingStatsValue, nullVals[k])
+                _placeEntryColumns(ic2, fc2, bic, bfc, bfast, fast[bandOfStat == k])
+        ic[:, ids] = ic2[:, 1:]
+        fc[:, ids] = fc2[:, 1:]
+    if info is not None:
+        info.update(straddlers=int(len(numpy.unique(segs))), straddler_pixels=int(len(segs)), path='host',
+                    bands=len(planes), exchange_bytes=nBytes)
+    if comm.world > 1:
+        # one all-reduce: the integer columns and the float columns' bit patterns side by side
+        block = numpy.concatenate([ic.reshape(-1), fc.view(numpy.int32).reshape(-1).astype(numpy.int64)])
+        block = comm.allreduce_sum_i64(block)
+        ic = block[:ic.size].reshape(nInt, S + 1)
+        fc = block[ic.size:].astype(numpy.int32).view(numpy.float32).reshape(nFloat, S + 1)
+    return ic, fc, fast
+
+
+def deviceStatsBands(c, comm, d_seg, d_bands, dtypeCode, nRows, nCols, hist, fast, perBand, hasNull, nullVals, nInt,
+                     nFloat, missing, fetch=True):
+    """deviceStats for several entries at once, the device-resident data path of
+    calcPerSegmentStatsDistributedBands for ONE rank.  d_bands: one device address per entry (this rank's rows of
+    the entry's band; entries that read the same band give the same address, and the distinct addresses must
+    number alike on every rank -- a rank without rows (nRows 0) passes distinct made-up ones, which are not read,
+    and may pass dtypeCode None: it learns the pixel type from the other ranks);
+    perBand / hasNull / nullVals: statistics, null flag and null value per entry; ``fast`` the combined selection.
+    The other arguments and conventions are deviceStats'.  Two all-gathers (the ids; the values, every rank's block
+    = one row per distinct band, the same stride on every rank) and one all-reduce.  A histogram that cannot belong
+    to these labels (shp_dstats_local_bands_dev) raises _lib.ShepsegHipError on every rank.
+    Returns (ic, fc, straddling segments, their pixels, payload bytes of the all-gathers over all ranks)."""
+    L = c._L
+    planes = list(dict.fromkeys(int(p) for p in d_bands))
+    nPlanes = len(planes)
+    d_planes = (ctypes.c_void_p * nPlanes)(*planes)
+    planeOfBand = numpy.ascontiguousarray([planes.index(int(p)) for p in d_bands], dtype=numpy.int32)
+    nBandsIn = len(planeOfBand)
+    fast = numpy.ascontiguousarray(fast, dtype=numpy.uint32)
+    perBand = numpy.ascontiguousarray(perBand, dtype=numpy.int32)
+    hasNull = numpy.ascontiguousarray(hasNull, dtype=numpy.int32)
+    nullVals = numpy.ascontiguousarray(nullVals, dtype=numpy.int64)
+    if isinstance(hist, tuple):
+        (d_hist, ns, ownHist) = (ctypes.c_void_p(hist[1]), int(hist[2]), False)
+    else:
+        h32 = numpy.ascontiguousarray(hist, dtype=numpy.uint32)
+        ns = len(h32)
+        d_hist = tiling._devAlloc(c, ns * 4)
+        c.check(L.shp_dev_upload(c.handle, d_hist, _lib.ptr(h32), ns * 4))
+        ownHist = True
+    S = ns - 1
+    colWords = ((nInt * 8 + nFloat * 4) * ns + 7) // 8
+    d_cols = tiling._devAlloc(c, colWords * 8)
+    toFree = [(d_cols, colWords * 8)] + ([(d_hist, ns * 4)] if ownHist else [])
+    try:
+        c.check(L.shp_dev_memset(c.handle, ctypes.c_void_p(d_cols.value + (colWords - 1) * 8), 0, 8))
+        (pSeg, pVal) = (ctypes.c_void_p(), ctypes.c_void_p())
+        (nPairs, nStrad, rowBytes) = (ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0))
+        err = None
+        try:
+            c.check(L.shp_dstats_local_bands_dev(c.handle, ctypes.c_void_p(d_seg), d_planes, nPlanes, _lib.ptr(planeOfBand),
+                                                 dtypeCode or 0, nBandsIn, nRows, nCols, S, _lib.ptr(hasNull),
+                                                 _lib.ptr(nullVals), _lib.ptr(fast), _lib.ptr(perBand), int(missing), d_hist,
+                                                 int(comm.rank == 0), d_cols, ctypes.byref(pSeg), ctypes.byref(pVal),
+                                                 ctypes.byref(rowBytes), ctypes.byref(nPairs), ctypes.byref(nStrad)))
+        except _lib.ShepsegHipError as e:      # (raised below, on every rank: the pair counts carry it)
+            err = e
+        got = comm.allgather_obj((None if err is None else (type(err).__name__, str(err)), int(nPairs.value),
+                                  dtypeCode))                                          # control data
+        _raiseFirstError(comm, err, [g[0] for g in got])
+        if dtypeCode is None:
+            dtypeCode = ([g[2] for g in got if g[2] is not None] or [0])[0]
+        itemsize = [dt for (dt, code) in _lib.SHP_DTYPES.items() if code == dtypeCode][0].itemsize
+        counts = [int(g[1]) for g in got]
+        slot = max(counts)
+        slotRow = (slot * itemsize + 15) // 16 * 16           # a plane's row of a rank's block: the same on every rank
+        (merged, nIds) = (ctypes.c_int64(0), ctypes.c_int64(0))
+        if slot > 0:
+            bufs = []
+            for sz in (slot * 4, nPlanes * slotRow, comm.world * slot * 4, comm.world * nPlanes * slotRow):
+                p = tiling._devAlloc(c, sz)
+                bufs.append(p)
+                toFree.append((p, sz))
+            (d_sendS, d_sendV, d_allS, d_allV) = bufs
+            if nPairs.value:
+                c.check(L.shp_dev_copy(c.handle, d_sendS, pSeg, nPairs.value * 4))
+                for p in range(nPlanes):
+                    c.check(L.shp_dev_copy(c.handle, ctypes.c_void_p(d_sendV.value + p * slotRow),
+                                           ctypes.c_void_p(pVal.value + p * rowBytes.value), nPairs.value * itemsize))
+            comm.allgather_dev(d_sendS.value, d_allS.value, slot * 4)
+            comm.allgather_dev(d_sendV.value, d_allV.value, nPlanes * slotRow)
+            (lo, hi) = idRange(comm.rank, comm.world, S)
+            cnts = numpy.array(counts, dtype=numpy.uint32)
+            c.check(L.shp_dstats_merge_bands_dev(c.handle, d_allS, d_allV, slot, slotRow, comm.world, _lib.ptr(cnts),
+                                                 dtypeCode, nBandsIn, nPlanes, _lib.ptr(planeOfBand), S, _lib.ptr(hasNull),
+                                                 _lib.ptr(nullVals), _lib.ptr(fast), _lib.ptr(perBand), int(missing), lo, hi,
+                                                 d_cols, ctypes.byref(merged), ctypes.byref(nIds)))
+        if comm.world > 1:
+            comm.allreduce_dev_i64(d_cols.value, colWords)
+        (ic, fc) = (None, None)
+        if fetch:
+            ic = numpy.empty((nInt, ns), dtype=numpy.int64)
+            fc = numpy.empty((nFloat, ns), dtype=numpy.float32)
+        if fetch and nInt:
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(ic), d_cols, ic.nbytes))
+        if fetch and nFloat:
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(fc), ctypes.c_void_p(d_cols.value + nInt * 8 * ns), fc.nbytes))
+    finally:
+        for (p, sz) in toFree:
+            tiling._devRelease(c, p, sz)
+    # the job's figures: the ranks' id shares partition the straddlers, the ranks' rows their pixels
+    tot = comm.allgather_obj((int(nIds.value), int(nPairs.value)))
+    nPix = int(sum(t[1] for t in tot))
+    return ic, fc, int(sum(t[0] for t in tot)), nPix, nPix * (4 + nPlanes * itemsize)
+
+
 def spatialHaloPlan(rowRanges, rank, nRows, above, below):
     """Where rank ``rank`` finds the halo rows of the spatial statistics.  rowRanges: every rank's output rows
     (outLo, outHi); ``above`` / ``below``: rows needed above / below the shard (mean coordinates 0 / 0, edge
@@ -1796,6 +2042,94 @@ class HipEngine(object):
                            self._bandPtr(imgbandnum), _lib.SHP_DTYPES[self.ras.dtype], self.outHi - self.outLo,
                            self.nCols, hist, fast, nInt, nFloat, missing, imgNullVal)
 
+    # ---- several bands in one call (calcPerSegmentStatsDistributedBands)
+    @property
+    def numBands(self):
+        """image bands this rank holds rows of (None: no rows, so it cannot tell)"""
+        return self.ras.shape[0] if self.ras is not None else None
+
+    def _bandPointers(self, bandNums):
+        arr = (ctypes.c_void_p * len(bandNums))()
+        for (k, b) in enumerate(bandNums):
+            arr[k] = self._bandPtr(b)
+        return arr
+
+    def localStatsBands(self, bandNums, S, fast, perBand, nInt, nFloat, missing, nullVals):
+        """localStats of several entries in one pass over the labels: all entries' columns (shp_segstats2d_bands_dev)"""
+        nRows = self.outHi - self.outLo
+        ic = numpy.zeros((max(nInt, 1), S + 1), dtype=numpy.int64)
+        fc = numpy.zeros((max(nFloat, 1), S + 1), dtype=numpy.float32)
+        if nRows * self.nCols > 0:
+            hasNull = numpy.ascontiguousarray([int(v is not None) for v in nullVals], dtype=numpy.int32)
+            nullArr = numpy.ascontiguousarray([0 if v is None else int(v) for v in nullVals], dtype=numpy.int64)
+            self.c.check(self.L.shp_segstats2d_bands_dev(
+                self.c.handle, self._lastOut, self._bandPointers(bandNums), _lib.SHP_DTYPES[self.ras.dtype], len(bandNums),
+                nRows, self.nCols, S, _lib.ptr(hasNull), _lib.ptr(nullArr), _lib.ptr(fast), _lib.ptr(perBand), int(missing),
+                _lib.ptr(ic), _lib.ptr(fc)))
+        return ic[:nInt], fc[:nFloat]
+
+    def gatherFlaggedBands(self, planes, S, flags, count):
+        """gatherFlagged for several distinct bands: the ids once and (len(planes), count) values in the image's pixel
+        type, every row in the order of the ids (shp_gather_flagged_bands_dev)"""
+        n = (self.outHi - self.outLo) * self.nCols
+        dt = self.ras.dtype if self.ras is not None else numpy.dtype(numpy.uint16)
+        segs = numpy.empty(max(count, 1), dtype=numpy.uint32)
+        vals = numpy.empty((len(planes), max(count, 1)), dtype=numpy.int64)
+        got = ctypes.c_int64(0)
+        if n > 0 and count > 0:
+            self.c.check(self.L.shp_gather_flagged_bands_dev(
+                self.c.handle, self._lastOut, self._bandPointers(planes), _lib.SHP_DTYPES[self.ras.dtype], len(planes), n, S,
+                _lib.ptr(flags), count, _lib.ptr(segs), _lib.ptr(vals), ctypes.byref(got)))
+            if got.value != count:
+                raise tiling.PyShepSegTilingError(
+                    "straddling-segment gather found %d pixels, histogram says %d" % (got.value, count))
+        return segs[:count], vals[:, :count].astype(dt)
+
+    def statsOfPairsBands(self, segs, vals, K, planeOfEntry, fast, perBand, nInt, nFloat, missing, nullVals):
+        """statsOfPairs of several entries: ``vals`` one array per distinct band in the order of ``segs`` (compact ids
+        1..K), entry e reads vals[planeOfEntry[e]] -- the bands kernels on a 1 x M raster."""
+        m = len(segs)
+        dt = numpy.dtype(self.ras.dtype if self.ras is not None else vals[0].dtype)
+        ic = numpy.zeros((max(nInt, 1), K + 1), dtype=numpy.int64)
+        fc = numpy.zeros((max(nFloat, 1), K + 1), dtype=numpy.float32)
+        rowBytes = (m * dt.itemsize + 15) // 16 * 16
+        sizes = [m * 4] + [rowBytes] * len(vals)
+        blocks = [tiling._devAlloc(self.c, sz) for sz in sizes]
+        try:
+            segs = numpy.ascontiguousarray(segs, dtype=numpy.uint32)
+            self.c.check(self.L.shp_dev_upload(self.c.handle, blocks[0], _lib.ptr(segs), m * 4))
+            for (k, v) in enumerate(vals):
+                v = numpy.ascontiguousarray(v).astype(dt, copy=False)
+                self.c.check(self.L.shp_dev_upload(self.c.handle, blocks[1 + k], _lib.ptr(v), m * dt.itemsize))
+            ptrs = (ctypes.c_void_p * len(planeOfEntry))(*[blocks[1 + p].value for p in planeOfEntry])
+            hasNull = numpy.ascontiguousarray([int(v is not None) for v in nullVals], dtype=numpy.int32)
+            nullArr = numpy.ascontiguousarray([0 if v is None else int(v) for v in nullVals], dtype=numpy.int64)
+            self.c.check(self.L.shp_segstats2d_bands_dev(
+                self.c.handle, blocks[0], ptrs, _lib.SHP_DTYPES[dt], len(planeOfEntry), 1, m, K, _lib.ptr(hasNull),
+                _lib.ptr(nullArr), _lib.ptr(fast), _lib.ptr(perBand), int(missing), _lib.ptr(ic), _lib.ptr(fc)))
+        finally:
+            for (p, sz) in zip(blocks, sizes):
+                tiling._devRelease(self.c, p, sz)
+        return ic[:nInt], fc[:nFloat]
+
+    def statsBandsOnDevice(self, comm, hist, planes, planeOfEntry, fast, perBand, nullVals, nInt, nFloat, missing):
+        """calcPerSegmentStatsDistributedBands' device path for this rank's output rows (deviceStatsBands).
+        planes: the distinct band numbers, planeOfEntry[e]: which of them entry e reads."""
+        held = self.ras is not None and self.outHi > self.outLo
+        if held:
+            d_out = self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut)
+            d_planes = [self._bandPtr(b) for b in planes]
+            dtypeCode = _lib.SHP_DTYPES[self.ras.dtype]
+        else:
+            # (no rows: nothing is read; the addresses only say which entries share a band, and the pixel type, which
+            #  sizes this rank's empty block of the exchange, is taken from the other ranks)
+            (d_out, d_planes, dtypeCode) = (0, [16 * (p + 1) for p in range(len(planes))], None)
+        hasNull = [int(v is not None) for v in nullVals]
+        nullArr = [0 if v is None else int(v) for v in nullVals]
+        return deviceStatsBands(self.c, comm, d_out, [d_planes[p] for p in planeOfEntry], dtypeCode,
+                                (self.outHi - self.outLo) if held else 0, self.nCols, hist, fast, perBand, hasNull, nullArr,
+                                nInt, nFloat, missing)
+
     def spatialOnDevice(self, comm, hist, imgbandnum, colTypes, userFunc, userParam, missing, imgNullVal,
                         tileSize=tiling.TILESIZE, batchPoints=None, info=None):
         """calcPerSegmentSpatialStatsDistributed's path for this rank's output rows (deviceSpatialStats)."""
@@ -1928,20 +2262,26 @@ class _FileSliceEngine(HipEngine):
 
 
 _SAME_TYPE_ERRORS = (TypeError, ValueError, IndexError, OSError, tiling.PyShepSegTilingError,
-                     _lib.ShepsegHipError)
+                     _lib.ShepsegHipError)      # (and tilingstats.PyShepSegStatsError: _raiseFirstError adds it)
 
 
 def _raiseOnAllRanks(comm, err):
     """All-gather this rank's exception (or None); the first rank's is raised on every rank, with its type when
     that is one of _SAME_TYPE_ERRORS (else as tiling.PyShepSegTilingError)."""
-    got = comm.allgather_obj(None if err is None else (type(err).__name__, str(err)))
+    _raiseFirstError(comm, err, comm.allgather_obj(None if err is None else (type(err).__name__, str(err))))
+
+
+def _raiseFirstError(comm, err, got):
+    """The raising half of _raiseOnAllRanks for a caller whose own collective carried the errors: ``got`` = every
+    rank's (type name, message) or None."""
     bad = [(r, x) for (r, x) in enumerate(got) if x is not None]
     if not bad:
         return
     (r, (name, msg)) = bad[0]
     if err is not None and r == comm.rank:
         raise err
-    types = {t.__name__: t for t in _SAME_TYPE_ERRORS}
+    from . import tilingstats
+    types = {t.__name__: t for t in _SAME_TYPE_ERRORS + (tilingstats.PyShepSegStatsError,)}
     typ = types.get(name, tiling.PyShepSegTilingError)
     raise typ(msg if name in types else '%s: %s' % (name, msg))
 
