@@ -578,6 +578,27 @@ int shp_dspatial_vario_store_dev(shp_ctx *ctx, const uint64_t *pairs, int64_t np
                                  const uint32_t *cnt, int maxd, uint32_t max_seg_id, int nint, int nflt,
                                  void *d_cols, int write);
 
+/* ---- colour tables and their rendering ---------------------------------------------------------------
+ * utils.writeColorTableFromRatColumns (utils.py:162-230) stretches three RAT columns to 0..255 between their
+ * 5th and 95th percentiles with numpy (:216-221), a desktop viewer then paints the labels through the table.
+ *  shp_colour_stretch: one column (host, n rows; ctype 0 float64, 1 float32, 2 int64 -- the last two are
+ *    converted to float64 on the device, int64 exactly: a magnitude of 2^53 or more is an error, as is a NaN or
+ *    an infinity in any column) -> out (host, n bytes) = (255 * ((col - lo) / (hi - lo)).clip(0, 1)).astype(uint8)
+ *    with lo, hi = numpy.percentile(col, 5), numpy.percentile(col, 95) (method 'linear'), byte for byte;
+ *    stretch_out[2] = (lo, hi).  hi == lo gives 255 where col > lo and 0 elsewhere (numpy's result on x86-64).
+ *    The four order statistics come from a radix selection on the device (csrc/colour.h), not from a sort.
+ *    dev_ms_out (may be NULL): device time between the column's upload and the bytes' download.
+ *  shp_colour_pack: four byte columns (host, n rows each) -> d_table (device, n words): row i =
+ *    red[i] | green[i] << 8 | blue[i] << 16 | alpha[i] << 24, the (rows, cols, 4) uint8 pixel of label i.
+ *  shp_colour_lookup_dev: d_out[p] = d_table[d_seg[p]] for npix labels in device memory.  A label that is not
+ *    below nrows is an error whose message names the smallest such label; nothing is read outside the table. */
+int shp_colour_stretch(shp_ctx *ctx, const void *col, int ctype, int64_t n, uint8_t *out, double *stretch_out,
+                       double *dev_ms_out);
+int shp_colour_pack(shp_ctx *ctx, const uint8_t *red, const uint8_t *green, const uint8_t *blue, const uint8_t *alpha,
+                    int64_t n, uint32_t *d_table);
+int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, const uint32_t *d_table, int64_t nrows,
+                          uint32_t *d_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

@@ -3,5 +3,6 @@
 ``shepseg``      per-tile Shepherd segmentation (k-means -> clump -> elimination) on HIP
 ``tiling``       tiled driver + cross-tile stitch
 ``tilingstats``  per-segment statistics
+``utils``        colour tables from per-segment columns, RGBA rendering of the labels
 """
 __version__ = '0.1.0'

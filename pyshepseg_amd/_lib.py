@@ -203,6 +203,9 @@ _SIGS = {
                                                _c.c_uint32, _c.c_int64, _c.c_int, _vp, _c.c_int64, _vp, _vp]),
     'shp_dspatial_vario_store_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _vp, _c.c_int, _c.c_uint32, _c.c_int,
                                                 _c.c_int, _vp, _c.c_int]),
+    'shp_colour_stretch': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _vp, _vp, _c.POINTER(_c.c_double)]),
+    'shp_colour_pack': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int64, _vp]),
+    'shp_colour_lookup_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int64, _vp]),
 }
 
 _lib = None

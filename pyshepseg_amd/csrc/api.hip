@@ -16,6 +16,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "spatial.h"
 #include "segpoints.h"
 #include "dsegpoints.h"
+#include "colour.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1398,6 +1399,37 @@ API int shp_dsubset_merge_dev(shp_ctx *ctx, const void *d_pairs, int64_t slot, i
     if (g.nr > 0 && !d_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_dsubset_merge(ctx, (const uint32_t *)d_pairs, (uint32_t)slot, (uint32_t)world, counts, g, max_seg_id,
                              d_out, d_hist, orig_out, cap, n_new_out);
+}
+
+// ---- colour tables and their rendering (utils.py:123-230) --------------------------------------------
+API int shp_colour_stretch(shp_ctx *ctx, const void *col, int ctype, int64_t n, uint8_t *out, double *stretch_out,
+                           double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!col || !out || !stretch_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    if (n < 1 || n > 0xffffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows", (long long)n);
+    return run_colour_stretch(ctx, col, ctype, (size_t)n, out, stretch_out, dev_ms_out);
+}
+
+API int shp_colour_pack(shp_ctx *ctx, const uint8_t *red, const uint8_t *green, const uint8_t *blue, const uint8_t *alpha,
+                        int64_t n, uint32_t *d_table)
+{
+    CHK(enter(ctx));
+    if (!red || !green || !blue || !alpha || !d_table) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n < 1 || n > 0xffffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "a colour table of %lld rows", (long long)n);
+    const uint8_t *const cols[4] = {red, green, blue, alpha};
+    return run_colour_pack(ctx, cols, (size_t)n, d_table);
+}
+
+API int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, const uint32_t *d_table, int64_t nrows,
+                              uint32_t *d_out)
+{
+    CHK(enter(ctx));
+    if (npix < 0 || nrows < 1 || nrows > 0xffffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (npix > 0 && (!d_seg || !d_table || !d_out)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_out & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_colour_lookup(ctx, d_seg, (size_t)npix, d_table, (uint32_t)nrows, d_out);
 }
 
 // ---- spatial statistics ------------------------------------------------------------

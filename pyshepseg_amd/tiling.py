@@ -610,19 +610,23 @@ class _NpyRowWriter(object):
     map ahead of the data with madvise(MADV_POPULATE_WRITE) from background threads was slower
     still: 3.2 s for 6.4 GB), a write into the page cache is one kernel copy.  Buffered writes to one
     file serialise on its inode lock, so the sink tops out near 5 GB/s whatever the thread count."""
-    def __init__(self, path, nrows, ncols):
+    pixelBytes = 4
+
+    def __init__(self, path, nrows, ncols, dtype=numpy.uint32, pixelShape=()):
+        """pixelShape: the trailing axes of a pixel, e.g. (4,) with uint8 for an RGBA raster"""
         (self.nrows, self.ncols) = (nrows, ncols)
+        self.pixelBytes = numpy.dtype(dtype).itemsize * int(numpy.prod(pixelShape, dtype=numpy.int64))
         with open(path, 'wb') as f:
             numpy.lib.format.write_array_header_1_0(
-                f, {'descr': numpy.lib.format.dtype_to_descr(numpy.dtype(numpy.uint32)),
-                    'fortran_order': False, 'shape': (nrows, ncols)})
+                f, {'descr': numpy.lib.format.dtype_to_descr(numpy.dtype(dtype)),
+                    'fortran_order': False, 'shape': (nrows, ncols) + tuple(pixelShape)})
             self.offset = f.tell()
         self.fd = os.open(path, os.O_WRONLY)
-        os.ftruncate(self.fd, self.offset + nrows * ncols * 4)
+        os.ftruncate(self.fd, self.offset + nrows * ncols * self.pixelBytes)
 
     def writeRows(self, y0, y1, v):
         mv = memoryview(numpy.ascontiguousarray(v)).cast('B')
-        pos = self.offset + y0 * self.ncols * 4
+        pos = self.offset + y0 * self.ncols * self.pixelBytes
         done = 0
         while done < len(mv):
             done += os.pwrite(self.fd, mv[done:], pos + done)
