@@ -599,6 +599,45 @@ int shp_colour_pack(shp_ctx *ctx, const uint8_t *red, const uint8_t *green, cons
 int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, const uint32_t *d_table, int64_t nrows,
                           uint32_t *d_out);
 
+/* The same on the row-sharded output of several ranks (distributed.writeColorTableFromRatColumnsDistributed,
+ * renderColourTableDistributed).  They replace what a user of the multi-rank driver had to do in one process on one
+ * GPU: stretch the whole columns with shp_colour_stretch and push the written label file through
+ * shp_colour_lookup_dev.
+ *  shp_dcolour_begin / _hist / _pick / _finish / shp_dcolour_stretch_dev: shp_colour_stretch of a column of n rows of
+ *    which this rank holds m (host, may be 0), in steps the caller puts a collective between.  begin uploads and
+ *    widens the share and sets the four ranks of the WHOLE column; *d_block_out is the device block the ranks sum
+ *    (as int64 words) between _hist(pass) and _pick(pass), pass = 0..7: 512 words of digit histograms (two uint32
+ *    counts per word; n < 2^32, so no carry) and, in pass 0 only, a 513th whose lanes count the ranks whose share
+ *    holds a NaN or an infinity / an integer of magnitude 2^53 or more.  After the sum every rank picks the same
+ *    digits.  finish: stretch_out[2] = (lo, hi), the whole column's percentiles as shp_colour_stretch gives them;
+ *    *bad_out = bit 0 a non-finite value, bit 1 a wide integer, in ANY rank's share (then nothing can be
+ *    stretched).  stretch_dev: the share's m bytes -> d_out (device, 4-byte aligned); dev_ms_out (may be NULL): the
+ *    device time of the column's steps.  The share lives in the context's workspace: no other call of the context
+ *    that uses the workspace may come between the steps (shp_dev_* transfers may).
+ *  shp_colour_pack_dev: shp_colour_pack from four byte columns that are in device memory already (each 4-byte
+ *    aligned): the ranks' gathered bytes become the table without a host round trip.
+ *  shp_colour_render_rows_dev: shp_colour_lookup_dev plus the download, pipelined: npix labels in device memory ->
+ *    h_dst (npix words of pinned memory, shp_host_alloc) in blocks of block_pixels; the download of a block runs on
+ *    the context's side stream while the next block is looked up into a second device buffer.  bad_out[2] =
+ *    (1 when a label has no row in the table, the smallest such label) -- reported, not raised, so that the ranks
+ *    can agree on one message; ms_out[3] = summed device time of the lookups, of the downloads, wall time of the
+ *    call (the overlap pays when the third is below the sum of the first two).
+ *  shp_colour_overview_rects_dev: shp_overview_rects_dev with the table lookup fused in -- the rectangle table and
+ *    its checks are the label layers', d_packed receives (R, G, B, A) words; bad_out as above. */
+int shp_dcolour_begin(shp_ctx *ctx, const void *col, int ctype, int64_t m, int64_t n, void **d_block_out);
+int shp_dcolour_hist(shp_ctx *ctx, int pass);
+int shp_dcolour_pick(shp_ctx *ctx, int pass);
+int shp_dcolour_finish(shp_ctx *ctx, double *stretch_out, int *bad_out);
+int shp_dcolour_stretch_dev(shp_ctx *ctx, uint8_t *d_out, double *dev_ms_out);
+int shp_colour_pack_dev(shp_ctx *ctx, const uint8_t *d_red, const uint8_t *d_green, const uint8_t *d_blue,
+                        const uint8_t *d_alpha, int64_t n, uint32_t *d_table);
+int shp_colour_render_rows_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, int64_t block_pixels,
+                               const uint32_t *d_table, int64_t nrows, uint32_t *h_dst, uint32_t *bad_out,
+                               double *ms_out);
+int shp_colour_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
+                                  int nrects, const uint32_t *d_table, int64_t nrows, uint32_t *d_packed,
+                                  int64_t npacked, uint32_t *bad_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

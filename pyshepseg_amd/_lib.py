@@ -206,6 +206,15 @@ _SIGS = {
     'shp_colour_stretch': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _vp, _vp, _c.POINTER(_c.c_double)]),
     'shp_colour_pack': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int64, _vp]),
     'shp_colour_lookup_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int64, _vp]),
+    'shp_dcolour_begin': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.POINTER(_vp)]),
+    'shp_dcolour_hist': (_c.c_int, [_vp, _c.c_int]),
+    'shp_dcolour_pick': (_c.c_int, [_vp, _c.c_int]),
+    'shp_dcolour_finish': (_c.c_int, [_vp, _vp, _c.POINTER(_c.c_int)]),
+    'shp_dcolour_stretch_dev': (_c.c_int, [_vp, _vp, _c.POINTER(_c.c_double)]),
+    'shp_colour_pack_dev': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int64, _vp]),
+    'shp_colour_render_rows_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp]),
+    'shp_colour_overview_rects_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int, _vp, _c.c_int64, _vp, _c.c_int64,
+                                                 _vp]),
 }
 
 _lib = None

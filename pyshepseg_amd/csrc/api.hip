@@ -953,14 +953,10 @@ API int shp_overview_window_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t 
     return 0;
 }
 
-// overview rectangles of a row-sharded raster, every level in one launch (k_overview_rects); the table is
-// checked here, on the host, so that no rectangle reads outside the npix pixels of d_raster.  Synchronous.
-API int shp_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
-                               int nrects, uint32_t *d_packed, int64_t npacked)
+// a table of overview rectangles against the npix pixels of the raster they sample and the packed buffer they fill
+// (shp_overview_rects_dev, shp_colour_overview_rects_dev)
+static int overview_rects_check(shp_ctx *ctx, int64_t npix, const int64_t *rects, int nrects, int64_t npacked)
 {
-    CHK(enter(ctx));
-    if (npix < 0 || nrects < 0 || npacked < 0 || (nrects > 0 && !rects) || (npacked > 0 && (!d_raster || !d_packed)))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
     int64_t at = 0;
     for (int k = 0; k < nrects; k++) {
         const int64_t *q = rects + 6 * (size_t)k;
@@ -977,6 +973,18 @@ API int shp_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t n
     }
     if (at != npacked) SHP_FAIL(ctx, SHP_ERR_ARG, "overview rectangles fill %lld of %lld packed pixels",
                                 (long long)at, (long long)npacked);
+    return 0;
+}
+
+// overview rectangles of a row-sharded raster, every level in one launch (k_overview_rects); the table is
+// checked here, on the host, so that no rectangle reads outside the npix pixels of d_raster.  Synchronous.
+API int shp_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
+                               int nrects, uint32_t *d_packed, int64_t npacked)
+{
+    CHK(enter(ctx));
+    if (npix < 0 || nrects < 0 || npacked < 0 || (nrects > 0 && !rects) || (npacked > 0 && (!d_raster || !d_packed)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(overview_rects_check(ctx, npix, rects, nrects, npacked));
     if (npacked == 0) return 0;
     CHK(buf_ensure(ctx, ctx->tlist, (size_t)nrects * 48));
     HIPCHK(ctx, hipMemcpyAsync(ctx->tlist.p, rects, (size_t)nrects * 48, hipMemcpyHostToDevice, ctx->stream));
@@ -1430,6 +1438,87 @@ API int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix,
     if (npix > 0 && (!d_seg || !d_table || !d_out)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_out & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
     return run_colour_lookup(ctx, d_seg, (size_t)npix, d_table, (uint32_t)nrows, d_out);
+}
+
+// a column shared by rows over the ranks: shp_colour_stretch in steps (colour.h)
+API int shp_dcolour_begin(shp_ctx *ctx, const void *col, int ctype, int64_t m, int64_t n, void **d_block_out)
+{
+    CHK(enter(ctx));
+    if (!d_block_out || (m > 0 && !col)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    if (n < 1 || n > 0xffffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows", (long long)n);
+    if (m < 0 || m > n) SHP_FAIL(ctx, SHP_ERR_ARG, "a share of %lld rows of %lld", (long long)m, (long long)n);
+    return run_dcolour_begin(ctx, col, ctype, (size_t)m, (size_t)n, d_block_out);
+}
+
+API int shp_dcolour_hist(shp_ctx *ctx, int pass)
+{
+    CHK(enter(ctx));
+    if (pass < 0 || pass >= SEL_PASSES) SHP_FAIL(ctx, SHP_ERR_ARG, "pass %d", pass);
+    return run_dcolour_hist(ctx, pass);
+}
+
+API int shp_dcolour_pick(shp_ctx *ctx, int pass)
+{
+    CHK(enter(ctx));
+    if (pass < 0 || pass >= SEL_PASSES) SHP_FAIL(ctx, SHP_ERR_ARG, "pass %d", pass);
+    return run_dcolour_pick(ctx, pass);
+}
+
+API int shp_dcolour_finish(shp_ctx *ctx, double *stretch_out, int *bad_out)
+{
+    CHK(enter(ctx));
+    if (!stretch_out || !bad_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_dcolour_finish(ctx, stretch_out, bad_out);
+}
+
+API int shp_dcolour_stretch_dev(shp_ctx *ctx, uint8_t *d_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dcol.m > 0 && !d_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_out & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned byte column");
+    return run_dcolour_stretch(ctx, d_out, dev_ms_out);
+}
+
+API int shp_colour_pack_dev(shp_ctx *ctx, const uint8_t *d_red, const uint8_t *d_green, const uint8_t *d_blue,
+                            const uint8_t *d_alpha, int64_t n, uint32_t *d_table)
+{
+    CHK(enter(ctx));
+    if (!d_red || !d_green || !d_blue || !d_alpha || !d_table) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n < 1 || n > 0xffffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "a colour table of %lld rows", (long long)n);
+    const uint8_t *const cols[4] = {d_red, d_green, d_blue, d_alpha};
+    for (int k = 0; k < 4; k++)
+        if ((uintptr_t)cols[k] & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned byte column");
+    return run_colour_pack_dev(ctx, cols, (size_t)n, d_table);
+}
+
+API int shp_colour_render_rows_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, int64_t block_pixels,
+                                   const uint32_t *d_table, int64_t nrows, uint32_t *h_dst, uint32_t *bad_out,
+                                   double *ms_out)
+{
+    CHK(enter(ctx));
+    if (npix < 0 || nrows < 1 || nrows > 0xffffffffll || block_pixels < 1 || block_pixels > 0x7fffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (!bad_out || !ms_out || (npix > 0 && (!d_seg || !d_table || !h_dst))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)h_dst & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_colour_render_rows(ctx, d_seg, (size_t)npix, (size_t)block_pixels, d_table, (uint32_t)nrows, h_dst, bad_out,
+                                  ms_out);
+}
+
+API int shp_colour_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_t npix, const int64_t *rects,
+                                      int nrects, const uint32_t *d_table, int64_t nrows, uint32_t *d_packed,
+                                      int64_t npacked, uint32_t *bad_out)
+{
+    CHK(enter(ctx));
+    if (npix < 0 || nrects < 0 || npacked < 0 || nrows < 1 || nrows > 0xffffffffll || !bad_out || (nrects > 0 && !rects) ||
+        (npacked > 0 && (!d_raster || !d_packed || !d_table)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(overview_rects_check(ctx, npix, rects, nrects, npacked));
+    bad_out[0] = 0u;
+    bad_out[1] = 0xffffffffu;
+    if (npacked == 0) return 0;
+    return run_colour_overview_rects(ctx, d_raster, rects, nrects, d_table, (uint32_t)nrows, d_packed, (size_t)npacked,
+                                     bad_out);
 }
 
 // ---- spatial statistics ------------------------------------------------------------

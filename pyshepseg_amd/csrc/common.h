@@ -53,6 +53,15 @@ struct DSegPointsState {
     unsigned long long max_visit = 0;       // largest visit index of the whole raster
 };
 
+// a row-sharded column between the steps of its selection (colour.h: shp_dcolour_*): the share lives in the
+// workspace, so no other workspace call of the context may come between the steps
+struct DColourState {
+    int stage = 0;                  // 0 none, 1 selecting (next: `pass`, histogram then pick), 2 (lo, hi) known
+    int pass = 0, picked = 1;
+    size_t m = 0, n = 0;            // rows of the share, of the whole column
+    double gamma[2] = {}, lo = 0.0, hi = 0.0, dev_ms = 0.0;
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -71,6 +80,7 @@ struct shp_ctx {
         vflag, vlist, vredo;
     SegPointsState pts;
     DSegPointsState dpts;
+    DColourState dcol;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)
     int64_t vario_redo = 0;         // last built-in variogram: (segment, bin) pairs recomputed in the reference's order
     std::vector<unsigned long long> vario_pairs;  // last multi-GPU variogram step: its flagged pairs
