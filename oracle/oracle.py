@@ -175,6 +175,24 @@ def kmeans_fit(xsample, init, max_iter=300, tol=1e-4, mstep='rows', algorithm='f
     return centres, labels, nit.value
 
 
+def kmeans_fit_elkan_near_ties(xsample, init, max_iter=300, tol=1e-4):
+    """kmeans_fit(..., algorithm='elkan') and, fourth, the number of its comparisons `upper > lower bound`, past
+    the half-distance test, whose sides were positive and within 2^-31 of each other (relative): what a float32
+    bracket around the bound cannot decide (k > 1)"""
+    x = np.ascontiguousarray(xsample, dtype=np.float64)
+    init = np.ascontiguousarray(init, dtype=np.float64)
+    n, nb = x.shape
+    k = init.shape[0]
+    centres = np.empty((k, nb), dtype=np.float64)
+    labels = np.empty(n, dtype=np.int32)
+    nit = ctypes.c_int(0)
+    near = ctypes.c_longlong(0)
+    rc = lib().orc_kmeans_fit_elkan_near(_p(x), ctypes.c_int64(n), nb, k, _p(init), int(max_iter), ctypes.c_double(tol),
+                                         _p(centres), _p(labels), ctypes.byref(nit), ctypes.byref(near))
+    assert rc == 0
+    return centres, labels, nit.value, near.value
+
+
 def recode_tile(tile, overlap, top_b, left_b, max_seg_id, top, bottom, left, right):
     """tiling.recodeTile for one tile: returns the recoded copy.  top_b / left_b: the saved
     (recoded) bottom strip of the tile above / right strip of the tile to the left, or None."""

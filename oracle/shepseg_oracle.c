@@ -756,19 +756,36 @@ static void elk_init_bounds(const double *X, size_t n, int nb, const double *C, 
     }
 }
 
-static void elk_estep(const double *X, size_t n, int nb, const double *C, int k, const double *half,
-                      const double *next, int32_t *lab, double *ub, double *lb)
+/* *near (optional) += the comparisons `upper > lower_bounds[i][j]` of this E-step, past the half-distance
+ * test, whose two sides were positive and within 2^-31 of each other, relative to the bound: equal, or apart by the rounding of two
+ * distances that are equal in real arithmetic.  The HIP fit brackets a bound lb by a float32 of d + S >= lb
+ * widened by 1e-9 (d + S) on either side (fit_bounds.h, ELK2_EPS_REL), against a float64 error of the bound of
+ * ~1e-14 (d + S): it cannot decide such a comparison by the bracket and has to recompute the bound exactly.
+ * A centre j counts once per sample and E-step, whether the bound was near before the upper bound was tightened,
+ * after, or both (the HIP fit recomputes the bound once for both tests).  The golden generator keeps samples by
+ * this count. */
+static int elk_near(double upper, double lb)
 {
+    return lb > 0.0 && upper > 0.0 && fabs(upper - lb) <= lb * 4.656612873077393e-10;
+}
+
+static void elk_estep(const double *X, size_t n, int nb, const double *C, int k, const double *half,
+                      const double *next, int32_t *lab, double *ub, double *lb, long long *near)
+{
+    long long near_ties = 0;
     for (size_t i = 0; i < n; i++) {
         double upper = ub[i];
         int tight = 0, label = lab[i];
         if (!(next[label] >= upper)) {
-            for (int j = 0; j < k; j++)
+            for (int j = 0; j < k; j++) {
+                const int near1 = j != label && elk_near(upper, lb[i * k + j]) && upper > half[(size_t)label * k + j];
+                near_ties += near1;
                 if (j != label && upper > lb[i * k + j] && upper > half[(size_t)label * k + j]) {
                     if (!tight) {
                         upper = elk_dist(X + i * nb, C + (size_t)label * nb, nb);
                         lb[i * k + label] = upper;
                         tight = 1;
+                        if (!near1 && elk_near(upper, lb[i * k + j])) near_ties++;
                     }
                     if (upper > lb[i * k + j] || upper > half[(size_t)label * k + j]) {
                         const double dist = elk_dist(X + i * nb, C + (size_t)j * nb, nb);
@@ -776,10 +793,12 @@ static void elk_estep(const double *X, size_t n, int nb, const double *C, int k,
                         if (dist < upper) { label = j; upper = dist; }
                     }
                 }
+            }
             lab[i] = label;
             ub[i] = upper;
         }
     }
+    if (near) *near += near_ties;
 }
 
 /* chunk_rows == 0: the M-step sums rows one after the other, as sklearn does with one OpenMP
@@ -793,10 +812,11 @@ static void elk_estep(const double *X, size_t n, int nb, const double *C, int k,
 static int kmeans_fit_impl(const double *xin, int64_t nrows, int nbands, int k,
                            const double *init, int max_iter, double tol_rel,
                            int chunk_rows, int group_chunks, int elkan,
-                           double *centres_out, int32_t *labels_out, int *n_iter_out)
+                           double *centres_out, int32_t *labels_out, int *n_iter_out, long long *near_out)
 {
     size_t n = (size_t)nrows;
     int nb = nbands;
+    if (near_out) *near_out = 0;
     double *X = (double *)malloc(sizeof(double) * n * nb);
     double *mu = (double *)calloc(nb, sizeof(double));
     double *C = (double *)malloc(sizeof(double) * k * nb);
@@ -836,7 +856,7 @@ static int kmeans_fit_impl(const double *xin, int64_t nrows, int nbands, int k,
         elk_init_bounds(X, n, nb, C, k, half, lab, ub, lb);
     }
     for (it = 1; it <= max_iter; it++) {
-        if (elkan) elk_estep(X, n, nb, C, k, half, next, lab, ub, lb);
+        if (elkan) elk_estep(X, n, nb, C, k, half, next, lab, ub, lb, near_out);
         else lloyd_assign(X, n, nb, C, k, lab);
         memset(Cn, 0, sizeof(double) * k * nb);
         memset(w, 0, sizeof(double) * k);
@@ -957,7 +977,7 @@ static int kmeans_fit_impl(const double *xin, int64_t nrows, int nbands, int k,
     }
     if (it > max_iter) it = max_iter;
     if (!strict) {
-        if (elkan) elk_estep(X, n, nb, C, k, half, next, lab, ub, lb);
+        if (elkan) elk_estep(X, n, nb, C, k, half, next, lab, ub, lb, near_out);
         else lloyd_assign(X, n, nb, C, k, lab);
     }
     free(half); free(next); free(ub); free(lb); free(cshift);
@@ -974,7 +994,7 @@ ORC_API int orc_kmeans_fit(const double *xin, int64_t nrows, int nbands, int k,
                            double *centres_out, int32_t *labels_out, int *n_iter_out)
 {
     return kmeans_fit_impl(xin, nrows, nbands, k, init, max_iter, tol_rel, 0, 0, 0, centres_out, labels_out,
-                           n_iter_out);
+                           n_iter_out, NULL);
 }
 
 ORC_API int orc_kmeans_fit_assoc(const double *xin, int64_t nrows, int nbands, int k,
@@ -983,7 +1003,7 @@ ORC_API int orc_kmeans_fit_assoc(const double *xin, int64_t nrows, int nbands, i
                                  double *centres_out, int32_t *labels_out, int *n_iter_out)
 {
     return kmeans_fit_impl(xin, nrows, nbands, k, init, max_iter, tol_rel, chunk_rows, group_chunks, 0,
-                           centres_out, labels_out, n_iter_out);
+                           centres_out, labels_out, n_iter_out, NULL);
 }
 
 ORC_API int orc_kmeans_fit_elkan(const double *xin, int64_t nrows, int nbands, int k,
@@ -992,7 +1012,17 @@ ORC_API int orc_kmeans_fit_elkan(const double *xin, int64_t nrows, int nbands, i
                                  double *centres_out, int32_t *labels_out, int *n_iter_out)
 {
     return kmeans_fit_impl(xin, nrows, nbands, k, init, max_iter, tol_rel, chunk_rows, group_chunks, 1,
-                           centres_out, labels_out, n_iter_out);
+                           centres_out, labels_out, n_iter_out, NULL);
+}
+
+/* orc_kmeans_fit_elkan in sklearn's row order, and the near ties of the bounds it met (elk_estep) */
+ORC_API int orc_kmeans_fit_elkan_near(const double *xin, int64_t nrows, int nbands, int k,
+                                      const double *init, int max_iter, double tol_rel,
+                                      double *centres_out, int32_t *labels_out, int *n_iter_out,
+                                      long long *near_ties_out)
+{
+    return kmeans_fit_impl(xin, nrows, nbands, k, init, max_iter, tol_rel, 0, 0, 1,
+                           centres_out, labels_out, n_iter_out, near_ties_out);
 }
 
 /* ------------------------------------------------------------------ */

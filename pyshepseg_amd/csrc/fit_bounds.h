@@ -14,7 +14,9 @@
 // so it can be RECOMPUTED bit for bit from a 2-byte stamp tau_ij, the history of the centres (k x nb
 // float64 per iteration) and of their shifts -- and it can be BRACKETED without any of that by
 //       A_ij - S_j(t) -/+ eps,   A_ij = float32(d + S_j(tau)) rounded down,  S_j(t) = sum of s_1..t-1[j]
-// (both ends clipped at 0; a pair never computed is exactly 0).  The bracket is ~1e-3 wide; a comparison
+// (both ends clipped at 0; a pair never computed is exactly 0).  The bracket is one float32 ulp of A plus 2 eps
+// wide, eps = 1e-6 + 1e-9 A: ~1e-3 on 16-bit imagery (A ~ 1e4), up to ~1e3 on 32-bit pixel values (A ~ 1e10, where
+// the ulp is 1024 and the relative term of eps, 10, covers the float64 error of the bound); a comparison
 // whose `upper` falls outside it -- all but a handful per million -- is decided by the bracket, the rest
 // by the exact recomputation.  Nothing is updated per iteration: a row changes only where the reference
 // computes a distance.  Per iteration the E-step reads n x k float32 (248 MB) instead of moving 960 MB,
