@@ -638,6 +638,32 @@ int shp_colour_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_
                                   int nrects, const uint32_t *d_table, int64_t nrows, uint32_t *d_packed,
                                   int64_t npacked, uint32_t *bad_out);
 
+/* ---- segment neighbours and border lengths (neighbours.findSegmentNeighbours; csrc/neighbours.h) ------------
+ * Which segments of a uint32 label raster touch which, and along how many pixel pairs.  Two pixels are adjacent when
+ * one is the E or S neighbour of the other (four_connected == 0: SE and SW as well); every adjacent pair with labels
+ * a != b, both non-zero, adds 1 to the border length of (a, b) and of (b, a).  The result is a CSR table over the ids
+ * 0 .. max_seg_id: offsets (max_seg_id + 2 int64; offsets[0] == offsets[1] == 0, label 0 is no segment), neighbour ids
+ * (uint32, ascending within a row) and border lengths (int64).  All of it is integer work: the table does not depend
+ * on how the raster is cut into row blocks.  The state lives in buffers of its own, so other calls of the context
+ * (shp_dev_* transfers, say) may come between the steps.
+ *  shp_nbr_begin: starts a table.  max_seg_id >= 0: the rows the table gets; -1: the largest label met.
+ *  shp_nbr_accumulate_dev: a block of nrows rows of ncols labels in device memory (4-byte aligned).  has_next_row != 0:
+ *    the block is not the raster's last and one more row follows it in memory (nrows + 1 rows are readable); only
+ *    pairs whose UPPER pixel lies in the block count, so a pair across two blocks counts once.  Blocks may come in
+ *    any order.  Workgroups count the pairs of 32 x 64 patches in LDS and append their distinct pairs to a record
+ *    buffer that grows between blocks (device memory is bounded by records, not by pixel pairs).
+ *  shp_nbr_finish: sorts and reduces the records and builds the table on the device.  *max_seg_id_out: the table's
+ *    last row; *n_entries_out: entries of the neighbour and length arrays; *bad_label_out: 0, or the largest label
+ *    above the max_seg_id given to begin -- then there is no table (n_entries_out = 0) and download fails.
+ *    counters_out (may be NULL) [2]: differing pixel pairs met, records handed to the sort; dev_ms_out (may be NULL):
+ *    device time of the accumulate kernels and of this call.
+ *  shp_nbr_download: the three arrays to host memory (max_seg_id + 2, n_entries, n_entries elements). */
+int shp_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected);
+int shp_nbr_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_next_row);
+int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entries_out, uint32_t *bad_label_out,
+                   int64_t *counters_out, double *dev_ms_out);
+int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

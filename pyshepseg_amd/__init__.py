@@ -4,5 +4,6 @@
 ``tiling``       tiled driver + cross-tile stitch
 ``tilingstats``  per-segment statistics
 ``utils``        colour tables from per-segment columns, RGBA rendering of the labels
+``neighbours``   per-segment neighbour lists and border lengths from the label raster
 """
 __version__ = '0.1.0'

@@ -215,6 +215,11 @@ _SIGS = {
     'shp_colour_render_rows_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _vp, _c.c_int64, _vp, _vp, _vp]),
     'shp_colour_overview_rects_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int, _vp, _c.c_int64, _vp, _c.c_int64,
                                                  _vp]),
+    'shp_nbr_begin': (_c.c_int, [_vp, _c.c_int64, _c.c_int]),
+    'shp_nbr_accumulate_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int]),
+    'shp_nbr_finish': (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint32), _vp,
+                                  _c.POINTER(_c.c_double)]),
+    'shp_nbr_download': (_c.c_int, [_vp, _vp, _vp, _vp]),
 }
 
 _lib = None

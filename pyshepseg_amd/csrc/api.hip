@@ -17,6 +17,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "segpoints.h"
 #include "dsegpoints.h"
 #include "colour.h"
+#include "neighbours.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -101,7 +102,10 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage,
                  &ctx->dpts_lh, &ctx->dpts_cls, &ctx->dpts_spos, &ctx->dpts_rec, &ctx->dpts_moff, &ctx->dpts_eoff,
                  &ctx->dpts_cnt, &ctx->dpts_kpos, &ctx->dpts_mrec, &ctx->dpts_key, &ctx->dpts_idx, &ctx->dpts_k0,
-                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo};
+                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo,
+                 &ctx->nbr_ctr, &ctx->nbr_rec, &ctx->nbr_key, &ctx->nbr_val, &ctx->nbr_uidx, &ctx->nbr_ua, &ctx->nbr_ub,
+                 &ctx->nbr_ucnt, &ctx->nbr_deg, &ctx->nbr_hoff, &ctx->nbr_loff, &ctx->nbr_offs, &ctx->nbr_ids,
+                 &ctx->nbr_lens};
     *out = ctx;
     return SHP_OK;
 }
@@ -1438,6 +1442,47 @@ API int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix,
     if (npix > 0 && (!d_seg || !d_table || !d_out)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_out & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
     return run_colour_lookup(ctx, d_seg, (size_t)npix, d_table, (uint32_t)nrows, d_out);
+}
+
+// ---- segment neighbours and border lengths (neighbours.h) -----------------------------------------------
+API int shp_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected)
+{
+    CHK(enter(ctx));
+    if (max_seg_id < -1 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    return run_nbr_begin(ctx, max_seg_id, four_connected);
+}
+
+API int shp_nbr_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_next_row)
+{
+    CHK(enter(ctx));
+    if (ctx->nbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
+    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_seg & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_nbr_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, has_next_row);
+}
+
+API int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entries_out, uint32_t *bad_label_out,
+                       int64_t *counters_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!max_seg_id_out || !n_entries_out || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctx->nbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
+    CHK(run_nbr_finish(ctx, max_seg_id_out, n_entries_out, bad_label_out));
+    if (counters_out) {
+        counters_out[0] = (int64_t)ctx->nbr.pairs;
+        counters_out[1] = (int64_t)ctx->nbr.used;
+    }
+    if (dev_ms_out) *dev_ms_out = ctx->nbr.dev_ms;
+    return 0;
+}
+
+API int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths)
+{
+    CHK(enter(ctx));
+    if (ctx->nbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish must come first");
+    if (!offsets || (ctx->nbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_nbr_download(ctx, offsets, neighbours, border_lengths);
 }
 
 // a column shared by rows over the ranks: shp_colour_stretch in steps (colour.h)

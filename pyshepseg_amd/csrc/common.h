@@ -23,7 +23,7 @@
 // pinned block) instead of by a copy command queued behind it -- under load every command on a
 // stream costs 40-80 us, and there were ten such copies per tile.
 #define PIN_MIRROR (SHP_PINNED_BYTES / 4u - 64u)
-enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5, MIR_PTS = 8 };     // (MIR_PTS: 8 words, segpoints.h)
+enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5, MIR_PTS = 8, MIR_NBR = 16 };     // (MIR_PTS: 8 words, segpoints.h; MIR_NBR: 3, neighbours.h)
 #define MIRROR_STORE(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
 
 struct DevBuf {
@@ -62,6 +62,19 @@ struct DColourState {
     double gamma[2] = {}, lo = 0.0, hi = 0.0, dev_ms = 0.0;
 };
 
+// a segment-adjacency table between shp_nbr_begin and shp_nbr_download (neighbours.h).  The records and the
+// finished table live in buffers of their own (nbr_*), so transfers and other calls may come between the steps.
+struct NbrState {
+    int stage = 0;                  // 0 none, 1 accumulating, 2 finished
+    int eight = 0;
+    int64_t given = -1;             // the caller's max_seg_id, -1: take the largest label
+    unsigned long long cap = 0, used = 0, last_block = 0;      // records: room, stored, of the last block
+    unsigned long long pairs = 0;   // differing pixel pairs met
+    unsigned long long nent = 0;    // entries of the finished table
+    uint32_t max_label = 0, S = 0;
+    double dev_ms = 0.0;
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -77,8 +90,11 @@ struct shp_ctx {
         pts_runs, pts_off, pts_offs, pts_stage,
         dpts_lh, dpts_cls, dpts_spos, dpts_rec, dpts_moff, dpts_eoff, dpts_cnt, dpts_kpos, dpts_mrec, dpts_key,
         dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix,
-        vflag, vlist, vredo;
+        vflag, vlist, vredo,
+        nbr_ctr, nbr_rec, nbr_key, nbr_val, nbr_uidx, nbr_ua, nbr_ub, nbr_ucnt, nbr_deg, nbr_hoff, nbr_loff, nbr_offs,
+        nbr_ids, nbr_lens;
     SegPointsState pts;
+    NbrState nbr;
     DSegPointsState dpts;
     DColourState dcol;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)
