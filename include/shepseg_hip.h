@@ -655,8 +655,9 @@ int shp_colour_overview_rects_dev(shp_ctx *ctx, const uint32_t *d_raster, int64_
  *  shp_nbr_finish: sorts and reduces the records and builds the table on the device.  *max_seg_id_out: the table's
  *    last row; *n_entries_out: entries of the neighbour and length arrays; *bad_label_out: 0, or the largest label
  *    above the max_seg_id given to begin -- then there is no table (n_entries_out = 0) and download fails.
- *    counters_out (may be NULL) [2]: differing pixel pairs met, records handed to the sort; dev_ms_out (may be NULL):
- *    device time of the accumulate kernels and of this call.
+ *    counters_out (may be NULL) [3]: differing pixel pairs met, records handed to the sort, row blocks that did not
+ *    fit the record buffer and ran a second time since shp_nbr_begin; dev_ms_out (may be NULL): device time of the
+ *    accumulate kernels and of this call.
  *  shp_nbr_download: the three arrays to host memory (max_seg_id + 2, n_entries, n_entries elements). */
 int shp_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected);
 int shp_nbr_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_next_row);

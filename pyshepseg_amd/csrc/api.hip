@@ -1472,6 +1472,7 @@ API int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entrie
     if (counters_out) {
         counters_out[0] = (int64_t)ctx->nbr.pairs;
         counters_out[1] = (int64_t)ctx->nbr.used;
+        counters_out[2] = (int64_t)ctx->nbr.reruns;
     }
     if (dev_ms_out) *dev_ms_out = ctx->nbr.dev_ms;
     return 0;

@@ -70,6 +70,7 @@ struct NbrState {
     int64_t given = -1;             // the caller's max_seg_id, -1: take the largest label
     unsigned long long cap = 0, used = 0, last_block = 0;      // records: room, stored, of the last block
     unsigned long long pairs = 0;   // differing pixel pairs met
+    unsigned long long reruns = 0;  // row blocks that did not fit and ran a second time
     unsigned long long nent = 0;    // entries of the finished table
     uint32_t max_label = 0, S = 0;
     double dev_ms = 0.0;

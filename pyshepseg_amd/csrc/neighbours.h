@@ -379,6 +379,7 @@ static int run_nbr_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrow
         if (attempt == 1) break;
         // the block needs exactly reserved - used records: make room, put the counters back, run it again
         CHK(nbr_rec_grow(ctx, reserved, s.used));
+        s.reruns++;
         pin[NBR_C_REC] = s.used;
         pin[NBR_C_PAIRS] = s.pairs;
         HIPCHK(ctx, hipMemcpyAsync(ctr, pin, 16, hipMemcpyHostToDevice, st));

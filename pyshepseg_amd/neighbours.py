@@ -33,10 +33,10 @@ class SegmentNeighbours(object):
     ``offsets``: int64, ``maxSegId + 2`` row boundaries (``offsets[0] == offsets[1] == 0``);
     ``neighbours``: uint32 neighbour ids, ascending within a row; ``borderLengths``: int64, the pixel pairs
     shared with that neighbour.  ``pairsSeen``: differing pixel pairs met; ``recordsSorted``: (pair, count)
-    records the patches handed to the global sort.  ``timings``: seconds per step; ``deviceMs``: GPU time of
-    the kernels."""
+    records the patches handed to the global sort; ``blocksRerun``: row blocks whose records did not fit the
+    buffer and that ran a second time.  ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels."""
     def __init__(self, offsets, neighbours, borderLengths, maxSegId, fourConnected, pairsSeen=0, recordsSorted=0,
-                 timings=None, deviceMs=None):
+                 timings=None, deviceMs=None, blocksRerun=0):
         self.offsets = offsets
         self.neighbours = neighbours
         self.borderLengths = borderLengths
@@ -44,6 +44,7 @@ class SegmentNeighbours(object):
         self.fourConnected = fourConnected
         self.pairsSeen = pairsSeen
         self.recordsSorted = recordsSorted
+        self.blocksRerun = blocksRerun
         self.timings = timings if timings is not None else {}
         self.deviceMs = deviceMs
 
@@ -120,7 +121,7 @@ def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixel
         timings['accumulate'] = time.perf_counter() - t0
         t1 = time.perf_counter()
         (S, nent, bad) = (ctypes.c_uint32(0), ctypes.c_int64(0), ctypes.c_uint32(0))
-        counters = numpy.zeros(2, dtype=numpy.int64)
+        counters = numpy.zeros(3, dtype=numpy.int64)
         ms = ctypes.c_double(0)
         c.check(L.shp_nbr_finish(c.handle, ctypes.byref(S), ctypes.byref(nent), ctypes.byref(bad), _lib.ptr(counters),
                                  ctypes.byref(ms)))
@@ -137,4 +138,5 @@ def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixel
         src.close()
     timings['total'] = time.perf_counter() - t0
     return SegmentNeighbours(offsets, nbrs, lens, S.value, bool(fourConnected), pairsSeen=int(counters[0]),
-                             recordsSorted=int(counters[1]), timings=timings, deviceMs=ms.value)
+                             recordsSorted=int(counters[1]), timings=timings, deviceMs=ms.value,
+                             blocksRerun=int(counters[2]))
