@@ -5,6 +5,7 @@ child process (tests/knob_worker.py): the library reads these knobs once per pro
 is the GPU side of a case, expected() the oracle's; both return dicts of arrays compared exactly."""
 import numpy as np
 
+import clump_shape_cases
 import segtable_cases
 from seg_cases import (STATS_SEL, cut_components, fixed_centres, many_sources_one_target, oracle_tiled,
                        stats_band, synth_tile, uniform_region)
@@ -12,7 +13,11 @@ from seg_cases import (STATS_SEL, cut_components, fixed_centres, many_sources_on
 STATS_DTYPES = ('uint8', 'uint16', 'int16', 'int32', 'uint32')
 TILED = ('tiled4',)
 SMALL = ('tile256', 'tile1000', 'many_sources')
-CLUMP = ('clump_cut4', 'clump_cut8', 'clump_uniform')
+# clump_shapes4 / 8: every shape of tests/clump_shape_cases.py but many_big, whose walks reach every step of the
+# depth-first cut replay (under dfs_pool_1 on the walker whose bitmap lives in global memory); clump_many_big: more
+# cut components than one-walker workgroups are launched, so the counter hands out the rest
+CLUMP = ('clump_cut4', 'clump_cut8', 'clump_uniform', 'clump_shapes4', 'clump_shapes8')
+MANY_BIG = ('clump_many_big',)
 
 # (name, environment of the child, cases that reach the code the setting changes)
 MATRIX = [
@@ -29,8 +34,8 @@ MATRIX = [
     ('dfs_oldwalk', {'SHEPSEG_DFS_OLDWALK': '1'}, CLUMP + TILED),
     ('dfs_pool_1', {'SHEPSEG_DFS_POOL': '1'}, CLUMP + TILED),
     ('dfs_pool_64', {'SHEPSEG_DFS_POOL': '64'}, CLUMP + TILED),
-    ('dfs_per_wg_1', {'SHEPSEG_DFS_PER_WG': '1'}, CLUMP + TILED),
-    ('dfs_per_wg_3', {'SHEPSEG_DFS_PER_WG': '3'}, CLUMP + TILED),
+    ('dfs_per_wg_1', {'SHEPSEG_DFS_PER_WG': '1'}, CLUMP + MANY_BIG + TILED),
+    ('dfs_per_wg_3', {'SHEPSEG_DFS_PER_WG': '3'}, CLUMP + MANY_BIG + TILED),
     ('own_streams', {'SHEPSEG_SHARED_STREAMS': '0'}, TILED),
     ('walk_streams_1', {'SHEPSEG_WALK_STREAMS': '1'}, TILED),
     ('tile_order_rowmajor', {'SHEPSEG_TILE_ORDER': 'rowmajor'}, TILED),
@@ -86,6 +91,18 @@ def _msd(cen):
     return float(shepseg.autoMaxSpectralDiff(shepseg.KMeansModel(cen), 'auto', 50))
 
 
+def _clump_shapes(name, clump):
+    """a clump_shapes4 / clump_shapes8 / clump_many_big case: clump(cl, four) -> (labels, next id) on its shapes,
+    the outputs keyed by shape"""
+    four = name != 'clump_shapes8'
+    out = {}
+    for shape in (('many_big',) if name == 'clump_many_big' else clump_shape_cases.MODEL_SHAPES):
+        seg, nxt = clump(clump_shape_cases.make(shape), four)
+        out[shape + '/seg'] = seg
+        out[shape + '/next'] = np.array([nxt])
+    return out
+
+
 def _subset_inputs():
     rng = np.random.RandomState(11)
     base = rng.permutation(np.arange(1, 20 * 18 + 1)).reshape(20, 18).astype(np.uint32)
@@ -134,6 +151,8 @@ def run_case(name, oracle, tmpdir):
         np.save(src, seg)
         r = subset.subsetImage(src, os.path.join(tmpdir, 'subset_out.npy'), 150, 200, 1250, 1150, maskImage=mask)
         return {'seg': r.segimg, 'orig': r.origSegIds, 'hist': r.hist}
+    if name.startswith('clump_shapes') or name in MANY_BIG:
+        return _clump_shapes(name, lambda cl, four: shepseg.clump(cl, 0, fourConnected=four))
     if name in CLUMP:
         cl = uniform_region() if name == 'clump_uniform' else cut_components()
         seg, nxt = shepseg.clump(cl, 0, fourConnected=name != 'clump_cut8')
@@ -166,6 +185,8 @@ def expected(name, oracle):
         seg, mask = _subset_inputs()
         want, worig, whist = oracle.subset_recode(seg, 150, 200, 1250, 1150, mask, 1024)
         return {'seg': want, 'orig': worig, 'hist': whist}
+    if name.startswith('clump_shapes') or name in MANY_BIG:
+        return _clump_shapes(name, lambda cl, four: oracle.clump(cl, 0, four, 1))
     if name in CLUMP:
         cl = uniform_region() if name == 'clump_uniform' else cut_components()
         seg, nxt = oracle.clump(cl, 0, name != 'clump_cut8', 1)

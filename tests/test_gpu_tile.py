@@ -12,7 +12,7 @@ from conftest import GOLDEN
 pytestmark = pytest.mark.gpu
 
 TILE_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'tile_*.npz')))
-CLUMP_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'clump_*.npz')))
+CLUMP_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, 'clump_*conn.npz')))
 
 
 @pytest.fixture(scope='module')
