@@ -72,6 +72,12 @@ int shp_last_timings(const shp_ctx *ctx, double *out);
  * instrumented kernels: ids 0 assign, 1 ccl, 2 dfs_pool (the replay), 3 radix sort, 4 spectra,
  * 5 small-segment pass loop, 7 seed scan + final labels.  reset != 0 clears the counters. */
 int shp_prof_get(shp_ctx *ctx, double *ms_out, uint64_t *count_out, int n, int reset);
+/* process-wide counters of the launches that carry the tiles' latency-bound kernels, one launch for every
+ * tile that is ready (csrc/walkbatch.h).  out receives six values: launches, jobs (tiles) and the largest
+ * batch of the depth-first replay, then the same three of the small-segment pass loop.  A launch of a
+ * context that owns its stream counts as a batch of one.  reset != 0 clears the counters.  Read-only
+ * otherwise: it changes nothing about how the work runs. */
+int shp_walk_batch_stats(uint64_t *out, int reset);
 
 /* ---- k-means ------------------------------------------------------------------------ */
 /* replaces sklearn KMeans(init=<array>, n_init=1).fit as called by

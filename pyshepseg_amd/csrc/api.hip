@@ -124,6 +124,9 @@ API void shp_ctx_destroy(shp_ctx *ctx)
             if (ctx->prof_ev[i][j]) hipEventDestroy(ctx->prof_ev[i][j]);
     if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
     if (ctx->h_fit) hipHostFree(ctx->h_fit);
+    if (ctx->h_jobs) hipHostFree(ctx->h_jobs);
+    for (int j = 0; j < 2; j++)
+        if (ctx->wb_ev[j]) hipEventDestroy(ctx->wb_ev[j]);
     if (ctx->scan_ctr) hipFree(ctx->scan_ctr);
     if (ctx->stream2) { hipStreamSynchronize(ctx->stream2); hipStreamDestroy(ctx->stream2); }
     if (ctx->evfork) hipEventDestroy(ctx->evfork);
@@ -1122,6 +1125,17 @@ API int shp_prof_get(shp_ctx *ctx, double *ms_out, uint64_t *count_out, int n, i
     prof_collect(ctx);
     for (int i = 0; i < n && i < PROF_N; i++) { ms_out[i] = ctx->prof_ms[i]; count_out[i] = ctx->prof_cnt[i]; }
     if (reset) for (int i = 0; i < PROF_N; i++) { ctx->prof_ms[i] = 0; ctx->prof_cnt[i] = 0; }
+    return 0;
+}
+
+// launches, jobs and largest batch of the replay, then of the pass loop (walkbatch.h); process-wide
+API int shp_walk_batch_stats(uint64_t *out, int reset)
+{
+    if (!out) return SHP_ERR_ARG;
+    for (int c = 0; c < walkbatch::NCLS; c++) {
+        const walkbatch::Stats s = walk_batcher().stats(c, reset != 0);
+        out[3 * c] = s.launches; out[3 * c + 1] = s.jobs; out[3 * c + 2] = s.largest;
+    }
     return 0;
 }
 

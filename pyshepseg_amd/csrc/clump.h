@@ -1157,7 +1157,7 @@ __global__ __launch_bounds__(256) void k_big_order(const BigInfo *__restrict__ b
     order[rank] = i;
 }
 
-// One launch per tile.  A workgroup holds DFS_WAVES independent walkers (one wavefront each) that
+// One job per tile (several tiles' jobs may share a launch, see DfsBatch).  A workgroup holds DFS_WAVES independent walkers (one wavefront each) that
 // share a pool of LDS granules: a walker takes a component, claims the contiguous granules its
 // bounding-box bitmap needs (a bit mask in LDS, claimed with one atomic OR), walks, gives them back,
 // takes the next component.  The bitmaps are sized by the component (median 6 KiB, 99 % below 28 KiB
@@ -1166,7 +1166,7 @@ __global__ __launch_bounds__(256) void k_big_order(const BigInfo *__restrict__ b
 // stays free for the other streams' kernels; the LDS footprint above 80 KiB keeps a second walker
 // workgroup off the same CU.
 // Components are taken largest first.  The first pass is static and interleaved (walker w of
-// workgroup b takes rank w * gridDim.x + b), which hands every workgroup one component of each
+// workgroup b of a job of G workgroups takes rank w * G + b), which hands every workgroup one component of each
 // size class instead of the eight largest to workgroup 0; whatever is left is pulled from a
 // counter.  A walker that finds no room waits for its neighbours' releases (they never wait for
 // anything, so the wait is finite); after DFS_ALLOC_SPINS polls, or for a bitmap larger than the
@@ -1208,13 +1208,47 @@ __device__ __forceinline__ int dfs_pool_alloc(unsigned long long *mask, uint32_t
     return __builtin_amdgcn_readfirstlane(res);
 }
 
-__global__ __launch_bounds__(DFS_WAVES * 64) void k_dfs_pool(        // blockDim.x / 64 walkers (<= DFS_WAVES)
+// One launch carries the replays of several tiles (walkbatch.h): a JOB is what one tile's launch took as
+// arguments.  Workgroups pre[j] .. pre[j + 1] - 1 belong to job j; inside, a workgroup knows only its index within
+// its job and the job's block count, so a job runs exactly as it would alone.  Walkers of different jobs share
+// nothing.  The records travel by value in the kernel-argument segment (DFS_MAX_JOBS * 104 B + the prefix < 4 KB).
+#define DFS_MAX_JOBS 16
+struct DfsJob {
+    uint32_t *lab;
+    const BigInfo *big;
+    uint32_t *counters, *stackbuf, *singles, *nsingles;
+    const uint32_t *order;
+    uint32_t *csize;
+    unsigned long long *dbg;
+    uint32_t *snap, *gscratch;
+    uint32_t gscratch_words, nrows, ncols;
+    int four;
+};
+struct DfsBatch {
+    uint32_t njobs;
+    uint32_t pre[DFS_MAX_JOBS + 1];
+    DfsJob job[DFS_MAX_JOBS];
+};
+static_assert(sizeof(DfsBatch) <= 3072, "the replay's job records must fit the kernel-argument segment");
 
-    uint32_t *lab, const BigInfo *__restrict__ big, uint32_t *counters, uint32_t *stackbuf, uint32_t nrows,
-    uint32_t ncols, int four, uint32_t pool_grans, uint32_t *singles, uint32_t *nsingles,
-    const uint32_t *__restrict__ order, uint32_t *csize, unsigned long long *dbg, int oldwalk, uint32_t *snap,
-    uint32_t *gscratch, uint32_t gscratch_words)
+__global__ __launch_bounds__(DFS_WAVES * 64) void k_dfs_pool(        // blockDim.x / 64 walkers (<= DFS_WAVES)
+    const DfsBatch bt, const uint32_t pool_grans, const int oldwalk)
 {
+    // the workgroup's job: uniform per workgroup, found by a scalar walk over the prefix
+    uint32_t jb = 0;
+    while (jb + 1u < bt.njobs && blockIdx.x >= bt.pre[jb + 1u]) jb++;
+    jb = UNI(jb);
+    const uint32_t bid = UNI(blockIdx.x - bt.pre[jb]), nblk = UNI(bt.pre[jb + 1u] - bt.pre[jb]);
+    uint32_t *const lab = bt.job[jb].lab;
+    const BigInfo *__restrict__ const big = bt.job[jb].big;
+    uint32_t *const counters = bt.job[jb].counters, *const stackbuf = bt.job[jb].stackbuf;
+    uint32_t *const singles = bt.job[jb].singles, *const nsingles = bt.job[jb].nsingles;
+    const uint32_t *__restrict__ const order = bt.job[jb].order;
+    uint32_t *const csize = bt.job[jb].csize;
+    unsigned long long *const dbg = bt.job[jb].dbg;
+    uint32_t *const snap = bt.job[jb].snap, *const gscratch = bt.job[jb].gscratch;
+    const uint32_t gscratch_words = bt.job[jb].gscratch_words, nrows = bt.job[jb].nrows, ncols = bt.job[jb].ncols;
+    const int four = bt.job[jb].four;
     extern __shared__ __attribute__((aligned(16))) uint32_t dfs_lds[];
     unsigned long long *mask = (unsigned long long *)dfs_lds;             // 4 words (2 used)
     // (readfirstlane: the walker index is wave-uniform, and everything derived from it -- the
@@ -1228,7 +1262,7 @@ __global__ __launch_bounds__(DFS_WAVES * 64) void k_dfs_pool(        // blockDim
     __syncthreads();                        // the only workgroup-wide rendezvous: walkers are independent
     const uint32_t nbig = counters[0];
     __builtin_amdgcn_s_setprio(3);          // lone latency-bound waves: win issue arbitration
-    uint32_t idx = w * gridDim.x + blockIdx.x;
+    uint32_t idx = w * nblk + bid;
     bool first = true;
     for (;;) {
         if (first) {
@@ -1265,7 +1299,7 @@ __global__ __launch_bounds__(DFS_WAVES * 64) void k_dfs_pool(        // blockDim
         const unsigned long long t1 = dbg ? wall_clock64() : 0ull;
         if (g0 >= 0) {
             uint32_t *bmw = pool + (uint32_t)g0 * DFS_GRAN_WORDS;
-            uint32_t *snapw = snap + (size_t)(blockIdx.x * nwalk + w) * ((size_t)pool_grans * DFS_GRAN_WORDS);
+            uint32_t *snapw = snap + (size_t)(bid * nwalk + w) * ((size_t)pool_grans * DFS_GRAN_WORDS);
             if (oldwalk) dfs_split_lds(lab, B, bmw, sw, stackbuf, ncols, four, singles, nsingles, csize);
             else if (four) dfs_split_win<true>(lab, B, bmw, sw, stackbuf, ncols, singles, nsingles, csize, snapw, dbg ? dbg + (size_t)idx * DFS_DBG_WORDS + 6u : nullptr);
             else dfs_split_win<false>(lab, B, bmw, sw, stackbuf, ncols, singles, nsingles, csize, snapw, dbg ? dbg + (size_t)idx * DFS_DBG_WORDS + 6u : nullptr);
@@ -1304,12 +1338,42 @@ __global__ __launch_bounds__(DFS_WAVES * 64) void k_dfs_pool(        // blockDim
         if (dbg && lane == 0) {          // SHEPSEG_DFS_STATS: size, bitmap words, wait / walk ticks (100 MHz), start
             unsigned long long *d = dbg + (size_t)idx * DFS_DBG_WORDS;
             d[0] = B.size; d[1] = words; d[2] = t1 - t0; d[3] = wall_clock64() - t1; d[4] = t0;
-            d[5] = ((unsigned long long)blockIdx.x << 8) | w | (g0 < 0 ? 1ull << 40 : 0ull);
+            d[5] = ((unsigned long long)bid << 8) | w | (g0 < 0 ? 1ull << 40 : 0ull);
         }
         uint32_t nx = 0;
         if (lane == 0) nx = atomicAdd(&counters[3], 1u);
-        idx = nwalk * gridDim.x + (uint32_t)__builtin_amdgcn_readfirstlane((int)nx);
+        idx = nwalk * nblk + (uint32_t)__builtin_amdgcn_readfirstlane((int)nx);
     }
+}
+
+// one launch for nj replays (nj <= DFS_MAX_JOBS); jobs[i]->arg is the tile's DfsJob
+static void dfs_launch(hipStream_t st, walkbatch::Job *const *jobs, int nj, uint32_t pw, size_t lds, uint32_t pg, int oldwalk)
+{
+    DfsBatch bt;
+    memset(&bt, 0, sizeof(bt));
+    bt.njobs = (uint32_t)nj;
+    for (int i = 0; i < nj; i++) {
+        bt.job[i] = *(const DfsJob *)jobs[i]->arg;
+        bt.pre[i + 1] = bt.pre[i] + jobs[i]->blocks;
+    }
+    hipLaunchKernelGGL(k_dfs_pool, dim3(bt.pre[nj]), dim3(pw * 64u), lds, st, bt, pg, oldwalk);
+}
+// the leader's side of a batched replay: borrow a walker stream, launch, wait, give the stream back
+static int dfs_lead(shp_ctx *ctx, walkbatch::Job *const *jobs, int nj, uint32_t pw, size_t lds, uint32_t pg, int oldwalk,
+                    double *ms)
+{
+    CHK(walk_lead_begin(ctx));
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipEventRecord(ctx->wb_ev[0], st));
+    dfs_launch(st, jobs, nj, pw, lds, pg, oldwalk);
+    const hipError_t lerr = hipGetLastError();
+    (void)hipEventRecord(ctx->wb_ev[1], st);
+    const hipError_t serr = hipStreamSynchronize(st);
+    stream_give(ctx);
+    HIPCHK(ctx, lerr); HIPCHK(ctx, serr);
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, ctx->wb_ev[0], ctx->wb_ev[1]) == hipSuccess) *ms = f;
+    return 0;
 }
 
 struct SeedFn {
@@ -1449,13 +1513,14 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
     HIPCHK(ctx, hipStreamSynchronize(st));
     const uint32_t nbig_h = *(volatile uint32_t *)mir_nbig;
     fill_release(ctx, false);
-    if (nbig_h) walk_begin(ctx);
     st = ctx->stream;
-    ps = prof_begin(ctx, PROF_DFS);              // events hug the kernel
+    // a stream-sharing worker hands the replay to the walker batcher: one launch carries every tile that is ready
+    const bool batched = nbig_h && stream_sharing(ctx) && !ctx->borrowed;
     unsigned long long *dbg = nullptr;
     if (getenv("SHEPSEG_DFS_STATS") && nbig_h) {
         CHK(buf_ensure(ctx, ctx->dbg, (size_t)nbig_h * DFS_DBG_WORDS * 8u));
         HIPCHK(ctx, hipMemsetAsync(ctx->dbg.p, 0, (size_t)nbig_h * DFS_DBG_WORDS * 8u, st));
+        if (batched) HIPCHK(ctx, hipStreamSynchronize(st));      // (the launch is on another stream)
         dbg = bp<unsigned long long>(ctx->dbg);
     }
     if (nbig_h) {
@@ -1470,17 +1535,48 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
             HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dfs_pool, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
             attr_set = true;
         }
-        // at most DFS_MAX_BLOCKS workgroups (the rest of the components is pulled from the counter):
+        // a walker workgroup takes one CU's LDS, so a batch of about one workgroup per CU fills the device; more
+        // would only queue behind them
+        static const bool caps_set = [] {
+            int dev = 0, ncu = 0;
+            if (hipGetDevice(&dev) != hipSuccess ||
+                hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 64;
+            walkbatch::Caps c;
+            c.max_jobs = DFS_MAX_JOBS; c.max_blocks = (unsigned)ncu; c.budget = 0;
+            walk_batcher().set_caps(walkbatch::CLS_REPLAY, c);
+            return true;
+        }();
+        (void)caps_set;
+        // at most DFS_MAX_BLOCKS workgroups per tile (the rest of the components is pulled from the counter):
         // every walker owns a slot of the snapshot buffer as large as the walker pool
         uint32_t nblk = (nbig_h + pw - 1u) / pw;
         nblk = nblk > DFS_MAX_BLOCKS ? DFS_MAX_BLOCKS : nblk;
         CHK(buf_ensure(ctx, ctx->snap, (size_t)nblk * pw * pg * DFS_GRAN_WORDS * 4u));
-        hipLaunchKernelGGL(k_dfs_pool, dim3(nblk), dim3(pw * 64u), lds, st, lab, big,
-                           counters, bp<uint32_t>(ctx->stack), nrows, ncols, four, pg, d_singles, d_nsingles,
-                           order, csize, dbg, oldwalk, bp<uint32_t>(ctx->snap), rank /* aux2: free until the seed scan */,
-                           n); KCHK(ctx);
+        DfsJob job;
+        job.lab = lab; job.big = big; job.counters = counters; job.stackbuf = bp<uint32_t>(ctx->stack);
+        job.singles = d_singles; job.nsingles = d_nsingles; job.order = order; job.csize = csize; job.dbg = dbg;
+        job.snap = bp<uint32_t>(ctx->snap); job.gscratch = rank /* aux2: free until the seed scan */;
+        job.gscratch_words = n; job.nrows = nrows; job.ncols = ncols; job.four = four;
+        walkbatch::Job wj;
+        wj.cls = walkbatch::CLS_REPLAY; wj.blocks = nblk; wj.arg = &job;
+        if (batched) {
+            walk_batcher().run(&wj, [=](int, walkbatch::Job *const *jobs, int nj, double *ms, char *msg, size_t cap) {
+                const int rc = dfs_lead(ctx, jobs, nj, pw, lds, pg, oldwalk, ms);
+                if (rc) walk_msg(msg, cap, ctx->err);
+                return rc;
+            });
+            if (wj.launch_rc) SHP_FAIL(ctx, wj.launch_rc, "%s", wj.msg);
+            ctx->prof_ms[PROF_DFS] += wj.ms;          // an equal share of the batch's time, one launch's worth
+            ctx->prof_cnt[PROF_DFS] += 1;
+        } else {
+            walk_batcher().direct_begin(walkbatch::CLS_REPLAY);
+            walk_batcher().direct_end(walkbatch::CLS_REPLAY);      // (no residency rule for replays: counted only)
+            walkbatch::Job *one = &wj;
+            ps = prof_begin(ctx, PROF_DFS);              // events hug the kernel
+            dfs_launch(st, &one, 1, pw, lds, pg, oldwalk); KCHK(ctx);
+            prof_end(ctx, ps);
+        }
     }
-    prof_end(ctx, ps);
     if (dbg) {
         const size_t DW = DFS_DBG_WORDS;
         std::vector<unsigned long long> h((size_t)nbig_h * DW);
@@ -1517,7 +1613,6 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
     }
     if (fill_gating(ctx) || stream_sharing(ctx)) {
         HIPCHK(ctx, hipStreamSynchronize(st));
-        walk_end(ctx);
         fill_acquire(ctx, 1);
         st = ctx->stream;
     }

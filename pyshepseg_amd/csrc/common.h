@@ -10,6 +10,7 @@
 #include <mutex>
 #include <condition_variable>
 #include "../../include/shepseg_hip.h"
+#include "walkbatch.h"
 
 #define WAVE 64
 #define NULL_LAB 0xFFFFFFFFu   // CCL label of a null pixel
@@ -118,7 +119,10 @@ struct shp_ctx {
     bool gate_held = false;
     bool shared = false;    // a worker context without a stream of its own: it borrows one per phase
     int borrowed = 0;       // 0 = none (ctx->stream is the pool's idle stream), 1 = a fill stream, 2 = a walker stream
+    hipEvent_t wb_ev[2] = {};       // around a batched walker launch this context leads (walkbatch.h)
+    void *h_jobs = nullptr;         // pinned, SHP_JOBS_BYTES: the job records of such a launch
 };
+#define SHP_JOBS_BYTES 8192u
 
 // Fill gate.  A tile alternates between phases that fill the GPU (HBM-bound passes over the whole
 // tile: ~3.4 ms of device time) and phases that are one long dependent chain on a few wavefronts
@@ -137,18 +141,47 @@ struct FillGate {
     int waiting[FILL_PRIOS] = {};
 };
 static FillGate g_fill;
-static const int g_fill_max = getenv("SHEPSEG_FILL_MAX") ? atoi(getenv("SHEPSEG_FILL_MAX")) : FILL_MAX_DEFAULT;
+// Stream counts from the queue budget.  Streams that share a hardware queue get in each other's way: a 10-ms
+// walker kernel holds up the fill kernels queued behind it on the same queue (at 4 queues the fill kernels'
+// union covers a third of the step, LABNOTES "walker batches"), so the pools are sized to the queues the
+// process gets: Q = GPU_MAX_HW_QUEUES (read, never set; 4 when unset, the
+// runtime's own default).  Three streams live beside the pools (the pool's idle stream, the main context's,
+// the chain context's).  From Q = 21 the round-4 sizes hold; below, what is left of Q after those three is
+// split two to one between fill and walker streams (the walker work of all ready tiles travels in one
+// launch per stream, walkbatch.h, so few walker streams carry many tiles); where Q cannot hold even that,
+// as at 4, the floors apply: a queue for each fill stream and one for the walker stream, the fourth for the
+// three others (reasoned, not yet swept on the GPU: LABNOTES "walker batches").
+#define FILL_FLOOR_DEFAULT 2
+#define WALK_FLOOR_DEFAULT 1
+static inline int hw_queue_budget()
+{
+    const char *e = getenv("GPU_MAX_HW_QUEUES");
+    const int q = e ? atoi(e) : 0;
+    return q > 0 ? q : 4;
+}
+static inline int pool_default(int cls)
+{
+    const int q = hw_queue_budget();
+    if (q >= 21) return cls ? 10 : FILL_MAX_DEFAULT;      // 6 + 10 + 3 and two to spare, as measured in round 4
+    const int avail = q - 3;
+    int walk = avail / 3, fill = avail - walk;
+    if (walk < WALK_FLOOR_DEFAULT) walk = WALK_FLOOR_DEFAULT;
+    if (fill < FILL_FLOOR_DEFAULT) fill = FILL_FLOOR_DEFAULT;
+    if (fill > FILL_MAX_DEFAULT) fill = FILL_MAX_DEFAULT;
+    return cls ? walk : fill;
+}
+static const int g_fill_max = getenv("SHEPSEG_FILL_MAX") ? atoi(getenv("SHEPSEG_FILL_MAX")) : pool_default(0);
 
-// Stream pool.  A process gets about 24 hardware queues before the driver time-slices them, so the
-// number of streams is what bounds the tiles in flight -- and a tile that owns a stream keeps it
-// through its host-side waits (for the fill gate, for a pass-loop slot) as well.  A SHARED context
-// has no stream of its own: inside a worker call of the tiled driver it borrows a fill stream for
-// each GPU-filling phase (with the gate slot: there are as many as the gate admits) and a walker
-// stream for each latency-bound kernel, and gives it back once the phase has left the GPU (every
-// phase ends in a host synchronisation, so the next phase may run on any other stream).  More tiles
-// than streams can then be in flight.  Outside worker calls a shared context uses the pool's idle
-// stream, which all of them share.
-#define WALK_STREAMS_DEFAULT 10
+// Stream pool.  A process gets GPU_MAX_HW_QUEUES hardware queues (4 unless the environment says otherwise)
+// and streams beyond that share them, so a tile that owned a stream would hold a queue through its
+// host-side waits (for the fill gate, for a pass-loop slot) as well.  A SHARED context has no stream
+// of its own: inside a worker call of the tiled driver it borrows a fill stream for each GPU-filling
+// phase (with the gate slot: there are as many as the gate admits) and gives it back once the phase
+// has left the GPU (every phase ends in a host synchronisation, so the next phase may run on any
+// other stream).  Its latency-bound kernels go through the walker batcher (g_walk below): whoever
+// finds a walker stream free launches the pending jobs of all tiles at once.  More tiles than
+// streams can then be in flight.  Outside worker calls a shared context uses the pool's idle stream,
+// which all of them share.
 struct StreamPool {
     std::mutex mu;
     std::condition_variable cv;
@@ -158,7 +191,7 @@ struct StreamPool {
     hipStream_t misc = nullptr;
 };
 static StreamPool g_streams;
-static const int g_walk_streams = getenv("SHEPSEG_WALK_STREAMS") ? atoi(getenv("SHEPSEG_WALK_STREAMS")) : WALK_STREAMS_DEFAULT;
+static const int g_walk_streams = getenv("SHEPSEG_WALK_STREAMS") ? atoi(getenv("SHEPSEG_WALK_STREAMS")) : pool_default(1);
 static inline int stream_pool_cap(int cls)
 {
     if (cls == 1) return g_walk_streams < 1 ? 1 : g_walk_streams;
@@ -238,14 +271,14 @@ static inline void fill_release(shp_ctx *ctx, bool sync)
     }
     ctx->fill_held = false;
 }
-// a latency-bound kernel of a shared context runs on a borrowed walker stream
-static inline void walk_begin(shp_ctx *ctx)
+// The walker batcher: the latency-bound kernels of stream-sharing contexts (walkbatch.h).  It hands out as
+// many leaderships as there are walker streams, so a leader's stream_take(ctx, 1) finds one.
+static walkbatch::Batcher g_walk;
+static inline walkbatch::Batcher &walk_batcher()
 {
-    if (stream_sharing(ctx) && !ctx->borrowed) stream_take(ctx, 1);
-}
-static inline void walk_end(shp_ctx *ctx)       // (after the caller's stream synchronisation)
-{
-    if (ctx->borrowed == 2) stream_give(ctx);
+    static const bool once = [] { g_walk.set_streams(stream_pool_cap(1)); return true; }();
+    (void)once;
+    return g_walk;
 }
 struct FillScope {          // an API call never leaves with the gate or a borrowed stream held (error paths)
     shp_ctx *ctx;
@@ -311,6 +344,20 @@ static inline void prof_collect(shp_ctx *ctx)
     } while (0)
 
 #define KCHK(ctx) HIPCHK(ctx, hipGetLastError())
+
+// what a leader needs around its launch: a walker stream, the event pair, the pinned block of job records
+static inline int walk_lead_begin(shp_ctx *ctx)
+{
+    if (!ctx->wb_ev[0]) { HIPCHK(ctx, hipEventCreate(&ctx->wb_ev[0])); HIPCHK(ctx, hipEventCreate(&ctx->wb_ev[1])); }
+    if (!ctx->h_jobs) HIPCHK(ctx, hipHostMalloc(&ctx->h_jobs, SHP_JOBS_BYTES, hipHostMallocDefault));
+    if (!ctx->borrowed) stream_take(ctx, 1);
+    return 0;
+}
+// (copies a leader's error text into the batch's)
+static inline void walk_msg(char *msg, size_t cap, const std::string &err)
+{
+    if (cap) { strncpy(msg, err.c_str(), cap - 1); msg[cap - 1] = 0; }
+}
 
 // the side stream is only created when a call really forks: every stream costs a slot in the
 // hardware queues the worker streams are spread over

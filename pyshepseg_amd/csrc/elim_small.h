@@ -888,8 +888,16 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
 #ifndef SMALL_MINWAVES
 #define SMALL_MINWAVES 4
 #endif
-__global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
+// One launch carries the pass loops of several tiles (walkbatch.h): job j is the group of `nblk` consecutive
+// workgroups j * nblk .. (j + 1) * nblk - 1 and jobs[j] what a launch for that tile alone took as its argument.
+// A group knows only itself: G, bid, the grid barriers' state (its own SmallCtl, xcd_n counted per group) and the
+// pinned report block are the job's, so a loop runs exactly as it would alone, and a group whose barrier times
+// out sets only its own `fail` and leaves alone.  The records sit in a buffer nobody writes while the kernel
+// runs (pinned host memory, filled before the launch).
+__global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallArgs *__restrict__ jobs, const uint32_t nblk)
 {
+    const uint32_t jb = UNI(blockIdx.x / nblk), bid = UNI(blockIdx.x - jb * nblk);
+    const SmallArgs a = jobs[jb];       // (uniform address, nothing stored before it: scalar loads)
     __shared__ uint32_t wpix[4][64];
     __shared__ uint32_t wids[4][SMALL_BATCH_IDS];
     __shared__ unsigned long long wkeys[4][SMALL_BATCH_SRC + SMALL_BATCH_SRC / 2u];     // keys, then the winners' targets
@@ -897,8 +905,8 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
     __shared__ uint32_t lhist[256];
     SmallCtl *ctl = a.ctl;
     __builtin_amdgcn_s_setprio(2);
-    const uint32_t G = gridDim.x;
-    const uint32_t gtid = blockIdx.x * 256u + threadIdx.x, gthreads = G * 256u;
+    const uint32_t G = nblk;
+    const uint32_t gtid = bid * 256u + threadIdx.x, gthreads = G * 256u;
     const uint32_t gwave = gtid >> 6, gwaves = gthreads >> 6;
     const unsigned lane = lane_id(), w = threadIdx.x >> 6;
     // where does this workgroup run?  count the launch's workgroups per XCD, meet once with the
@@ -931,7 +939,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
     const uint32_t cap = (a.S + 1u) / (a.min_seg ? a.min_seg : 1u);
     const bool lists = a.lists && a.min_seg >= 2u && a.min_seg <= 256u && 4u * a.min_seg + 1u <= a.S + 1u && cap >= 64u;
     if (lists) {
-        if (blockIdx.x == 0) {
+        if (bid == 0) {
             for (uint32_t u = threadIdx.x; u < a.min_seg; u += 256u) { gcount[u] = 0u; gover[u] = 0u; cursor[u] = 0u; }
             if (threadIdx.x == 0) {
                 uint32_t acc = 0;
@@ -944,7 +952,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
         // (workgroup, size) to reserve the run (a global atomic per id put 77 000 of them on ONE address for the
         // two-pixel segments of a tile -- a millisecond, and far more with twelve loops at it)
         __shared__ uint32_t lbase[256];
-        const uint32_t per = (a.S + G - 1u) / G, lo = blockIdx.x * per + 1u;
+        const uint32_t per = (a.S + G - 1u) / G, lo = bid * per + 1u;
         const uint32_t hi = lo + per - 1u < a.S ? lo + per - 1u : a.S;
         lhist[threadIdx.x] = 0u;
         __syncthreads();
@@ -995,7 +1003,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
                 }
             }
             s_target = target; s_done = done; s_count = done ? 0u : (uint32_t)prev;      // sources of this pass
-            if (blockIdx.x == 0) {
+            if (bid == 0) {
                 ctl->st[par ^ 1u].target = target; ctl->st[par ^ 1u].prev = prev;
                 ctl->st[par ^ 1u].passes = passes;
                 SmallCnt *nx = &ctl->cnt[(slot + 1u) % 3u];
@@ -1007,7 +1015,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
         if (s_done) {
             // workgroup 0 hands the control block to the host (every other workgroup's counters
             // reached the L2 before the last barrier)
-            if (blockIdx.x == 0)
+            if (bid == 0)
                 for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(SmallCtl) / 4); i += 256u)
                     MIRROR_STORE(&a.pin[i], L2LOAD(&((const uint32_t *)ctl)[i]));
             break;
@@ -1290,14 +1298,36 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(SmallArgs a)
     }
 }
 
-// at most this many persistent loop kernels run at once (co-residency of all their workgroups)
-#include <mutex>
-#include <condition_variable>
-static std::mutex g_small_mu;
-static std::condition_variable g_small_cv;
-static int g_small_running = 0;
+// At most SHEPSEG_SMALL_MAX pass loops run at once, and never more than fit the device (co-residency of all
+// their workgroups): the walker batcher keeps that count over batched and direct launches alike.
 #define SMALL_MAX_CONCURRENT 20
 static const int g_small_max = getenv("SHEPSEG_SMALL_MAX") ? atoi(getenv("SHEPSEG_SMALL_MAX")) : SMALL_MAX_CONCURRENT;
+
+// one launch for nj pass loops; jobs[i]->arg is the tile's SmallArgs, `rec` a pinned block that stays untouched
+// until the kernel has left
+static void small_launch(hipStream_t st, walkbatch::Job *const *jobs, int nj, unsigned small_blocks, void *rec)
+{
+    SmallArgs *r = (SmallArgs *)rec;
+    for (int i = 0; i < nj; i++) r[i] = *(const SmallArgs *)jobs[i]->arg;
+    hipLaunchKernelGGL(k_small_loop, dim3((unsigned)nj * small_blocks), dim3(256), 0, st, (const SmallArgs *)r, (uint32_t)small_blocks);
+}
+// the leader's side of a batched pass loop: borrow a walker stream, launch, wait, give the stream back
+static int small_lead(shp_ctx *ctx, walkbatch::Job *const *jobs, int nj, unsigned small_blocks, double *ms)
+{
+    CHK(walk_lead_begin(ctx));
+    if ((size_t)nj * sizeof(SmallArgs) > SHP_JOBS_BYTES) SHP_FAIL(ctx, SHP_ERR_STATE, "pass-loop batch of %d jobs", nj);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, hipEventRecord(ctx->wb_ev[0], st));
+    small_launch(st, jobs, nj, small_blocks, ctx->h_jobs);
+    const hipError_t lerr = hipGetLastError();
+    (void)hipEventRecord(ctx->wb_ev[1], st);
+    const hipError_t serr = hipStreamSynchronize(st);
+    stream_give(ctx);
+    HIPCHK(ctx, lerr); HIPCHK(ctx, serr);
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, ctx->wb_ev[0], ctx->wb_ev[1]) == hipSuccess) *ms = f;
+    return 0;
+}
 
 // d_seg in place; *max_id in: seg.max(); out: seg.max() after the final relabel.
 // sizes_in_origsz: ctx->origsz already holds makeSegSize(d_seg) (run_eliminate_single leaves it)
@@ -1383,7 +1413,8 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
     fill_release(ctx, true);            // the pass loop is a latency-bound phase
     static const unsigned small_blocks = getenv("SHEPSEG_SMALL_BLOCKS") ? (unsigned)atoi(getenv("SHEPSEG_SMALL_BLOCKS")) : SMALL_BLOCKS;
     // how many loops fit the device at once, from the kernel's own occupancy (its register count decides:
-    // 168 VGPRs = 3 workgroups per CU = 768 on the device = 12 loops of 64); never more than SHEPSEG_SMALL_MAX
+    // 128 VGPRs = 4 workgroups per CU = 1024 on the device = 16 loops of 64); never more than SHEPSEG_SMALL_MAX.
+    // A batch of B loops counts as B against it
     static const int cap = [] {
         int per_cu = 0, dev = 0, ncu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_loop, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
@@ -1393,28 +1424,41 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
         c = c < 1 ? 1 : c;
         return c < g_small_max ? c : g_small_max;
     }();
-    {
-        std::unique_lock<std::mutex> lk(g_small_mu);
-        g_small_cv.wait(lk, [] { return g_small_running < cap; });
-        g_small_running++;
-    }
+    static const bool caps_set = [] {
+        walkbatch::Caps c;
+        const int fit = (int)(SHP_JOBS_BYTES / sizeof(SmallArgs));       // records per pinned block
+        c.max_jobs = cap < fit ? cap : fit; c.max_blocks = ~0u; c.budget = cap;
+        walk_batcher().set_caps(walkbatch::CLS_LOOP, c);
+        return true;
+    }();
+    (void)caps_set;
     static const int dbg_skip_loop = getenv("SHEPSEG_DBG_SKIP_SMALL") ? atoi(getenv("SHEPSEG_DBG_SKIP_SMALL")) : 0;
     if (dbg_skip_loop) args.min_seg = 1;      // diagnostic only: the loop ends at once (wrong labels)
-    walk_begin(ctx);
-    st = ctx->stream;
-    ps = prof_begin(ctx, PROF_SMALL_LOOP);           // events hug the kernel: no copies, no host waits
-    hipLaunchKernelGGL(k_small_loop, dim3(small_blocks), dim3(256), 0, st, args);
-    hipError_t lerr = hipGetLastError();
-    prof_end(ctx, ps);
-    hipError_t cerr = hipSuccess;
-    hipError_t serr = hipStreamSynchronize(st);
-    walk_end(ctx);
-    {
-        std::lock_guard<std::mutex> lk(g_small_mu);
-        g_small_running--;
+    walkbatch::Job wj;
+    wj.cls = walkbatch::CLS_LOOP; wj.blocks = small_blocks; wj.arg = &args;
+    if (stream_sharing(ctx) && !ctx->borrowed) {
+        // a stream-sharing worker hands the loop to the walker batcher: one launch carries every tile that is ready
+        walk_batcher().run(&wj, [=](int, walkbatch::Job *const *jobs, int nj, double *ms, char *msg, size_t mcap) {
+            const int rc = small_lead(ctx, jobs, nj, small_blocks, ms);
+            if (rc) walk_msg(msg, mcap, ctx->err);
+            return rc;
+        });
+        if (wj.launch_rc) SHP_FAIL(ctx, wj.launch_rc, "%s", wj.msg);
+        ctx->prof_ms[PROF_SMALL_LOOP] += wj.ms;       // an equal share of the batch's time, one launch's worth
+        ctx->prof_cnt[PROF_SMALL_LOOP] += 1;
+    } else {
+        if (!ctx->h_jobs) HIPCHK(ctx, hipHostMalloc(&ctx->h_jobs, SHP_JOBS_BYTES, hipHostMallocDefault));
+        walk_batcher().direct_begin(walkbatch::CLS_LOOP);
+        st = ctx->stream;
+        walkbatch::Job *one = &wj;
+        ps = prof_begin(ctx, PROF_SMALL_LOOP);           // events hug the kernel: no copies, no host waits
+        small_launch(st, &one, 1, small_blocks, ctx->h_jobs);
+        hipError_t lerr = hipGetLastError();
+        prof_end(ctx, ps);
+        hipError_t serr = hipStreamSynchronize(st);
+        walk_batcher().direct_end(walkbatch::CLS_LOOP);
+        HIPCHK(ctx, lerr); HIPCHK(ctx, serr);
     }
-    g_small_cv.notify_one();
-    HIPCHK(ctx, lerr); HIPCHK(ctx, cerr); HIPCHK(ctx, serr);
     fill_acquire(ctx, 2);
     if (pin->fail || !pin->done)
         SHP_FAIL(ctx, SHP_ERR_STATE, "small-segment loop: grid barrier timed out (fail=%u done=%u)",
