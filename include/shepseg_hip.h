@@ -671,6 +671,37 @@ int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entries_ou
                    int64_t *counters_out, double *dev_ms_out);
 int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths);
 
+/* ---- columns reduced over the neighbour table (neighbours.reduceOverNeighbours) ----------------------
+ * The finished table stays in the context; these calls reduce per-segment columns over its rows on the device.
+ * Row r has entries with neighbour id n and border length w; v is the column widened to float64.  A value is ignored
+ * when it is NaN or (has_ignore != 0) equals ignore_value; C is the set of the row's entries whose v[n] is not ignored.
+ * Statistic i (bit i of stat_mask, output outs[i], max_seg_id + 1 rows of 8 bytes in host memory):
+ *   0 count |C| (int64); 1 border: sum of w over C (int64); 2 min and 3 max of v[n] (float64); 4 mean: (sum v[n]) / |C|;
+ *   5 bordermean: (sum w v[n]) / sum w; and with the row's own value v[r]: 6 meanabsdiff: (sum w |v[n] - v[r]|) / sum w;
+ *   7 bordertohigher: sum of w over v[n] > v[r] (int64); 8 nearest: the id with the smallest |v[n] - v[r]|, ties to the
+ *   smallest id (int64).  A float statistic without a value (C empty; 6 also when v[r] is ignored) is missing_value, an
+ *   integer one 0.  All arithmetic is float64, a product rounded before it is added; the order of a row's additions
+ *   depends on the row's length alone (csrc/nbrreduce.h states it), so a row's result does not depend on the other
+ *   rows, on the launch or on how the table got here.
+ *  shp_nbr_upload: a host table (max_seg_id + 2 offsets, n_entries ids and lengths) becomes the context's finished
+ *    table, for tables read from disk or built by hand.  It is checked on the device: offsets[0] == offsets[1] == 0, the
+ *    offsets do not decrease and end at n_entries, a row's ids ascend strictly, lie in 1..max_seg_id and differ from
+ *    the row, every length is >= 1 (symmetry is not required).  The first violation fails with SHP_ERR_ARG and its
+ *    position in the message, and leaves no finished table.  dev_ms_out (may be NULL): device time of the check.
+ *  shp_nbr_table_serial: *serial_out: a number no other table of the process has, new with every shp_nbr_begin and
+ *    shp_nbr_upload of this context; *finished_out: 1 while the context holds a finished table.  A caller that
+ *    remembers (context, serial) of a table can tell whether it is still resident and skip the upload.
+ *  shp_nbr_reduce: one column (host memory, ctype 0 float64, 1 float32, 2 int64; n_rows == max_seg_id + 1) over the
+ *    finished table; SHP_ERR_STATE ("no finished table") without one.  outs: 9 host pointers, those of the mask's
+ *    bits non-NULL.  Device memory beyond the table: the widened column and the selected outputs.  dev_ms_out (may be
+ *    NULL): device time of the kernels (with the listing of the table's long rows in the first call after a new
+ *    table), transfers excluded. */
+int shp_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *neighbours, const int64_t *border_lengths,
+                   int64_t max_seg_id, int64_t n_entries, double *dev_ms_out);
+int shp_nbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out);
+int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
+                   double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

@@ -18,6 +18,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "dsegpoints.h"
 #include "colour.h"
 #include "neighbours.h"
+#include "nbrreduce.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -105,7 +106,7 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo,
                  &ctx->nbr_ctr, &ctx->nbr_rec, &ctx->nbr_key, &ctx->nbr_val, &ctx->nbr_uidx, &ctx->nbr_ua, &ctx->nbr_ub,
                  &ctx->nbr_ucnt, &ctx->nbr_deg, &ctx->nbr_hoff, &ctx->nbr_loff, &ctx->nbr_offs, &ctx->nbr_ids,
-                 &ctx->nbr_lens};
+                 &ctx->nbr_lens, &ctx->nbrr_col, &ctx->nbrr_out, &ctx->nbrr_lrow, &ctx->nbrr_lcoff, &ctx->nbrr_part};
     *out = ctx;
     return SHP_OK;
 }
@@ -1498,6 +1499,43 @@ API int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, i
     if (ctx->nbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish must come first");
     if (!offsets || (ctx->nbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_nbr_download(ctx, offsets, neighbours, border_lengths);
+}
+
+// ---- columns reduced over the neighbour table (nbrreduce.h) -----------------------------------------------
+API int shp_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *neighbours, const int64_t *border_lengths,
+                       int64_t max_seg_id, int64_t n_entries, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    if (n_entries < 0 || n_entries >= (1ll << 40)) SHP_FAIL(ctx, SHP_ERR_ARG, "%lld entries", (long long)n_entries);
+    if (!offsets || (n_entries > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_nbr_upload(ctx, offsets, neighbours, border_lengths, (uint32_t)max_seg_id, (long long)n_entries, dev_ms_out);
+}
+
+API int shp_nbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out)
+{
+    if (!ctx) return SHP_ERR_ARG;
+    ctx->err.clear();
+    if (!serial_out || !finished_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *serial_out = ctx->nbr_serial;
+    *finished_out = ctx->nbr.stage == 2 ? 1 : 0;
+    return 0;
+}
+
+API int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
+                       double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->nbr.stage != 2)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    if (!col || !outs) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    if (n_rows != (int64_t)ctx->nbr.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
+    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    for (int i = 0; i < NBRR_NSTATS; i++)
+        if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
+    return run_nbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
 }
 
 // a column shared by rows over the ranks: shp_colour_stretch in steps (colour.h)

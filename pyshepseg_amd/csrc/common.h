@@ -94,9 +94,15 @@ struct shp_ctx {
         dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix,
         vflag, vlist, vredo,
         nbr_ctr, nbr_rec, nbr_key, nbr_val, nbr_uidx, nbr_ua, nbr_ub, nbr_ucnt, nbr_deg, nbr_hoff, nbr_loff, nbr_offs,
-        nbr_ids, nbr_lens;
+        nbr_ids, nbr_lens,
+        nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part;
     SegPointsState pts;
     NbrState nbr;
+    // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
+    // has, new with every shp_nbr_begin and shp_nbr_upload (kept here: run_nbr_begin resets `nbr`); the list of the
+    // table's long rows (nbrr_lrow, nbrr_lcoff) belongs to the table nbrr_list_serial
+    unsigned long long nbr_serial = 0, nbrr_list_serial = 0;
+    uint32_t nbrr_nlong = 0, nbrr_nchunks = 0;
     DSegPointsState dpts;
     DColourState dcol;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)

@@ -30,6 +30,7 @@
 #include "common.h"
 #include "scan.h"
 #include "sort.h"
+#include <atomic>
 
 #define NBR_PH 32u              // patch rows (8 per wavefront)
 #define NBR_PW 64u              // patch columns: a wavefront per image row
@@ -298,6 +299,14 @@ __global__ __launch_bounds__(256) void k_nbr_fill_low(const uint32_t *__restrict
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
+// a number for the next table of the process: whoever remembers a table's serial (and its context) can tell
+// whether nbr_offs / nbr_ids / nbr_lens still hold that table
+static inline unsigned long long nbr_next_serial()
+{
+    static std::atomic<unsigned long long> serial{0};
+    return ++serial;
+}
+
 static int nbr_ms(shp_ctx *ctx)         // device time between ev[0] and ev[1] (the stream is synchronised)
 {
     float ms = 0.f;
@@ -334,6 +343,7 @@ static int run_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected)
 {
     NbrState &s = ctx->nbr;
     s = NbrState{};
+    ctx->nbr_serial = nbr_next_serial();        // (the table of an earlier serial is gone from here on)
     CHK(buf_ensure(ctx, ctx->nbr_ctr, NBR_C_WORDS * 8));
     HIPCHK(ctx, hipMemsetAsync(ctx->nbr_ctr.p, 0, NBR_C_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));

@@ -47,6 +47,9 @@ class SegmentNeighbours(object):
         self.blocksRerun = blocksRerun
         self.timings = timings if timings is not None else {}
         self.deviceMs = deviceMs
+        self.residentSerial = None
+        self._residentCtx = None
+        self.reduceTimings = {}
 
     def neighboursOf(self, segId):
         """(ids, lengths) of one segment: views of ``neighbours`` and ``borderLengths``"""
@@ -134,9 +137,151 @@ def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixel
         lens = numpy.empty(nent.value, dtype=numpy.int64)
         c.check(L.shp_nbr_download(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens)))
         timings['download'] = time.perf_counter() - t1
+        serial = _tableSerial(c)
     finally:
         src.close()
     timings['total'] = time.perf_counter() - t0
-    return SegmentNeighbours(offsets, nbrs, lens, S.value, bool(fourConnected), pairsSeen=int(counters[0]),
-                             recordsSorted=int(counters[1]), timings=timings, deviceMs=ms.value,
-                             blocksRerun=int(counters[2]))
+    nb = SegmentNeighbours(offsets, nbrs, lens, S.value, bool(fourConnected), pairsSeen=int(counters[0]),
+                           recordsSorted=int(counters[1]), timings=timings, deviceMs=ms.value,
+                           blocksRerun=int(counters[2]))
+    (nb.residentSerial, nb._residentCtx) = (serial, c.handle.value)
+    return nb
+
+
+# ---- columns reduced over the table (csrc/nbrreduce.h) ---------------------------------------------------------
+# statName -> (bit of the C call's mask, dtype of the column)
+REDUCE_STATS = {'count': (0, numpy.int64), 'border': (1, numpy.int64), 'min': (2, numpy.float64),
+                'max': (3, numpy.float64), 'mean': (4, numpy.float64), 'bordermean': (5, numpy.float64),
+                'meanabsdiff': (6, numpy.float64), 'bordertohigher': (7, numpy.int64), 'nearest': (8, numpy.int64)}
+_COLUMN_TYPES = {numpy.dtype(numpy.float64): 0, numpy.dtype(numpy.float32): 1, numpy.dtype(numpy.int64): 2}
+
+
+def _tableSerial(c):
+    """the serial of the context's finished table, None when it has none"""
+    (serial, finished) = (ctypes.c_uint64(0), ctypes.c_int(0))
+    c.check(c._L.shp_nbr_table_serial(c.handle, ctypes.byref(serial), ctypes.byref(finished)))
+    return serial.value if finished.value else None
+
+
+def residentTableSerial():
+    """The serial of the neighbour table the calling thread's context holds on the device, None without one.
+    Every table built or uploaded in the process has a serial of its own."""
+    return _tableSerial(_lib.ctx())
+
+
+def _number(value, name):
+    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, (int, float, numpy.integer, numpy.floating)):
+        raise PyShepSegNeighboursError("{} must be a number (got {!r})".format(name, value))
+    return float(value)
+
+
+def _checkReduceArgs(nb, columnSelections, ignoreValue, missingStatsValue):
+    """([(contiguous column, type code, [(outName, bit, dtype), ...]), ...], ignore or None, missing): everything
+    that can be refused before the GPU is touched"""
+    if not isinstance(nb, SegmentNeighbours):
+        raise PyShepSegNeighboursError("nb must be a SegmentNeighbours")
+    missing = _number(missingStatsValue, 'missingStatsValue')
+    ignore = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
+    nrows = int(nb.maxSegId) + 1
+    if len(nb.offsets) != nrows + 1 or len(nb.neighbours) != len(nb.borderLengths):
+        raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
+    try:
+        selections = [(column, list(stats)) for (column, stats) in columnSelections]
+    except (TypeError, ValueError):
+        raise PyShepSegNeighboursError("columnSelections must be a list of (column, [(outName, statName), ...])")
+    if not selections:
+        raise PyShepSegNeighboursError("columnSelections is empty")
+    seen = set()
+    plan = []
+    for (i, (column, stats)) in enumerate(selections):
+        if not isinstance(column, numpy.ndarray) or column.ndim != 1:
+            raise PyShepSegNeighboursError("column {} must be a 1-D numpy array".format(i))
+        if column.dtype not in _COLUMN_TYPES:
+            raise PyShepSegNeighboursError("column {} has dtype {}: float64, float32 or int64 wanted".format(
+                i, column.dtype))
+        if len(column) != nrows:
+            raise PyShepSegNeighboursError("column {} has {} rows, the table maxSegId + 1 = {}".format(
+                i, len(column), nrows))
+        if not stats:
+            raise PyShepSegNeighboursError("column {} has an empty selection".format(i))
+        picked = []
+        for item in stats:
+            try:
+                (outName, statName) = item
+            except (TypeError, ValueError):
+                raise PyShepSegNeighboursError("a selection must be (outName, statName) (got {!r})".format(item))
+            if statName not in REDUCE_STATS:
+                raise PyShepSegNeighboursError("unknown statName {!r}: one of {} wanted".format(
+                    statName, ', '.join(sorted(REDUCE_STATS))))
+            if outName in seen:
+                raise PyShepSegNeighboursError("outName {!r} appears twice".format(outName))
+            seen.add(outName)
+            picked.append((outName,) + REDUCE_STATS[statName])
+        plan.append((numpy.ascontiguousarray(column), _COLUMN_TYPES[column.dtype], picked))
+    return (plan, ignore, missing)
+
+
+def reduceOverNeighbours(nb, columnSelections, ignoreValue=None, missingStatsValue=-9999):
+    """
+    Per-segment columns reduced over each segment's neighbours, on the GPU: a dictionary outName -> numpy array of
+    ``maxSegId + 1`` rows, which merges into the statistics' column dictionaries as ``nb.columns`` does.
+
+    ``nb`` is a SegmentNeighbours, from findSegmentNeighbours (its table is still on the device unless another one
+    was built since: then, and for a table built by hand, the three arrays are uploaded and checked there).
+    ``columnSelections``: a list of ``(column, [(outName, statName), ...])``; a column is a 1-D float64, float32 or
+    int64 array of ``maxSegId + 1`` values and is widened to float64.
+
+    With v the column, n the neighbour ids of a row r and w their border lengths, over the neighbours whose value
+    is not ignored (NaN, or equal to ``ignoreValue``): ``count`` of them and ``border`` = sum w (int64); ``min``,
+    ``max``, ``mean`` of v[n]; ``bordermean`` = sum(w v[n]) / sum w; and against the row's own value v[r]:
+    ``meanabsdiff`` = sum(w |v[n] - v[r]|) / sum w, ``bordertohigher`` = sum of w where v[n] > v[r] (int64),
+    ``nearest`` = the id with the smallest |v[n] - v[r]|, ties to the smallest id (int64).  A float statistic
+    without a value (no neighbour left; an ignored v[r] for meanabsdiff) is ``missingStatsValue``, an integer one
+    0.  The float sums are float64 in an order that depends on the row's length alone (csrc/nbrreduce.h), so a
+    row's result does not depend on the rest of the table or on where the table came from.
+    """
+    (plan, ignore, missing) = _checkReduceArgs(nb, columnSelections, ignoreValue, missingStatsValue)
+    t0 = time.perf_counter()
+    c = _lib.ctx()
+    L = c._L
+    timings = {'upload': 0.0, 'uploaded': False, 'deviceMs': 0.0}
+    serial = _tableSerial(c)
+    if serial is None or nb.residentSerial != serial or nb._residentCtx != c.handle.value:
+        offsets = numpy.ascontiguousarray(nb.offsets, dtype=numpy.int64)
+        nbrs = numpy.ascontiguousarray(nb.neighbours, dtype=numpy.uint32)
+        lens = numpy.ascontiguousarray(nb.borderLengths, dtype=numpy.int64)
+        ms = ctypes.c_double(0)
+        (nb.residentSerial, nb._residentCtx) = (None, None)
+        rc = L.shp_nbr_upload(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens), int(nb.maxSegId), len(nbrs),
+                              ctypes.byref(ms))
+        if rc != 0:
+            raise PyShepSegNeighboursError((L.shp_last_error(c.handle) or b'').decode())
+        (nb.residentSerial, nb._residentCtx) = (_tableSerial(c), c.handle.value)
+        timings['upload'] = time.perf_counter() - t0
+        timings['uploaded'] = True
+        timings['deviceMs'] += ms.value
+    t1 = time.perf_counter()
+    out = {}
+    nrows = int(nb.maxSegId) + 1
+    for (column, ctype, picked) in plan:
+        # one run per distinct statistic of the column; outNames that ask for the same one share it
+        arrays = {}
+        mask = 0
+        ptrs = (ctypes.c_void_p * len(REDUCE_STATS))()
+        for (_outName, bit, dtype) in picked:
+            if bit not in arrays:
+                arrays[bit] = numpy.empty(nrows, dtype=dtype)
+                ptrs[bit] = arrays[bit].ctypes.data
+                mask |= 1 << bit
+        ms = ctypes.c_double(0)
+        c.check(L.shp_nbr_reduce(c.handle, _lib.ptr(column), ctype, nrows, int(ignore is not None),
+                                 0.0 if ignore is None else ignore, missing, mask, ptrs, ctypes.byref(ms)))
+        timings['deviceMs'] += ms.value
+        first = set()
+        for (outName, bit, _dtype) in picked:
+            out[outName] = arrays[bit] if bit not in first else arrays[bit].copy()
+            first.add(bit)
+    timings['reduce'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    nb.reduceTimings = timings
+    return out
