@@ -356,53 +356,34 @@ int shp_gather_flagged_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void
                                  int nbands, int64_t npix, uint32_t max_seg_id, const uint8_t *flags, int64_t cap,
                                  uint32_t *seg_out, int64_t *val_out, int64_t *count_out);
 
-/* The same split with everything left in device memory (the data path of calcPerSegmentStatsDistributed
- * under RCCL; the reference has no counterpart: its per-segment dictionaries live in one process,
- * tilingstats.py:466-553).
- *  shp_dstats_local_dev: the statistics of this rank's nrows x ncols rows, then every id judged against the
+/* The same split with everything left in device memory (the data path of calcPerSegmentStatsDistributed and
+ * calcPerSegmentStatsDistributedBands under RCCL; the reference has no counterpart: its per-segment dictionaries
+ * live in one process, tilingstats.py:466-553).  One pair of calls serves any number of entries, and does what
+ * depends on the labels alone once; a one-band caller passes nbands = nplanes = 1.  A "band" is an entry of the
+ * caller's list (a plane, a null value, nstats_per_band[b] rows of stats_sel, built as for
+ * shp_segstats2d_bands_dev), a "plane" a distinct image band; plane_of_band[b] < nplanes names the plane entry b
+ * reads.
+ *  shp_dstats_local_bands_dev: the statistics of all entries over this rank's nrows x ncols rows in one pass over
+ *    the labels (as shp_segstats2d_bands_dev; one entry as shp_segstats2d_dev), then every id judged against the
  *    GLOBAL histogram d_hist (max_seg_id + 1 uint32 in device memory: the reference's segSize, :165): rows of
  *    segments complete on this rank stay, rows of straddlers (fewer pixels here than the histogram says) are
- *    cleared and their pixels packed as (id, value) pairs, rows of ids nobody holds keep the "missing" values
- *    on the one rank that passes keep_unheld != 0 -- so the ranks' columns ADD UP to the one-GPU columns.
- *    d_cols (caller's device memory): (#int stats) int64 columns then (#float stats) float32 columns of
- *    max_seg_id + 1 rows.  *d_pair_seg_out / *d_pair_val_out: the pairs (uint32 ids, int64 values) in the
- *    context's workspace, valid until its next call; *n_pairs_out of them, *n_straddlers_out segments.
- *  shp_dstats_merge_dev: after the all-gather -- `world` slots of `slot` pairs, counts[r] valid in slot r --
- *    the pairs with id_lo <= id < id_hi (*n_merged_out of them, of *n_ids_out segments) are reduced with the
- *    same code and their rows written into d_cols.
- *  Summing d_cols over the ranks (one integer all-reduce over the whole block read as int64 words: every
- *  32-bit half has at most one non-zero contributor) gives the columns shp_segstats2d_dev returns. */
-int shp_dstats_local_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, int64_t nrows,
-                         int64_t ncols, uint32_t max_seg_id, int has_null, int64_t null_val,
-                         const uint32_t *stats_sel, int nstats, int64_t missing, const uint32_t *d_hist,
-                         int keep_unheld, void *d_cols, void **d_pair_seg_out, void **d_pair_val_out,
-                         int64_t *n_pairs_out, int64_t *n_straddlers_out);
-int shp_dstats_merge_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const int64_t *d_pair_val, int64_t slot, int world,
-                         const uint32_t *counts, int dtype, uint32_t max_seg_id, int has_null, int64_t null_val,
-                         const uint32_t *stats_sel, int nstats, int64_t missing, uint32_t id_lo, uint32_t id_hi,
-                         void *d_cols, int64_t *n_merged_out, int64_t *n_ids_out);
-
-/* The device-resident split for several bands in one call (the data path of
- * calcPerSegmentStatsDistributedBands): they replace one shp_dstats_local_dev / shp_dstats_merge_dev pair PER
- * ENTRY, and do what depends on the labels alone once.  A "band" is an entry of the caller's list (a plane, a null
- * value, nstats_per_band[b] rows of stats_sel, built as for shp_segstats2d_bands_dev), a "plane" a distinct image
- * band; plane_of_band[b] < nplanes names the plane entry b reads.
- *  shp_dstats_local_bands_dev replaces nbands calls of shp_dstats_local_dev: the statistics of all entries in one
- *    pass over the labels (as shp_segstats2d_bands_dev), ONE local histogram, ONE classification that keeps or
- *    clears the rows of all entries' columns in d_cols, ONE gather of the straddlers' pixels: *d_pair_seg_out =
- *    *n_pairs_out uint32 ids, *d_pair_val_out = nplanes rows of raw pixel values IN THE PLANES' PIXEL TYPE,
- *    *pair_row_bytes_out bytes apart (a multiple of 16), every row in the order of the ids; both in the context's
- *    workspace, valid until its next call.  Null values are not applied to the pairs: they belong to the entries
- *    and are applied at the merge.  Unlike shp_dstats_local_dev it refuses a histogram that cannot belong to these
- *    labels: ids with MORE pixels in these rows than d_hist gives them fail with SHP_ERR_ARG, the message naming
- *    their number (the one-band call clears their rows silently).  nrows * ncols may be 0 (d_seg is not read).
- *  shp_dstats_merge_bands_dev replaces nbands calls of shp_dstats_merge_dev: d_pair_seg = `world` slots of `slot`
- *    ids, d_pair_val = `world` blocks of nplanes rows of values, slot_row_bytes apart on every rank; the pairs with
- *    id_lo <= id < id_hi are picked once, all planes' values with them, reduced per entry and their rows written
- *    into d_cols.
- *  4 + nplanes * itemsize bytes per straddler pixel travel, against 12 * nbands with the one-band pair.  Summing
- *  d_cols over the ranks as above gives the columns of shp_segstats2d_bands_dev, each with the bits
- *  shp_dstats_local_dev / _merge_dev give for its entry alone. */
+ *    cleared and their pixels packed, rows of ids nobody holds keep the "missing" values on the one rank that
+ *    passes keep_unheld != 0 -- so the ranks' columns ADD UP to the one-GPU columns.  d_cols (caller's device
+ *    memory): (#int stats) int64 columns then (#float stats) float32 columns of max_seg_id + 1 rows, all entries'
+ *    side by side.  The straddlers' pixels: *d_pair_seg_out = *n_pairs_out uint32 ids (of *n_straddlers_out
+ *    segments), *d_pair_val_out = nplanes rows of raw pixel values IN THE PLANES' PIXEL TYPE, *pair_row_bytes_out
+ *    bytes apart (a multiple of 16), every row in the order of the ids; both in the context's workspace, valid
+ *    until its next call.  Null values are not applied to the pairs: they belong to the entries and are applied at
+ *    the merge.  A histogram that cannot belong to these labels is refused: ids with MORE pixels in these rows than
+ *    d_hist gives them fail with SHP_ERR_ARG, the message naming their number.  nrows * ncols may be 0 (d_seg is
+ *    not read).
+ *  shp_dstats_merge_bands_dev: after the all-gathers -- d_pair_seg = `world` slots of `slot` ids, counts[r] valid in
+ *    slot r, d_pair_val = `world` blocks of nplanes rows of values, slot_row_bytes apart on every rank -- the pairs
+ *    with id_lo <= id < id_hi (*n_merged_out of them, of *n_ids_out segments) are picked once, all planes' values
+ *    with them, reduced per entry with the same code and their rows written into d_cols.
+ *  4 + nplanes * itemsize bytes per straddler pixel travel.  Summing d_cols over the ranks (one integer all-reduce
+ *  over the whole block read as int64 words: every 32-bit half has at most one non-zero contributor) gives the
+ *  columns shp_segstats2d_bands_dev returns, each with the bits shp_segstats2d_dev gives for its entry alone. */
 int shp_dstats_local_bands_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *const *d_planes, int nplanes,
                                const int *plane_of_band, int dtype, int nbands, int64_t nrows, int64_t ncols,
                                uint32_t max_seg_id, const int *has_null, const int64_t *null_val,
@@ -536,13 +517,13 @@ int shp_dsegpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *o
                         int64_t *npts_out);
 
 /* The spatial statistics split by rows over the ranks (the data path of
- * distributed.calcPerSegmentSpatialStatsDistributed), modelled on shp_dstats_local_dev / _merge_dev.
+ * distributed.calcPerSegmentSpatialStatsDistributed), modelled on shp_dstats_local_bands_dev / _merge_bands_dev.
  *  shp_dspatial_local_dev: this rank's rows [row0, row0 + nrows) of an img_rows-row raster in place (d_seg,
  *    d_band: nrows x ncols), with rows_up halo rows just above them (d_seg_up / d_band_up) and rows_dn just
  *    below (d_seg_dn / d_band_dn) -- other ranks' rows; the halo must reach the needed distance or the
  *    image's border (edges: 1 row each way, variogram: maxDist rows below, mean coordinates: none).  The own
  *    pixels are accumulated, then every id is judged against the GLOBAL label histogram d_hist as in
- *    shp_dstats_local_dev: rows of segments complete here are finished, ids nobody holds get their "missing"
+ *    shp_dstats_local_bands_dev: rows of segments complete here are finished, ids nobody holds get their "missing"
  *    row where keep_unheld != 0, all other rows of d_cols are zero.  The straddlers' partial sums are packed
  *    as records of *rec_words_out uint64 words -- (id, cnt, sumx, sumy), (id, cnt, edges) or (id, cnt,
  *    vcnt[maxDist], vsum[maxDist]) -- *n_rec_out of them at *d_rec_out in the context's workspace, valid until

@@ -177,10 +177,6 @@ _SIGS = {
                                             _vp, _vp, _vp, _vp, _c.c_int64, _vp, _vp]),
     'shp_gather_flagged_bands_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int, _c.c_int64, _c.c_uint32, _vp,
                                                 _c.c_int64, _vp, _vp, _vp]),
-    'shp_dstats_local_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int,
-                                        _c.c_int64, _vp, _c.c_int, _c.c_int64, _vp, _c.c_int, _vp,
-                                        _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_c.c_int64),
-                                        _c.POINTER(_c.c_int64)]),
     'shp_dspatial_local_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _vp, _c.c_int64,
                                           _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_uint32, _c.c_int64,
                                           _c.c_int, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int, _vp,
@@ -188,9 +184,6 @@ _SIGS = {
     'shp_dspatial_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_uint32, _c.c_int, _vp,
                                           _c.c_int64, _c.c_int, _c.c_int, _c.c_uint32, _c.c_uint32, _vp,
                                           _c.POINTER(_c.c_int64)]),
-    'shp_dstats_merge_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int, _c.c_uint32, _c.c_int,
-                                        _c.c_int64, _vp, _c.c_int, _c.c_int64, _c.c_uint32, _c.c_uint32, _vp,
-                                        _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     'shp_dstats_local_bands_dev': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _vp, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64,
                                               _c.c_uint32, _vp, _vp, _vp, _vp, _c.c_int64, _vp, _c.c_int, _vp,
                                               _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_c.c_int64),

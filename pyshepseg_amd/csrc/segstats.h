@@ -1128,13 +1128,15 @@ static int run_gather_flagged_bands(shp_ctx *ctx, const uint32_t *d_seg, const v
     return gather_flagged_end(ctx, cap, nbands, seg_out, val_out, count_out);
 }
 
-// ---- multi-GPU split, device-resident (pyshepseg_amd/distributed.py) ---------------------------
+// ---- multi-GPU split, device-resident (distributed.calcPerSegmentStatsDistributedBands) --------
 // Rank-local part.  The statistics of this rank's rows are computed as on one GPU; then every id is
 // classified against the global histogram (the reference's segSize, tilingstats.py:165): a segment whose
 // local pixel count equals it is complete here and its row is final (checkSegComplete, :518-553); a segment
-// with fewer is a straddler -- its row is cleared and its pixels are packed as (id, value) pairs for the
-// exchange; ids nobody holds (global count 0, row 0 among them) keep their "missing" row on the rank that is
-// told to (keep_unheld), so that the columns of all ranks ADD UP to the single-GPU columns.
+// with fewer is a straddler -- its row is cleared and its pixels are packed, the id and every plane's value, for
+// the exchange; ids nobody holds (global count 0, row 0 among them) keep their "missing" row on the rank that is
+// told to (keep_unheld), so that the columns of all ranks ADD UP to the single-GPU columns.  An id with MORE
+// pixels here than the histogram gives it in the whole raster would count as complete nowhere and straddling
+// nowhere, and its row would be cleared silently: the sign of a histogram that belongs to other labels.
 // cols: nint int64 columns then nflt float columns of S + 1 rows, in device memory of the caller.
 __global__ __launch_bounds__(256) void k_dstats_classify(const uint32_t *__restrict__ lh,
                                                          const uint32_t *__restrict__ gh, uint32_t S,
@@ -1148,12 +1150,13 @@ __global__ __launch_bounds__(256) void k_dstats_classify(const uint32_t *__restr
 {
     const size_t ns = (size_t)S + 1;
     const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
-    bool strad = false;
+    bool strad = false, stale = false;
     uint32_t l = 0;
     if (id < ns) {
         l = id == 0 ? 0u : lh[id];
         const uint32_t g = id == 0 ? 0u : gh[id];
         strad = l > 0u && l < g;
+        stale = l > g;
         const bool keep = (l > 0u && l == g) || (keep_unheld && g == 0u);
         flags[id] = strad ? 1 : 0;
         for (int c = 0; c < nint; c++) dst_int[(size_t)c * ns + id] = keep ? src_int[(size_t)c * ns + id] : 0ll;
@@ -1166,92 +1169,13 @@ __global__ __launch_bounds__(256) void k_dstats_classify(const uint32_t *__restr
         for (int o = 32; o > 0; o >>= 1) px += __shfl_xor(px, o);
         if (lane_id() == 0) { atomicAdd(&counters[0], px); atomicAdd(&counters[1], (unsigned long long)__popcll(m)); }
     }
+    // counters[2] += ids with more pixels here than the histogram gives them
+    const unsigned long long ms = __ballot(stale);
+    if (ms != 0ull && lane_id() == 0) atomicAdd(&counters[2], (unsigned long long)__popcll(ms));
 }
 
-static int run_dstats_local(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype, uint32_t nrows,
-                            uint32_t ncols, uint32_t S, int has_null, int64_t null_val, const uint32_t *sel_host,
-                            int nstats, int64_t missing, const uint32_t *d_hist, int keep_unheld, void *d_cols,
-                            uint32_t **d_pair_seg, long long **d_pair_val, int64_t *n_pairs, int64_t *n_strad)
-{
-    hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
-    const uint32_t n = nrows * ncols;
-    int nint = 0, nflt = 0;
-    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt));
-    long long *di = nullptr;
-    float *df = nullptr;
-    CHK(run_segstats(ctx, d_seg, d_band, dtype, n, S, has_null, null_val, sel_host, nstats, missing, nullptr, nullptr,
-                     nrows, ncols, &di, &df));
-    // the local label histogram (all pixels of a label, valid or not) | flags | two counters
-    CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
-    CHK(buf_ensure(ctx, ctx->chtail, ns + 64));
-    uint32_t *lh = bp<uint32_t>(ctx->chnext);
-    unsigned long long *ctr = (unsigned long long *)bp<uint8_t>(ctx->chtail);
-    uint8_t *flags = bp<uint8_t>(ctx->chtail) + 64;
-    HIPCHK(ctx, hipMemsetAsync(lh, 0, ns * 4, st));
-    HIPCHK(ctx, hipMemsetAsync(ctr, 0, 16, st));
-    if (n) { hipLaunchKernelGGL(k_label_hist, dim3(grid_for(n, 256)), dim3(256), 0, st, d_seg, n, S, lh); KCHK(ctx); }
-    hipLaunchKernelGGL(k_dstats_classify, dim3(grid_for(ns, 256)), dim3(256), 0, st, lh, d_hist, S, keep_unheld, nint, nflt,
-                       di, df, (long long *)d_cols, (float *)((long long *)d_cols + (size_t)nint * ns), flags, ctr); KCHK(ctx);
-    unsigned long long h[2] = {0, 0};
-    HIPCHK(ctx, hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    if (h[0] >= 0xffffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "too many straddling pixels (%llu)", h[0]);
-    const uint32_t cap = (uint32_t)h[0];
-    // the straddlers' pixels, packed (the sorts of run_segstats are done with aux / aux2)
-    CHK(buf_ensure(ctx, ctx->aux, (size_t)cap * 4 + 64));
-    CHK(buf_ensure(ctx, ctx->aux2, (size_t)cap * 8 + 64));
-    uint32_t *d_count = (uint32_t *)(ctr + 4);
-    HIPCHK(ctx, hipMemsetAsync(d_count, 0, 4, st));
-    if (n && cap) {
-        hipLaunchKernelGGL(k_gather_flagged, dim3(grid_for(n, 4096)), dim3(256), 0, st, d_seg, d_band, dtype, n, S, flags,
-                           bp<uint32_t>(ctx->aux), (long long *)ctx->aux2.p, cap, d_count); KCHK(ctx);
-        uint32_t got = 0;
-        CHK(read_u32(ctx, d_count, &got));
-        if (got != cap) SHP_FAIL(ctx, SHP_ERR_STATE, "straddler gather found %u pixels, the histogram says %u", got, cap);
-    }
-    *d_pair_seg = bp<uint32_t>(ctx->aux);
-    *d_pair_val = (long long *)ctx->aux2.p;
-    *n_pairs = (int64_t)cap;
-    *n_strad = (int64_t)h[1];
-    return 0;
-}
-
-// Merge part.  pairs: `world` slots of `slot` (id, value) pairs as the all-gather left them, counts[r] valid
-// in slot r.  The pairs whose id lies in [id_lo, id_hi) -- this rank's share of the id space -- are compacted
-// into a 1 x m raster, reduced by the same statistics code, and the rows of the ids that occur are written
-// into cols (they were cleared by every rank's classify step).
-__global__ __launch_bounds__(256) void k_dstats_pick(const uint32_t *__restrict__ pseg, const long long *__restrict__ pval,
-                                                     uint32_t slot, uint32_t world, const uint32_t *__restrict__ counts,
-                                                     uint32_t id_lo, uint32_t id_hi, int dtype,
-                                                     uint32_t *__restrict__ out_seg, void *__restrict__ out_band,
-                                                     uint32_t *count)
-{
-    const size_t q = (size_t)blockIdx.x * 256u + threadIdx.x;
-    bool take = false;
-    uint32_t sg = 0;
-    long long v = 0;
-    if (q < (size_t)slot * world) {
-        const uint32_t r = (uint32_t)(q / slot), e = (uint32_t)(q - (size_t)r * slot);
-        if (e < counts[r]) { sg = pseg[q]; v = pval[q]; take = sg >= id_lo && sg < id_hi; }
-    }
-    const unsigned long long m = __ballot(take);
-    if (m == 0ull) return;
-    uint32_t base = 0;
-    if (lane_id() == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    if (take) {
-        const uint32_t o = base + (uint32_t)__popcll(m & lanemask_lt());
-        out_seg[o] = sg;
-        switch (dtype) {
-        case SHP_U8: ((uint8_t *)out_band)[o] = (uint8_t)v; break;
-        case SHP_I16: ((int16_t *)out_band)[o] = (int16_t)v; break;
-        case SHP_U16: ((uint16_t *)out_band)[o] = (uint16_t)v; break;
-        case SHP_I32: ((int32_t *)out_band)[o] = (int32_t)v; break;
-        default: ((uint32_t *)out_band)[o] = (uint32_t)v; break;
-        }
-    }
-}
+// The rows of the ids that occur among the pairs a rank has reduced (present[id] != 0) go into cols: every rank's
+// classify step cleared them.  *n_ids += how many.
 __global__ __launch_bounds__(256) void k_dstats_take(const uint32_t *__restrict__ present, uint32_t S, int nint, int nflt,
                                                      const long long *__restrict__ src_int, const float *__restrict__ src_flt,
                                                      long long *__restrict__ dst_int, float *__restrict__ dst_flt,
@@ -1267,55 +1191,11 @@ __global__ __launch_bounds__(256) void k_dstats_take(const uint32_t *__restrict_
     for (int c = 0; c < nflt; c++) dst_flt[(size_t)c * ns + id] = src_flt[(size_t)c * ns + id];
 }
 
-static int run_dstats_merge(shp_ctx *ctx, const uint32_t *d_pseg, const long long *d_pval, uint32_t slot, uint32_t world,
-                            const uint32_t *counts_host, int dtype, uint32_t S, int has_null, int64_t null_val,
-                            const uint32_t *sel_host, int nstats, int64_t missing, uint32_t id_lo, uint32_t id_hi,
-                            void *d_cols, int64_t *n_merged, int64_t *n_ids)
-{
-    hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
-    int nint = 0, nflt = 0;
-    CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt));
-    *n_merged = 0;
-    *n_ids = 0;
-    const size_t total = (size_t)slot * world;
-    if (total == 0 || id_lo >= id_hi) return 0;
-    if (total >= 0xffffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "too many gathered pairs");
-    CHK(buf_ensure(ctx, ctx->lab, total * 4 + 64));
-    CHK(buf_ensure(ctx, ctx->img, total * dtype_size(dtype) + 64));
-    CHK(buf_ensure(ctx, ctx->chtail, (size_t)world * 4 + 128));
-    uint32_t *d_counts = bp<uint32_t>(ctx->chtail) + 16, *d_n = bp<uint32_t>(ctx->chtail);
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    HIPCHK(ctx, hipMemcpyAsync(d_counts, counts_host, (size_t)world * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(d_n, 0, 4, st));
-    hipLaunchKernelGGL(k_dstats_pick, dim3(grid_for(total, 256)), dim3(256), 0, st, d_pseg, d_pval, slot, world, d_counts,
-                       id_lo, id_hi, dtype, bp<uint32_t>(ctx->lab), ctx->img.p, d_n); KCHK(ctx);
-    uint32_t m = 0;
-    CHK(read_u32(ctx, d_n, &m));
-    *n_merged = (int64_t)m;
-    if (m == 0) return 0;
-    long long *di = nullptr;
-    float *df = nullptr;
-    CHK(run_segstats(ctx, bp<uint32_t>(ctx->lab), ctx->img.p, dtype, m, S, has_null, null_val, sel_host, nstats, missing,
-                     nullptr, nullptr, 0, 0, &di, &df));
-    CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
-    uint32_t *present = bp<uint32_t>(ctx->chnext);
-    HIPCHK(ctx, hipMemsetAsync(present, 0, ns * 4, st));
-    hipLaunchKernelGGL(k_label_hist, dim3(grid_for(m, 256)), dim3(256), 0, st, bp<uint32_t>(ctx->lab), m, S, present); KCHK(ctx);
-    HIPCHK(ctx, hipMemsetAsync(d_n, 0, 4, st));
-    hipLaunchKernelGGL(k_dstats_take, dim3(grid_for(ns, 256)), dim3(256), 0, st, present, S, nint, nflt, di, df,
-                       (long long *)d_cols, (float *)((long long *)d_cols + (size_t)nint * ns), d_n); KCHK(ctx);
-    uint32_t ids = 0;
-    CHK(read_u32(ctx, d_n, &ids));
-    *n_ids = (int64_t)ids;
-    return 0;
-}
-
-// ---- the same split for several bands in one call (distributed.calcPerSegmentStatsDistributedBands) ---------------
+// ---- the split's two drivers, over entries (one entry is no special route: nbands = nplanes = 1) ------------------
 // "band" = an entry of the caller's bandSelections (a plane, a null value, some statistics), "plane" = a distinct
 // image band; plane_of_band[e] says which plane entry e reads.  Everything that depends on the labels alone -- the
 // local label histogram, the classification against the global one, the straddlers' ids on the wire, the pick of
-// this rank's id share, the `present` histogram -- is done once instead of once per entry, and the straddlers'
+// this rank's id share, the `present` histogram -- is done once whatever the number of entries, and the straddlers'
 // values travel in the planes' own pixel type: 4 + nplanes * itemsize bytes per straddler pixel.
 // Values travel RAW, nulls included: a null value belongs to an entry, and two entries may read one plane with
 // different ones, so it is applied where the statistics are computed (k_stats_keys at the merge).
@@ -1323,17 +1203,6 @@ static int run_dstats_merge(shp_ctx *ctx, const uint32_t *d_pseg, const long lon
 // rows of values lie this many bytes apart (16-byte aligned, so that every plane's row can be copied and read
 // with wide accesses whatever the count)
 static inline size_t dstats_row_bytes(size_t count, int dtype) { return (count * dtype_size(dtype) + 15) & ~(size_t)15; }
-
-// ids whose local count EXCEEDS the global histogram: k_dstats_classify would take them for complete nowhere and
-// straddling nowhere and clear their rows silently -- the sign of a histogram that belongs to other labels
-__global__ __launch_bounds__(256) void k_dstats_stale(const uint32_t *__restrict__ lh, const uint32_t *__restrict__ gh,
-                                                      uint32_t S, unsigned long long *counter)
-{
-    const size_t id = (size_t)blockIdx.x * 256u + threadIdx.x;
-    const bool over = id != 0 && id <= (size_t)S && lh[id] > gh[id];
-    const unsigned long long m = __ballot(over);
-    if (m != 0ull && lane_id() == 0) atomicAdd(counter, (unsigned long long)__popcll(m));
-}
 
 // k_gather_flagged_bands with the values left in the planes' pixel type T (only its width matters: nothing is
 // computed here): the id once, and row b of out_val = plane b's raw values, rows row_bytes apart.
@@ -1359,11 +1228,31 @@ __global__ __launch_bounds__(256) void k_gather_flagged_planes(const uint32_t *_
     }
 }
 
+// The statistics of the entries over nrows x ncols labels, the columns left in ctx->ssum (*di, *df).  The only place
+// in the split that knows "one or several": one entry goes through run_segstats, whose k_stats_patch is faster for
+// one band than k_stats_patch_bands (both give a row the same bits), several through run_segstats_bands.
+// allow_patches false (the merge's 1 x m list of pairs): everything goes through the sorts, which run_segstats does
+// when it is not told the shape.
+static int dstats_segstats(shp_ctx *ctx, const uint32_t *d_seg, const void *const *bands_host, int dtype, int nbands,
+                           uint32_t nrows, uint32_t ncols, uint32_t S, const int *has_null, const int64_t *null_val,
+                           const uint32_t *sel_host, const int *nstats_per_band, int64_t missing, bool allow_patches,
+                           long long **di, float **df)
+{
+    if (nbands != 1)
+        return run_segstats_bands(ctx, d_seg, bands_host, dtype, nbands, nrows, ncols, S, has_null, null_val, sel_host,
+                                  nstats_per_band, missing, nullptr, nullptr, di, df, allow_patches);
+    if (nstats_per_band[0] < 1 || !bands_host[0]) SHP_FAIL(ctx, SHP_ERR_ARG, "band entry 0: no statistics or no band");
+    return run_segstats(ctx, d_seg, bands_host[0], dtype, nrows * ncols, S, has_null[0] ? 1 : 0,
+                        has_null[0] ? null_val[0] : 0, sel_host, nstats_per_band[0], missing, nullptr, nullptr,
+                        allow_patches ? nrows : 0u, allow_patches ? ncols : 0u, di, df);
+}
+
 // Local part.  planes_host: nplanes device pointers (this rank's rows of the distinct planes).  The pairs end up in
 // ctx->aux (cap ids) and ctx->aux2 (nplanes rows of cap values of the pixel type, dstats_row_bytes(cap) apart): both
-// hold run_segstats_bands' sort keys until the statistics are done, so they are sized for the pairs only AFTER the
-// classify kernel has read the columns out of ctx->ssum into d_cols (nothing between the statistics and that kernel
-// touches ssum, aux or aux2), and the pairs stay valid until the context's next call.
+// hold the sort keys of the statistics (run_segstats and run_segstats_bands alike: stats_workspace) until those are
+// done, so they are sized for the pairs only AFTER the classify kernel has read the columns out of ctx->ssum into
+// d_cols (nothing between the statistics and that kernel touches ssum, aux or aux2), and the pairs stay valid until
+// the context's next call.
 static int run_dstats_local_bands(shp_ctx *ctx, const uint32_t *d_seg, const void *const *planes_host, int nplanes,
                                   const int *plane_of_band, int dtype, int nbands, uint32_t nrows, uint32_t ncols,
                                   uint32_t S, const int *has_null, const int64_t *null_val, const uint32_t *sel_host,
@@ -1385,8 +1274,8 @@ static int run_dstats_local_bands(shp_ctx *ctx, const uint32_t *d_seg, const voi
     if (tab_bytes + 1024 > SHP_PINNED_BYTES) SHP_FAIL(ctx, SHP_ERR_ARG, "too many bands");
     long long *di = nullptr;
     float *df = nullptr;
-    CHK(run_segstats_bands(ctx, d_seg, bands.data(), dtype, nbands, nrows, ncols, S, has_null, null_val, sel_host,
-                           nstats_per_band, missing, nullptr, nullptr, &di, &df));
+    CHK(dstats_segstats(ctx, d_seg, bands.data(), dtype, nbands, nrows, ncols, S, has_null, null_val, sel_host,
+                        nstats_per_band, missing, true, &di, &df));
     int nint = 0, nflt = 0;
     CHK(stats_sel_check(ctx, sel_host, nstats, &nint, &nflt, true));
     // the local label histogram (all pixels of a label, valid or not) | counters, the planes' table, flags
@@ -1399,7 +1288,6 @@ static int run_dstats_local_bands(shp_ctx *ctx, const uint32_t *d_seg, const voi
     HIPCHK(ctx, hipMemsetAsync(lh, 0, ns * 4, st));
     HIPCHK(ctx, hipMemsetAsync(ctr, 0, 64, st));
     if (n) { hipLaunchKernelGGL(k_label_hist, dim3(grid_for(n, 256)), dim3(256), 0, st, d_seg, n, S, lh); KCHK(ctx); }
-    hipLaunchKernelGGL(k_dstats_stale, dim3(grid_for(ns, 256)), dim3(256), 0, st, lh, d_hist, S, ctr + 2); KCHK(ctx);
     hipLaunchKernelGGL(k_dstats_classify, dim3(grid_for(ns, 256)), dim3(256), 0, st, lh, d_hist, S, keep_unheld, nint, nflt,
                        di, df, (long long *)d_cols, (float *)((long long *)d_cols + (size_t)nint * ns), flags, ctr); KCHK(ctx);
     unsigned long long h[3] = {0, 0, 0};
@@ -1532,8 +1420,8 @@ static int run_dstats_merge_bands(shp_ctx *ctx, const uint32_t *d_pseg, const vo
     for (int b = 0; b < nbands; b++) bands[(size_t)b] = bp<uint8_t>(ctx->img) + (size_t)plane_of_band[b] * out_row_bytes;
     long long *di = nullptr;
     float *df = nullptr;
-    CHK(run_segstats_bands(ctx, bp<uint32_t>(ctx->lab), bands.data(), dtype, nbands, 1u, m, S, has_null, null_val, sel_host,
-                           nstats_per_band, missing, nullptr, nullptr, &di, &df, false));
+    CHK(dstats_segstats(ctx, bp<uint32_t>(ctx->lab), bands.data(), dtype, nbands, 1u, m, S, has_null, null_val, sel_host,
+                        nstats_per_band, missing, false, &di, &df));
     CHK(buf_ensure(ctx, ctx->chnext, ns * 4 + 64));
     uint32_t *present = bp<uint32_t>(ctx->chnext);
     HIPCHK(ctx, hipMemsetAsync(present, 0, ns * 4, st));

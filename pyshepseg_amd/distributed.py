@@ -65,7 +65,8 @@ recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six nu
       {(kind, col, row): strip}): maxSegId, then the strips in plan order.
   histogram(maxSegId) -> pixel counts per id of the output rows (after finish too, if kept);
       finish(): the run's buffers released, bar a kept output.
-  localStats, gatherFlagged, statsOfPairs (optional statsOnDevice): calcPerSegmentStatsDistributed.
+  localStatsBands, gatherFlaggedBands, statsOfPairsBands (optional statsBandsOnDevice), or localStats,
+      gatherFlagged, statsOfPairs: calcPerSegmentStatsDistributed[Bands] (the protocol: _distributedStats).
   spatialOnDevice (optional): calcPerSegmentSpatialStatsDistributed.
   subsetOnDevice (optional): subsetImageDistributed.
   outputRows(y0, y1) -> image rows [y0, y1) of the kept output (inside outRows), uint32, on the host;
@@ -545,57 +546,22 @@ def calcPerSegmentStatsDistributed(engine, comm, hist, imgbandnum, statsSelectio
     8e).  ``hist`` is the global histogram of the labels (DistResult.hist), which plays the part
     of the reference's segSize: a segment whose local pixel count equals hist[id] is complete on
     this rank and its statistics are final (checkSegComplete, tilingstats.py:518-553).  The
-    pixels of the segments that straddle a rank boundary are packed as (id, value) pairs and
+    pixels of the segments that straddle a rank boundary are packed, id and value, and
     all-gathered; every rank then reduces the straddlers whose id lies in ITS share of the id space
     (idRange) with the same kernel.  Finished rows are disjoint between ranks, so one integer
     all-reduce assembles the columns.
-      With a device engine under RCCL nothing of this crosses the host (shp_dstats_local_dev ->
-    ncclAllGather of the pairs -> shp_dstats_merge_dev -> ncclAllReduce of the column block); other
-    transports carry the same arrays as raw bytes.  ``info`` (a dict, optional) receives 'straddlers'
-    (segments) and 'straddler_pixels' of the whole job and 'path'.
+      This is calcPerSegmentStatsDistributedBands with the one entry (imgbandnum, statsSelection): the same
+    driver (_distributedStats), the same transports, the same ``info`` keys; the band number is not checked
+    against the image here.  A ``hist`` that gives an id FEWER pixels than a rank holds of it raises on every
+    rank: _lib.ShepsegHipError on the device path, tilingstats.PyShepSegStatsError on the host path.
     Returns (intcols int64 (nInt, maxSegId+1), floatcols float32 (nFloat, maxSegId+1),
     statsSelection_fast) on every rank -- bit-identical to the single-GPU result."""
     from . import tilingstats
-    (fast, nInt, nFloat) = tilingstats.makeFastStatsSelection(
-        list(range(len(statsSelection))), statsSelection)
-    if getattr(comm, 'onDevice', False) and hasattr(engine, 'statsOnDevice'):
-        (ic, fc, nStrad, nPix) = engine.statsOnDevice(comm, hist, imgbandnum, fast, nInt, nFloat,
-                                                      missingStatsValue, imgNullVal)
-        if info is not None:
-            info.update(straddlers=nStrad, straddler_pixels=nPix, path='device')
-        return ic, fc, fast
-    hist = numpy.asarray(hist).astype(numpy.int64)
-    S = len(hist) - 1
-    lh = numpy.asarray(engine.histogram(S)).astype(numpy.int64)
-    lh[0] = 0
-    complete = (lh == hist) & (lh > 0)
-    strad = (lh > 0) & (lh < hist)
-    (ic, fc) = engine.localStats(imgbandnum, S, fast, nInt, nFloat, missingStatsValue, imgNullVal)
-    keep = complete.copy()
-    if comm.rank == 0:
-        keep |= (hist == 0)                 # ids nobody holds (and row 0): "missing" rows, once
-    ic[:, ~keep] = 0
-    fc[:, ~keep] = 0
-    pairs = engine.gatherFlagged(imgbandnum, S, strad.astype(numpy.uint8), int(lh[strad].sum()))
-    allPairs = comm.allgather_arrays([pairs[0], pairs[1]])
-    (lo, hi) = idRange(comm.rank, comm.world, S)
-    segs = numpy.concatenate([p[0] for p in allPairs])
-    vals = numpy.concatenate([p[1] for p in allPairs])
-    mine = (segs >= lo) & (segs < hi)
-    if mine.any():
-        (ids, compact) = numpy.unique(segs[mine], return_inverse=True)
-        (ic2, fc2) = engine.statsOfPairs((compact + 1).astype(numpy.uint32), vals[mine], len(ids), fast,
-                                         nInt, nFloat, missingStatsValue, imgNullVal)
-        ic[:, ids] = ic2[:, 1:]
-        fc[:, ids] = fc2[:, 1:]
-    if info is not None:
-        # (a straddler is counted by every rank that holds a part of it: count the ids, once each)
-        info.update(straddlers=int(len(numpy.unique(segs))), straddler_pixels=int(len(segs)), path='host')
-    if comm.world > 1:
-        ic = comm.allreduce_sum_i64(ic.reshape(-1)).reshape(nInt, S + 1)
-        fbits = comm.allreduce_sum_i64(fc.view(numpy.int32).reshape(-1).astype(numpy.int64))
-        fc = fbits.astype(numpy.int32).view(numpy.float32).reshape(nFloat, S + 1)
-    return ic, fc, fast
+    statsSelection = list(statsSelection)
+    (fast, nInt, nFloat) = tilingstats.makeFastStatsSelection(list(range(len(statsSelection))), statsSelection)
+    return _distributedStats(engine, comm, hist, [(int(imgbandnum), statsSelection)], fast,
+                             numpy.zeros(len(statsSelection), dtype=numpy.intp), nInt, nFloat, [imgNullVal],
+                             missingStatsValue, info)
 
 
 def calcPerSegmentSpatialStatsDistributed(engine, comm, hist, imgbandnum, colTypes, userFunc, userParam,
@@ -646,71 +612,12 @@ def calcPerSegmentSpatialStatsDistributed(engine, comm, hist, imgbandnum, colTyp
 
 def deviceStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, hist, fast, nInt, nFloat, missing, imgNullVal,
                 fetch=True):
-    """The device-resident data path of calcPerSegmentStatsDistributed for ONE rank: label rows d_seg
-    (nRows x nCols uint32) and band rows d_band in the HBM of context ``c``; comm: allgather_obj (control
-    data only), allgather_dev, allreduce_dev_i64.  ``hist``: the global histogram, a numpy array or
-    ('dev', address, length) when it is in device memory already.  fetch=False: the assembled columns are not
-    copied to the host (ic = fc = None).  Returns (ic, fc, straddling segments, their pixels)."""
-    L = c._L
-    if isinstance(hist, tuple):
-        (d_hist, ns, ownHist) = (ctypes.c_void_p(hist[1]), int(hist[2]), False)
-    else:
-        h32 = numpy.ascontiguousarray(hist, dtype=numpy.uint32)
-        ns = len(h32)
-        d_hist = tiling._devAlloc(c, ns * 4)
-        c.check(L.shp_dev_upload(c.handle, d_hist, _lib.ptr(h32), ns * 4))
-        ownHist = True
-    S = ns - 1
-    colWords = ((nInt * 8 + nFloat * 4) * ns + 7) // 8
-    # (blocks from / back to the driver's cache of device scratch blocks: a 1.2-GB hipMalloc per call otherwise)
-    d_cols = tiling._devAlloc(c, colWords * 8)
-    toFree = [(d_cols, colWords * 8)] + ([(d_hist, ns * 4)] if ownHist else [])
-    try:
-        c.check(L.shp_dev_memset(c.handle, ctypes.c_void_p(d_cols.value + (colWords - 1) * 8), 0, 8))
-        (pSeg, pVal) = (ctypes.c_void_p(), ctypes.c_void_p())
-        (nPairs, nStrad) = (ctypes.c_int64(0), ctypes.c_int64(0))
-        hasNull = int(imgNullVal is not None)
-        nullVal = 0 if imgNullVal is None else int(imgNullVal)
-        c.check(L.shp_dstats_local_dev(c.handle, ctypes.c_void_p(d_seg), ctypes.c_void_p(d_band), dtypeCode, nRows, nCols,
-                                       S, hasNull, nullVal, _lib.ptr(fast), fast.shape[0], int(missing), d_hist,
-                                       int(comm.rank == 0), d_cols, ctypes.byref(pSeg), ctypes.byref(pVal),
-                                       ctypes.byref(nPairs), ctypes.byref(nStrad)))
-        counts = [int(x) for x in comm.allgather_obj(int(nPairs.value))]          # control data
-        slot = max(counts)
-        (merged, nIds) = (ctypes.c_int64(0), ctypes.c_int64(0))
-        if slot > 0:
-            bufs = []
-            for sz in (slot * 4, slot * 8, comm.world * slot * 4, comm.world * slot * 8):
-                p = tiling._devAlloc(c, sz)
-                bufs.append(p)
-                toFree.append((p, sz))
-            (d_sendS, d_sendV, d_allS, d_allV) = bufs
-            if nPairs.value:
-                c.check(L.shp_dev_copy(c.handle, d_sendS, pSeg, nPairs.value * 4))
-                c.check(L.shp_dev_copy(c.handle, d_sendV, pVal, nPairs.value * 8))
-            comm.allgather_dev(d_sendS.value, d_allS.value, slot * 4)
-            comm.allgather_dev(d_sendV.value, d_allV.value, slot * 8)
-            (lo, hi) = idRange(comm.rank, comm.world, S)
-            cnts = numpy.array(counts, dtype=numpy.uint32)
-            c.check(L.shp_dstats_merge_dev(c.handle, d_allS, d_allV, slot, comm.world, _lib.ptr(cnts), dtypeCode, S,
-                                           hasNull, nullVal, _lib.ptr(fast), fast.shape[0], int(missing), lo, hi, d_cols,
-                                           ctypes.byref(merged), ctypes.byref(nIds)))
-        if comm.world > 1:
-            comm.allreduce_dev_i64(d_cols.value, colWords)
-        (ic, fc) = (None, None)
-        if fetch:
-            ic = numpy.empty((nInt, ns), dtype=numpy.int64)
-            fc = numpy.empty((nFloat, ns), dtype=numpy.float32)
-        if fetch and nInt:
-            c.check(L.shp_dev_download(c.handle, _lib.ptr(ic), d_cols, ic.nbytes))
-        if fetch and nFloat:
-            c.check(L.shp_dev_download(c.handle, _lib.ptr(fc), ctypes.c_void_p(d_cols.value + nInt * 8 * ns), fc.nbytes))
-    finally:
-        for (p, sz) in toFree:
-            tiling._devRelease(c, p, sz)
-    # the job's figures: the ranks' id shares partition the straddlers, the ranks' rows their pixels
-    tot = comm.allgather_obj((int(nIds.value), int(nPairs.value)))
-    return ic, fc, int(sum(t[0] for t in tot)), int(sum(t[1] for t in tot))
+    """deviceStatsBands for ONE entry: band rows d_band, selection ``fast``, null value imgNullVal (None: none).  A
+    rank without rows (nRows 0) passes any non-zero d_band, which is not read, and may pass dtypeCode None.
+    Returns (ic, fc, straddling segments, their pixels)."""
+    return deviceStatsBands(c, comm, d_seg, [d_band], dtypeCode, nRows, nCols, hist, fast, [len(fast)],
+                            [int(imgNullVal is not None)], [0 if imgNullVal is None else int(imgNullVal)], nInt, nFloat,
+                            missing, fetch=fetch)[:4]
 
 
 def _engineBandCount(engine):
@@ -741,37 +648,52 @@ def calcPerSegmentStatsDistributedBands(engine, comm, hist, bandSelections, miss
     or a list with one per entry (None: no null value).  The columns lie in the order of the entries.  Bad
     arguments raise tilingstats.PyShepSegStatsError before any collective, alike on every rank.
 
-    What depends on the labels alone happens once instead of once per entry: the local histogram and the
+    What depends on the labels alone happens once whatever the number of entries: the local histogram and the
     classification of every id against ``hist``, the straddlers' ids on the wire (each distinct band's values
     travel beside them, once), the pick of this rank's id share, and ONE all-reduce of all columns.  Under RCCL
     with a device engine nothing crosses the host (shp_dstats_local_bands_dev -> all-gather of the ids and of the
-    values in the bands' pixel type -> shp_dstats_merge_bands_dev -> ncclAllReduce); on the other transports the
-    engine's localStatsBands / gatherFlaggedBands / statsOfPairsBands do the work, or, on an engine without them,
-    its one-band methods entry by entry.  One entry takes the route of calcPerSegmentStatsDistributed.  A ``hist``
-    that gives an id FEWER pixels than a rank holds of it raises on every rank.
+    values in the bands' pixel type -> shp_dstats_merge_bands_dev -> ncclAllReduce); the other transports carry
+    the same arrays as raw bytes between the engine's host methods (_distributedStats).  One entry is no special
+    route.  A ``hist`` that gives an id FEWER pixels than a rank holds of it raises on every rank.
 
-    ``info`` (a dict, optional) receives 'straddlers', 'straddler_pixels', 'path', 'bands' (distinct bands read)
-    and 'exchange_bytes' (the straddlers' ids and values all ranks put on the wire, without padding: on the device
-    path straddler_pixels * (4 + bands * itemsize)).  Returns (intcols int64 (nInt, maxSegId+1), floatcols float32
-    (nFloat, maxSegId+1), statsSelection_fast) on every rank, every column bit-identical to the column
-    calcPerSegmentStatsDistributed returns for its entry alone."""
+    ``info`` (a dict, optional) receives 'straddlers' (segments) and 'straddler_pixels' of the whole job, 'path',
+    'bands' (distinct bands read) and 'exchange_bytes' (the straddlers' ids and values all ranks put on the wire,
+    without padding: on the device path straddler_pixels * (4 + bands * itemsize)).  Returns (intcols int64 (nInt,
+    maxSegId+1), floatcols float32 (nFloat, maxSegId+1), statsSelection_fast) on every rank, every column
+    bit-identical to the column calcPerSegmentStatsDistributed returns for its entry alone."""
     from . import tilingstats
-    Err = tilingstats.PyShepSegStatsError
     (fast, bandOfStat, nInt, nFloat) = tilingstats.makeBandStatsSelection(bandSelections)
     bandSelections = [(int(b), list(sel)) for (b, sel) in bandSelections]
-    nEntries = len(bandSelections)
-    nullVals = tilingstats._entryNullVals(imgNullVal, nEntries, [None] * nEntries)
+    nullVals = tilingstats._entryNullVals(imgNullVal, len(bandSelections), [None] * len(bandSelections))
     nBands = _engineBandCount(engine)
     for (b, _sel) in bandSelections:
         if b < 1 or (nBands is not None and b > nBands):
-            raise Err("band %d not in image" % b)
-    if nEntries == 1:
-        oneInfo = {}
-        (ic, fc, fast1) = calcPerSegmentStatsDistributed(engine, comm, hist, bandSelections[0][0], bandSelections[0][1],
-                                                         missingStatsValue, nullVals[0], oneInfo)
-        if info is not None:
-            info.update(oneInfo, bands=1, exchange_bytes=12 * oneInfo['straddler_pixels'])
-        return ic, fc, fast1
+            raise tilingstats.PyShepSegStatsError("band %d not in image" % b)
+    return _distributedStats(engine, comm, hist, bandSelections, fast, bandOfStat, nInt, nFloat, nullVals,
+                             missingStatsValue, info)
+
+
+def _distributedStats(engine, comm, hist, bandSelections, fast, bandOfStat, nInt, nFloat, nullVals, missingStatsValue,
+                      info):
+    """What calcPerSegmentStatsDistributed and calcPerSegmentStatsDistributedBands share: the split over entries.
+    bandSelections: a list of (imgbandnum, statsSelection), ``fast`` their combined fast selection, bandOfStat[i]
+    the entry of statistic i, nullVals one null value (or None) per entry.
+
+    What it calls on the engine, beside histogram(maxSegId) -- either set of methods will do:
+      statsBandsOnDevice(comm, hist, planes, planeOfEntry, fast, perBand, nullVals, nInt, nFloat, missing) ->
+          (ic, fc, straddlers, their pixels, bytes exchanged): the whole split on the device (deviceStatsBands);
+          optional, and only asked of a communicator that is on the device.
+      localStatsBands(bandNums, S, fast, perBand, nInt, nFloat, missing, nullVals) -> (ic, fc): all entries' columns
+          over this rank's rows; gatherFlaggedBands(planes, S, flags, count) -> (ids, (len(planes), count) values):
+          the pixels of the flagged ids, every distinct band's values in the order of the ids;
+          statsOfPairsBands(segs, vals, K, planeOfEntry, fast, perBand, nInt, nFloat, missing, nullVals) -> (ic, fc):
+          the entries' columns of a list of (compact id 1..K, values per distinct band) pairs.
+      or, entry by entry, localStats(imgbandnum, S, fast, nInt, nFloat, missing, imgNullVal) -> (ic, fc),
+          gatherFlagged(imgbandnum, S, flags, count) -> (ids, values) in any order, statsOfPairs(segs, vals, K,
+          fast, nInt, nFloat, missing, imgNullVal) -> (ic, fc), each with the entry's own fast selection."""
+    from . import tilingstats
+    Err = tilingstats.PyShepSegStatsError
+    nEntries = len(bandSelections)
     planes = tilingstats._planeNumbers(bandSelections)
     planeOfEntry = [planes.index(b) for (b, _sel) in bandSelections]
     perBand = numpy.ascontiguousarray([len(sel) for (_b, sel) in bandSelections], dtype=numpy.int32)
@@ -865,16 +787,18 @@ def calcPerSegmentStatsDistributedBands(engine, comm, hist, bandSelections, miss
 
 def deviceStatsBands(c, comm, d_seg, d_bands, dtypeCode, nRows, nCols, hist, fast, perBand, hasNull, nullVals, nInt,
                      nFloat, missing, fetch=True):
-    """deviceStats for several entries at once, the device-resident data path of
-    calcPerSegmentStatsDistributedBands for ONE rank.  d_bands: one device address per entry (this rank's rows of
+    """The device-resident data path of calcPerSegmentStatsDistributed[Bands] for ONE rank, over entries: label
+    rows d_seg (nRows x nCols uint32) in the HBM of context ``c``; comm: allgather_obj (control data only),
+    allgather_dev, allreduce_dev_i64.  d_bands: one device address per entry (this rank's rows of
     the entry's band; entries that read the same band give the same address, and the distinct addresses must
     number alike on every rank -- a rank without rows (nRows 0) passes distinct made-up ones, which are not read,
     and may pass dtypeCode None: it learns the pixel type from the other ranks);
     perBand / hasNull / nullVals: statistics, null flag and null value per entry; ``fast`` the combined selection.
-    The other arguments and conventions are deviceStats'.  Two all-gathers (the ids; the values, every rank's block
-    = one row per distinct band, the same stride on every rank) and one all-reduce.  A histogram that cannot belong
-    to these labels (shp_dstats_local_bands_dev) raises _lib.ShepsegHipError on every rank.
-    Returns (ic, fc, straddling segments, their pixels, payload bytes of the all-gathers over all ranks)."""
+    ``hist``: the global histogram, a numpy array or ('dev', address, length) when it is in device memory already.
+    fetch=False: the assembled columns are not copied to the host (ic = fc = None).  Two all-gathers (the ids; the
+    values, every rank's block = one row per distinct band, the same stride on every rank) and one all-reduce.  A
+    histogram that cannot belong to these labels (shp_dstats_local_bands_dev) raises _lib.ShepsegHipError on every
+    rank.  Returns (ic, fc, straddling segments, their pixels, payload bytes of the all-gathers over all ranks)."""
     L = c._L
     planes = list(dict.fromkeys(int(p) for p in d_bands))
     nPlanes = len(planes)
@@ -895,6 +819,7 @@ def deviceStatsBands(c, comm, d_seg, d_bands, dtypeCode, nRows, nCols, hist, fas
         ownHist = True
     S = ns - 1
     colWords = ((nInt * 8 + nFloat * 4) * ns + 7) // 8
+    # (blocks from / back to the driver's cache of device scratch blocks: a 1.2-GB hipMalloc per call otherwise)
     d_cols = tiling._devAlloc(c, colWords * 8)
     toFree = [(d_cols, colWords * 8)] + ([(d_hist, ns * 4)] if ownHist else [])
     try:
@@ -2020,51 +1945,7 @@ class HipEngine(object):
         isz = numpy.dtype(self.ras.dtype).itemsize
         return self.ras.ptr + (((imgbandnum - 1) * rows + (self.outLo - self.yLo)) * cols) * isz
 
-    def localStats(self, imgbandnum, S, fast, nInt, nFloat, missing, imgNullVal):
-        n = (self.outHi - self.outLo) * self.nCols
-        ic = numpy.zeros((nInt, S + 1), dtype=numpy.int64)
-        fc = numpy.zeros((nFloat, S + 1), dtype=numpy.float32)
-        if n > 0:
-            self.c.check(self.L.shp_segstats_dev(
-                self.c.handle, self._lastOut, ctypes.c_void_p(self._bandPtr(imgbandnum)),
-                _lib.SHP_DTYPES[self.ras.dtype], n, S, int(imgNullVal is not None),
-                0 if imgNullVal is None else int(imgNullVal), _lib.ptr(fast), fast.shape[0],
-                int(missing), _lib.ptr(ic), _lib.ptr(fc)))
-        return ic, fc
-
-    def gatherFlagged(self, imgbandnum, S, flags, count):
-        n = (self.outHi - self.outLo) * self.nCols
-        segs = numpy.empty(max(count, 1), dtype=numpy.uint32)
-        vals = numpy.empty(max(count, 1), dtype=numpy.int64)
-        got = ctypes.c_int64(0)
-        if n > 0 and count > 0:
-            self.c.check(self.L.shp_gather_flagged_dev(
-                self.c.handle, self._lastOut, ctypes.c_void_p(self._bandPtr(imgbandnum)),
-                _lib.SHP_DTYPES[self.ras.dtype], n, S, _lib.ptr(flags), count, _lib.ptr(segs),
-                _lib.ptr(vals), ctypes.byref(got)))
-            if got.value != count:
-                raise tiling.PyShepSegTilingError(
-                    "straddling-segment gather found %d pixels, histogram says %d" % (got.value, count))
-        return segs[:count], vals[:count]
-
-    def statsOfPairs(self, segs, vals, K, fast, nInt, nFloat, missing, imgNullVal):
-        """Statistics of a list of (compact id 1..K, value) pairs: the same kernel on a 1 x M raster."""
-        band = vals.astype(self.ras.dtype if self.ras is not None else numpy.uint16)
-        ic = numpy.zeros((nInt, K + 1), dtype=numpy.int64)
-        fc = numpy.zeros((nFloat, K + 1), dtype=numpy.float32)
-        self.c.check(self.L.shp_segstats(
-            self.c.handle, _lib.ptr(segs), _lib.ptr(band), _lib.SHP_DTYPES[band.dtype], len(segs), K,
-            int(imgNullVal is not None), 0 if imgNullVal is None else int(imgNullVal),
-            _lib.ptr(fast), fast.shape[0], int(missing), _lib.ptr(ic), _lib.ptr(fc)))
-        return ic, fc
-
-    def statsOnDevice(self, comm, hist, imgbandnum, fast, nInt, nFloat, missing, imgNullVal):
-        """calcPerSegmentStatsDistributed's device path for this rank's output rows (deviceStats)."""
-        return deviceStats(self.c, comm, self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut),
-                           self._bandPtr(imgbandnum), _lib.SHP_DTYPES[self.ras.dtype], self.outHi - self.outLo,
-                           self.nCols, hist, fast, nInt, nFloat, missing, imgNullVal)
-
-    # ---- several bands in one call (calcPerSegmentStatsDistributedBands)
+    # ---- the split of the per-segment statistics (_distributedStats: the ...Bands set of methods)
     @property
     def numBands(self):
         """image bands this rank holds rows of (None: no rows, so it cannot tell)"""
@@ -2077,7 +1958,7 @@ class HipEngine(object):
         return arr
 
     def localStatsBands(self, bandNums, S, fast, perBand, nInt, nFloat, missing, nullVals):
-        """localStats of several entries in one pass over the labels: all entries' columns (shp_segstats2d_bands_dev)"""
+        """all entries' columns over this rank's output rows, in one pass over the labels (shp_segstats2d_bands_dev)"""
         nRows = self.outHi - self.outLo
         ic = numpy.zeros((max(nInt, 1), S + 1), dtype=numpy.int64)
         fc = numpy.zeros((max(nFloat, 1), S + 1), dtype=numpy.float32)
@@ -2091,8 +1972,8 @@ class HipEngine(object):
         return ic[:nInt], fc[:nFloat]
 
     def gatherFlaggedBands(self, planes, S, flags, count):
-        """gatherFlagged for several distinct bands: the ids once and (len(planes), count) values in the image's pixel
-        type, every row in the order of the ids (shp_gather_flagged_bands_dev)"""
+        """the pixels of the flagged ids in this rank's output rows: the ids once and (len(planes), count) values in
+        the image's pixel type, every row in the order of the ids (shp_gather_flagged_bands_dev)"""
         n = (self.outHi - self.outLo) * self.nCols
         dt = self.ras.dtype if self.ras is not None else numpy.dtype(numpy.uint16)
         segs = numpy.empty(max(count, 1), dtype=numpy.uint32)
@@ -2108,8 +1989,8 @@ class HipEngine(object):
         return segs[:count], vals[:, :count].astype(dt)
 
     def statsOfPairsBands(self, segs, vals, K, planeOfEntry, fast, perBand, nInt, nFloat, missing, nullVals):
-        """statsOfPairs of several entries: ``vals`` one array per distinct band in the order of ``segs`` (compact ids
-        1..K), entry e reads vals[planeOfEntry[e]] -- the bands kernels on a 1 x M raster."""
+        """the entries' columns of a list of pairs: ``vals`` one array per distinct band in the order of ``segs``
+        (compact ids 1..K), entry e reads vals[planeOfEntry[e]] -- the bands kernels on a 1 x M raster."""
         m = len(segs)
         dt = numpy.dtype(self.ras.dtype if self.ras is not None else vals[0].dtype)
         ic = numpy.zeros((max(nInt, 1), K + 1), dtype=numpy.int64)
@@ -2135,7 +2016,7 @@ class HipEngine(object):
         return ic[:nInt], fc[:nFloat]
 
     def statsBandsOnDevice(self, comm, hist, planes, planeOfEntry, fast, perBand, nullVals, nInt, nFloat, missing):
-        """calcPerSegmentStatsDistributedBands' device path for this rank's output rows (deviceStatsBands).
+        """calcPerSegmentStatsDistributed[Bands]' device path for this rank's output rows (deviceStatsBands).
         planes: the distinct band numbers, planeOfEntry[e]: which of them entry e reads."""
         held = self.ras is not None and self.outHi > self.outLo
         if held:
@@ -2877,8 +2758,9 @@ def renderColourTableDistributed(engine, comm, dres, colours=None, outfile=None,
 def bench_stats_main(args, rank, world, local_rank):
     """One rank of `bench.py --workload c5 --gpus N`: the label raster of 4 x 8-pixel blocks (50 M segments at
     40000^2) and one uint16 band, sharded by rows at boundaries that CUT blocks (every shard boundary makes
-    nCols / 8 straddling segments); a step = calcPerSegmentStatsDistributed's device path (deviceStats), the
-    assembled columns copied to the host on rank 0."""
+    nCols / 8 straddling segments); a step = calcPerSegmentStatsDistributed's device path (deviceStats: one entry
+    through deviceStatsBands, the driver of any number of entries), the assembled columns copied to the host on
+    rank 0."""
     from . import comm as _comm
     from . import tilingstats
     comm = _comm.fromEnvironment()

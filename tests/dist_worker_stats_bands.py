@@ -3,7 +3,8 @@ driver on OUTDIR/img.npy, then calcPerSegmentStatsDistributedBands against one c
 per entry in the same process.
 
   dist_worker_stats_bands.py OUTDIR TILE OVERLAP          writes OUTDIR/bands<rank>.npz and rank<rank>.npz
-  dist_worker_stats_bands.py OUTDIR TILE OVERLAP errors   every bad argument must raise on this rank; then exits 0"""
+  dist_worker_stats_bands.py OUTDIR TILE OVERLAP errors   every bad argument, and a stale histogram in the one-band
+                                                          call, must raise on this rank; then exits 0"""
 import os
 import sys
 
@@ -27,6 +28,7 @@ BAD_ARGUMENTS = [
     ('band zero', dict(bandSelections=[(0, [('x', 'min')]), (2, [('y', 'max')])])),
     ('null list of the wrong length', dict(bandSelections=ENTRIES, imgNullVal=[1, 2])),
 ]
+STALE_HISTOGRAM = 'stale histogram, one band'
 
 
 def main():
@@ -48,7 +50,22 @@ def main():
                 sys.stderr.write('rank %d, %s: %s\n' % (comm.rank, what, e))
             else:
                 raise AssertionError('%s did not raise' % what)
-        # nobody is stranded in a collective: the next call works
+        # the one-band call with a histogram that gives one id (whole on a rank) a pixel fewer than that rank holds:
+        # the rank that holds it finds out, every rank raises
+        lh = np.asarray(eng.histogram(r.maxSegId)).astype(np.int64)
+        whole = np.flatnonzero((lh[1:] == np.asarray(r.hist)[1:]) & (lh[1:] > 0)) + 1
+        victim = [v for v in comm.allgather_obj(int(whole[0]) if len(whole) else None) if v is not None][0]
+        stale = np.array(r.hist, copy=True)
+        stale[victim] -= 1
+        try:
+            distributed.calcPerSegmentStatsDistributed(eng, comm, stale, ENTRIES[0][0], ENTRIES[0][1], imgNullVal=NULLS[0])
+        except tilingstats.PyShepSegStatsError as e:
+            assert '1 segment ids have more pixels' in str(e), e
+            sys.stderr.write('rank %d, %s: %s\n' % (comm.rank, STALE_HISTOGRAM, e))
+        else:
+            raise AssertionError('%s did not raise' % STALE_HISTOGRAM)
+        # nobody is stranded in a collective: the next calls work
+        distributed.calcPerSegmentStatsDistributed(eng, comm, r.hist, ENTRIES[0][0], ENTRIES[0][1], imgNullVal=NULLS[0])
         distributed.calcPerSegmentStatsDistributedBands(eng, comm, r.hist, ENTRIES, imgNullVal=NULLS)
         comm.close()
         return
@@ -63,7 +80,7 @@ def main():
                                                                     info=one)
         out.update({'ic%d' % k: ic1, 'fc%d' % k: fc1, 'straddlers%d' % k: one['straddlers'],
                     'straddler_pixels%d' % k: one['straddler_pixels']})
-    # one entry: the one-band route, the same columns
+    # one entry is no special route: the same columns
     (icS, fcS, _f) = distributed.calcPerSegmentStatsDistributedBands(eng, comm, r.hist, [ENTRIES[1]], imgNullVal=[NULLS[1]])
     out.update(icS=icS, fcS=fcS)
     np.savez(os.path.join(outdir, 'bands%d.npz' % comm.rank), **out)

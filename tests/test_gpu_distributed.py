@@ -182,9 +182,9 @@ class _ThreadDevComm(object):
 
 @pytest.mark.parametrize('world,dtype,nullv', [(2, np.uint16, None), (3, np.uint16, 7), (3, np.uint8, None), (2, np.int16, -5)])
 def test_device_stats_split_with_straddlers(world, dtype, nullv, oracle):
-    """The device-resident data path of calcPerSegmentStatsDistributed (shp_dstats_local_dev -> all-gather of
-    the packed pairs -> shp_dstats_merge_dev by id share -> all-reduce of the column block) with `world`
-    row shards of one raster on this one GPU, segments crossing every shard boundary, against the oracle on
+    """The device-resident data path of calcPerSegmentStatsDistributed (deviceStats: shp_dstats_local_bands_dev with
+    one entry -> all-gather of the packed ids and values -> shp_dstats_merge_bands_dev by id share -> all-reduce of
+    the column block) with `world` row shards of one raster on this one GPU, segments crossing every shard boundary, against the oracle on
     the whole raster: every column bit for bit on every rank."""
     import ctypes
     import threading

@@ -1,7 +1,8 @@
-"""GPU: per-segment statistics of several bands in ONE call on the row-sharded multi-rank output
+"""GPU: per-segment statistics of one or several bands in ONE call on the row-sharded multi-rank output
 (distributed.calcPerSegmentStatsDistributedBands / deviceStatsBands; shp_dstats_local_bands_dev,
-shp_dstats_merge_bands_dev).  Every column bit for bit against the one-band distributed call of its entry and
-against the oracle on the whole raster; nothing here has a tolerance."""
+shp_dstats_merge_bands_dev).  Every column bit for bit against the one-band distributed call of its entry
+(deviceStats, the same driver with one entry) and against the oracle on the whole raster, which is what keeps the
+first comparison honest; nothing here has a tolerance."""
 import os
 
 import numpy as np
@@ -127,10 +128,11 @@ def test_device_stats_bands_split(field, world, dtype, form, patch, oracle, monk
         assert min(cnt['whole']) >= 100, cnt['whole']
     itemsize = np.dtype(dtype).itemsize
     wantBytes = cnt['pixels'] * (4 + 2 * itemsize)
-    assert wantBytes < 12 * len(ENTRY_SELS) * cnt['pixels']
+    assert wantBytes < len(ENTRY_SELS) * (4 + itemsize) * cnt['pixels']      # (three calls with one entry each)
     print('field %s world %d: %d straddlers (%s per id share), %d of %d pixels, whole per rank %s, %d bytes exchanged '
           'against %d of three one-band calls' % (field, world, len(cnt['strad']), cnt['perShare'], cnt['pixels'],
-                                                  int((seg != 0).sum()), cnt['whole'], wantBytes, 36 * cnt['pixels']))
+                                                  int((seg != 0).sum()), cnt['whole'], wantBytes,
+                                                  3 * (4 + itemsize) * cnt['pixels']))
     (results, errors) = H.runRankThreads(world, _rankBody(seg, planes, nulls, hist, dtype, world))
     assert not any(errors), errors
     (fast, _perBand, nInt, nFloat) = _combined()
@@ -199,6 +201,119 @@ def test_stale_histogram_raises_on_every_rank(world):
     (results, errors) = H.runRankThreads(world, _rankBody(seg, planes, NULL_FORMS['none'], hist, np.uint16, world,
                                                           oneBandToo=False), timeout=120)
     assert results == [None] * world
+    for (r, e) in enumerate(errors):
+        assert isinstance(e, _lib.ShepsegHipError), (r, e)
+        assert '1 segment ids have more pixels' in str(e), (r, e)
+
+
+# ---- one entry: no special route (nbands = nplanes = 1), but the library's one-band statistics kernels
+ONE_SEL = [('o_min', 'min'), ('o_max', 'max'), ('o_mean', 'mean'), ('o_sd', 'stddev'), ('o_med', 'median'),
+           ('o_mode', 'mode'), ('o_p30', 'percentile', 30), ('o_n', 'pixcount')]
+
+
+def _widePlane(dtype, seg, null, rng):
+    """plane 0 of _planes with a multiple of 2^20 added to a third of the pixels: values that need all four bytes of
+    a 4-byte pixel on the wire (null pixels stay null)"""
+    plane = _planes(dtype, seg, [null, None, null], rng)[0]
+    lift = (rng.integers(1, 4, size=seg.shape) << 20).astype(dtype)
+    where = rng.random(seg.shape) < 0.33
+    if null is not None:
+        where &= plane != null
+    plane[where] += lift[where]
+    assert int(plane.max()) >= 1 << 20
+    return plane
+
+
+def _oneEntryBody(seg, plane, null, hist, dtype, world, cuts=None, bandsToo=True):
+    """what every rank thread does with ONE entry: deviceStatsBands (bandsToo), then deviceStats.  A rank without rows
+    passes a made-up band address and no pixel type."""
+    from pyshepseg_amd import distributed, tilingstats, _lib
+    (f1, n1, m1) = tilingstats.makeFastStatsSelection(list(range(len(ONE_SEL))), ONE_SEL)
+    cuts = cuts or H.cutsOf(world)
+    code = _lib.SHP_DTYPES[np.dtype(dtype)]
+
+    def body(r, comm, c):
+        (lo, hi) = (cuts[r], cuts[r + 1])
+        ds = H.uploadRows(c, seg[lo:hi])
+        dp = H.uploadRows(c, plane[lo:hi])
+        (d_seg, d_band, dt) = (ds.value, dp.value, code) if hi > lo else (0, 16, None)
+        try:
+            res = None
+            if bandsToo:
+                res = distributed.deviceStatsBands(c, comm, d_seg, [d_band], dt, hi - lo, H.NC, hist, f1, [len(ONE_SEL)],
+                                                   [int(null is not None)], [0 if null is None else null], n1, m1, -9999)
+            one = distributed.deviceStats(c, comm, d_seg, d_band, dt, hi - lo, H.NC, hist, f1, n1, m1, -9999, null)
+        finally:
+            for d in (ds, dp):
+                c.check(c._L.shp_dev_free(c.handle, d))
+        return res, one
+    return body
+
+
+@pytest.mark.parametrize('world', [2, 3])
+@pytest.mark.parametrize('null', [None, 7])
+@pytest.mark.parametrize('patch', [0, 1])
+@pytest.mark.parametrize('dtype', [np.int32, np.uint32], ids=['int32', 'uint32'])
+def test_one_entry_four_byte_pixels(dtype, patch, null, world, oracle, monkeypatch):
+    """One entry of a 4-byte pixel type through deviceStatsBands and through deviceStats (its wrapper): every column ==
+    the oracle on the whole raster, bit for bit, on every rank; the straddlers' values travel in the pixel type, 4 +
+    4 bytes a pixel.  (The library computes one entry with k_stats_patch / the one-band sorts, several with
+    k_stats_patch_bands: SHEPSEG_STATS_PATCH 0 and 1 take both forms of the former.)"""
+    monkeypatch.setenv('SHEPSEG_STATS_PATCH', str(patch))
+    rng = np.random.default_rng(3)
+    (seg, S) = H.labelField('A', rng)
+    plane = _widePlane(dtype, seg, null, rng)
+    hist = np.bincount(seg.ravel(), minlength=S + 1).astype(np.uint32)
+    hist[0] = 0
+    cnt = H.countField(seg, S, world)
+    assert len(cnt['strad']) >= 50
+    (wic, wfc) = oracle.segstats(seg, plane, ONE_SEL, null, -9999, max_seg_id=S)
+    if null is not None:
+        assert int(wic[-1][_allNullId(seg)]) == 0            # (pixcount, the last integer column)
+    (results, errors) = H.runRankThreads(world, _oneEntryBody(seg, plane, null, hist, dtype, world))
+    assert not any(errors), errors
+    for (r, ((ic, fc, nStrad, nPix, nBytes), (ic1, fc1, nStrad1, nPix1))) in enumerate(results):
+        assert (nStrad, nPix, nBytes) == (len(cnt['strad']), cnt['pixels'], cnt['pixels'] * (4 + 4)), r
+        assert (nStrad1, nPix1) == (len(cnt['strad']), cnt['pixels']), r
+        assert _sameBits(ic, wic) and _sameBits(fc, wfc), ('deviceStatsBands', r)
+        assert _sameBits(ic1, wic) and _sameBits(fc1, wfc), ('deviceStats', r)
+
+
+def test_one_entry_rank_without_rows(oracle):
+    """deviceStats with more ranks than row shards: the middle rank passes nRows 0, a made-up band address and no pixel
+    type, and gets the same columns as the others"""
+    cuts = [0, 100, 100, 203]
+    rng = np.random.default_rng(2)
+    (seg, S) = H.labelField('A', rng)
+    plane = _planes(np.int16, seg, [7, None, 7], rng)[0]
+    hist = np.bincount(seg.ravel(), minlength=S + 1).astype(np.uint32)
+    hist[0] = 0
+    (results, errors) = H.runRankThreads(3, _oneEntryBody(seg, plane, 7, hist, np.int16, 3, cuts=cuts, bandsToo=False))
+    assert not any(errors), errors
+    (wic, wfc) = oracle.segstats(seg, plane, ONE_SEL, 7, -9999, max_seg_id=S)
+    strad = (set(np.unique(seg[:100]).tolist()) & set(np.unique(seg[100:]).tolist())) - {0}
+    assert len(strad) >= 50
+    for (r, (_none, (ic, fc, nStrad, nPix))) in enumerate(results):
+        assert (nStrad, nPix) == (len(strad), int(np.isin(seg, sorted(strad)).sum())), r
+        assert _sameBits(ic, wic) and _sameBits(fc, wfc), r
+
+
+def test_stale_histogram_raises_through_device_stats():
+    """the one-band call refuses a histogram that gives an id fewer pixels than a rank holds of it, as the several-band
+    call does: every rank raises, none is left in a collective"""
+    from pyshepseg_amd import _lib
+    rng = np.random.default_rng(5)
+    (seg, S) = H.labelField('B', rng)
+    plane = _planes(np.uint16, seg, NULL_FORMS['none'], rng)[0]
+    hist = np.bincount(seg.ravel(), minlength=S + 1).astype(np.uint32)
+    hist[0] = 0
+    cnt = H.countField(seg, S, 2)
+    victim = sorted(cnt['held'][1] - cnt['strad'])[0]                  # whole on the last rank
+    assert hist[victim] > 1
+    hist[victim] -= 1
+    (results, errors) = H.runRankThreads(2, _oneEntryBody(seg, plane, None, hist, np.uint16, 2, bandsToo=False),
+                                         timeout=120)
+    assert results == [None] * 2
     for (r, e) in enumerate(errors):
         assert isinstance(e, _lib.ShepsegHipError), (r, e)
         assert '1 segment ids have more pixels' in str(e), (r, e)

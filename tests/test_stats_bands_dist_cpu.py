@@ -1,6 +1,7 @@
 """calcPerSegmentStatsDistributedBands on the host path without a GPU: socket ranks with the oracle engine, which
 offers the one-band methods only, so the call drives it entry by entry.  Every column against the one-band
-distributed call of its entry (same process) and against the oracle on the gathered mosaic, bit for bit."""
+distributed call of its entry (same process, the same driver with one entry) and against the oracle on the gathered
+mosaic, bit for bit; the oracle is what keeps the first comparison honest."""
 import os
 
 import numpy as np
@@ -78,7 +79,7 @@ def test_bands_equal_one_band_calls_and_oracle(world, tmp_path, oracle):
                 else:
                     assert np.array_equal(col.view(np.int32), one.view(np.int32)), (r, k, s)
                     assert np.array_equal(col.view(np.int32), want.view(np.int32)), (r, k, s)
-        # one entry takes the one-band route: its columns again
+        # one entry through the several-band front end: its columns again
         assert np.array_equal(st['icS'], st['ic1'])
         assert np.array_equal(st['fcS'].view(np.int32), st['fc1'].view(np.int32))
 
@@ -96,10 +97,12 @@ def test_entries_differ_where_their_nulls_differ(tmp_path, oracle):
 @pytest.mark.parametrize('world', [2, 3])
 def test_bad_arguments_raise_on_every_rank(world, tmp_path, oracle):
     """empty list, duplicate column name, band out of range, null list of the wrong length: every rank raises
-    before any collective and goes on (a stranded rank would run into the launcher's time limit)"""
+    before any collective and goes on (a stranded rank would run into the launcher's time limit).  Then the one-band
+    call with a histogram entry lowered by one: PyShepSegStatsError on every rank, and the next call works."""
     _image(oracle, tmp_path)
     errs = dist_cases.runRanks(world, [WORKER, str(tmp_path), str(TILE), str(OV), 'errors'], tmp_path, 600,
                                extra_env={'OMP_NUM_THREADS': '1', 'SHEPSEG_SHARD': 'rows'})
     for (r, e) in enumerate(errs):
         for (what, _kw) in W.BAD_ARGUMENTS:
             assert 'rank %d, %s:' % (r, what) in e, (r, what, e[-2000:])
+        assert 'rank %d, %s:' % (r, W.STALE_HISTOGRAM) in e, (r, e[-2000:])

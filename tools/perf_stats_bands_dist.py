@@ -1,6 +1,6 @@
-"""Per-segment statistics of N bands on the row-sharded multi-rank layout: ONE call of the several-band device
-path (distributed.deviceStatsBands, what calcPerSegmentStatsDistributedBands runs under a device communicator)
-against N calls of the one-band path (distributed.deviceStats), on the C5 label raster of `bench.py --workload c5
+"""Per-segment statistics of N bands on the row-sharded multi-rank layout: ONE call of the device path with N
+entries (distributed.deviceStatsBands, what calcPerSegmentStatsDistributedBands runs under a device communicator)
+against N calls with one entry each (distributed.deviceStats, a wrapper over the same driver), on the C5 label raster of `bench.py --workload c5
 --gpus N` (4 x 8-pixel blocks, shard boundaries two rows into a block row, so every boundary cuts nCols / 8
 segments), (a) world 1 under RCCL, (b) two socket ranks sharing GPU 0 (device buffers staged through the host: that
 times the code path, not a second GPU).
@@ -13,10 +13,10 @@ times the code path, not a second GPU).
 Every (variant, N) is run once untimed and then --repeats times.  A line of JSON per timed run, printed by rank 0:
 wall = the slowest rank's host clock around the call(s), between two barriers (the assembled columns are copied to
 the host on rank 0, as in the benchmark); dev = rank 0's PROF_SEGSTATS event counter (the statistics kernels of
-the local and the merge part; not the classification, the gather or the exchange).  With N = 1 the public function
-takes the one-band path, and so does the 'bands' variant here.  --root imports pyshepseg_amd from another checkout
-(one without deviceStatsBands runs --variant single only): baseline and candidate are then two processes over the
-same inputs, to be alternated.  --summarise prints min / median / max per (world, variant, N) and the ratio of the
+the local and the merge part; not the classification, the gather or the exchange).  With N = 1 the two variants
+run the same code.  --root imports pyshepseg_amd from another checkout (one without deviceStatsBands runs --variant
+single only, and one whose deviceStats still has a driver of its own puts 12 bytes per straddler pixel on the wire):
+baseline and candidate are then two processes over the same inputs, to be alternated.  --summarise prints min / median / max per (world, variant, N) and the ratio of the
 medians with the baseline's own spread.  The label raster is held whole by every rank, as in the benchmark:
 choose --size so that it fits the GPU `world` times."""
 import argparse
@@ -98,6 +98,7 @@ def rank(a, transport):
     hist = ('dev', d_hist.value, S + 1)
     (fast1, nInt1, nFloat1) = tilingstats.makeFastStatsSelection(list(range(len(SEL))), SEL)
     plane = (y1 - y0) * N * 2
+    oldSingle = 'shp_dstats_local_dev' in _lib._SIGS        # (a --root from before deviceStats became a wrapper)
     out = open(a.out, 'a') if (a.out and r == 0) else None
 
     def dev_ms(reset):
@@ -108,7 +109,7 @@ def rank(a, transport):
 
     def run(variant, nb):
         """-> (pixels counted by the last band's pixcount column on rank 0, straddler pixels, exchanged bytes)"""
-        if variant == 'bands' and nb > 1:
+        if variant == 'bands':
             sels = [(b + 1, [('b%d_%s' % (b + 1, s[0]),) + s[1:] for s in SEL]) for b in range(nb)]
             (fast, _bo, nInt, nFloat) = tilingstats.makeBandStatsSelection(sels)
             (ic, _fc, _ns, nPix, nBytes) = distributed.deviceStatsBands(
@@ -118,7 +119,7 @@ def rank(a, transport):
         for b in range(nb):
             (ic, _fc, _ns, nPix) = distributed.deviceStats(c, dcomm, d_seg, ras.ptr + b * plane, 2, y1 - y0, N, hist, fast1,
                                                            nInt1, nFloat1, -9999, None, fetch=(r == 0))
-        return (int(ic[nInt1 - 1].sum()) if r == 0 else None), nPix, 12 * nb * nPix
+        return (int(ic[nInt1 - 1].sum()) if r == 0 else None), nPix, (12 if oldSingle else 4 + 2) * nb * nPix
 
     if r == 0:
         print('world %d (%s): %d x %d labels, %d segments, %d bands of uint16, rows per rank %s'
