@@ -78,6 +78,10 @@ int shp_prof_get(shp_ctx *ctx, double *ms_out, uint64_t *count_out, int n, int r
  * context that owns its stream counts as a batch of one.  reset != 0 clears the counters.  Read-only
  * otherwise: it changes nothing about how the work runs. */
 int shp_walk_batch_stats(uint64_t *out, int reset);
+/* the workgroups of the same launches.  out receives four values: the sum of workgroups over all launches
+ * and the most workgroups in one launch of the replay, then the same two of the pass loop.  The reset of
+ * shp_walk_batch_stats clears them too.  Read-only. */
+int shp_walk_batch_blocks(uint64_t *out);
 
 /* ---- k-means ------------------------------------------------------------------------ */
 /* replaces sklearn KMeans(init=<array>, n_init=1).fit as called by

@@ -1140,6 +1140,17 @@ API int shp_walk_batch_stats(uint64_t *out, int reset)
     return 0;
 }
 
+// workgroups summed over all launches and the most in one launch, of the replay, then of the pass loop
+API int shp_walk_batch_blocks(uint64_t *out)
+{
+    if (!out) return SHP_ERR_ARG;
+    for (int c = 0; c < walkbatch::NCLS; c++) {
+        const walkbatch::Stats s = walk_batcher().stats(c, false);
+        out[2 * c] = s.blocks; out[2 * c + 1] = s.most_blocks;
+    }
+    return 0;
+}
+
 // ---- per-segment statistics (tilingstats) -------------------------------------------------------
 API int shp_segstats_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
                          int64_t npix, uint32_t max_seg_id, int has_null, int64_t null_val,

@@ -1569,7 +1569,7 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
             ctx->prof_ms[PROF_DFS] += wj.ms;          // an equal share of the batch's time, one launch's worth
             ctx->prof_cnt[PROF_DFS] += 1;
         } else {
-            walk_batcher().direct_begin(walkbatch::CLS_REPLAY);
+            walk_batcher().direct_begin(walkbatch::CLS_REPLAY, nblk);
             walk_batcher().direct_end(walkbatch::CLS_REPLAY);      // (no residency rule for replays: counted only)
             walkbatch::Job *one = &wj;
             ps = prof_begin(ctx, PROF_DFS);              // events hug the kernel

@@ -1448,7 +1448,7 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
         ctx->prof_cnt[PROF_SMALL_LOOP] += 1;
     } else {
         if (!ctx->h_jobs) HIPCHK(ctx, hipHostMalloc(&ctx->h_jobs, SHP_JOBS_BYTES, hipHostMallocDefault));
-        walk_batcher().direct_begin(walkbatch::CLS_LOOP);
+        walk_batcher().direct_begin(walkbatch::CLS_LOOP, small_blocks);
         st = ctx->stream;
         walkbatch::Job *one = &wj;
         ps = prof_begin(ctx, PROF_SMALL_LOOP);           // events hug the kernel: no copies, no host waits

@@ -39,7 +39,8 @@ struct Job {
 // budget: jobs of the class in flight at once over ALL launches, direct ones included (0 = no such rule):
 // the co-residency rule of the pass loop's grid barriers.
 struct Caps { int max_jobs = 1; unsigned max_blocks = ~0u; int budget = 0; };
-struct Stats { unsigned long long launches = 0, jobs = 0, largest = 0; };
+// blocks: workgroups summed over all launches.  most_blocks: the most workgroups one launch carried.
+struct Stats { unsigned long long launches = 0, jobs = 0, largest = 0, blocks = 0, most_blocks = 0; };
 
 class Batcher {
     std::mutex mu;
@@ -51,11 +52,13 @@ class Batcher {
     Stats st[NCLS];
 
     int budget_free(int cls) const { return caps[cls].budget > 0 ? caps[cls].budget - used[cls] : 0x7fffffff; }
-    void count(int cls, int n)
+    void count(int cls, int n, unsigned blocks)
     {
         st[cls].launches++;
         st[cls].jobs += (unsigned long long)n;
         if ((unsigned long long)n > st[cls].largest) st[cls].largest = (unsigned long long)n;
+        st[cls].blocks += blocks;
+        if (blocks > st[cls].most_blocks) st[cls].most_blocks = blocks;
     }
 
 public:
@@ -102,7 +105,7 @@ public:
         const int n = (int)batch.size();
         streams_free--;
         used[cls] += n;
-        count(cls, n);
+        count(cls, n, blocks);
         lk.unlock();
         double ms = 0.0;
         char msg[sizeof(j->msg)] = {0};
@@ -121,13 +124,13 @@ public:
     }
 
     // a one-job launch on the caller's own stream (a context that owns its stream never waits for a batch):
-    // it counts against the budget and in the statistics like a batch of one
-    void direct_begin(int cls)
+    // it counts against the budget and in the statistics like a batch of one job of `blocks` workgroups
+    void direct_begin(int cls, unsigned blocks)
     {
         std::unique_lock<std::mutex> lk(mu);
         cv.wait(lk, [&] { return budget_free(cls) >= 1; });
         used[cls]++;
-        count(cls, 1);
+        count(cls, 1, blocks);
     }
     void direct_end(int cls)
     {

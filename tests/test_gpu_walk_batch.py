@@ -1,10 +1,14 @@
 """The latency-bound kernels of several tiles in one launch (csrc/walkbatch.h): a tiled run of 24 tiles of four
 sizes under one walker stream, two, and the default environment, both connectivities, against the oracle.
 
-4-connected, 23 tiles hold 2-7 components above the depth-first cut's cap and tile (0, 0) holds none: its worker
-skips the replay while the others batch.  8-connected, all 24 hold 4-12.  Every tile eliminates at least 21 small
-segments, so every tile runs a pass loop.  The library reads its knobs once per process, so every setting runs in a
-fresh child (tests/walk_batch_worker.py), one at a time; after a child that ended abnormally none is started."""
+4-connected, 23 tiles hold 1-3 components above the depth-first cut's cap and tile (0, 0) holds none: its worker
+skips the replay while the others batch.  8-connected, all 24 hold 1-3.  Every tile eliminates at least 21 small
+segments, so every tile runs a pass loop.  A replay job has ceil(components / SHEPSEG_DFS_PER_WG) workgroups, so at
+the default of 8 every replay job here is ONE workgroup: these cases pin the batcher and the batch kernels' job
+lookup for such jobs only; jobs of several workgroups, other pass-loop group sizes and the caps are the business of
+tests/test_gpu_walk_batch_uneven.py, and tests/walk_batch_cases.census('even', ...) recounts the figures above.
+The library reads its knobs once per process, so every setting runs in a fresh child (tests/walk_batch_worker.py),
+one at a time; after a child that ended abnormally (here or in the sibling file) none is started."""
 import os
 import subprocess
 import sys
@@ -13,6 +17,7 @@ import numpy as np
 import pytest
 
 import seg_cases
+import walk_batch_cases as wbc
 import walk_batch_worker as wbw
 from conftest import ROOT
 
@@ -20,7 +25,7 @@ pytestmark = pytest.mark.gpu
 
 WORKER = os.path.join(ROOT, 'tests', 'walk_batch_worker.py')
 WORKERS = 8
-_abnormal = []          # the first child that crashed or timed out
+_abnormal = wbc.ABNORMAL     # the first child that crashed or timed out, shared with the sibling file
 
 SETTINGS = [('walk_streams_1', {'SHEPSEG_WALK_STREAMS': '1'}), ('walk_streams_2', {'SHEPSEG_WALK_STREAMS': '2'}),
             ('default', {})]

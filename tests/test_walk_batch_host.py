@@ -3,7 +3,9 @@
 cannot start.  The program has its own main: nothing is preloaded and nothing is loaded into Python.  It asserts
 that every job ran exactly once, that no batch mixes classes or exceeds the job, block and residency caps, that
 the batch after a held launch carries all pending jobs of its class, that a launch error reaches exactly its
-batch and a per-job failure only its job, and it ends within its own 30-s alarm."""
+batch and a per-job failure only its job, that the workgroup counters hold the sum over the submitted jobs and
+the largest launch, that in rounds of unequal workgroup counts a replay above the block cap runs once and alone
+while the leader that skips it still takes every job that fits, and it ends within its own 30-s alarm."""
 import os
 import shutil
 import subprocess
