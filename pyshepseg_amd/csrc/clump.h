@@ -19,6 +19,7 @@
 #include "common.h"
 #include "scan.h"
 #include <stdlib.h>
+#include <math.h>
 
 struct BigInfo {
     uint32_t root, size, off, minc, maxc, maxr;
@@ -1137,7 +1138,9 @@ __device__ __forceinline__ void dfs_split_win(uint32_t *lab, const BigInfo &B, u
 // order[rank] = component index, largest first: the longest replays start first (LPT), which
 // shortens the makespan whenever there are more components than resident workgroups
 // counters[2] = how many of them do not fit the walker pool (bitmap above bmw_small words)
-// (mirror: the component count for the host, see PIN_MIRROR)
+// (mirror: for the host, see PIN_MIRROR: word 0 the component count, word 1 the sum of the component sizes,
+//  word 2 the largest size -- the replay's work and its critical path, which size the launch (run_clump);
+//  words 1 and 2 are written only when there is a component, and read only then)
 __global__ __launch_bounds__(256) void k_big_order(const BigInfo *__restrict__ big,
                                                    uint32_t *counters,
                                                    uint32_t *__restrict__ order, uint32_t ncols,
@@ -1149,12 +1152,18 @@ __global__ __launch_bounds__(256) void k_big_order(const BigInfo *__restrict__ b
     if (i >= nbig) return;
     if (dfs_bitmap_words(big[i], ncols) > bmw_small) atomicAdd(&counters[2], 1u);
     const uint32_t si = big[i].size;
-    uint32_t rank = 0;
+    uint32_t rank = 0, sum = 0, mx = 0;         // (a tile window has fewer than 2^32 pixels)
     for (uint32_t j = 0; j < nbig; j++) {
         const uint32_t sj = big[j].size;
         rank += (sj > si || (sj == si && j < i)) ? 1u : 0u;
+        sum += sj;
+        mx = sj > mx ? sj : mx;
     }
     order[rank] = i;
+    if (i == 0u && mirror) {
+        MIRROR_STORE(mirror + 1, sum);
+        MIRROR_STORE(mirror + 2, mx);
+    }
 }
 
 // One job per tile (several tiles' jobs may share a launch, see DfsBatch).  A workgroup holds DFS_WAVES independent walkers (one wavefront each) that
@@ -1175,8 +1184,32 @@ __global__ __launch_bounds__(256) void k_big_order(const BigInfo *__restrict__ b
 #define DFS_DBG_WORDS 20u        // SHEPSEG_DFS_STATS: 6 words per component + 11 of the DFS_PROF build
 #define DFS_GRAN_WORDS 512u          // granule = 2 KiB
 #define DFS_POOL_GRANS_DEFAULT 34u   // 68 KiB pool (+ 16 KiB of stack windows + the mask = 84 KiB)
+// Jobs sized by their work (dfs_job_blocks) put the largest components of a tile into few workgroups: eight of them
+// do not fit 68 KiB together, and their walkers waited for room for longer than they walked.  Such a process takes
+// the largest pool the 64-bit mask allows, 128 KiB: a third of the workgroups, each with all of its CU's LDS.
+#define DFS_POOL_GRANS_PACKED 64u
 #define DFS_ALLOC_SPINS 200000u
 #define DFS_MAX_BLOCKS 256u          // 2048 walkers: 8 per CU
+// A job cannot end before its largest component is walked (one component is one wavefront), so it needs no more
+// walkers than keep step with that one: sum of the sizes / (largest size * DFS_FILL), DFS_FILL = the share of the
+// critical path a walker is planned to be busy for (largest first from the counter: the LPT tail is what is left).
+// Jobs of up to DFS_PACK_MIN components keep a walker per component (at most two workgroups: nothing to gain).
+#ifndef DFS_FILL
+#define DFS_FILL 0.75
+#endif
+#define DFS_PACK_MIN (2u * DFS_WAVES)
+
+// workgroups of a replay job of nbig components of sum_px pixels, the largest of max_px, at the default of DFS_WAVES
+// walkers per workgroup
+static inline uint32_t dfs_job_blocks(uint32_t nbig, uint32_t sum_px, uint32_t max_px)
+{
+    uint32_t u = (nbig + DFS_WAVES - 1u) / DFS_WAVES;
+    u = u > DFS_MAX_BLOCKS ? DFS_MAX_BLOCKS : u;
+    if (nbig <= DFS_PACK_MIN || max_px == 0u) return u;
+    const double walkers = ceil((double)sum_px / ((double)max_px * DFS_FILL));
+    const double blocks = ceil(walkers / (double)DFS_WAVES);
+    return blocks < 1.0 ? 1u : blocks > (double)u ? u : (uint32_t)blocks;
+}
 
 // start granule of `need` contiguous free granules, or -1; wave-uniform, lane 0 talks to the mask
 __device__ __forceinline__ int dfs_pool_alloc(unsigned long long *mask, uint32_t need, uint32_t ngrans,
@@ -1508,10 +1541,13 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
     hipLaunchKernelGGL(k_big_order, dim3(grid_for(maxbig, 256)), dim3(256), 0, st, big, counters, order, ncols,
                        DFS_POOL_GRANS_DEFAULT * DFS_GRAN_WORDS, mir_nbig); KCHK(ctx);
     // the replay is a latency-bound phase: outside the fill gate.  The component count comes back
-    // first, so that the launch is sized exactly (a workgroup per DFS_WAVES components; every one of
-    // them reserves the whole walker pool in LDS, so none is launched for nothing).
+    // first, with the sum of the component sizes and the largest one, so that the launch is sized exactly (no more
+    // workgroups than the work needs beside its largest component; every one of them reserves the whole walker
+    // pool in LDS, so none is launched for nothing).
     HIPCHK(ctx, hipStreamSynchronize(st));
     const uint32_t nbig_h = *(volatile uint32_t *)mir_nbig;
+    const uint32_t sum_px_h = nbig_h ? *(volatile uint32_t *)(mir_nbig + 1) : 0u;
+    const uint32_t max_px_h = nbig_h ? *(volatile uint32_t *)(mir_nbig + 2) : 0u;
     fill_release(ctx, false);
     st = ctx->stream;
     // a stream-sharing worker hands the replay to the walker batcher: one launch carries every tile that is ready
@@ -1524,8 +1560,10 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
         dbg = bp<unsigned long long>(ctx->dbg);
     }
     if (nbig_h) {
-        static const uint32_t pool_grans = getenv("SHEPSEG_DFS_POOL") ? (uint32_t)atoi(getenv("SHEPSEG_DFS_POOL")) : DFS_POOL_GRANS_DEFAULT;
-        static const uint32_t per_wg = getenv("SHEPSEG_DFS_PER_WG") ? (uint32_t)atoi(getenv("SHEPSEG_DFS_PER_WG")) : DFS_WAVES;
+        static const bool per_wg_set = getenv("SHEPSEG_DFS_PER_WG") != nullptr;
+        static const uint32_t pool_grans = getenv("SHEPSEG_DFS_POOL") ? (uint32_t)atoi(getenv("SHEPSEG_DFS_POOL"))
+                                           : per_wg_set ? DFS_POOL_GRANS_DEFAULT : DFS_POOL_GRANS_PACKED;
+        static const uint32_t per_wg = per_wg_set ? (uint32_t)atoi(getenv("SHEPSEG_DFS_PER_WG")) : DFS_WAVES;
         static const int oldwalk = getenv("SHEPSEG_DFS_OLDWALK") ? atoi(getenv("SHEPSEG_DFS_OLDWALK")) : 0;
         const uint32_t pg = pool_grans < 1u ? 1u : pool_grans > 64u ? 64u : pool_grans;
         const uint32_t pw = per_wg < 1u ? 1u : per_wg > DFS_WAVES ? DFS_WAVES : per_wg;
@@ -1548,9 +1586,11 @@ static int run_clump(shp_ctx *ctx, const uint16_t *d_clus, uint32_t nrows, uint3
         }();
         (void)caps_set;
         // at most DFS_MAX_BLOCKS workgroups per tile (the rest of the components is pulled from the counter):
-        // every walker owns a slot of the snapshot buffer as large as the walker pool
+        // every walker owns a slot of the snapshot buffer as large as the walker pool.  By default the job is
+        // sized by its work (dfs_job_blocks); SHEPSEG_DFS_PER_WG, once set, gives a workgroup per `pw` components
         uint32_t nblk = (nbig_h + pw - 1u) / pw;
         nblk = nblk > DFS_MAX_BLOCKS ? DFS_MAX_BLOCKS : nblk;
+        if (!per_wg_set) nblk = dfs_job_blocks(nbig_h, sum_px_h, max_px_h);
         CHK(buf_ensure(ctx, ctx->snap, (size_t)nblk * pw * pg * DFS_GRAN_WORDS * 4u));
         DfsJob job;
         job.lab = lab; job.big = big; job.counters = counters; job.stackbuf = bp<uint32_t>(ctx->stack);

@@ -1,6 +1,7 @@
 """Timeline of the last bench step in a rocprofv3 kernel_trace.csv: per 20-ms bin, the number of
 streams with a kernel in flight, the share of the bin covered by GPU-filling kernels (>= 1024
-workgroups) and by the latency-bound ones (k_dfs_split, k_small_loop).  python tools/timeline.py TRACE.csv"""
+workgroups) and by the latency-bound ones (k_dfs_pool, k_small_loop), and for each of those two the share of the
+tile phase with a launch in flight.  python tools/timeline.py TRACE.csv"""
 import csv, sys, collections
 rows = []
 with open(sys.argv[1]) as fh:
@@ -31,6 +32,21 @@ F = [(s, e) for s, e, n, q, b in rows if b >= 1024 and not n.startswith(('k_dfs_
 Lt = [(s, e) for s, e, n, q, b in rows if n.startswith(('k_dfs_split', 'k_dfs_pool', 'k_small_loop'))]
 print('step span %.1f ms; sum of GPU-filling kernel durations %.1f ms; union %.1f ms' % (
     (t1 - t0) / 1e6, sum(e - s for s, e in F) / 1e6, cover(F, t0, t1) / 1e6))
+# the tile phase (first k_ccl_local to the end of the last latency-bound kernel) and what the two walker classes
+# hold of it: launches, the share of the phase with a launch in flight (union), time and workgroups per launch
+ccl = [s for s, e, n, q, b in rows if n.startswith('k_ccl_local')]
+if ccl and Lt:
+    p0, p1 = min(ccl), max(e for s, e in Lt)
+    print('tile phase %.1f ms' % ((p1 - p0) / 1e6))
+    for cls in ('k_dfs_pool', 'k_small_loop'):
+        K = [(s, e, b) for s, e, n, q, b in rows if n.startswith(cls)]
+        if K:
+            d = sorted((e - s) / 1e6 for s, e, b in K)
+            print('   %-13s %4d launches  in flight %.2f of the tile phase  ms per launch mean %.2f median %.2f max %.2f  '
+                  'workgroups mean %.1f most %d' % (cls, len(K), cover([(s, e) for s, e, b in K], p0, p1) / (p1 - p0),
+                                                    sum(d) / len(d), d[len(d) // 2], d[-1],
+                                                    sum(b for s, e, b in K) / len(K), max(b for s, e, b in K)))
+    print('   either        in flight %.2f of the tile phase' % (cover(Lt, p0, p1) / (p1 - p0)))
 for i in range(nb):
     lo, hi = t0 + i * BIN, min(t0 + (i + 1) * BIN, t1)
     nq = len({q for s, e, n, q, b in rows if e > lo and s < hi})
