@@ -155,9 +155,15 @@ static FillGate g_fill;
 // the chain context's).  From Q = 21 the round-4 sizes hold; below, what is left of Q after those three is
 // split two to one between fill and walker streams (the walker work of all ready tiles travels in one
 // launch per stream, walkbatch.h, so few walker streams carry many tiles); where Q cannot hold even that,
-// as at 4, the floors apply: a queue for each fill stream and one for the walker stream, the fourth for the
-// three others (reasoned, not yet swept on the GPU: LABNOTES "walker batches").
-#define FILL_FLOOR_DEFAULT 2
+// as at 4, the floors apply.  They were swept at 4 queues (LABNOTES "fill-stream hold"; three alternating processes a
+// side, medians of the steps): 2 + 1 536-539 ms, 3 + 1 488-491, 4 + 1 477-482.  At 2 + 1 the two fill streams are
+// held 0.88 of the tile phase, half of that between kernels (host round trips inside a borrow).  With four borrowers
+// the kernels of different tiles overlap and each runs about twice as long, but some filling kernel is running 0.92
+// of the tile phase where it was 0.77 (profiles/fill_hold_timeline_*.txt); one walker stream carries every ready tile
+// in one launch and is busy 0.98 of the tile phase either way.
+// Only Q = 4 was measured.  The floor also decides the fill count wherever the share above comes to less, that is
+// for every Q up to 7 (Q = 7: 3 -> 4; Q = 8 gets 4 anyway): there it is extrapolated, not swept.
+#define FILL_FLOOR_DEFAULT 4
 #define WALK_FLOOR_DEFAULT 1
 static inline int hw_queue_budget()
 {
