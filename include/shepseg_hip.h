@@ -687,6 +687,50 @@ int shp_nbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out);
 int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
                    double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out);
 
+/* ---- the neighbour table of a row-sharded raster (distributed.findSegmentNeighboursDistributed; csrc/dneighbours.h)
+ * The table above for a label raster whose rows are spread over the ranks, without gathering the labels.  The result
+ * is sharded by ID: a rank ends up with the finished CSR rows of the ids id_lo .. id_hi - 1 (its share; the shares
+ * partition 0 .. max_seg_id) -- whole rows, equal to those of the one-GPU table of the assembled raster.  The share
+ * table lives in buffers of its own: it is not the "finished table" of shp_nbr_reduce and has a serial of its own.
+ * shp_dnbr_local_dev starts a one-GPU accumulation internally, so it ends any one-GPU table of the context.
+ *  shp_dnbr_local_dev: the rank's nrows rows of ncols labels in device memory (nrows may be 0) and d_halo_row, the
+ *    raster's row after them (NULL when the raster ends there: it is the first row of the next rank that holds rows).
+ *    Pairs whose upper pixel lies in the rank's rows are counted, sorted and reduced to the rank's distinct pairs
+ *    and packed as 16-byte records (b, a, count low word, count high word), a < b, at most one per pair: the HOME
+ *    records (both ids in the share) stay in the context, the TRAVELLING ones are at *d_travel_out (context memory,
+ *    valid until the next shp_dnbr_local_dev).  *max_label_out: the largest label met; when it is above max_seg_id
+ *    nothing else is done (the counts are 0) and shp_dnbr_merge_dev fails.  counts_out[3]: distinct pairs, home
+ *    records, travelling records.
+ *  shp_dnbr_merge_dev: d_all holds `world` blocks of `slot` records, the all-gathered travelling records, counts[r]
+ *    (host) valid ones in block r.  The records with an id in the share are picked, joined with the home records,
+ *    sorted, reduced with 64-bit sums, and the CSR of the share is built: offsets (id_hi - id_lo + 1 int64 from 0),
+ *    neighbour ids ascending within a row, border lengths.  d_cols: 2 (max_seg_id + 1) int64 in device memory,
+ *    numNeighbours then borderLength; they are zeroed and the share's rows filled, so an integer all-reduce over the
+ *    ranks completes them.  *n_picked_out: records taken from d_all; *n_entries_out: entries of the share table.
+ *  shp_dnbr_download: the share table's three arrays to host memory.
+ *  shp_dnbr_upload: a share table from host memory (as downloaded; the caller vouches for its ids and order) becomes
+ *    the context's share table, with a new serial.
+ *  shp_dnbr_table_serial: as shp_nbr_table_serial, for the share table.  The serials of share tables and of one-GPU
+ *    tables come from one numbering, so no two tables of a process share one.
+ *  shp_dnbr_reduce_dev: shp_nbr_reduce over the share table.  col: the FULL column (host, max_seg_id + 1 values); row i
+ *    of the share is id id_lo + i, its own value col[id_lo + i].  d_out: device memory for the mask's statistics in
+ *    the order of their bits, max_seg_id + 1 values of 8 bytes each; zeroed, then the share's rows written (a row
+ *    without neighbours gets missing_value from this rank), so an integer all-reduce of the bit patterns assembles
+ *    the columns.  A row's additions run in the order csrc/nbrreduce.h states: the results are bit for bit those of
+ *    shp_nbr_reduce over the whole table.  dev_ms_out of all calls may be NULL; local and merge report the device
+ *    time of the build so far. */
+int shp_dnbr_local_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, const uint32_t *d_halo_row,
+                       int64_t max_seg_id, int four_connected, int64_t id_lo, int64_t id_hi, uint32_t *max_label_out,
+                       int64_t *counts_out, void **d_travel_out, double *dev_ms_out);
+int shp_dnbr_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, void *d_cols,
+                       int64_t *n_picked_out, int64_t *n_entries_out, double *dev_ms_out);
+int shp_dnbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths);
+int shp_dnbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *neighbours, const int64_t *border_lengths,
+                    int64_t max_seg_id, int64_t id_lo, int64_t id_hi, int64_t n_entries);
+int shp_dnbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out);
+int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
+                        double missing_value, uint32_t stat_mask, void *d_out, double *dev_ms_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

@@ -19,6 +19,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "colour.h"
 #include "neighbours.h"
 #include "nbrreduce.h"
+#include "dneighbours.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -106,7 +107,9 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo,
                  &ctx->nbr_ctr, &ctx->nbr_rec, &ctx->nbr_key, &ctx->nbr_val, &ctx->nbr_uidx, &ctx->nbr_ua, &ctx->nbr_ub,
                  &ctx->nbr_ucnt, &ctx->nbr_deg, &ctx->nbr_hoff, &ctx->nbr_loff, &ctx->nbr_offs, &ctx->nbr_ids,
-                 &ctx->nbr_lens, &ctx->nbrr_col, &ctx->nbrr_out, &ctx->nbrr_lrow, &ctx->nbrr_lcoff, &ctx->nbrr_part};
+                 &ctx->nbr_lens, &ctx->nbrr_col, &ctx->nbrr_out, &ctx->nbrr_lrow, &ctx->nbrr_lcoff, &ctx->nbrr_part,
+                 &ctx->dnbr_blk, &ctx->dnbr_cnt, &ctx->dnbr_home, &ctx->dnbr_trav, &ctx->dnbr_mrg, &ctx->dnbr_rcnt,
+                 &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff};
     *out = ctx;
     return SHP_OK;
 }
@@ -1510,6 +1513,88 @@ API int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows,
     for (int i = 0; i < NBRR_NSTATS; i++)
         if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
     return run_nbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
+}
+
+// ---- the neighbour table of a row-sharded raster, by id share (dneighbours.h) ------------------------------
+API int shp_dnbr_local_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, const uint32_t *d_halo_row,
+                           int64_t max_seg_id, int four_connected, int64_t id_lo, int64_t id_hi, uint32_t *max_label_out,
+                           int64_t *counts_out, void **d_travel_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!max_label_out || !counts_out || !d_travel_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    if (id_lo < 0 || id_hi < id_lo || id_hi > max_seg_id + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%lld", (long long)id_lo, (long long)id_hi, (long long)max_seg_id);
+    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_halo_row & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    CHK(run_dnbr_local(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, nrows > 0 ? d_halo_row : nullptr, (uint32_t)max_seg_id,
+                       four_connected, (uint32_t)id_lo, (uint32_t)id_hi, max_label_out, counts_out, d_travel_out));
+    if (dev_ms_out) *dev_ms_out = ctx->dnbr.dev_ms;
+    return 0;
+}
+
+API int shp_dnbr_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, void *d_cols,
+                           int64_t *n_picked_out, int64_t *n_entries_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dnbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no local step: shp_dnbr_local_dev must come first");
+    if (!d_cols || !n_picked_out || !n_entries_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (slot < 0 || world < 0 || (slot > 0 && world > 0 && (!d_all || !counts))) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (((uintptr_t)d_all & 15u) || ((uintptr_t)d_cols & 7u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
+    if (slot == 0) world = 0;
+    CHK(run_dnbr_merge(ctx, (const uint4 *)d_all, (unsigned long long)slot, (uint32_t)world, counts, (long long *)d_cols,
+                       n_picked_out, n_entries_out));
+    if (dev_ms_out) *dev_ms_out = ctx->dnbr.dev_ms;
+    return 0;
+}
+
+API int shp_dnbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths)
+{
+    CHK(enter(ctx));
+    if (ctx->dnbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev must come first");
+    if (!offsets || (ctx->dnbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_dnbr_download(ctx, offsets, neighbours, border_lengths);
+}
+
+API int shp_dnbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *neighbours, const int64_t *border_lengths,
+                        int64_t max_seg_id, int64_t id_lo, int64_t id_hi, int64_t n_entries)
+{
+    CHK(enter(ctx));
+    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    if (id_lo < 0 || id_hi < id_lo || id_hi > max_seg_id + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%lld", (long long)id_lo, (long long)id_hi, (long long)max_seg_id);
+    if (n_entries < 0 || n_entries >= (1ll << 40)) SHP_FAIL(ctx, SHP_ERR_ARG, "%lld entries", (long long)n_entries);
+    if (!offsets || (n_entries > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (offsets[0] != 0 || offsets[id_hi - id_lo] != n_entries)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "not a share table: the offsets must run from 0 to the number of entries");
+    return run_dnbr_upload(ctx, offsets, neighbours, border_lengths, (uint32_t)max_seg_id, (uint32_t)id_lo, (uint32_t)id_hi,
+                           (unsigned long long)n_entries);
+}
+
+API int shp_dnbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out)
+{
+    if (!ctx) return SHP_ERR_ARG;
+    ctx->err.clear();
+    if (!serial_out || !finished_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *serial_out = ctx->dnbr.serial;
+    *finished_out = ctx->dnbr.stage == 2 ? 1 : 0;
+    return 0;
+}
+
+API int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
+                            double missing_value, uint32_t stat_mask, void *d_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dnbr.stage != 2)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev or shp_dnbr_upload must come first");
+    if (!col || !d_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_out & 7u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    if (n_rows != (int64_t)ctx->dnbr.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
+    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    return run_dnbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, d_out, dev_ms_out);
 }
 
 // a column shared by rows over the ranks: shp_colour_stretch in steps (colour.h)

@@ -77,6 +77,19 @@ struct NbrState {
     double dev_ms = 0.0;
 };
 
+// the neighbour table of this rank's id share [id_lo, id_hi) of a row-sharded raster (dneighbours.h): rows
+// id_hi - id_lo, in dnbr_offs / dnbr_ids / dnbr_lens -- buffers of its own, so the one-GPU table (nbr_*) and the share
+// table do not displace each other.  serial: from the numbering of nbr_serial, new with every local step and
+// upload; list_serial: the share table whose long rows dnbr_lrow / dnbr_lcoff list.
+struct DNbrState {
+    int stage = 0;                  // 0 none, 1 local step done (home and travelling records packed), 2 share table built
+    uint32_t S = 0, id_lo = 0, id_hi = 0;
+    unsigned long long nlocal = 0, nhome = 0, ntrav = 0, nent = 0;
+    unsigned long long serial = 0, list_serial = 0;
+    uint32_t nlong = 0, nchunks = 0;
+    double dev_ms = 0.0;
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -95,9 +108,11 @@ struct shp_ctx {
         vflag, vlist, vredo,
         nbr_ctr, nbr_rec, nbr_key, nbr_val, nbr_uidx, nbr_ua, nbr_ub, nbr_ucnt, nbr_deg, nbr_hoff, nbr_loff, nbr_offs,
         nbr_ids, nbr_lens,
-        nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part;
+        nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part,
+        dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff;
     SegPointsState pts;
     NbrState nbr;
+    DNbrState dnbr;
     // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
     // has, new with every shp_nbr_begin and shp_nbr_upload (kept here: run_nbr_begin resets `nbr`); the list of the
     // table's long rows (nbrr_lrow, nbrr_lcoff) belongs to the table nbrr_list_serial

@@ -35,6 +35,9 @@
 //     thread per long row adds the chunks' records in chunk order.  The long rows and their chunks are listed once
 //     per table (a flag scan, a fill, a scan of the chunk counts: scan.h) and kept while the table is resident.
 //  k_nbrr_validate: the rules of an uploaded table (below), one launch.
+// The three reduction kernels take a row base (NbrrParams::row0): the table's row i is id row0 + i.  The one-GPU
+// table has row0 = 0; the share table of a row-sharded raster (dneighbours.h) holds the whole rows of the ids
+// row0 .. row0 + ns - 1, and since a row's order above depends on nothing but the row, its results are the same bits.
 #pragma once
 #include "common.h"
 #include "scan.h"
@@ -64,7 +67,9 @@ struct NbrrParams {
     const uint32_t *ids;
     const long long *lens;
     const double *col;
-    uint32_t ns;                // rows of the table and of the column: max_seg_id + 1
+    uint32_t ns;                // rows of the table: max_seg_id + 1, or the rows of an id share (dneighbours.h)
+    uint32_t row0;              // the id of the table's row 0: 0, or the share's first id.  Row i is id row0 + i: its own
+                                // value is col[row0 + i], its results go to out[..][row0 + i]; col and out span all ids
     int has_ign;
     double ign, missing;
     void *out[NBRR_NSTATS];     // device columns of ns rows (8 bytes each), nullptr where not asked for
@@ -125,6 +130,7 @@ __device__ __forceinline__ void nbrr_merge(NbrrAcc &a, const NbrrAcc &b)
 __device__ __forceinline__ void nbrr_store(const NbrrParams &p, uint32_t r, const NbrrAcc &a, bool own_ok)
 {
     const bool any = a.cnt > 0;
+    r += p.row0;
     if (p.out[NBRR_COUNT]) ((long long *)p.out[NBRR_COUNT])[r] = a.cnt;
     if (p.out[NBRR_BORDER]) ((long long *)p.out[NBRR_BORDER])[r] = a.bor;
     if (p.out[NBRR_MIN]) ((double *)p.out[NBRR_MIN])[r] = any ? a.mn : p.missing;
@@ -149,7 +155,7 @@ __global__ __launch_bounds__(256) void k_nbrr_short(NbrrParams p)
     const bool in = r < p.ns;
     const long long a = in ? p.offs[r] : s1, b = in ? p.offs[r + 1u] : s1;
     const bool mine = in && b - a <= (long long)NBRR_LONG;         // (a long row is written by k_nbrr_long_combine)
-    const double own = in ? p.col[r] : 0.0;
+    const double own = in ? p.col[p.row0 + r] : 0.0;
     const bool own_ok = !nbrr_ignored(own, p.has_ign, p.ign);
     NbrrAcc acc;
     nbrr_init(acc);
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(256) void k_nbrr_long(NbrrParams p, const uint32_t 
     const uint32_t r = lrow[lo], c = item - lcoff[lo];
     const long long a = p.offs[r] + (long long)c * (long long)NBRR_CHUNK, rowend = p.offs[r + 1u];
     const long long b = a + (long long)NBRR_CHUNK < rowend ? a + (long long)NBRR_CHUNK : rowend;
-    const double own = p.col[r];
+    const double own = p.col[p.row0 + r];
     const bool own_ok = !nbrr_ignored(own, p.has_ign, p.ign);
     NbrrAcc acc;
     nbrr_init(acc);
@@ -232,7 +238,7 @@ __global__ __launch_bounds__(256) void k_nbrr_long_combine(NbrrParams p, const u
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= nlong) return;
     const uint32_t r = lrow[k];
-    const bool own_ok = !nbrr_ignored(p.col[r], p.has_ign, p.ign);
+    const bool own_ok = !nbrr_ignored(p.col[p.row0 + r], p.has_ign, p.ign);
     NbrrAcc acc;
     nbrr_init(acc);
     for (uint32_t i = lcoff[k]; i < lcoff[k + 1u]; i++) {
@@ -378,15 +384,12 @@ static int run_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *
     return 0;
 }
 
-// the long rows of the resident table and their chunks, once per table
-static int nbrr_long_list(shp_ctx *ctx)
+// the long rows of a table of ns rows (offsets offs) and their chunks, into lrow / lcoff
+static int nbrr_long_list_of(shp_ctx *ctx, const long long *offs, uint32_t ns, DevBuf &b_lrow, DevBuf &b_lcoff,
+                             uint32_t *nlong_out, uint32_t *nchunks_out)
 {
-    if (ctx->nbrr_list_serial == ctx->nbr_serial) return 0;
-    const NbrState &s = ctx->nbr;
     hipStream_t st = ctx->stream;
-    const uint32_t ns = s.S + 1u;
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
-    const long long *offs = (const long long *)ctx->nbr_offs.p;
     CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
     CHK(buf_ensure(ctx, ctx->nbr_deg, (size_t)ns * 4));
     uint32_t *lidx = bp<uint32_t>(ctx->nbr_deg);
@@ -396,21 +399,49 @@ static int nbrr_long_list(shp_ctx *ctx)
     const uint32_t nlong = *(volatile uint32_t *)mir;
     uint32_t nchunks = 0;
     if (nlong) {
-        CHK(buf_ensure(ctx, ctx->nbrr_lrow, (size_t)nlong * 4));
-        CHK(buf_ensure(ctx, ctx->nbrr_lcoff, ((size_t)nlong + 1) * 4));
+        CHK(buf_ensure(ctx, b_lrow, (size_t)nlong * 4));
+        CHK(buf_ensure(ctx, b_lcoff, ((size_t)nlong + 1) * 4));
         hipLaunchKernelGGL(k_nbrr_long_fill, dim3(grid_for(ns, 256)), dim3(256), 0, st, offs, ns, (const uint32_t *)lidx,
-                           bp<uint32_t>(ctx->nbrr_lrow));
+                           bp<uint32_t>(b_lrow));
         KCHK(ctx);
-        NbrrChunksFn cf{offs, bp<uint32_t>(ctx->nbrr_lrow)};
-        uint32_t *lcoff = bp<uint32_t>(ctx->nbrr_lcoff);
+        NbrrChunksFn cf{offs, bp<uint32_t>(b_lrow)};
+        uint32_t *lcoff = bp<uint32_t>(b_lcoff);
         CHK(scan_exclusive(ctx, cf, nlong, lcoff, lcoff + nlong, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 1));
         HIPCHK(ctx, hipStreamSynchronize(st));
         nchunks = *(volatile uint32_t *)(mir + 1);
         if (nchunks < nlong) SHP_FAIL(ctx, SHP_ERR_STATE, "%u chunks for %u long rows", nchunks, nlong);
     }
-    ctx->nbrr_nlong = nlong;
-    ctx->nbrr_nchunks = nchunks;
+    *nlong_out = nlong;
+    *nchunks_out = nchunks;
+    return 0;
+}
+
+// the long rows of the resident table and their chunks, once per table
+static int nbrr_long_list(shp_ctx *ctx)
+{
+    if (ctx->nbrr_list_serial == ctx->nbr_serial) return 0;
+    CHK(nbrr_long_list_of(ctx, (const long long *)ctx->nbr_offs.p, ctx->nbr.S + 1u, ctx->nbrr_lrow, ctx->nbrr_lcoff,
+                          &ctx->nbrr_nlong, &ctx->nbrr_nchunks));
     ctx->nbrr_list_serial = ctx->nbr_serial;
+    return 0;
+}
+
+// the reduction's kernels over the table of p, its long rows listed in lrow / lcoff
+static int nbrr_launch(shp_ctx *ctx, const NbrrParams &p, const uint32_t *lrow, const uint32_t *lcoff, uint32_t nlong,
+                       uint32_t nchunks)
+{
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(k_nbrr_short, dim3(grid_for(p.ns, NBRR_ROWS)), dim3(256), 0, st, p);
+    KCHK(ctx);
+    if (nlong) {
+        CHK(buf_ensure(ctx, ctx->nbrr_part, (size_t)nchunks * sizeof(NbrrPart)));
+        hipLaunchKernelGGL(k_nbrr_long, dim3(grid_for(nchunks, 4)), dim3(256), 0, st, p, lrow, lcoff, nlong, nchunks,
+                           (NbrrPart *)ctx->nbrr_part.p);
+        KCHK(ctx);
+        hipLaunchKernelGGL(k_nbrr_long_combine, dim3(grid_for(nlong, 256)), dim3(256), 0, st, p, lrow, lcoff, nlong,
+                           (const NbrrPart *)ctx->nbrr_part.p);
+        KCHK(ctx);
+    }
     return 0;
 }
 
@@ -450,25 +481,15 @@ static int run_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int has_ign,
     p.lens = (const long long *)ctx->nbr_lens.p;
     p.col = d_col;
     p.ns = (uint32_t)ns;
+    p.row0 = 0u;
     p.has_ign = has_ign;
     p.ign = ign;
     p.missing = missing;
     int slot = 0;
     for (int i = 0; i < NBRR_NSTATS; i++)
         p.out[i] = ((mask >> i) & 1u) ? (void *)((char *)ctx->nbrr_out.p + (size_t)(slot++) * ns * 8) : nullptr;
-    hipLaunchKernelGGL(k_nbrr_short, dim3(grid_for(ns, NBRR_ROWS)), dim3(256), 0, st, p);
-    KCHK(ctx);
-    if (ctx->nbrr_nlong) {
-        const uint32_t nlong = ctx->nbrr_nlong, nchunks = ctx->nbrr_nchunks;
-        CHK(buf_ensure(ctx, ctx->nbrr_part, (size_t)nchunks * sizeof(NbrrPart)));
-        const uint32_t *lrow = bp<uint32_t>(ctx->nbrr_lrow), *lcoff = bp<uint32_t>(ctx->nbrr_lcoff);
-        hipLaunchKernelGGL(k_nbrr_long, dim3(grid_for(nchunks, 4)), dim3(256), 0, st, p, lrow, lcoff, nlong, nchunks,
-                           (NbrrPart *)ctx->nbrr_part.p);
-        KCHK(ctx);
-        hipLaunchKernelGGL(k_nbrr_long_combine, dim3(grid_for(nlong, 256)), dim3(256), 0, st, p, lrow, lcoff, nlong,
-                           (const NbrrPart *)ctx->nbrr_part.p);
-        KCHK(ctx);
-    }
+    CHK(nbrr_launch(ctx, p, bp<uint32_t>(ctx->nbrr_lrow), bp<uint32_t>(ctx->nbrr_lcoff), ctx->nbrr_nlong,
+                    ctx->nbrr_nchunks));
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     for (int i = 0; i < NBRR_NSTATS; i++)
         if (p.out[i]) HIPCHK(ctx, hipMemcpyAsync(outs[i], p.out[i], ns * 8, hipMemcpyDeviceToHost, st));

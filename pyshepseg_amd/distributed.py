@@ -74,6 +74,8 @@ recoded overlap strip, None for no neighbour; win: tiling.trimmedWindow's six nu
       writeOutputDistributed, after finish.
   colourTableOnDevice, renderOnDevice (optional): writeColorTableFromRatColumnsDistributed,
       renderColourTableDistributed.
+  neighboursOnDevice (optional): findSegmentNeighboursDistributed; reduceOverNeighboursDistributed needs only
+      the engine's context ``c``.
 """
 import collections
 import collections.abc
@@ -1729,6 +1731,302 @@ def _userFuncSpatialStats(c, comm, d_seg, d_band, dtypeCode, nRows, nCols, rowRa
 # ------------------------------------------------------------------------------------------
 # HIP engine: this rank's GPU
 # ------------------------------------------------------------------------------------------
+# ---- the segment-neighbour table and its reductions on the row-sharded output (csrc/dneighbours.h) -------------
+def _rowsCoverError(ranges, nRows):
+    """None when the ranks' output rows tile 0..nRows without a gap (they are known not to overlap)"""
+    at = 0
+    for (a, b) in sorted((a, b) for (a, b) in ranges if b > a):
+        if a != at:
+            return "rows %d..%d of the raster are held by no rank" % (at, a)
+        at = b
+    if at != nRows:
+        return "rows %d..%d of the raster are held by no rank" % (at, nRows)
+    return None
+
+
+def deviceNeighbours(c, comm, d_seg, nRows, nCols, rowRange, maxSegId, fourConnected=True, fetch=True, info=None):
+    """The device-resident data path of findSegmentNeighboursDistributed for ONE rank: output rows rowRange =
+    (outLo, outHi) of an nRows x nCols label raster (nRows None: the largest outHi of the ranks) at d_seg (uint32)
+    in the HBM of context ``c``; comm: allgather_obj, allgather_dev, allreduce_dev_i64.  maxSegId bounds the labels
+    (DistResult.maxSegId) and is the table's last row.
+
+    Every rank counts the pairs whose upper pixel lies in its rows, reading one halo row below them (the first row
+    of the next rank that holds rows: spatialHaloPlan, one all-gather of a row per rank), and reduces them to its
+    distinct pairs (shp_dnbr_local_dev).  Pairs with both ids in the rank's own id share (idRange) stay home; the
+    others travel in one all-gather of 16-byte records, slot = the largest count of the ranks.  Every rank then
+    picks the records with an id in its share, adds its home records and builds the CSR rows of its share
+    (shp_dnbr_merge_dev); one integer all-reduce completes the numNeighbours / borderLength columns.  Control data
+    travels first, so every error that depends on a rank's data is raised on every rank: a label above maxSegId
+    (the message names the largest over all ranks), output rows shared by several ranks (SHEPSEG_SHARD=tiles).
+
+    Returns a neighbours.SegmentNeighboursShare whose table stays in the context for reduceOverNeighboursDistributed
+    (fetch=False: its arrays and columns are None, nothing is copied to the host).  ``info`` (a dict, optional)
+    receives 'halo_rows' (of all ranks), 'records_local' (this rank's distinct pairs), 'records_home',
+    'records_sent', 'records_picked' (taken from the gathered blocks, this rank's own among them), 'exchange_bytes'
+    (16 x the records sent by all ranks + 4 nCols x the ranks that sent a halo row: what every rank receives) and
+    'entries' (of this share)."""
+    from . import neighbours
+    Err = neighbours.PyShepSegNeighboursError
+    t0 = time.perf_counter()
+    err = None
+    try:
+        if int(maxSegId) != maxSegId or maxSegId < 0 or maxSegId >= 0xFFFFFFFE:
+            err = "maxSegId must be an integer in 0..2^32 - 3 (got {})".format(maxSegId)
+    except (TypeError, ValueError):
+        err = "maxSegId must be an integer (got {!r})".format(maxSegId)
+    ctrl = comm.allgather_obj((int(rowRange[0]), int(rowRange[1]), err, None if err else int(maxSegId), int(nCols),
+                               bool(fourConnected)))                                          # control data
+    errs = [x[2] for x in ctrl if x[2]]
+    if errs:
+        raise Err(errs[0])
+    if len({x[3:] for x in ctrl}) != 1:
+        raise Err("the ranks pass different maxSegId, columns or connectivity: %s" % sorted({x[3:] for x in ctrl}))
+    (S, nCols) = (int(maxSegId), int(nCols))
+    ranges = [(x[0], x[1]) for x in ctrl]
+    if nRows is None:
+        nRows = max(b for (a, b) in ranges)
+    nRows = int(nRows)
+    err = disjointRowsError(ranges, 'findSegmentNeighboursDistributed') or _rowsCoverError(ranges, nRows)
+    if err:
+        raise Err(err)
+    plan = spatialHaloPlan(ranges, comm.rank, nRows, 0, 1)
+    (lo, hi) = ranges[comm.rank]
+    h = max(hi - lo, 0)
+    (idLo, idHi) = idRange(comm.rank, comm.world, S)
+    L = c._L
+    timings = {}
+    toFree = []
+
+    def alloc(nbytes):
+        p = tiling._devAlloc(c, max(int(nbytes), 16))
+        toFree.append((p, max(int(nbytes), 16)))
+        return p
+    try:
+        # ---- the halo row: every rank's first row in one all-gather
+        d_halo = None
+        rowB = nCols * 4
+        haloSenders = 0
+        if comm.world > 1 and nCols > 0:
+            d_send = alloc(rowB)
+            d_rows = alloc(comm.world * rowB)
+            if plan['send']:
+                c.check(L.shp_dev_copy(c.handle, d_send, ctypes.c_void_p(d_seg), rowB))
+            comm.allgather_dev(d_send.value, d_rows.value, rowB)
+            haloSenders = sum(1 for (a, b) in ranges if b > a)
+            if plan['recvBelow']:
+                (_row, src, _slotRow, _n) = plan['recvBelow'][0]
+                d_halo = ctypes.c_void_p(d_rows.value + src * rowB)
+        timings['halo'] = time.perf_counter() - t0
+        # ---- own rows: distinct pairs, home and travelling records
+        t1 = time.perf_counter()
+        (maxLabel, pTrav, ms) = (ctypes.c_uint32(0), ctypes.c_void_p(), ctypes.c_double(0))
+        cnt = numpy.zeros(3, dtype=numpy.int64)
+        c.check(L.shp_dnbr_local_dev(c.handle, ctypes.c_void_p(d_seg if h else None), h, nCols, d_halo if h else None, S,
+                                     int(bool(fourConnected)), idLo, idHi, ctypes.byref(maxLabel), _lib.ptr(cnt),
+                                     ctypes.byref(pTrav), ctypes.byref(ms)))
+        got = comm.allgather_obj((int(maxLabel.value), int(cnt[2]), plan['below']))
+        worst = max(g[0] for g in got)
+        if worst > S:
+            raise Err("segment id {} is above maxSegId {}".format(worst, S))
+        timings['local'] = time.perf_counter() - t1
+        # ---- the travelling records of all ranks
+        t1 = time.perf_counter()
+        counts = [g[1] for g in got]
+        slot = max(counts)
+        d_all = None
+        if slot > 0:
+            d_send = alloc(slot * 16)
+            d_all = alloc(comm.world * slot * 16)
+            if cnt[2]:
+                c.check(L.shp_dev_copy(c.handle, d_send, pTrav, int(cnt[2]) * 16))
+            comm.allgather_dev(d_send.value, d_all.value, slot * 16)
+        timings['exchange'] = time.perf_counter() - t1
+        # ---- the rows of this rank's id share
+        t1 = time.perf_counter()
+        ns = S + 1
+        d_cols = alloc(2 * ns * 8)
+        (picked, nent) = (ctypes.c_int64(0), ctypes.c_int64(0))
+        cnts = numpy.array(counts, dtype=numpy.uint32)
+        c.check(L.shp_dnbr_merge_dev(c.handle, d_all, slot, comm.world, _lib.ptr(cnts), d_cols, ctypes.byref(picked),
+                                     ctypes.byref(nent), ctypes.byref(ms)))
+        if comm.world > 1:
+            comm.allreduce_dev_i64(d_cols.value, 2 * ns)
+        timings['merge'] = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        (offsets, nbrs, lens, columns) = (None, None, None, None)
+        if fetch:
+            offsets = numpy.empty(idHi - idLo + 1, dtype=numpy.int64)
+            nbrs = numpy.empty(nent.value, dtype=numpy.uint32)
+            lens = numpy.empty(nent.value, dtype=numpy.int64)
+            c.check(L.shp_dnbr_download(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens)))
+            cols = numpy.empty((2, ns), dtype=numpy.int64)
+            c.check(L.shp_dev_download(c.handle, _lib.ptr(cols), d_cols, cols.nbytes))
+            columns = {'numNeighbours': cols[0].copy(), 'borderLength': cols[1].copy()}
+        timings['download'] = time.perf_counter() - t1
+    finally:
+        for (p, sz) in toFree:
+            tiling._devRelease(c, p, sz)
+    timings['total'] = time.perf_counter() - t0
+    figures = dict(halo_rows=int(sum(g[2] for g in got)), records_local=int(cnt[0]), records_home=int(cnt[1]),
+                   records_sent=int(cnt[2]), records_picked=int(picked.value),
+                   exchange_bytes=16 * int(sum(counts)) + rowB * haloSenders, entries=int(nent.value))
+    if info is not None:
+        info.update(figures)
+    share = neighbours.SegmentNeighboursShare((idLo, idHi), S, bool(fourConnected), offsets, nbrs, lens, columns,
+                                              timings=timings, deviceMs=ms.value, info=figures)
+    (share.residentSerial, share._residentCtx) = (_shareSerial(c), c.handle.value)
+    return share
+
+
+def _shareSerial(c):
+    """the serial of the context's share table, None when it has none"""
+    (serial, finished) = (ctypes.c_uint64(0), ctypes.c_int(0))
+    c.check(c._L.shp_dnbr_table_serial(c.handle, ctypes.byref(serial), ctypes.byref(finished)))
+    return serial.value if finished.value else None
+
+
+def findSegmentNeighboursDistributed(engine, comm, dres, fourConnected=True, info=None):
+    """neighbours.findSegmentNeighbours of the label raster that runDistributed(engine, comm, ...) /
+    doTiledShepherdSegmentationDistributed(keepOutput=True) left sharded by rows over the ranks (a
+    HipEngine(keepOutput=True); ``dres`` its DistResult), without gathering it.  The table comes back sharded by id:
+    every rank gets a neighbours.SegmentNeighboursShare with the finished rows of the ids of its idRange, equal to
+    those rows of the one-GPU table of the mosaic, and the complete numNeighbours / borderLength columns
+    (deviceNeighbours).  A communicator that is not on the device carries the device buffers through the host
+    (comm.HostStagedDev).  Output rows shared by several ranks (SHEPSEG_SHARD=tiles) are refused on every rank:
+    run the segmentation with SHEPSEG_SHARD=rows.  ``info``: see deviceNeighbours."""
+    from . import comm as _comm
+    from . import neighbours
+    if not hasattr(engine, 'neighboursOnDevice'):
+        raise neighbours.PyShepSegNeighboursError("the distributed neighbour table needs a device engine (HipEngine)")
+    dcomm = comm if getattr(comm, 'onDevice', False) else _comm.HostStagedDev(comm, engine.c)
+    return engine.neighboursOnDevice(dcomm, dres.maxSegId, fourConnected=fourConnected, info=info)
+
+
+def _checkShare(share):
+    """the rules a share table must keep before its ids index a column on the device"""
+    from . import neighbours
+    Err = neighbours.PyShepSegNeighboursError
+    (lo, hi) = share.idRange
+    off = numpy.asarray(share.offsets)
+    if not (0 <= lo <= hi <= share.maxSegId + 1) or len(off) != hi - lo + 1:
+        raise Err("the share's offsets do not have the length of its id range")
+    if off[0] != 0 or off[-1] != len(share.neighbours) or (numpy.diff(off) < 0).any():
+        raise Err("the share's offsets must run from 0 to the number of entries and not decrease")
+    if len(share.neighbours) and int(numpy.max(share.neighbours)) > share.maxSegId:
+        raise Err("the share names a neighbour above maxSegId {}".format(share.maxSegId))
+
+
+def reduceOverNeighboursDistributed(engine, comm, share, columnSelections, ignoreValue=None, missingStatsValue=-9999):
+    """neighbours.reduceOverNeighbours over the table findSegmentNeighboursDistributed left sharded by id: the same
+    dictionary outName -> array of maxSegId + 1 rows, complete on every rank and bit for bit the one-GPU result.
+    ``share``: this rank's neighbours.SegmentNeighboursShare; ``columnSelections`` as in reduceOverNeighbours, the
+    FULL columns (maxSegId + 1 values, the same on every rank -- the statistics' columns are).  ``engine``: a
+    HipEngine, or any object whose ``c`` is this rank's context.
+
+    Every rank reduces the rows of its share (their neighbours' values come from the full column), each row in the
+    summation order of csrc/nbrreduce.h, into full-length device columns that are 0 elsewhere; ONE integer
+    all-reduce over all selected outputs assembles them (float64 as bit patterns: adding zeros is exact).  The
+    arguments are checked by reduceOverNeighbours' rules before any collective; the column lengths and selections
+    are then compared between the ranks and a difference raises on all of them.  A share table that is no longer on
+    the device (another one was built or uploaded since) is uploaded again from the share's arrays."""
+    from . import comm as _comm
+    from . import neighbours
+    Err = neighbours.PyShepSegNeighboursError
+    if not isinstance(share, neighbours.SegmentNeighboursShare) or share.offsets is None:
+        raise Err("share must be a SegmentNeighboursShare with its arrays (findSegmentNeighboursDistributed)")
+    (idLo, idHi) = share.idRange
+    (plan, ignore, missing) = neighbours._checkReduceSelections(share, idHi - idLo, columnSelections, ignoreValue,
+                                                                missingStatsValue)
+    mine = (int(share.maxSegId), [(len(col), ctype, sorted({bit for (_n, bit, _d) in picked}))
+                                  for (col, ctype, picked) in plan], ignore, missing)
+    got = comm.allgather_obj(mine)
+    if any(g != got[0] and not _sameReduceCall(g, got[0]) for g in got):
+        raise Err("the ranks pass different columns or selections to reduceOverNeighboursDistributed "
+                  "(column lengths %s)" % [[x[0] for x in g[1]] for g in got])
+    t0 = time.perf_counter()
+    c = engine.c
+    L = c._L
+    dcomm = comm if getattr(comm, 'onDevice', False) else _comm.HostStagedDev(comm, c)
+    timings = {'upload': 0.0, 'uploaded': False, 'deviceMs': 0.0}
+    serial = _shareSerial(c)
+    if serial is None or share.residentSerial != serial or share._residentCtx != c.handle.value:
+        _checkShare(share)
+        offsets = numpy.ascontiguousarray(share.offsets, dtype=numpy.int64)
+        nbrs = numpy.ascontiguousarray(share.neighbours, dtype=numpy.uint32)
+        lens = numpy.ascontiguousarray(share.borderLengths, dtype=numpy.int64)
+        (share.residentSerial, share._residentCtx) = (None, None)
+        c.check(L.shp_dnbr_upload(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens), share.maxSegId, idLo, idHi,
+                                  len(nbrs)))
+        (share.residentSerial, share._residentCtx) = (_shareSerial(c), c.handle.value)
+        timings['upload'] = time.perf_counter() - t0
+        timings['uploaded'] = True
+    t1 = time.perf_counter()
+    ns = share.maxSegId + 1
+    bitsOf = [sorted({bit for (_n, bit, _d) in picked}) for (_col, _ctype, picked) in plan]
+    nOut = sum(len(b) for b in bitsOf)
+    d_out = tiling._devAlloc(c, nOut * ns * 8)
+    try:
+        at = 0
+        for ((column, ctype, _picked), bits) in zip(plan, bitsOf):
+            mask = sum(1 << b for b in bits)
+            ms = ctypes.c_double(0)
+            c.check(L.shp_dnbr_reduce_dev(c.handle, _lib.ptr(column), ctype, ns, int(ignore is not None),
+                                          0.0 if ignore is None else ignore, missing, mask,
+                                          ctypes.c_void_p(d_out.value + at * ns * 8), ctypes.byref(ms)))
+            timings['deviceMs'] += ms.value
+            at += len(bits)
+        if dcomm.world > 1:
+            dcomm.allreduce_dev_i64(d_out.value, nOut * ns)
+        block = numpy.empty((nOut, ns), dtype=numpy.int64)
+        c.check(L.shp_dev_download(c.handle, _lib.ptr(block), d_out, block.nbytes))
+    finally:
+        tiling._devRelease(c, d_out, nOut * ns * 8)
+    out = {}
+    at = 0
+    for ((_column, _ctype, picked), bits) in zip(plan, bitsOf):
+        for (outName, bit, dtype) in picked:
+            row = block[at + bits.index(bit)]
+            out[outName] = row.view(dtype).copy()        # (outNames that ask for the same statistic get copies)
+        at += len(bits)
+    timings['reduce'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    share.reduceTimings = timings
+    return out
+
+
+def _sameReduceCall(a, b):
+    """two ranks' (maxSegId, [(length, type, bits)], ignore, missing) agree (NaN ignore values compare equal)"""
+    def same(x, y):
+        return x == y or (isinstance(x, float) and isinstance(y, float) and x != x and y != y)
+    return a[0] == b[0] and a[1] == b[1] and same(a[2], b[2]) and same(a[3], b[3])
+
+
+def gatherSegmentNeighbours(comm, share):
+    """The whole table on every rank, as a neighbours.SegmentNeighbours, from the ranks' shares (host arrays through
+    the communicator: for small tables and for tests).  offsets, neighbours and borderLengths equal
+    neighbours.findSegmentNeighbours of the whole raster."""
+    from . import neighbours
+    mine = [numpy.asarray(share.idRange, dtype=numpy.int64), numpy.asarray(share.offsets, dtype=numpy.int64),
+            numpy.asarray(share.neighbours, dtype=numpy.uint32), numpy.asarray(share.borderLengths, dtype=numpy.int64)]
+    gather = getattr(comm, 'allgather_arrays', None) or comm.allgather_obj
+    parts = sorted(gather(mine), key=lambda p: (int(p[0][0]), int(p[0][1])))
+    S = share.maxSegId
+    offsets = numpy.zeros(S + 2, dtype=numpy.int64)
+    (at, base) = (0, 0)
+    for (rng, off, _n, _l) in parts:
+        (lo, hi) = (int(rng[0]), int(rng[1]))
+        if lo != at or len(off) != hi - lo + 1:
+            raise neighbours.PyShepSegNeighboursError("the ranks' shares do not partition the ids (share %d..%d after "
+                                                      "id %d)" % (lo, hi, at))
+        offsets[lo:hi + 1] = base + off
+        (at, base) = (hi, base + int(off[-1]))
+    if at != S + 1:
+        raise neighbours.PyShepSegNeighboursError("the ranks' shares end at id %d, not at maxSegId %d" % (at - 1, S))
+    nb = neighbours.SegmentNeighbours(offsets, numpy.concatenate([p[2] for p in parts]),
+                                      numpy.concatenate([p[3] for p in parts]), S, share.fourConnected)
+    return nb
+
+
 class HipEngine(object):
     """Holds rows [yLo, yHi) of the raster in HBM (a DeviceRaster created by `makeSlice`),
     segments this rank's tiles with pooled worker contexts and stitches them on the device.
@@ -2049,6 +2347,13 @@ class HipEngine(object):
         d_out = (self._lastOut.value if hasattr(self._lastOut, 'value') else int(self._lastOut)) if held else 0
         return deviceSubset(self.c, comm, d_out, None, self.nCols, (self.outLo, self.outHi), maxSegId, tlx, tly, xs,
                             ys, mask=mask, tileSize=tileSize)
+
+    def neighboursOnDevice(self, comm, maxSegId, fourConnected=True, info=None):
+        """findSegmentNeighboursDistributed's path for this rank's output rows (deviceNeighbours)."""
+        held = self.outHi > self.outLo
+        d_out = _addr(self._lastOut) if held else 0
+        return deviceNeighbours(self.c, comm, d_out, None, self.nCols, (self.outLo, self.outHi), maxSegId,
+                                fourConnected=fourConnected, info=info)
 
     def localOutput(self):
         out = numpy.empty((self.outHi - self.outLo, self.nCols), dtype=numpy.uint32)

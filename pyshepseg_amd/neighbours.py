@@ -10,6 +10,10 @@ Definition, all integers: two pixels are adjacent when one is the E or S neighbo
 both non-zero, adds 1 to the border length of ``(a, b)`` and of ``(b, a)``.  Label 0 is no segment: it has
 no neighbours and is nobody's neighbour.  Ids without pixels have empty rows.
 
+On the row-sharded output of a multi-rank run the same table is built without gathering the labels, sharded by
+segment id (distributed.findSegmentNeighboursDistributed -> SegmentNeighboursShare, csrc/dneighbours.h), and columns
+are reduced over it there (distributed.reduceOverNeighboursDistributed).
+
 There is no CPU fallback: without a GPU the call fails as every entry point of this package does.
 """
 import ctypes
@@ -69,6 +73,42 @@ class SegmentNeighbours(object):
         if len(rows):
             total[rows] = numpy.add.reduceat(self.borderLengths, self.offsets[rows])
         return {'numNeighbours': num, 'borderLength': total}
+
+
+class SegmentNeighboursShare(object):
+    """One rank's part of the table of distributed.findSegmentNeighboursDistributed: the finished rows of the ids
+    ``idRange`` = (idLo, idHi) (distributed.idRange), which are the rows idLo .. idHi - 1 of the one-GPU table of
+    the whole raster.
+
+    ``offsets``: int64, ``idHi - idLo + 1`` row boundaries from 0 (row i is id ``idLo + i``); ``neighbours``:
+    uint32 ids, ascending within a row; ``borderLengths``: int64.  ``columns``: {'numNeighbours', 'borderLength'}
+    of ALL ids, complete on every rank: the arrays SegmentNeighbours.columns gives.  ``timings``: seconds per step;
+    ``deviceMs``: GPU time of this rank's kernels.  ``info``: the figures of the exchange
+    (distributed.deviceNeighbours)."""
+    def __init__(self, idRange, maxSegId, fourConnected, offsets, neighbours, borderLengths, columns, timings=None,
+                 deviceMs=None, info=None):
+        self.idRange = (int(idRange[0]), int(idRange[1]))
+        self.maxSegId = int(maxSegId)
+        self.fourConnected = bool(fourConnected)
+        self.offsets = offsets
+        self.neighbours = neighbours
+        self.borderLengths = borderLengths
+        self.columns = columns
+        self.timings = timings if timings is not None else {}
+        self.deviceMs = deviceMs
+        self.info = info if info is not None else {}
+        self.residentSerial = None
+        self._residentCtx = None
+        self.reduceTimings = {}
+
+    def neighboursOf(self, segId):
+        """(ids, lengths) of one segment of the share: views of ``neighbours`` and ``borderLengths``"""
+        segId = int(segId)
+        (lo, hi) = self.idRange
+        if segId < lo or segId >= hi:
+            raise PyShepSegNeighboursError("segment id {} is outside this rank's share {}..{}".format(segId, lo, hi - 1))
+        (a, b) = (int(self.offsets[segId - lo]), int(self.offsets[segId - lo + 1]))
+        return (self.neighbours[a:b], self.borderLengths[a:b])
 
 
 def _checkArgs(segfile, maxSegId):
@@ -180,10 +220,16 @@ def _checkReduceArgs(nb, columnSelections, ignoreValue, missingStatsValue):
     that can be refused before the GPU is touched"""
     if not isinstance(nb, SegmentNeighbours):
         raise PyShepSegNeighboursError("nb must be a SegmentNeighbours")
+    return _checkReduceSelections(nb, int(nb.maxSegId) + 1, columnSelections, ignoreValue, missingStatsValue)
+
+
+def _checkReduceSelections(nb, tableRows, columnSelections, ignoreValue, missingStatsValue):
+    """_checkReduceArgs for a table ``nb`` of ``tableRows`` rows whose columns have maxSegId + 1 values (the whole
+    table, or a SegmentNeighboursShare)"""
     missing = _number(missingStatsValue, 'missingStatsValue')
     ignore = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
     nrows = int(nb.maxSegId) + 1
-    if len(nb.offsets) != nrows + 1 or len(nb.neighbours) != len(nb.borderLengths):
+    if len(nb.offsets) != tableRows + 1 or len(nb.neighbours) != len(nb.borderLengths):
         raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
     try:
         selections = [(column, list(stats)) for (column, stats) in columnSelections]
