@@ -687,6 +687,40 @@ int shp_nbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out);
 int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
                    double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out);
 
+/* ---- touching segments of one class merged into one (neighbours.mergeSegments; csrc/nbrmerge.h) ---------------
+ * keys[i] is the class of id i.  Entry (a, b, w) of the finished table is a LINK when keys[a] == keys[b], that key is
+ * not the ignored one, w >= min_border and (with seg_size) both ids have pixels; a GROUP is a connected component of
+ * the links over the ids 1 .. max_seg_id.  With seg_size an id of size 0 belongs to no group and recodes to 0; without
+ * it every id is a vertex and an id without links is a group of one.  Groups are numbered 1 .. M in ascending order of
+ * their smallest member.  The table is taken to name every pair from both sides, as every table built here does: only
+ * its entries with a < b are read.  All of it is integer work and a pure function of the arguments.
+ *  shp_nbr_merge: keys and seg_size (may be NULL) are host columns of n_rows == max_seg_id + 1 int64; has_ignore != 0:
+ *    ids of key ignore_key link to nobody.  The links are hooked into a union-find forest on the device, the roots
+ *    flagged, scanned and numbered.  *max_group_out = M; counters_out (may be NULL) [2]: the links, the entries with
+ *    a < b; dev_ms_out (may be NULL) [2]: device time of the hook, of the renumbering.  The groups stay in the context,
+ *    in buffers of their own, until the next shp_nbr_merge.
+ *  shp_nbr_merge_groups: the groups to host memory, a NULL pointer skipping its array: recode (max_seg_id + 1 uint32,
+ *    recode[0] == 0), representative (M + 1 uint32: the smallest old id of a group, row 0 is 0), group_size (M + 1
+ *    int64: the old ids of a group, row 0 is 0), hist (M + 1 int64: the sums of seg_size, row 0 the pixels of the ids
+ *    that recode to 0; without seg_size what shp_nbr_merge_recode_dev has counted so far).
+ *  shp_nbr_merge_contract: every entry (a, b, w), a < b, whose ends recode to different non-zero ids becomes a record
+ *    (recode a, recode b, w); the records go through the sort and reduction of shp_nbr_finish, and the table over
+ *    0 .. M that results REPLACES the table the groups were found in as the context's finished table, with a new
+ *    serial: shp_nbr_download and shp_nbr_reduce then work on it.  SHP_ERR_STATE when that table is no longer the
+ *    finished one.  *n_entries_out: its entries; *records_out: the records handed to the sort; a border length of
+ *    2^32 or more is SHP_ERR_ARG.  dev_ms_out (may be NULL): device time of the call.
+ *  shp_nbr_merge_recode_dev: d_out[p] = recode[d_seg[p]] for npix labels in device memory (both 4-byte aligned, not
+ *    overlapping).  A label above max_seg_id is not looked up and its pixel becomes 0; *bad_label_out: 0, or the
+ *    largest such label.  count_hist != 0: the new ids are counted into hist in the same pass (only for groups found
+ *    without seg_size: SHP_ERR_ARG otherwise).  dev_ms_out (may be NULL): device time of the kernel. */
+int shp_nbr_merge(shp_ctx *ctx, const int64_t *keys, int64_t n_rows, int has_ignore, int64_t ignore_key,
+                  int64_t min_border, const int64_t *seg_size, uint32_t *max_group_out, int64_t *counters_out,
+                  double *dev_ms_out);
+int shp_nbr_merge_groups(shp_ctx *ctx, uint32_t *recode, uint32_t *representative, int64_t *group_size, int64_t *hist);
+int shp_nbr_merge_contract(shp_ctx *ctx, int64_t *n_entries_out, int64_t *records_out, double *dev_ms_out);
+int shp_nbr_merge_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, uint32_t *d_out, int count_hist,
+                             uint32_t *bad_label_out, double *dev_ms_out);
+
 /* ---- the neighbour table of a row-sharded raster (distributed.findSegmentNeighboursDistributed; csrc/dneighbours.h)
  * The table above for a label raster whose rows are spread over the ranks, without gathering the labels.  The result
  * is sharded by ID: a rank ends up with the finished CSR rows of the ids id_lo .. id_hi - 1 (its share; the shares

@@ -219,6 +219,12 @@ _SIGS = {
     'shp_nbr_table_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
     'shp_nbr_reduce': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,
                                   _vp, _c.POINTER(_c.c_double)]),
+    'shp_nbr_merge': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64, _vp, _c.POINTER(_c.c_uint32), _vp,
+                                 _vp]),
+    'shp_nbr_merge_groups': (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    'shp_nbr_merge_contract': (_c.c_int, [_vp, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double)]),
+    'shp_nbr_merge_recode_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int, _c.POINTER(_c.c_uint32),
+                                            _c.POINTER(_c.c_double)]),
     'shp_dnbr_local_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
                                       _c.POINTER(_c.c_uint32), _vp, _c.POINTER(_vp), _c.POINTER(_c.c_double)]),
     'shp_dnbr_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _vp, _c.POINTER(_c.c_int64),

@@ -19,6 +19,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "colour.h"
 #include "neighbours.h"
 #include "nbrreduce.h"
+#include "nbrmerge.h"
 #include "dneighbours.h"
 #include "comm.h"
 
@@ -109,7 +110,9 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->nbr_ucnt, &ctx->nbr_deg, &ctx->nbr_hoff, &ctx->nbr_loff, &ctx->nbr_offs, &ctx->nbr_ids,
                  &ctx->nbr_lens, &ctx->nbrr_col, &ctx->nbrr_out, &ctx->nbrr_lrow, &ctx->nbrr_lcoff, &ctx->nbrr_part,
                  &ctx->dnbr_blk, &ctx->dnbr_cnt, &ctx->dnbr_home, &ctx->dnbr_trav, &ctx->dnbr_mrg, &ctx->dnbr_rcnt,
-                 &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff};
+                 &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff,
+                 &ctx->mrg_ctr, &ctx->mrg_key, &ctx->mrg_size, &ctx->mrg_par, &ctx->mrg_root, &ctx->mrg_idx,
+                 &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist};
     *out = ctx;
     return SHP_OK;
 }
@@ -1513,6 +1516,51 @@ API int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows,
     for (int i = 0; i < NBRR_NSTATS; i++)
         if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
     return run_nbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
+}
+
+// ---- touching segments of one class merged into one (nbrmerge.h) -------------------------------------------
+API int shp_nbr_merge(shp_ctx *ctx, const int64_t *keys, int64_t n_rows, int has_ignore, int64_t ignore_key,
+                      int64_t min_border, const int64_t *seg_size, uint32_t *max_group_out, int64_t *counters_out,
+                      double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    ctx->mrg.stage = 0;
+    if (ctx->nbr.stage != 2)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    if (!keys || !max_group_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n_rows != (int64_t)ctx->nbr.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
+    if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
+    return run_nbr_merge(ctx, keys, has_ignore, ignore_key, min_border, seg_size, max_group_out, counters_out, dev_ms_out);
+}
+
+API int shp_nbr_merge_groups(shp_ctx *ctx, uint32_t *recode, uint32_t *representative, int64_t *group_size, int64_t *hist)
+{
+    CHK(enter(ctx));
+    if (ctx->mrg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no groups: shp_nbr_merge must come first");
+    return run_nbr_merge_groups(ctx, recode, representative, group_size, hist);
+}
+
+API int shp_nbr_merge_contract(shp_ctx *ctx, int64_t *n_entries_out, int64_t *records_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!n_entries_out || !records_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctx->mrg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no groups: shp_nbr_merge must come first");
+    if (ctx->mrg.contracted || ctx->nbr.stage != 2 || ctx->nbr_serial != ctx->mrg.table_serial)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "the table the groups were found in is no longer the context's finished table");
+    return run_nbr_merge_contract(ctx, n_entries_out, records_out, dev_ms_out);
+}
+
+API int shp_nbr_merge_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, uint32_t *d_out, int count_hist,
+                                 uint32_t *bad_label_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->mrg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no groups: shp_nbr_merge must come first");
+    if (npix < 0 || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (npix > 0 && (!d_seg || !d_out)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_out & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    if (count_hist && ctx->mrg.has_size) SHP_FAIL(ctx, SHP_ERR_ARG, "the histogram holds the sums of seg_size: nothing to count");
+    return run_nbr_merge_recode(ctx, d_seg, (size_t)npix, d_out, count_hist, bad_label_out, dev_ms_out);
 }
 
 // ---- the neighbour table of a row-sharded raster, by id share (dneighbours.h) ------------------------------

@@ -90,6 +90,17 @@ struct DNbrState {
     double dev_ms = 0.0;
 };
 
+// the groups of neighbours.mergeSegments between shp_nbr_merge and the calls that use them (nbrmerge.h), in buffers
+// of their own (mrg_*): recode of S + 1 rows, representative / group size / histogram of M + 1.  table_serial: the
+// table the groups were found in; contracted: that table has been replaced by the groups' own.
+struct MrgState {
+    int stage = 0;                  // 0 none, 1 groups known
+    uint32_t S = 0, M = 0;
+    unsigned long long links = 0, half = 0;     // links; entries with a < b
+    unsigned long long table_serial = 0;
+    bool has_size = false, contracted = false;
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -109,12 +120,14 @@ struct shp_ctx {
         nbr_ctr, nbr_rec, nbr_key, nbr_val, nbr_uidx, nbr_ua, nbr_ub, nbr_ucnt, nbr_deg, nbr_hoff, nbr_loff, nbr_offs,
         nbr_ids, nbr_lens,
         nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part,
-        dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff;
+        dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff,
+        mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist;
     SegPointsState pts;
     NbrState nbr;
+    MrgState mrg;
     DNbrState dnbr;
     // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
-    // has, new with every shp_nbr_begin and shp_nbr_upload (kept here: run_nbr_begin resets `nbr`); the list of the
+    // has, new with every shp_nbr_begin, shp_nbr_upload and shp_nbr_merge_contract (kept here: run_nbr_begin resets `nbr`); the list of the
     // table's long rows (nbrr_lrow, nbrr_lcoff) belongs to the table nbrr_list_serial
     unsigned long long nbr_serial = 0, nbrr_list_serial = 0;
     uint32_t nbrr_nlong = 0, nbrr_nchunks = 0;

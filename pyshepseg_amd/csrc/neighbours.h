@@ -398,24 +398,14 @@ static int run_nbr_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrow
     SHP_FAIL(ctx, SHP_ERR_STATE, "a row block's records did not fit the buffer sized for them");
 }
 
-// The table of everything accumulated: offsets (S + 2 int64), neighbours and lengths (2 U entries) stay in the
-// context's nbr_offs / nbr_ids / nbr_lens for run_nbr_download.  *bad_out: 0, or the largest label above a given
-// max_seg_id (then nothing is built).
-static int run_nbr_finish(shp_ctx *ctx, uint32_t *S_out, int64_t *nent_out, uint32_t *bad_out)
+// The table over the ids 0 .. S of the first n records of nbr_rec (ids 1 .. S, a < b): steps 2 and 3 of the header.
+// Offsets (S + 2 int64), neighbours and lengths (2 U entries) stay in the context's nbr_offs / nbr_ids / nbr_lens;
+// the state becomes a finished table.  (nbrmerge.h builds the table of merged segments through it.)
+static int nbr_build_table(shp_ctx *ctx, uint32_t S, uint32_t n)
 {
     NbrState &s = ctx->nbr;
     hipStream_t st = ctx->stream;
-    *bad_out = 0u;
-    *nent_out = 0;
-    uint32_t S = s.max_label;
-    if (s.given >= 0) {
-        S = (uint32_t)s.given;
-        if (s.max_label > S) { *bad_out = s.max_label; *S_out = S; return 0; }
-    }
-    if (S >= 0xfffffffeu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
-    *S_out = S;
     const size_t ns = (size_t)S + 1;
-    const uint32_t n = (uint32_t)s.used;
     const int bits = bits_for(S);
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
@@ -504,6 +494,24 @@ static int run_nbr_finish(shp_ctx *ctx, uint32_t *S_out, int64_t *nent_out, uint
     s.S = S;
     s.nent = 2ull * U;
     s.stage = 2;
+    return 0;
+}
+
+// The table of everything accumulated, for run_nbr_download.  *bad_out: 0, or the largest label above a given
+// max_seg_id (then nothing is built).
+static int run_nbr_finish(shp_ctx *ctx, uint32_t *S_out, int64_t *nent_out, uint32_t *bad_out)
+{
+    NbrState &s = ctx->nbr;
+    *bad_out = 0u;
+    *nent_out = 0;
+    uint32_t S = s.max_label;
+    if (s.given >= 0) {
+        S = (uint32_t)s.given;
+        if (s.max_label > S) { *bad_out = s.max_label; *S_out = S; return 0; }
+    }
+    if (S >= 0xfffffffeu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
+    *S_out = S;
+    CHK(nbr_build_table(ctx, S, (uint32_t)s.used));
     *nent_out = (int64_t)s.nent;
     return 0;
 }

@@ -14,6 +14,10 @@ On the row-sharded output of a multi-rank run the same table is built without ga
 segment id (distributed.findSegmentNeighboursDistributed -> SegmentNeighboursShare, csrc/dneighbours.h), and columns
 are reduced over it there (distributed.reduceOverNeighboursDistributed).
 
+``reduceOverNeighbours`` computes per-segment columns over the table's rows; ``mergeSegments`` acts on a merge
+candidate: under a column of class codes, touching segments of one class become one object -- new ids, the recoded
+raster and the table of the merged objects (csrc/nbrmerge.h).
+
 There is no CPU fallback: without a GPU the call fails as every entry point of this package does.
 """
 import ctypes
@@ -209,6 +213,28 @@ def residentTableSerial():
     return _tableSerial(_lib.ctx())
 
 
+def _makeResident(c, nb, timings):
+    """``nb`` becomes the context's finished table unless it still is: then, and for a table built by hand, the three
+    arrays are uploaded and checked on the device.  timings: 'upload', 'uploaded' and 'deviceMs' are brought up to date"""
+    t0 = time.perf_counter()
+    L = c._L
+    serial = _tableSerial(c)
+    if serial is None or nb.residentSerial != serial or nb._residentCtx != c.handle.value:
+        offsets = numpy.ascontiguousarray(nb.offsets, dtype=numpy.int64)
+        nbrs = numpy.ascontiguousarray(nb.neighbours, dtype=numpy.uint32)
+        lens = numpy.ascontiguousarray(nb.borderLengths, dtype=numpy.int64)
+        ms = ctypes.c_double(0)
+        (nb.residentSerial, nb._residentCtx) = (None, None)
+        rc = L.shp_nbr_upload(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens), int(nb.maxSegId), len(nbrs),
+                              ctypes.byref(ms))
+        if rc != 0:
+            raise PyShepSegNeighboursError((L.shp_last_error(c.handle) or b'').decode())
+        (nb.residentSerial, nb._residentCtx) = (_tableSerial(c), c.handle.value)
+        timings['upload'] = time.perf_counter() - t0
+        timings['uploaded'] = True
+        timings['deviceMs'] += ms.value
+
+
 def _number(value, name):
     if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, (int, float, numpy.integer, numpy.floating)):
         raise PyShepSegNeighboursError("{} must be a number (got {!r})".format(name, value))
@@ -291,21 +317,7 @@ def reduceOverNeighbours(nb, columnSelections, ignoreValue=None, missingStatsVal
     c = _lib.ctx()
     L = c._L
     timings = {'upload': 0.0, 'uploaded': False, 'deviceMs': 0.0}
-    serial = _tableSerial(c)
-    if serial is None or nb.residentSerial != serial or nb._residentCtx != c.handle.value:
-        offsets = numpy.ascontiguousarray(nb.offsets, dtype=numpy.int64)
-        nbrs = numpy.ascontiguousarray(nb.neighbours, dtype=numpy.uint32)
-        lens = numpy.ascontiguousarray(nb.borderLengths, dtype=numpy.int64)
-        ms = ctypes.c_double(0)
-        (nb.residentSerial, nb._residentCtx) = (None, None)
-        rc = L.shp_nbr_upload(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens), int(nb.maxSegId), len(nbrs),
-                              ctypes.byref(ms))
-        if rc != 0:
-            raise PyShepSegNeighboursError((L.shp_last_error(c.handle) or b'').decode())
-        (nb.residentSerial, nb._residentCtx) = (_tableSerial(c), c.handle.value)
-        timings['upload'] = time.perf_counter() - t0
-        timings['uploaded'] = True
-        timings['deviceMs'] += ms.value
+    _makeResident(c, nb, timings)
     t1 = time.perf_counter()
     out = {}
     nrows = int(nb.maxSegId) + 1
@@ -331,3 +343,224 @@ def reduceOverNeighbours(nb, columnSelections, ignoreValue=None, missingStatsVal
     timings['total'] = time.perf_counter() - t0
     nb.reduceTimings = timings
     return out
+
+
+# ---- touching segments of one class merged into one (csrc/nbrmerge.h) ------------------------------------------
+class MergedSegments(object):
+    """The result of mergeSegments.
+
+    ``recode``: uint32, ``nb.maxSegId + 1`` rows, old id -> new id (0 for id 0 and, with ``segSize``, for ids without
+    pixels); ``maxSegId``: M, the number of groups; ``representative``: uint32, ``M + 1`` rows, the smallest old id of
+    every group; ``groupSize``: int64, the old ids in it (row 0 of both is 0); ``hist``: int64 pixel counts of the
+    new ids as the segmentation's ``hist`` holds them, None when neither ``segSize`` nor ``segfile`` was given;
+    ``neighbours``: the SegmentNeighbours of the groups, resident on the device; ``links``: the table's entries a < b
+    that joined two segments; ``recordsSorted``: the entries a < b between different groups, handed to the sort;
+    ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels, ``stepDeviceMs`` the same per step (hook,
+    renumber, contract, recode); ``segimg``: the recoded raster when ``segfile`` was an array and no ``outfile`` was
+    given; ``outDev``: the recoded raster in device memory when the labels were there, in the form findSegmentNeighbours
+    accepts (tiling.freeDeviceOutput releases it)."""
+    def __init__(self):
+        self.recode = None
+        self.maxSegId = 0
+        self.representative = None
+        self.groupSize = None
+        self.hist = None
+        self.neighbours = None
+        self.links = 0
+        self.recordsSorted = 0
+        self.timings = {}
+        self.deviceMs = 0.0
+        self.stepDeviceMs = {}
+        self.segimg = None
+        self.outDev = None
+
+
+def _integer(value, name):
+    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, (int, numpy.integer)):
+        raise PyShepSegNeighboursError("{} must be an integer (got {!r})".format(name, value))
+    return int(value)
+
+
+def _integerColumn(column, name, nrows):
+    """a 1-D integer column of nrows values as contiguous int64"""
+    column = numpy.asarray(column)
+    if column.ndim != 1:
+        raise PyShepSegNeighboursError("{} must be a 1-D array (got {} dimensions)".format(name, column.ndim))
+    if column.dtype.kind not in 'iu':
+        raise PyShepSegNeighboursError("{} has dtype {}: an integer type wanted".format(name, column.dtype))
+    if len(column) != nrows:
+        raise PyShepSegNeighboursError("{} has {} rows, the table maxSegId + 1 = {}".format(name, len(column), nrows))
+    return numpy.ascontiguousarray(column.astype(numpy.int64, copy=False))
+
+
+def _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile):
+    """(keys int64, ignore or None, minBorder, sizes int64 or None, the raster as _checkArgs gives it or None):
+    everything that can be refused before the GPU is touched"""
+    if not isinstance(nb, SegmentNeighbours):
+        raise PyShepSegNeighboursError("nb must be a SegmentNeighbours")
+    nrows = int(nb.maxSegId) + 1
+    if len(nb.offsets) != nrows + 1 or len(nb.neighbours) != len(nb.borderLengths):
+        raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
+    keys = _integerColumn(keyColumn, 'keyColumn', nrows)
+    ignore = None
+    if ignoreKey is not None:
+        ignore = _integer(ignoreKey, 'ignoreKey')
+        if ignore < -(1 << 63) or ignore >= (1 << 64):
+            raise PyShepSegNeighboursError("ignoreKey {} is no 64-bit integer".format(ignore))
+        if ignore >= (1 << 63):
+            ignore -= 1 << 64           # (as a uint64 key column is read)
+    minBorder = _integer(minBorder, 'minBorder')
+    if minBorder < 1:
+        raise PyShepSegNeighboursError("minBorder must be at least 1 (got {})".format(minBorder))
+    minBorder = min(minBorder, (1 << 63) - 1)       # (no border length is larger)
+    sizes = None
+    if segSize is not None:
+        sizes = _integerColumn(segSize, 'segSize', nrows)
+        if len(sizes) and int(sizes.min()) < 0:
+            raise PyShepSegNeighboursError("segSize holds a negative count")
+    if outfile is not None and not (isinstance(outfile, str) and outfile.endswith('.npy')):
+        raise PyShepSegNeighboursError("outfile must be None or a .npy path")
+    raster = None
+    if segfile is None:
+        if outfile is not None:
+            raise PyShepSegNeighboursError("outfile needs a segfile to recode")
+    else:
+        raster = _checkArgs(segfile, None)[:4]
+        if isinstance(segfile, str) and outfile is None:
+            raise PyShepSegNeighboursError("a .npy segfile is recoded into a file: outfile is required")
+    return (keys, ignore, minBorder, sizes, raster)
+
+
+def mergeSegments(nb, keyColumn, ignoreKey=None, minBorder=1, segSize=None, segfile=None, outfile=None,
+                  chunkPixels=None):
+    """
+    Touching segments of one class become one object, on the GPU: a MergedSegments.
+
+    ``nb`` is a SegmentNeighbours (uploaded when it is not the table on the device, as reduceOverNeighbours has it);
+    ``keyColumn`` a 1-D integer array of ``maxSegId + 1`` values, the class of every segment, read as int64.  Entry
+    (a, b, w) of the table is a link when ``key[a] == key[b]``, ``key[a] != ignoreKey`` and ``w >= minBorder``; a group
+    is a connected component of the links over the ids 1..maxSegId, so a path of links joins two segments whose own
+    border is below ``minBorder``.  ``segSize`` (``maxSegId + 1`` pixel counts, such as the segmentation's ``hist``):
+    an id of size 0 belongs to no group and recodes to 0; without it every id is a vertex and one with an empty row
+    is a group of one.  Groups are numbered 1..M in ascending order of their smallest member.  The table must name
+    every pair from both sides, as every table of findSegmentNeighbours does.
+
+    The contracted table (every entry between two groups adds its length to the groups' border) becomes the table
+    resident on the device: ``result.neighbours`` goes into reduceOverNeighbours without an upload, ``nb`` is
+    uploaded again when it is used.  When ``nb`` is the table of a raster, ``result.neighbours`` is array for array
+    ``findSegmentNeighbours(recode[raster], nb.fourConnected, maxSegId=M)``.
+
+    ``segfile`` (what findSegmentNeighbours takes) is recoded as well, in row blocks of ``chunkPixels`` pixels: an
+    array comes back as ``result.segimg`` or goes to ``outfile`` (a ``.npy`` path); a ``.npy`` path needs ``outfile``;
+    labels kept on the device are recoded into a second device raster, ``result.outDev``, unless ``outfile`` is
+    given.  A label above ``nb.maxSegId`` raises PyShepSegNeighboursError with the largest such label.  Without
+    ``segSize`` the new ``hist`` is counted in that pass.
+    """
+    (keys, ignore, minBorder, sizes, raster) = _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile,
+                                                                outfile)
+    t0 = time.perf_counter()
+    c = _lib.ctx()
+    L = c._L
+    res = MergedSegments()
+    timings = {'upload': 0.0, 'uploaded': False, 'deviceMs': 0.0}
+    _makeResident(c, nb, timings)
+    S = int(nb.maxSegId)
+    # the groups
+    t1 = time.perf_counter()
+    (M, counters, ms2) = (ctypes.c_uint32(0), numpy.zeros(2, dtype=numpy.int64), numpy.zeros(2, dtype=numpy.float64))
+    c.check(L.shp_nbr_merge(c.handle, _lib.ptr(keys), S + 1, int(ignore is not None), 0 if ignore is None else ignore,
+                            minBorder, None if sizes is None else _lib.ptr(sizes), ctypes.byref(M), _lib.ptr(counters),
+                            _lib.ptr(ms2)))
+    M = M.value
+    timings['merge'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    res.recode = numpy.empty(S + 1, dtype=numpy.uint32)
+    res.representative = numpy.empty(M + 1, dtype=numpy.uint32)
+    res.groupSize = numpy.empty(M + 1, dtype=numpy.int64)
+    if sizes is not None:
+        res.hist = numpy.empty(M + 1, dtype=numpy.int64)
+    c.check(L.shp_nbr_merge_groups(c.handle, _lib.ptr(res.recode), _lib.ptr(res.representative), _lib.ptr(res.groupSize),
+                                   None if res.hist is None else _lib.ptr(res.hist)))
+    timings['groups'] = time.perf_counter() - t1
+    # their table
+    t1 = time.perf_counter()
+    (nent, nrec, msc) = (ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0))
+    (nb.residentSerial, nb._residentCtx) = (None, None)
+    c.check(L.shp_nbr_merge_contract(c.handle, ctypes.byref(nent), ctypes.byref(nrec), ctypes.byref(msc)))
+    timings['contract'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    offsets = numpy.empty(M + 2, dtype=numpy.int64)
+    nbrs = numpy.empty(nent.value, dtype=numpy.uint32)
+    lens = numpy.empty(nent.value, dtype=numpy.int64)
+    c.check(L.shp_nbr_download(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens)))
+    timings['download'] = time.perf_counter() - t1
+    res.neighbours = SegmentNeighbours(offsets, nbrs, lens, M, nb.fourConnected, recordsSorted=nrec.value,
+                                       deviceMs=msc.value)
+    (res.neighbours.residentSerial, res.neighbours._residentCtx) = (_tableSerial(c), c.handle.value)
+    res.maxSegId = M
+    res.links = int(counters[0])
+    res.recordsSorted = nrec.value
+    res.stepDeviceMs = {'hook': float(ms2[0]), 'renumber': float(ms2[1]), 'contract': msc.value, 'recode': 0.0}
+    # the raster
+    if raster is not None:
+        t1 = time.perf_counter()
+        _recodeRaster(c, res, raster, S, outfile, chunkPixels, countHist=sizes is None)
+        timings['recode'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    res.deviceMs = timings.pop('deviceMs') + sum(res.stepDeviceMs.values())
+    res.timings = timings
+    return res
+
+
+def _recodeRaster(c, res, raster, S, outfile, chunkPixels, countHist):
+    """the label raster through the groups' recode on the device, in the row blocks of tilingstats._ChunkSource"""
+    L = c._L
+    (seg, devSeg, nrows, ncols) = raster
+    if chunkPixels is None:
+        chunkPixels = tilingstats.STATS_CHUNK_PIXELS
+    rowsPerChunk = max(1, min(max(nrows, 1), int(chunkPixels) // max(ncols, 1)))
+    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
+    (writer, block, out, devOut) = (None, None, None, None)
+    nbytes = nrows * ncols * 4
+    worst = 0
+    try:
+        if outfile is not None:
+            writer = tiling._NpyRowWriter(outfile, nrows, ncols)
+            block = numpy.empty((min(rowsPerChunk, nrows), ncols), dtype=numpy.uint32)
+        elif devSeg is not None:
+            devOut = tiling._devAlloc(c, nbytes)
+        else:
+            out = numpy.empty((nrows, ncols), dtype=numpy.uint32)
+        for y0 in range(0, nrows, rowsPerChunk):
+            y1 = min(nrows, y0 + rowsPerChunk)
+            n = (y1 - y0) * ncols
+            if n == 0:
+                break
+            (dseg, _planes) = src.chunk(y0, y1)
+            if devOut is not None:
+                dout = ctypes.c_void_p(devOut.value + 4 * y0 * ncols)
+            else:
+                # (the output starts at the labels' offset from a 16-byte boundary: the kernel then stores whole vectors)
+                dout = ctypes.c_void_p(src.scratch(0, n * 4 + 16).value + (dseg.value & 15))
+            (bad, ms) = (ctypes.c_uint32(0), ctypes.c_double(0))
+            c.check(L.shp_nbr_merge_recode_dev(c.handle, dseg, n, dout, int(countHist), ctypes.byref(bad), ctypes.byref(ms)))
+            res.stepDeviceMs['recode'] += ms.value
+            worst = max(worst, bad.value)
+            if devOut is None and not worst:
+                dest = block[:y1 - y0] if writer is not None else out[y0:y1]
+                c.check(L.shp_dev_download(c.handle, _lib.ptr(dest), dout, n * 4))
+                if writer is not None:
+                    writer.writeRows(y0, y1, dest)
+        if worst:
+            raise PyShepSegNeighboursError("segment id {} is above maxSegId {}".format(worst, S))
+        if countHist:
+            res.hist = numpy.empty(res.maxSegId + 1, dtype=numpy.int64)
+            c.check(L.shp_nbr_merge_groups(c.handle, None, None, None, _lib.ptr(res.hist)))
+        (res.segimg, res.outDev) = (out, None if devOut is None else (devOut.value, nrows, ncols, nbytes))
+        devOut = None
+    finally:
+        if writer is not None:
+            writer.close()
+        src.close()
+        if devOut is not None:
+            tiling._devRelease(c, devOut, nbytes)
