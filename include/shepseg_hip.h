@@ -698,7 +698,7 @@ int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int
  *    ids of key ignore_key link to nobody.  The links are hooked into a union-find forest on the device, the roots
  *    flagged, scanned and numbered.  *max_group_out = M; counters_out (may be NULL) [2]: the links, the entries with
  *    a < b; dev_ms_out (may be NULL) [2]: device time of the hook, of the renumbering.  The groups stay in the context,
- *    in buffers of their own, until the next shp_nbr_merge.
+ *    in buffers of their own, until the next shp_nbr_merge or shp_nbr_merge_similar.
  *  shp_nbr_merge_groups: the groups to host memory, a NULL pointer skipping its array: recode (max_seg_id + 1 uint32,
  *    recode[0] == 0), representative (M + 1 uint32: the smallest old id of a group, row 0 is 0), group_size (M + 1
  *    int64: the old ids of a group, row 0 is 0), hist (M + 1 int64: the sums of seg_size, row 0 the pixels of the ids
@@ -720,6 +720,56 @@ int shp_nbr_merge_groups(shp_ctx *ctx, uint32_t *recode, uint32_t *representativ
 int shp_nbr_merge_contract(shp_ctx *ctx, int64_t *n_entries_out, int64_t *records_out, double *dev_ms_out);
 int shp_nbr_merge_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, uint32_t *d_out, int count_hist,
                              uint32_t *bad_label_out, double *dev_ms_out);
+
+/* ---- touching segments that look alike merged into one (neighbours.mergeSimilarSegments; csrc/nbrmerge.h) -------
+ * shp_nbr_merge with another link rule; everything after the links is shp_nbr_merge's.  cols: n_cols (1 to 8) host
+ * columns of n_rows == max_seg_id + 1 float64.  A value is IGNORED when it is NaN or (has_ignore_value != 0) equals
+ * ignore_value; an id with an ignored value in any column links to nobody.  d2(a, b) = the sum over the columns, in
+ * their order and from +0.0, of t * t with t = x[a] - x[b], every operation rounded to float64 once.  Entry (a, b, w)
+ * is a CANDIDATE when w >= min_border, both ids have pixels (seg_size, may be NULL), d2 is finite and -- with keys
+ * (may be NULL) -- keys[a] == keys[b] and that key is not the ignored one.
+ *   mutual_nearest == 0: a candidate is a link when d2 <= thr2 (has_threshold must be set).  The groups are the
+ *     connected components: single linkage.
+ *   mutual_nearest != 0: best[a] is the candidate neighbour of row a with the smallest d2, the smallest id among
+ *     equals; a candidate is a link when best[a] == b, best[b] == a and (has_threshold != 0) d2 <= thr2.  Groups have
+ *     one or two members.  Every row is read from its own side: the table must name every pair from both sides.
+ * thr2 is the squared distance (>= 0, +inf allowed: every finite d2 passes).  Device memory beyond shp_nbr_merge's:
+ * one record of n_cols float64 per id, and for the mutual rule 12 bytes per id.  max_group_out and counters_out as
+ * shp_nbr_merge; dev_ms_out (may be NULL) [3]: device time of the hook (with the two passes that find best), of the
+ * renumbering, of laying the columns out as records.  The groups are left in the context exactly where shp_nbr_merge
+ * leaves them: shp_nbr_merge_groups, _contract and _recode_dev follow as they follow shp_nbr_merge. */
+int shp_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int n_cols, int64_t n_rows, int has_ignore_value,
+                          double ignore_value, int has_threshold, double thr2, int mutual_nearest, const int64_t *keys,
+                          int has_ignore_key, int64_t ignore_key, int64_t min_border, const int64_t *seg_size,
+                          uint32_t *max_group_out, int64_t *counters_out, double *dev_ms_out);
+
+/* ---- columns of the old ids carried to the groups of a merge (neighbours.aggregateToGroups; csrc/nbragg.h) -----
+ * The groups of a merge have a serial, new with every shp_nbr_merge / shp_nbr_merge_similar, from the numbering of
+ * the tables' serials.  Their MEMBER LIST is a CSR over the new ids 0 .. M: offsets (M + 2 int64, offsets[0] ==
+ * offsets[1] == 0) and the old ids of every group in ascending order; ids that recode to 0 are in no group.  It is
+ * kept in buffers of its own until the next merge call and does not touch the finished neighbour table.
+ *  shp_nbr_groups_serial: *groups_serial_out: the serial of the groups the context holds (0: none);
+ *    *members_serial_out: the serial of the groups whose member list it holds (0: none).
+ *  shp_nbr_members_build: recode == NULL: the member list of the resident groups, built unless it is there already.
+ *    Otherwise recode is a host column of n_rows uint32 with values 0 .. max_group and recode[0] == 0 (SHP_ERR_ARG
+ *    if not): it is uploaded, the groups' sizes are counted and the list is built; it gets a serial of its own.  The
+ *    list is a pure function of recode, so both ways give the same arrays.  *serial_out: the list's serial;
+ *    *n_members_out: its entries; dev_ms_out (may be NULL): device time of the build.
+ *  shp_nbr_members_download: offsets (M + 2 int64) and members (n_members uint32) to host memory.
+ *  shp_nbr_aggregate: one column of the OLD ids (host; ctype and n_rows as shp_nbr_reduce, n_rows == the recode's
+ *    rows) reduced per group over the members whose value is not ignored.  weights: host, n_rows int64 >= 0, or NULL
+ *    (every weight 1).  stat_mask bits / outs slots (host, M + 1 rows of 8 bytes): 0 count, 1 weight (sum of the
+ *    weights), both int64; 2 min, 3 max; 4 sum: int64, exact and wrapping, for ctype 2, float64 otherwise; 5 mean =
+ *    (float64 sum) / count; 6 weightedmean = (sum of float64(w) * v, each product rounded) / (sum w).  Row 0 and every
+ *    group without a value (for weightedmean also: weights that sum to 0) hold missing_value in the float statistics
+ *    and 0 in the integer ones.  The float sums run over a group's members in the order csrc/nbrreduce.h states for a
+ *    row of that length, so a group's result depends on nothing but the group. */
+int shp_nbr_groups_serial(shp_ctx *ctx, uint64_t *groups_serial_out, uint64_t *members_serial_out);
+int shp_nbr_members_build(shp_ctx *ctx, const uint32_t *recode, int64_t n_rows, int64_t max_group, uint64_t *serial_out,
+                          int64_t *n_members_out, double *dev_ms_out);
+int shp_nbr_members_download(shp_ctx *ctx, int64_t *offsets, uint32_t *members);
+int shp_nbr_aggregate(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, const int64_t *weights, int has_ignore,
+                      double ignore_value, double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out);
 
 /* ---- the neighbour table of a row-sharded raster (distributed.findSegmentNeighboursDistributed; csrc/dneighbours.h)
  * The table above for a label raster whose rows are spread over the ranks, without gathering the labels.  The result

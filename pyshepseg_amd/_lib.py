@@ -225,6 +225,15 @@ _SIGS = {
     'shp_nbr_merge_contract': (_c.c_int, [_vp, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double)]),
     'shp_nbr_merge_recode_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _vp, _c.c_int, _c.POINTER(_c.c_uint32),
                                             _c.POINTER(_c.c_double)]),
+    'shp_nbr_merge_similar': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _c.c_double,
+                                         _c.c_int, _vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _c.POINTER(_c.c_uint32), _vp,
+                                         _vp]),
+    'shp_nbr_groups_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    'shp_nbr_members_build': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_uint64),
+                                         _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double)]),
+    'shp_nbr_members_download': (_c.c_int, [_vp, _vp, _vp]),
+    'shp_nbr_aggregate': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _vp, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,
+                                     _vp, _c.POINTER(_c.c_double)]),
     'shp_dnbr_local_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _vp, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
                                       _c.POINTER(_c.c_uint32), _vp, _c.POINTER(_vp), _c.POINTER(_c.c_double)]),
     'shp_dnbr_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _vp, _c.POINTER(_c.c_int64),

@@ -20,6 +20,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "neighbours.h"
 #include "nbrreduce.h"
 #include "nbrmerge.h"
+#include "nbragg.h"
 #include "dneighbours.h"
 #include "comm.h"
 
@@ -112,7 +113,9 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->dnbr_blk, &ctx->dnbr_cnt, &ctx->dnbr_home, &ctx->dnbr_trav, &ctx->dnbr_mrg, &ctx->dnbr_rcnt,
                  &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff,
                  &ctx->mrg_ctr, &ctx->mrg_key, &ctx->mrg_size, &ctx->mrg_par, &ctx->mrg_root, &ctx->mrg_idx,
-                 &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist};
+                 &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist, &ctx->mrg_rec, &ctx->mrg_bestd,
+                 &ctx->mrg_best, &ctx->agg_recode, &ctx->agg_gsize, &ctx->agg_ctr, &ctx->agg_scan, &ctx->agg_offs,
+                 &ctx->agg_mem, &ctx->agg_wcol, &ctx->agg_w, &ctx->agg_lrow, &ctx->agg_lcoff};
     *out = ctx;
     return SHP_OK;
 }
@@ -1512,8 +1515,8 @@ API int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows,
     if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
     if (n_rows != (int64_t)ctx->nbr.S + 1)
         SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
-    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
-    for (int i = 0; i < NBRR_NSTATS; i++)
+    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NPUBLIC)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    for (int i = 0; i < NBRR_NPUBLIC; i++)
         if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
     return run_nbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
 }
@@ -1561,6 +1564,82 @@ API int shp_nbr_merge_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t np
     if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_out & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
     if (count_hist && ctx->mrg.has_size) SHP_FAIL(ctx, SHP_ERR_ARG, "the histogram holds the sums of seg_size: nothing to count");
     return run_nbr_merge_recode(ctx, d_seg, (size_t)npix, d_out, count_hist, bad_label_out, dev_ms_out);
+}
+
+API int shp_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int n_cols, int64_t n_rows, int has_ignore_value,
+                              double ignore_value, int has_threshold, double thr2, int mutual_nearest, const int64_t *keys,
+                              int has_ignore_key, int64_t ignore_key, int64_t min_border, const int64_t *seg_size,
+                              uint32_t *max_group_out, int64_t *counters_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    ctx->mrg.stage = 0;
+    if (ctx->nbr.stage != 2)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    if (!cols || !max_group_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n_cols < 1 || n_cols > MRGS_MAX_COLS) SHP_FAIL(ctx, SHP_ERR_ARG, "%d distance columns: 1 to %d wanted", n_cols, MRGS_MAX_COLS);
+    for (int c = 0; c < n_cols; c++)
+        if (!cols[c]) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n_rows != (int64_t)ctx->nbr.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
+    if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
+    if (!has_threshold && !mutual_nearest) SHP_FAIL(ctx, SHP_ERR_ARG, "no threshold: only the mutual-nearest rule does without");
+    if (has_threshold && !(thr2 >= 0.0)) SHP_FAIL(ctx, SHP_ERR_ARG, "thr2 %g", thr2);
+    return run_nbr_merge_similar(ctx, cols, n_cols, has_ignore_value, ignore_value, has_threshold, thr2, mutual_nearest, keys,
+                                 has_ignore_key, ignore_key, min_border, seg_size, max_group_out, counters_out, dev_ms_out);
+}
+
+// ---- columns carried to the groups of a merge (nbragg.h) ---------------------------------------------------
+API int shp_nbr_groups_serial(shp_ctx *ctx, uint64_t *groups_serial_out, uint64_t *members_serial_out)
+{
+    if (!ctx) return SHP_ERR_ARG;
+    ctx->err.clear();
+    if (!groups_serial_out || !members_serial_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *groups_serial_out = ctx->mrg.stage == 1 ? ctx->mrg.serial : 0;
+    *members_serial_out = ctx->agg.stage == 1 ? ctx->agg.serial : 0;
+    return 0;
+}
+
+API int shp_nbr_members_build(shp_ctx *ctx, const uint32_t *recode, int64_t n_rows, int64_t max_group, uint64_t *serial_out,
+                              int64_t *n_members_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!serial_out || !n_members_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (recode) {
+        if (n_rows < 1 || n_rows > 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "a recode of %lld rows", (long long)n_rows);
+        if (max_group < 0 || max_group >= n_rows)
+            SHP_FAIL(ctx, SHP_ERR_ARG, "%lld groups of %lld ids", (long long)max_group, (long long)n_rows - 1);
+        CHK(run_agg_build(ctx, recode, (uint32_t)(n_rows - 1), (uint32_t)max_group));
+    } else {
+        if (ctx->mrg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no groups: shp_nbr_merge must come first");
+        if (ctx->agg.stage != 1 || ctx->agg.serial != ctx->mrg.serial) CHK(run_agg_build(ctx, nullptr, ctx->mrg.S, ctx->mrg.M));
+    }
+    *serial_out = ctx->agg.serial;
+    *n_members_out = (int64_t)ctx->agg.nmem;
+    if (dev_ms_out) *dev_ms_out = ctx->agg.dev_ms;
+    return 0;
+}
+
+API int shp_nbr_members_download(shp_ctx *ctx, int64_t *offsets, uint32_t *members)
+{
+    CHK(enter(ctx));
+    if (ctx->agg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no member list: shp_nbr_members_build must come first");
+    if (!offsets || (ctx->agg.nmem > 0 && !members)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_agg_download(ctx, offsets, members);
+}
+
+API int shp_nbr_aggregate(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, const int64_t *weights, int has_ignore,
+                          double ignore_value, double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->agg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no member list: shp_nbr_members_build must come first");
+    if (!col || !outs) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    if (n_rows != (int64_t)ctx->agg.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for groups of %lld ids", (long long)n_rows, (long long)ctx->agg.S + 1);
+    if (stat_mask == 0u || stat_mask >= (1u << AGG_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    for (int i = 0; i < AGG_NSTATS; i++)
+        if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
+    return run_agg(ctx, col, ctype, weights, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
 }
 
 // ---- the neighbour table of a row-sharded raster, by id share (dneighbours.h) ------------------------------
@@ -1641,7 +1720,7 @@ API int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_
     if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
     if (n_rows != (int64_t)ctx->dnbr.S + 1)
         SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
-    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NPUBLIC)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
     return run_dnbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, d_out, dev_ms_out);
 }
 

@@ -98,7 +98,20 @@ struct MrgState {
     uint32_t S = 0, M = 0;
     unsigned long long links = 0, half = 0;     // links; entries with a < b
     unsigned long long table_serial = 0;
+    unsigned long long serial = 0;  // of these groups, from the numbering of nbr_serial: new with every merge
     bool has_size = false, contracted = false;
+};
+
+// the member list of a merge's groups (nbragg.h): the old ids of every group in ascending order, as a CSR over the
+// new ids 0 .. M in buffers of its own (agg_*), with the list of its long rows.  serial: the groups it belongs to
+// (MrgState::serial, or a number of its own when the recode came from the host).  It lasts until the next merge.
+struct AggState {
+    int stage = 0;                  // 0 none, 1 built
+    uint32_t S = 0, M = 0;
+    unsigned long long serial = 0, nmem = 0;
+    const uint32_t *recode = nullptr;   // the device recode it was built from: mrg_recode or agg_recode
+    uint32_t nlong = 0, nchunks = 0;
+    double dev_ms = 0.0;
 };
 
 struct shp_ctx {
@@ -121,10 +134,13 @@ struct shp_ctx {
         nbr_ids, nbr_lens,
         nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part,
         dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff,
-        mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist;
+        mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist,
+        mrg_rec, mrg_bestd, mrg_best,
+        agg_recode, agg_gsize, agg_ctr, agg_scan, agg_offs, agg_mem, agg_wcol, agg_w, agg_lrow, agg_lcoff;
     SegPointsState pts;
     NbrState nbr;
     MrgState mrg;
+    AggState agg;
     DNbrState dnbr;
     // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
     // has, new with every shp_nbr_begin, shp_nbr_upload and shp_nbr_merge_contract (kept here: run_nbr_begin resets `nbr`); the list of the

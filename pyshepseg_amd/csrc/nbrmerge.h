@@ -9,8 +9,12 @@
 // a < b are read, here and in the contraction.  All of it is integer work: no result depends on the order in which
 // the atomics below arrive.
 //
+// neighbours.mergeSimilarSegments is the same merge under another link rule (MrgSimRule below: a distance between
+// per-segment columns, by threshold or by mutually nearest neighbours); only k_mrg_hook's predicate and what feeds it
+// differ, everything after the links is shared (mrg_begin / mrg_number).
+//
 // Kernels:
-//  k_mrg_hook: the entries are cut into pieces of MRG_PIECE consecutive entries, a workgroup each, whatever rows they
+//  k_mrg_hook: a template over the link rule.  The entries are cut into pieces of MRG_PIECE consecutive entries, a workgroup each, whatever rows they
 //     belong to: a row of 20 000 entries is ten pieces, 500 rows of four entries are one.  Two threads find the
 //     rows of the piece's first and last entry in the offsets (a search over all rows), every thread then finds the row
 //     of each of its entries between those two.  A link is hooked into a uint32 parent array as the pixel CCL hooks
@@ -19,6 +23,8 @@
 //     parent array is read with agent-scope loads only: they are answered where the atomics land, never by a line
 //     of the CU's L1 or of another XCD's L2.  After a find the entry's own id is pointed at the root it found
 //     (atomicMin again), which keeps the paths of a long chain of hooks short.
+//  k_mrgs_place / k_mrgs_mark: the distance columns as one record per id; k_mrgs_best: the mutual rule's per-row best,
+//     two passes over the hook's pieces (at MrgSimRule and the kernels).
 //  k_mrg_flatten: root[i] of every id, in a launch of its own (nothing hooks any more: plain loads).
 //  MrgRootFn + scan.h: 1 at every root that is a vertex; its exclusive scan is the root's new id - 1.
 //  k_mrg_write: recode, representative, and by 64-bit atomics the group sizes and (with sizes) the new histogram;
@@ -52,11 +58,68 @@ struct MrgTable {
     long long nent;
 };
 
+// A link rule answers link(a, b, w) for an entry with a < b, both ids inside the table.
 struct MrgLinkRule {
     const long long *key;
     const long long *size;      // nullptr: every id 1 .. S is a vertex
     int has_ign;
     long long ign, minb;
+    __device__ __forceinline__ bool link(uint32_t a, uint32_t b, long long w) const
+    {
+        if (w < minb) return false;
+        const long long ka = key[a];
+        if (ka != key[b] || (has_ign && ka == ign)) return false;
+        if (size && (size[a] <= 0 || size[b] <= 0)) return false;
+        return true;
+    }
+};
+
+// The rule of neighbours.mergeSimilarSegments.  rec: one record of ncol float64 per id, the id's values in the order
+// of the columns (k_mrgs_place), its first value NaN when any of them is ignored (k_mrgs_mark): d2 of such an id is
+// NaN against everybody, and a d2 that is not finite is no candidate anyway.  A record and not ncol planes: the two
+// gathers of an entry are the only random accesses of the hook, and a record of up to 64 bytes lies in one or two
+// 128-byte lines where planes would touch ncol of them per end.
+// d2(a, b) = sum over the columns, in their order, of t * t with t = x[a] - x[b], from +0.0; every operation rounded
+// once (the library is built with -ffp-contract=off); t * t has the bits of (-t) * (-t), so d2(a, b) == d2(b, a).
+// An entry is a CANDIDATE when w >= minb, both ids have pixels (with sizes), the keys agree and are not the ignored
+// one (with keys) and d2 is finite.  best == nullptr: a candidate is a link when d2 <= thr2.  Otherwise best[i] is
+// the candidate neighbour of row i with the smallest d2, the smallest id among equals (0xffffffff: none), and a
+// candidate is a link when its ends name each other and (with has_thr) d2 <= thr2.
+#define MRGS_MAX_COLS 8
+struct MrgSimRule {
+    const double *rec;
+    int ncol;
+    const long long *key;       // nullptr: no key rule
+    const long long *size;      // nullptr: every id 1 .. S is a vertex
+    int has_ign;
+    long long ign, minb;
+    int has_thr;
+    double thr2;
+    const uint32_t *best;
+    __device__ __forceinline__ bool candidate(uint32_t a, uint32_t b, long long w, double &d) const
+    {
+        if (w < minb) return false;
+        if (size && (size[a] <= 0 || size[b] <= 0)) return false;
+        if (key) {
+            const long long ka = key[a];
+            if (ka != key[b] || (has_ign && ka == ign)) return false;
+        }
+        const double *xa = rec + (size_t)a * (size_t)ncol, *xb = rec + (size_t)b * (size_t)ncol;
+        double s = 0.0;
+        for (int c = 0; c < ncol; c++) {
+            const double t = xa[c] - xb[c];
+            s = s + t * t;
+        }
+        d = s;
+        return s < INFINITY;                                    // (false for NaN as well)
+    }
+    __device__ __forceinline__ bool link(uint32_t a, uint32_t b, long long w) const
+    {
+        double d;
+        if (!candidate(a, b, w, d)) return false;
+        if (best && (best[a] != b || best[b] != a)) return false;
+        return !has_thr || d <= thr2;
+    }
 };
 
 // the last row r of lo .. hi with offs[r] <= e (it is the row of entry e: offs[r + 1] > e)
@@ -111,7 +174,8 @@ __device__ __forceinline__ uint32_t mrg_wave_sum(uint32_t v)
     return v;
 }
 
-__global__ __launch_bounds__(256) void k_mrg_hook(MrgTable t, MrgLinkRule q, uint32_t *par, unsigned long long *ctr)
+template <class Rule>
+__global__ __launch_bounds__(256) void k_mrg_hook(MrgTable t, Rule q, uint32_t *par, unsigned long long *ctr)
 {
     __shared__ uint32_t s_r[2];
     const long long e0 = (long long)blockIdx.x * (long long)MRG_PIECE;
@@ -127,10 +191,7 @@ __global__ __launch_bounds__(256) void k_mrg_hook(MrgTable t, MrgLinkRule q, uin
         // (row 0 has no entries and no id lies past the table in a checked table: neither is relied on here)
         if (a == 0u || a >= b || b >= t.ns) continue;
         nhalf++;
-        if (t.lens[e] < q.minb) continue;
-        const long long ka = q.key[a];
-        if (ka != q.key[b] || (q.has_ign && ka == q.ign)) continue;
-        if (q.size && (q.size[a] <= 0 || q.size[b] <= 0)) continue;
+        if (!q.link(a, b, t.lens[e])) continue;
         nlink++;
         mrg_union(par, a, b);
     }
@@ -139,6 +200,59 @@ __global__ __launch_bounds__(256) void k_mrg_hook(MrgTable t, MrgLinkRule q, uin
     if (lane_id() == 0u) {
         if (nhalf) atomicAdd(&ctr[MRG_C_HALF], (unsigned long long)nhalf);
         if (nlink) atomicAdd(&ctr[MRG_C_LINKS], (unsigned long long)nlink);
+    }
+}
+
+// ---- the similarity rule's columns and per-row best -------------------------------------------------------------
+// column c of ncol into the records
+__global__ __launch_bounds__(256) void k_mrgs_place(const double *__restrict__ col, size_t ns, int c, int ncol,
+                                                    double *__restrict__ rec)
+{
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < ns; i += (size_t)gridDim.x * 256u)
+        rec[i * (size_t)ncol + (size_t)c] = col[i];
+}
+
+// an id with an ignored value (NaN, or the ignore value) in any column: its record's first value becomes NaN
+__global__ __launch_bounds__(256) void k_mrgs_mark(double *__restrict__ rec, size_t ns, int ncol, int has_ign, double ign)
+{
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < ns; i += (size_t)gridDim.x * 256u) {
+        bool bad = false;
+        for (int c = 0; c < ncol; c++) {
+            const double x = rec[i * (size_t)ncol + (size_t)c];
+            bad = bad || x != x || (has_ign && x == ign);
+        }
+        if (bad) rec[i * (size_t)ncol] = NAN;
+    }
+}
+
+// The per-row best of the mutual rule, over the pieces of the hook and EVERY entry (a row is read from its own
+// side).  PASS 0: bestd[a] = the smallest d2 of row a's candidates, by a 64-bit atomicMin on its bit pattern (d2 is
+// +0.0 or above: such doubles order as unsigned integers).  PASS 1, a launch later: best[a] = the smallest id among
+// the candidates at that minimum.  Both arrays start at all ones.  A value already at or below what the entry
+// brings needs no atomic (it only decreases), which spares a row of thousands of entries thousands of atomics on
+// one word; the look goes to the L2, where the atomics land.
+template <int PASS>
+__global__ __launch_bounds__(256) void k_mrgs_best(MrgTable t, MrgSimRule q, unsigned long long *bestd, uint32_t *best)
+{
+    __shared__ uint32_t s_r[2];
+    const long long e0 = (long long)blockIdx.x * (long long)MRG_PIECE;
+    const long long e1 = e0 + (long long)MRG_PIECE < t.nent ? e0 + (long long)MRG_PIECE : t.nent;
+    mrg_piece_rows(t, e0, e1, s_r);
+    const uint32_t rlo = s_r[0], rhi = s_r[1];
+    for (uint32_t k = 0; k < MRG_PIECE / 256u; k++) {
+        const long long e = e0 + (long long)(k * 256u + threadIdx.x);
+        if (e >= e1) break;
+        const uint32_t b = t.ids[e];
+        const uint32_t a = mrg_row_of(t.offs, rlo, rhi, e);
+        if (a == 0u || a == b || b == 0u || b >= t.ns) continue;
+        double d;
+        if (!q.candidate(a, b, t.lens[e], d)) continue;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(d);
+        if (PASS == 0) {
+            if (L2LOAD(&bestd[a]) > bits) atomicMin(&bestd[a], bits);
+        } else {
+            if (bestd[a] == bits && L2LOAD(&best[a]) > b) atomicMin(&best[a], b);
+        }
     }
 }
 
@@ -316,19 +430,18 @@ static inline unsigned mrg_pieces(unsigned long long nent)
     return (unsigned)((nent + MRG_PIECE - 1u) / MRG_PIECE);
 }
 
-// The groups of the finished table.  keys / seg_size: host, S + 1 int64 (seg_size may be NULL).  ms_out[2]: device
-// time of the hook, of the renumbering.
-static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t ign, int64_t min_border,
-                         const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+// The buffers of a merge, its host columns on the device (either may be NULL), zeroed counters and the parent array
+// with every id its own root: what comes before the hook of either link rule.  ev[0] is recorded in front of the
+// parent array's launch.  The groups of the merge before, and their member list (nbragg.h), end here.
+static int mrg_begin(shp_ctx *ctx, const int64_t *keys, const int64_t *seg_size)
 {
-    MrgState &g = ctx->mrg;
     hipStream_t st = ctx->stream;
-    g = MrgState{};
-    const uint32_t S = ctx->nbr.S;
-    const size_t ns = (size_t)S + 1;
+    ctx->mrg = MrgState{};
+    ctx->agg = AggState{};
+    const size_t ns = (size_t)ctx->nbr.S + 1;
     const unsigned long long nent = ctx->nbr.nent;
     if (nent > (unsigned long long)MRG_PIECE * 0x7fffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "%llu entries: too many", nent);
-    CHK(buf_ensure(ctx, ctx->mrg_key, ns * 8));
+    if (keys) CHK(buf_ensure(ctx, ctx->mrg_key, ns * 8));
     if (seg_size) CHK(buf_ensure(ctx, ctx->mrg_size, ns * 8));
     CHK(buf_ensure(ctx, ctx->mrg_par, ns * 4));
     CHK(buf_ensure(ctx, ctx->mrg_root, ns * 4));
@@ -336,23 +449,28 @@ static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t
     CHK(buf_ensure(ctx, ctx->mrg_recode, ns * 4));
     CHK(buf_ensure(ctx, ctx->mrg_ctr, MRG_C_WORDS * 8));
     CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
-    long long *d_key = bp<long long>(ctx->mrg_key);
-    long long *d_size = seg_size ? bp<long long>(ctx->mrg_size) : nullptr;
+    if (keys) HIPCHK(ctx, hipMemcpyAsync(ctx->mrg_key.p, keys, ns * 8, hipMemcpyHostToDevice, st));
+    if (seg_size) HIPCHK(ctx, hipMemcpyAsync(ctx->mrg_size.p, seg_size, ns * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(ctx, hipMemsetAsync(ctx->mrg_ctr.p, 0, MRG_C_WORDS * 8, st));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
+    hipLaunchKernelGGL(k_mrg_init, dim3(grid_for(ns, 256)), dim3(256), 0, st, bp<uint32_t>(ctx->mrg_par), (uint32_t)ns);
+    KCHK(ctx);
+    return 0;
+}
+
+// What follows the hook of either link rule: the roots flagged, scanned and numbered, the groups written.  ms_out[2]:
+// device time since ev[0] (the hook), of the renumbering.
+static int mrg_number(shp_ctx *ctx, bool has_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+{
+    MrgState &g = ctx->mrg;
+    hipStream_t st = ctx->stream;
+    const uint32_t S = ctx->nbr.S;
+    const size_t ns = (size_t)S + 1;
+    long long *d_size = has_size ? bp<long long>(ctx->mrg_size) : nullptr;
     uint32_t *par = bp<uint32_t>(ctx->mrg_par), *root = bp<uint32_t>(ctx->mrg_root), *idx = bp<uint32_t>(ctx->mrg_idx);
     unsigned long long *ctr = (unsigned long long *)ctx->mrg_ctr.p;
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
-    HIPCHK(ctx, hipMemcpyAsync(d_key, keys, ns * 8, hipMemcpyHostToDevice, st));
-    if (seg_size) HIPCHK(ctx, hipMemcpyAsync(d_size, seg_size, ns * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(ctr, 0, MRG_C_WORDS * 8, st));
     const unsigned gs = grid_for(ns, 256);
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    hipLaunchKernelGGL(k_mrg_init, dim3(gs), dim3(256), 0, st, par, (uint32_t)ns);
-    KCHK(ctx);
-    if (nent) {
-        const MrgLinkRule q{d_key, d_size, has_ign, (long long)ign, (long long)min_border};
-        hipLaunchKernelGGL(k_mrg_hook, dim3(mrg_pieces(nent)), dim3(256), 0, st, mrg_table(ctx), q, par, ctr);
-        KCHK(ctx);
-    }
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     hipLaunchKernelGGL(k_mrg_flatten, dim3(gs), dim3(256), 0, st, (const uint32_t *)par, (uint32_t)ns, root);
     KCHK(ctx);
@@ -389,14 +507,91 @@ static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t
     g.M = M;
     g.links = pin[MRG_C_LINKS];
     g.half = pin[MRG_C_HALF];
-    g.has_size = seg_size != nullptr;
+    g.has_size = has_size;
     g.table_serial = ctx->nbr_serial;
+    g.serial = nbr_next_serial();
     g.stage = 1;
     *M_out = M;
     if (counters_out) {
         counters_out[0] = (int64_t)g.links;
         counters_out[1] = (int64_t)g.half;
     }
+    return 0;
+}
+
+// The groups of the finished table under the key rule.  keys / seg_size: host, S + 1 int64 (seg_size may be NULL).
+// ms_out[2]: device time of the hook, of the renumbering.
+static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t ign, int64_t min_border,
+                         const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+{
+    CHK(mrg_begin(ctx, keys, seg_size));
+    const unsigned long long nent = ctx->nbr.nent;
+    if (nent) {
+        const MrgLinkRule q{bp<long long>(ctx->mrg_key), seg_size ? bp<long long>(ctx->mrg_size) : nullptr, has_ign,
+                            (long long)ign, (long long)min_border};
+        hipLaunchKernelGGL(k_mrg_hook<MrgLinkRule>, dim3(mrg_pieces(nent)), dim3(256), 0, ctx->stream, mrg_table(ctx), q,
+                           bp<uint32_t>(ctx->mrg_par), (unsigned long long *)ctx->mrg_ctr.p);
+        KCHK(ctx);
+    }
+    return mrg_number(ctx, seg_size != nullptr, M_out, counters_out, ms_out);
+}
+
+// The groups of the finished table under the similarity rule (MrgSimRule).  cols: ncol host columns of S + 1 float64;
+// keys and seg_size may be NULL.  The columns go through one staging plane into the records, in front of ev[0].
+// ms_out[3]: device time of the hook (with the two best passes of the mutual rule), of the renumbering, of the
+// records' kernels.
+static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int ncol, int has_ignv, double ignv, int has_thr,
+                                 double thr2, int mutual, const int64_t *keys, int has_ignk, int64_t ignk, int64_t min_border,
+                                 const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)ctx->nbr.S + 1;
+    const unsigned long long nent = ctx->nbr.nent;
+    CHK(buf_ensure(ctx, ctx->mrg_rec, ns * (size_t)ncol * 8));
+    CHK(buf_ensure(ctx, ctx->img, ns * 8));
+    if (mutual) {
+        CHK(buf_ensure(ctx, ctx->mrg_bestd, ns * 8));
+        CHK(buf_ensure(ctx, ctx->mrg_best, ns * 4));
+    }
+    double *rec = bp<double>(ctx->mrg_rec);
+    const unsigned gc = grid_for(ns, 256, 2048u);
+    float msr = 0.f, ms1 = 0.f;
+    for (int c = 0; c < ncol; c++) {
+        HIPCHK(ctx, hipMemcpyAsync(ctx->img.p, cols[c], ns * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipEventRecord(ctx->ev[5], st));
+        hipLaunchKernelGGL(k_mrgs_place, dim3(gc), dim3(256), 0, st, (const double *)ctx->img.p, ns, c, ncol, rec);
+        KCHK(ctx);
+        if (c == ncol - 1) {
+            hipLaunchKernelGGL(k_mrgs_mark, dim3(gc), dim3(256), 0, st, rec, ns, ncol, has_ignv, ignv);
+            KCHK(ctx);
+        }
+        HIPCHK(ctx, hipEventRecord(ctx->ev[6], st));
+        HIPCHK(ctx, hipStreamSynchronize(st));                  // (the staging plane is free again)
+        HIPCHK(ctx, hipEventElapsedTime(&ms1, ctx->ev[5], ctx->ev[6]));
+        msr += ms1;
+    }
+    CHK(mrg_begin(ctx, keys, seg_size));
+    if (nent) {
+        MrgSimRule q{rec, ncol, keys ? bp<long long>(ctx->mrg_key) : nullptr, seg_size ? bp<long long>(ctx->mrg_size) : nullptr,
+                     has_ignk, (long long)ignk, (long long)min_border, has_thr, thr2, nullptr};
+        const dim3 grid(mrg_pieces(nent));
+        if (mutual) {
+            unsigned long long *bestd = (unsigned long long *)ctx->mrg_bestd.p;
+            uint32_t *best = bp<uint32_t>(ctx->mrg_best);
+            HIPCHK(ctx, hipMemsetAsync(bestd, 0xff, ns * 8, st));
+            HIPCHK(ctx, hipMemsetAsync(best, 0xff, ns * 4, st));
+            hipLaunchKernelGGL(k_mrgs_best<0>, grid, dim3(256), 0, st, mrg_table(ctx), q, bestd, best);
+            KCHK(ctx);
+            hipLaunchKernelGGL(k_mrgs_best<1>, grid, dim3(256), 0, st, mrg_table(ctx), q, bestd, best);
+            KCHK(ctx);
+            q.best = best;
+        }
+        hipLaunchKernelGGL(k_mrg_hook<MrgSimRule>, grid, dim3(256), 0, st, mrg_table(ctx), q, bp<uint32_t>(ctx->mrg_par),
+                           (unsigned long long *)ctx->mrg_ctr.p);
+        KCHK(ctx);
+    }
+    CHK(mrg_number(ctx, seg_size != nullptr, M_out, counters_out, ms_out));
+    if (ms_out) ms_out[2] = msr;
     return 0;
 }
 

@@ -60,7 +60,10 @@ static_assert(NBRR_CHUNK >= 64u && NBRR_CHUNK % 64u == 0u && NBRR_LONG >= 1u, "N
 
 // bits of the statistics mask, and the slot of a statistic's output
 enum { NBRR_COUNT = 0, NBRR_BORDER = 1, NBRR_MIN = 2, NBRR_MAX = 3, NBRR_MEAN = 4, NBRR_BORDERMEAN = 5,
-       NBRR_MEANABSDIFF = 6, NBRR_BORDERTOHIGHER = 7, NBRR_NEAREST = 8, NBRR_NSTATS = 9 };
+       NBRR_MEANABSDIFF = 6, NBRR_BORDERTOHIGHER = 7, NBRR_NEAREST = 8, NBRR_NPUBLIC = 9,
+       NBRR_SUM = 9, NBRR_NSTATS = 10 };
+// (NBRR_NPUBLIC: the statistics shp_nbr_reduce / shp_dnbr_reduce_dev offer.  NBRR_SUM, sum v itself, is the
+//  aggregation's: nbragg.h runs these kernels over the member lists of a merge's groups)
 
 struct NbrrParams {
     const long long *offs;
@@ -136,7 +139,9 @@ __device__ __forceinline__ void nbrr_store(const NbrrParams &p, uint32_t r, cons
     if (p.out[NBRR_MIN]) ((double *)p.out[NBRR_MIN])[r] = any ? a.mn : p.missing;
     if (p.out[NBRR_MAX]) ((double *)p.out[NBRR_MAX])[r] = any ? a.mx : p.missing;
     if (p.out[NBRR_MEAN]) ((double *)p.out[NBRR_MEAN])[r] = any ? a.sv / (double)a.cnt : p.missing;
-    if (p.out[NBRR_BORDERMEAN]) ((double *)p.out[NBRR_BORDERMEAN])[r] = any ? a.swv / (double)a.bor : p.missing;
+    // (a table's border lengths are 1 or more; the weights of nbragg.h may all be 0)
+    if (p.out[NBRR_BORDERMEAN]) ((double *)p.out[NBRR_BORDERMEAN])[r] = (any && a.bor != 0) ? a.swv / (double)a.bor : p.missing;
+    if (p.out[NBRR_SUM]) ((double *)p.out[NBRR_SUM])[r] = any ? a.sv : p.missing;
     if (p.out[NBRR_MEANABSDIFF])
         ((double *)p.out[NBRR_MEANABSDIFF])[r] = (any && own_ok) ? a.swd / (double)a.bor : p.missing;
     if (p.out[NBRR_BORDERTOHIGHER]) ((long long *)p.out[NBRR_BORDERTOHIGHER])[r] = (any && own_ok) ? a.bth : 0;

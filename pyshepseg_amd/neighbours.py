@@ -16,7 +16,10 @@ are reduced over it there (distributed.reduceOverNeighboursDistributed).
 
 ``reduceOverNeighbours`` computes per-segment columns over the table's rows; ``mergeSegments`` acts on a merge
 candidate: under a column of class codes, touching segments of one class become one object -- new ids, the recoded
-raster and the table of the merged objects (csrc/nbrmerge.h).
+raster and the table of the merged objects (csrc/nbrmerge.h).  ``mergeSimilarSegments`` merges by a distance between
+per-segment columns instead, and ``aggregateToGroups`` carries columns of the old segments to the merged objects
+(csrc/nbragg.h): table -> merge -> columns of the groups -> reductions over the contracted table -> merge again, all on
+the device.
 
 There is no CPU fallback: without a GPU the call fails as every entry point of this package does.
 """
@@ -252,11 +255,17 @@ def _checkReduceArgs(nb, columnSelections, ignoreValue, missingStatsValue):
 def _checkReduceSelections(nb, tableRows, columnSelections, ignoreValue, missingStatsValue):
     """_checkReduceArgs for a table ``nb`` of ``tableRows`` rows whose columns have maxSegId + 1 values (the whole
     table, or a SegmentNeighboursShare)"""
-    missing = _number(missingStatsValue, 'missingStatsValue')
-    ignore = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
     nrows = int(nb.maxSegId) + 1
     if len(nb.offsets) != tableRows + 1 or len(nb.neighbours) != len(nb.borderLengths):
         raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
+    return _planSelections(nrows, columnSelections, ignoreValue, missingStatsValue, REDUCE_STATS, _COLUMN_TYPES.get)
+
+
+def _planSelections(nrows, columnSelections, ignoreValue, missingStatsValue, statTable, typeOf):
+    """the plan of _checkReduceArgs for columns of ``nrows`` values: the statistics' names from ``statTable``, a
+    dtype's type code from ``typeOf`` (None: not accepted)"""
+    missing = _number(missingStatsValue, 'missingStatsValue')
+    ignore = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
     try:
         selections = [(column, list(stats)) for (column, stats) in columnSelections]
     except (TypeError, ValueError):
@@ -268,7 +277,7 @@ def _checkReduceSelections(nb, tableRows, columnSelections, ignoreValue, missing
     for (i, (column, stats)) in enumerate(selections):
         if not isinstance(column, numpy.ndarray) or column.ndim != 1:
             raise PyShepSegNeighboursError("column {} must be a 1-D numpy array".format(i))
-        if column.dtype not in _COLUMN_TYPES:
+        if typeOf(column.dtype) is None:
             raise PyShepSegNeighboursError("column {} has dtype {}: float64, float32 or int64 wanted".format(
                 i, column.dtype))
         if len(column) != nrows:
@@ -282,14 +291,14 @@ def _checkReduceSelections(nb, tableRows, columnSelections, ignoreValue, missing
                 (outName, statName) = item
             except (TypeError, ValueError):
                 raise PyShepSegNeighboursError("a selection must be (outName, statName) (got {!r})".format(item))
-            if statName not in REDUCE_STATS:
+            if statName not in statTable:
                 raise PyShepSegNeighboursError("unknown statName {!r}: one of {} wanted".format(
-                    statName, ', '.join(sorted(REDUCE_STATS))))
+                    statName, ', '.join(sorted(statTable))))
             if outName in seen:
                 raise PyShepSegNeighboursError("outName {!r} appears twice".format(outName))
             seen.add(outName)
-            picked.append((outName,) + REDUCE_STATS[statName])
-        plan.append((numpy.ascontiguousarray(column), _COLUMN_TYPES[column.dtype], picked))
+            picked.append((outName,) + statTable[statName])
+        plan.append((numpy.ascontiguousarray(column), typeOf(column.dtype), picked))
     return (plan, ignore, missing)
 
 
@@ -358,7 +367,12 @@ class MergedSegments(object):
     ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels, ``stepDeviceMs`` the same per step (hook,
     renumber, contract, recode); ``segimg``: the recoded raster when ``segfile`` was an array and no ``outfile`` was
     given; ``outDev``: the recoded raster in device memory when the labels were there, in the form findSegmentNeighbours
-    accepts (tiling.freeDeviceOutput releases it)."""
+    accepts (tiling.freeDeviceOutput releases it).
+
+    For aggregateToGroups: ``membersOf(g)``, and ``memberOffsets`` (int64, ``maxSegId + 2``) with ``members`` (uint32):
+    the old ids of every group in ascending order, as a CSR over the new ids.  Both arrays are None until the first
+    call that needs them has brought them from the device.  ``aggregateTimings``: the last aggregateToGroups.  A
+    result put together by hand needs ``recode`` and ``maxSegId``."""
     def __init__(self):
         self.recode = None
         self.maxSegId = 0
@@ -373,6 +387,20 @@ class MergedSegments(object):
         self.stepDeviceMs = {}
         self.segimg = None
         self.outDev = None
+        self.memberOffsets = None
+        self.members = None
+        self.aggregateTimings = {}
+        self.groupsSerial = None
+        self._groupsCtx = None
+
+    def membersOf(self, group):
+        """the old ids of one group, ascending: a view of ``members`` (fetched from the device by the first call)"""
+        group = int(group)
+        if group < 0 or group > self.maxSegId:
+            raise PyShepSegNeighboursError("group {} is outside 0..{}".format(group, self.maxSegId))
+        if self.memberOffsets is None:
+            _fetchMembers(_lib.ctx(), _checkMerged(self), {})
+        return self.members[int(self.memberOffsets[group]):int(self.memberOffsets[group + 1])]
 
 
 def _integer(value, name):
@@ -393,17 +421,19 @@ def _integerColumn(column, name, nrows):
     return numpy.ascontiguousarray(column.astype(numpy.int64, copy=False))
 
 
-def _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile):
+def _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile, keyOptional=False):
     """(keys int64, ignore or None, minBorder, sizes int64 or None, the raster as _checkArgs gives it or None):
-    everything that can be refused before the GPU is touched"""
+    everything that can be refused before the GPU is touched.  keyOptional: ``keyColumn`` may be None (keys None)"""
     if not isinstance(nb, SegmentNeighbours):
         raise PyShepSegNeighboursError("nb must be a SegmentNeighbours")
     nrows = int(nb.maxSegId) + 1
     if len(nb.offsets) != nrows + 1 or len(nb.neighbours) != len(nb.borderLengths):
         raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
-    keys = _integerColumn(keyColumn, 'keyColumn', nrows)
+    keys = None if (keyOptional and keyColumn is None) else _integerColumn(keyColumn, 'keyColumn', nrows)
     ignore = None
     if ignoreKey is not None:
+        if keys is None:
+            raise PyShepSegNeighboursError("ignoreKey needs a keyColumn")
         ignore = _integer(ignoreKey, 'ignoreKey')
         if ignore < -(1 << 63) or ignore >= (1 << 64):
             raise PyShepSegNeighboursError("ignoreKey {} is no 64-bit integer".format(ignore))
@@ -458,6 +488,18 @@ def mergeSegments(nb, keyColumn, ignoreKey=None, minBorder=1, segSize=None, segf
     """
     (keys, ignore, minBorder, sizes, raster) = _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile,
                                                                 outfile)
+
+    def links(c, S, M, counters, ms):
+        c.check(c._L.shp_nbr_merge(c.handle, _lib.ptr(keys), S + 1, int(ignore is not None), 0 if ignore is None else ignore,
+                                   minBorder, None if sizes is None else _lib.ptr(sizes), ctypes.byref(M),
+                                   _lib.ptr(counters), _lib.ptr(ms)))
+    return _mergeByLinks(nb, links, sizes, raster, outfile, chunkPixels)
+
+
+def _mergeByLinks(nb, links, sizes, raster, outfile, chunkPixels):
+    """What mergeSegments and mergeSimilarSegments share, which is everything but the link rule: ``links(c, S, M,
+    counters, ms)`` makes the library's call that finds the groups of the resident table (M: c_uint32, counters: 2
+    int64, ms: 3 float64 -- hook, renumbering, and what the rule spends before the hook)."""
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
@@ -467,11 +509,10 @@ def mergeSegments(nb, keyColumn, ignoreKey=None, minBorder=1, segSize=None, segf
     S = int(nb.maxSegId)
     # the groups
     t1 = time.perf_counter()
-    (M, counters, ms2) = (ctypes.c_uint32(0), numpy.zeros(2, dtype=numpy.int64), numpy.zeros(2, dtype=numpy.float64))
-    c.check(L.shp_nbr_merge(c.handle, _lib.ptr(keys), S + 1, int(ignore is not None), 0 if ignore is None else ignore,
-                            minBorder, None if sizes is None else _lib.ptr(sizes), ctypes.byref(M), _lib.ptr(counters),
-                            _lib.ptr(ms2)))
+    (M, counters, ms2) = (ctypes.c_uint32(0), numpy.zeros(2, dtype=numpy.int64), numpy.zeros(3, dtype=numpy.float64))
+    links(c, S, M, counters, ms2)
     M = M.value
+    (res.groupsSerial, res._groupsCtx) = (_groupSerials(c)[0], c.handle.value)
     timings['merge'] = time.perf_counter() - t1
     t1 = time.perf_counter()
     res.recode = numpy.empty(S + 1, dtype=numpy.uint32)
@@ -501,6 +542,8 @@ def mergeSegments(nb, keyColumn, ignoreKey=None, minBorder=1, segSize=None, segf
     res.links = int(counters[0])
     res.recordsSorted = nrec.value
     res.stepDeviceMs = {'hook': float(ms2[0]), 'renumber': float(ms2[1]), 'contract': msc.value, 'recode': 0.0}
+    if ms2[2]:
+        res.stepDeviceMs['records'] = float(ms2[2])
     # the raster
     if raster is not None:
         t1 = time.perf_counter()
@@ -564,3 +607,214 @@ def _recodeRaster(c, res, raster, S, outfile, chunkPixels, countHist):
         src.close()
         if devOut is not None:
             tiling._devRelease(c, devOut, nbytes)
+
+
+# ---- touching segments that look alike merged into one (csrc/nbrmerge.h, MrgSimRule) --------------------------
+MAX_DISTANCE_COLUMNS = 8
+
+
+def _distanceColumns(distanceColumns, nrows):
+    """the columns as contiguous float64 arrays of nrows values"""
+    if isinstance(distanceColumns, numpy.ndarray) or not isinstance(distanceColumns, (list, tuple)):
+        raise PyShepSegNeighboursError("distanceColumns must be a list of 1-D columns")
+    if not 1 <= len(distanceColumns) <= MAX_DISTANCE_COLUMNS:
+        raise PyShepSegNeighboursError("distanceColumns has {} columns: 1 to {} wanted".format(
+            len(distanceColumns), MAX_DISTANCE_COLUMNS))
+    out = []
+    for (i, column) in enumerate(distanceColumns):
+        if not isinstance(column, numpy.ndarray) or column.ndim != 1:
+            raise PyShepSegNeighboursError("distance column {} must be a 1-D numpy array".format(i))
+        if column.dtype not in (numpy.float64, numpy.float32) and column.dtype.kind not in 'iu':
+            raise PyShepSegNeighboursError("distance column {} has dtype {}: float64, float32 or an integer type "
+                                           "wanted".format(i, column.dtype))
+        if len(column) != nrows:
+            raise PyShepSegNeighboursError("distance column {} has {} rows, the table maxSegId + 1 = {}".format(
+                i, len(column), nrows))
+        out.append(numpy.ascontiguousarray(column, dtype=numpy.float64))
+    return out
+
+
+def mergeSimilarSegments(nb, distanceColumns, maxDistance=None, mutualNearest=False, ignoreValue=None, keyColumn=None,
+                         ignoreKey=None, minBorder=1, segSize=None, segfile=None, outfile=None, chunkPixels=None):
+    """
+    Touching segments that look alike become one object, on the GPU: a MergedSegments.  It is mergeSegments with
+    another link rule; the groups' numbering, ``recode``, ``representative``, ``groupSize``, ``hist``, the contracted
+    table that becomes the resident one and the recoded raster are mergeSegments', as are ``nb``, ``minBorder``,
+    ``segSize``, ``segfile``, ``outfile`` and ``chunkPixels``.
+
+    ``distanceColumns``: a list of 1 to 8 one-dimensional columns of ``maxSegId + 1`` values, float64, float32 or any
+    integer type, each widened to float64.  A value is ignored when it is NaN or equals ``ignoreValue``; an id with an
+    ignored value in any column links to nobody.  ``d2(a, b)`` starts at +0.0 and adds, for the columns in list order,
+    ``t * t`` with ``t = x[a] - x[b]``, every operation rounded to float64 once; ``thr2 = float64(maxDistance) ** 2``.
+    ``maxDistance`` must be finite and not negative; None (no threshold) is allowed with ``mutualNearest`` only.
+
+    Entry (a, b, w) of the table is a candidate when ``w >= minBorder``, both ids have pixels (with ``segSize``),
+    neither has an ignored value, ``d2`` is finite and, with ``keyColumn``, ``key[a] == key[b] != ignoreKey``.
+
+    ``mutualNearest=False``: a candidate is a link when ``d2 <= thr2`` and the groups are the connected components
+    of the links.  This is SINGLE LINKAGE: a chain of small steps joins segments that are further apart than
+    ``maxDistance``, just as a path of links joins two segments whose own border is below ``minBorder``.
+
+    ``mutualNearest=True``: ``best[a]`` is the candidate neighbour of a with the smallest ``d2``, the smallest id among
+    equals; (a, b) is a link when ``best[a] == b``, ``best[b] == a`` and ``d2 <= thr2``.  A group then has one or two
+    members: one round of pairwise merging.  The table must name every pair from both sides, as every table of
+    findSegmentNeighbours does.
+
+    Nothing depends on the order in which the GPU gets to the entries.  Columns for the groups:
+    aggregateToGroups(result, ...); the next round: mergeSimilarSegments(result.neighbours, ..., segSize=result.hist).
+    """
+    (keys, ignoreK, minBorder, sizes, raster) = _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile,
+                                                                 outfile, keyOptional=True)
+    columns = _distanceColumns(distanceColumns, int(nb.maxSegId) + 1)
+    if isinstance(mutualNearest, (bool, numpy.bool_)) is False:
+        raise PyShepSegNeighboursError("mutualNearest must be True or False (got {!r})".format(mutualNearest))
+    ignoreV = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
+    thr2 = None
+    if maxDistance is None:
+        if not mutualNearest:
+            raise PyShepSegNeighboursError("maxDistance=None (no threshold) needs mutualNearest=True")
+    else:
+        md = numpy.float64(_number(maxDistance, 'maxDistance'))
+        if not numpy.isfinite(md) or md < 0:
+            raise PyShepSegNeighboursError("maxDistance must be finite and not negative (got {!r})".format(maxDistance))
+        with numpy.errstate(over='ignore'):
+            thr2 = float(md * md)
+    cols = (ctypes.c_void_p * len(columns))(*[column.ctypes.data for column in columns])
+
+    def links(c, S, M, counters, ms):
+        c.check(c._L.shp_nbr_merge_similar(
+            c.handle, cols, len(columns), S + 1, int(ignoreV is not None), 0.0 if ignoreV is None else ignoreV,
+            int(thr2 is not None), 0.0 if thr2 is None else thr2, int(bool(mutualNearest)),
+            None if keys is None else _lib.ptr(keys), int(ignoreK is not None), 0 if ignoreK is None else ignoreK, minBorder,
+            None if sizes is None else _lib.ptr(sizes), ctypes.byref(M), _lib.ptr(counters), _lib.ptr(ms)))
+    return _mergeByLinks(nb, links, sizes, raster, outfile, chunkPixels)
+
+
+# ---- columns of the old ids carried to the groups (csrc/nbragg.h) ---------------------------------------------
+# statName -> (bit of the C call's mask, dtype of the column; None: int64 for an integer column, float64 otherwise)
+AGGREGATE_STATS = {'count': (0, numpy.int64), 'weight': (1, numpy.int64), 'min': (2, numpy.float64),
+                   'max': (3, numpy.float64), 'sum': (4, None), 'mean': (5, numpy.float64),
+                   'weightedmean': (6, numpy.float64)}
+
+
+def _aggregateType(dtype):
+    """the library's type code of a column (integers of any width go as int64), None for a dtype it does not take"""
+    if dtype in _COLUMN_TYPES:
+        return _COLUMN_TYPES[dtype]
+    return _COLUMN_TYPES[numpy.dtype(numpy.int64)] if dtype.kind in 'iu' else None
+
+
+def _groupSerials(c):
+    """(serial of the groups the context holds, serial of the groups whose member list it holds), None for none"""
+    (groups, members) = (ctypes.c_uint64(0), ctypes.c_uint64(0))
+    c.check(c._L.shp_nbr_groups_serial(c.handle, ctypes.byref(groups), ctypes.byref(members)))
+    return (groups.value or None, members.value or None)
+
+
+def _checkMerged(merged):
+    if not isinstance(merged, MergedSegments) or not isinstance(merged.recode, numpy.ndarray):
+        raise PyShepSegNeighboursError("merged must be a MergedSegments")
+    M = _integer(merged.maxSegId, 'merged.maxSegId')
+    if merged.recode.ndim != 1 or merged.recode.dtype != numpy.uint32 or not 0 <= M < max(len(merged.recode), 1):
+        raise PyShepSegNeighboursError("merged.recode must be a 1-D uint32 array with more rows than merged.maxSegId")
+    return merged
+
+
+def _residentMembers(c, merged, timings):
+    """the member list of ``merged`` on the device: there already, built from the groups the last merge call left
+    there, or -- for an older result -- from ``merged.recode``, uploaded"""
+    (groups, members) = _groupSerials(c)
+    mine = merged.groupsSerial if merged._groupsCtx == c.handle.value else None
+    timings.update(uploaded=False, built=False, buildDeviceMs=0.0)
+    if mine is not None and mine == members:
+        return
+    (serial, n, ms) = (ctypes.c_uint64(0), ctypes.c_int64(0), ctypes.c_double(0))
+    if mine is not None and mine == groups:
+        c.check(c._L.shp_nbr_members_build(c.handle, None, 0, 0, ctypes.byref(serial), ctypes.byref(n), ctypes.byref(ms)))
+    else:
+        recode = numpy.ascontiguousarray(merged.recode)
+        rc = c._L.shp_nbr_members_build(c.handle, _lib.ptr(recode), len(recode), int(merged.maxSegId), ctypes.byref(serial),
+                                        ctypes.byref(n), ctypes.byref(ms))
+        if rc != 0:
+            raise PyShepSegNeighboursError((c._L.shp_last_error(c.handle) or b'').decode())
+        timings['uploaded'] = True
+        (merged.groupsSerial, merged._groupsCtx) = (serial.value, c.handle.value)
+    timings.update(built=True, buildDeviceMs=ms.value)
+
+
+def _fetchMembers(c, merged, timings):
+    _residentMembers(c, merged, timings)
+    offsets = numpy.empty(int(merged.maxSegId) + 2, dtype=numpy.int64)
+    members = numpy.empty(numpy.count_nonzero(merged.recode), dtype=numpy.uint32)
+    c.check(c._L.shp_nbr_members_download(c.handle, _lib.ptr(offsets), _lib.ptr(members) if len(members) else None))
+    (merged.memberOffsets, merged.members) = (offsets, members)
+
+
+def aggregateToGroups(merged, columnSelections, weights=None, ignoreValue=None, missingStatsValue=-9999):
+    """
+    Columns of the old segments carried to the groups of a merge, on the GPU: a dictionary outName -> numpy array of
+    ``merged.maxSegId + 1`` rows.
+
+    ``merged`` is the MergedSegments of mergeSegments or mergeSimilarSegments.  ``columnSelections`` has the form
+    reduceOverNeighbours takes, ``[(column, [(outName, statName), ...]), ...]``; a column holds a value for every OLD
+    id (``len(merged.recode)`` values: float64, float32 or an integer type, integers read as int64).  ``weights``: an
+    integer column of the same length with values of 0 or more, typically the ``segSize`` the merge was given; None:
+    every weight is 1.
+
+    The members of group g are the old ids i with ``recode[i] == g`` in ascending order (``merged.membersOf(g)``); ids
+    that recode to 0 are in no group.  Over the members whose value is not ignored (NaN, or equal to ``ignoreValue``):
+    ``count`` of them and ``weight`` = sum w (int64); ``min``, ``max`` (float64); ``sum``: exact int64, wrapping as
+    numpy's, for an integer column and float64 otherwise; ``mean`` = (float64 sum) / count; ``weightedmean`` =
+    sum(float64(w) v) / sum w, each product rounded before it is added.  Row 0, and a group without a value (for
+    ``weightedmean`` also one whose weights sum to 0), hold ``missingStatsValue`` in the float statistics and 0 in the
+    integer ones.  The weighted mean of a ``Band_n_mean`` column by ``segSize`` is the merged object's band mean; the
+    class of a group after a key merge is ``keys[merged.representative]``.
+
+    The float sums are float64 in the order csrc/nbrreduce.h states for a row, here the group's member list: a group's
+    result depends on nothing but the group.  The member list is built on the device once per merge result and stays
+    there until the next merge call; on an older result ``recode`` is uploaded and the list rebuilt, with the same
+    bits as the result.  The resident neighbour table is not touched.
+    """
+    merged = _checkMerged(merged)
+    nrows = len(merged.recode)
+    (plan, ignore, missing) = _planSelections(nrows, columnSelections, ignoreValue, missingStatsValue, AGGREGATE_STATS,
+                                              _aggregateType)
+    w = None
+    if weights is not None:
+        w = _integerColumn(weights, 'weights', nrows)
+        if len(w) and int(w.min()) < 0:
+            raise PyShepSegNeighboursError("weights holds a negative value")
+    t0 = time.perf_counter()
+    c = _lib.ctx()
+    L = c._L
+    timings = {'deviceMs': 0.0}
+    _residentMembers(c, merged, timings)
+    t1 = time.perf_counter()
+    out = {}
+    ngroups = int(merged.maxSegId) + 1
+    for (column, ctype, picked) in plan:
+        if ctype == _COLUMN_TYPES[numpy.dtype(numpy.int64)]:
+            column = numpy.ascontiguousarray(column.astype(numpy.int64, copy=False))
+        arrays = {}
+        mask = 0
+        ptrs = (ctypes.c_void_p * len(AGGREGATE_STATS))()
+        for (_outName, bit, dtype) in picked:
+            if bit not in arrays:
+                if dtype is None:
+                    dtype = numpy.int64 if column.dtype.kind in 'iu' else numpy.float64
+                arrays[bit] = numpy.empty(ngroups, dtype=dtype)
+                ptrs[bit] = arrays[bit].ctypes.data
+                mask |= 1 << bit
+        ms = ctypes.c_double(0)
+        c.check(L.shp_nbr_aggregate(c.handle, _lib.ptr(column), ctype, nrows, None if w is None else _lib.ptr(w),
+                                    int(ignore is not None), 0.0 if ignore is None else ignore, missing, mask, ptrs,
+                                    ctypes.byref(ms)))
+        timings['deviceMs'] += ms.value
+        first = set()
+        for (outName, bit, _dtype) in picked:
+            out[outName] = arrays[bit] if bit not in first else arrays[bit].copy()
+            first.add(bit)
+    timings['aggregate'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    merged.aggregateTimings = timings
+    return out
