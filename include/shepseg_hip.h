@@ -815,6 +815,42 @@ int shp_dnbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_out)
 int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows, int has_ignore, double ignore_value,
                         double missing_value, uint32_t stat_mask, void *d_out, double *dev_ms_out);
 
+/* ---- shp_nbr_merge / shp_nbr_merge_similar over the share table (csrc/dnbrmerge.h) ---------------------
+ * The groups of the WHOLE table on every rank, from the ranks' share tables, and the contracted table sharded by the
+ * new ids.  The links, the groups' numbering and the contracted table are shp_nbr_merge's; columns are the full ones
+ * (max_seg_id + 1 values, host memory, the same on every rank).  Between the calls the caller runs the collectives.
+ *  shp_dnbr_mrg_begin: the rule (n_cols 0: the key rule of shp_nbr_merge, keys required; otherwise the rule of
+ *    shp_nbr_merge_similar) over the context's share table, which every later step reads.  With mutual_nearest the
+ *    rows' best neighbours are found and *d_best_out is an int64 column of max_seg_id + 1 values in context memory,
+ *    best + 1 in the share's rows and 0 elsewhere: an integer all-reduce over the ranks completes it in place.
+ *    Otherwise *d_best_out is NULL.  dev_ms_out[2]: the records' kernels, the best passes.
+ *  shp_dnbr_mrg_hook: the share's entries a < b that are links are hooked into a forest over all ids.
+ *    counts_out[3]: links, entries a < b, forest pairs; *d_pairs_out: that many 8-byte pairs (id, root of the id in
+ *    this rank's forest) of the ids that are not their own root, in context memory (NULL for none), for an all-gather
+ *    with slot = the largest count.  dev_ms_out[2]: the hook, the flatten and the compaction.
+ *  shp_dnbr_mrg_number: d_all holds `world` blocks of `slot` pairs, counts[r] (host) valid ones in block r; the pairs
+ *    of the blocks other than `rank` are hooked into the rank's forest and the groups are numbered.  From here on the
+ *    context holds the groups as after shp_nbr_merge: shp_nbr_merge_groups, shp_nbr_merge_recode_dev,
+ *    shp_nbr_members_build and shp_nbr_aggregate serve them (shp_nbr_merge_contract does not: there is no one-GPU
+ *    table).  *d_hist_out: the groups' histogram, max_group + 1 int64 in context memory (after
+ *    shp_nbr_merge_recode_dev with count_hist an integer all-reduce completes it).  dev_ms_out[2]: the pairs' hook,
+ *    the renumbering.
+ *  shp_dnbr_mrg_records: the share's entries a < b between two groups become records, are reduced to distinct pairs
+ *    and split against the rank's share new_id_lo .. new_id_hi - 1 of the new ids, as shp_dnbr_local_dev leaves them:
+ *    *d_travel_out for the all-gather, then shp_dnbr_merge_dev builds the new share table (max_seg_id = max_group),
+ *    which replaces the old one under a new serial.  counts_out[5]: records, distinct pairs, home records, travelling
+ *    records, border lengths outside 1 .. 2^32 - 1; with such a length nothing else is done, the old share table stays
+ *    and the merge has ended. */
+int shp_dnbr_mrg_begin(shp_ctx *ctx, const double *const *cols, int n_cols, int64_t n_rows, int has_ignore_value,
+                       double ignore_value, int has_threshold, double thr2, int mutual_nearest, const int64_t *keys,
+                       int has_ignore_key, int64_t ignore_key, int64_t min_border, const int64_t *seg_size,
+                       void **d_best_out, double *dev_ms_out);
+int shp_dnbr_mrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, double *dev_ms_out);
+int shp_dnbr_mrg_number(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, int rank,
+                        uint32_t *max_group_out, void **d_hist_out, double *dev_ms_out);
+int shp_dnbr_mrg_records(shp_ctx *ctx, int64_t new_id_lo, int64_t new_id_hi, int64_t *counts_out, void **d_travel_out,
+                         double *dev_ms_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

@@ -243,6 +243,12 @@ _SIGS = {
     'shp_dnbr_table_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
     'shp_dnbr_reduce_dev': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,
                                        _vp, _c.POINTER(_c.c_double)]),
+    'shp_dnbr_mrg_begin': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _c.c_double,
+                                      _c.c_int, _vp, _c.c_int, _c.c_int64, _c.c_int64, _vp, _c.POINTER(_vp), _vp]),
+    'shp_dnbr_mrg_hook': (_c.c_int, [_vp, _vp, _c.POINTER(_vp), _vp]),
+    'shp_dnbr_mrg_number': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _c.c_int, _c.POINTER(_c.c_uint32),
+                                       _c.POINTER(_vp), _vp]),
+    'shp_dnbr_mrg_records': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _vp, _c.POINTER(_vp), _vp]),
 }
 
 _lib = None

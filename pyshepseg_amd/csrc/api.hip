@@ -22,6 +22,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "nbrmerge.h"
 #include "nbragg.h"
 #include "dneighbours.h"
+#include "dnbrmerge.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -114,7 +115,7 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff,
                  &ctx->mrg_ctr, &ctx->mrg_key, &ctx->mrg_size, &ctx->mrg_par, &ctx->mrg_root, &ctx->mrg_idx,
                  &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist, &ctx->mrg_rec, &ctx->mrg_bestd,
-                 &ctx->mrg_best, &ctx->agg_recode, &ctx->agg_gsize, &ctx->agg_ctr, &ctx->agg_scan, &ctx->agg_offs,
+                 &ctx->mrg_best, &ctx->dmrg_b64, &ctx->dmrg_pairs, &ctx->dmrg_pcnt, &ctx->agg_recode, &ctx->agg_gsize, &ctx->agg_ctr, &ctx->agg_scan, &ctx->agg_offs,
                  &ctx->agg_mem, &ctx->agg_wcol, &ctx->agg_w, &ctx->agg_lrow, &ctx->agg_lcoff};
     *out = ctx;
     return SHP_OK;
@@ -1722,6 +1723,69 @@ API int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_
         SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
     if (stat_mask == 0u || stat_mask >= (1u << NBRR_NPUBLIC)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
     return run_dnbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, d_out, dev_ms_out);
+}
+
+// ---- the merges of nbrmerge.h over the share table (dnbrmerge.h) ------------------------------------------
+API int shp_dnbr_mrg_begin(shp_ctx *ctx, const double *const *cols, int n_cols, int64_t n_rows, int has_ignore_value,
+                           double ignore_value, int has_threshold, double thr2, int mutual_nearest, const int64_t *keys,
+                           int has_ignore_key, int64_t ignore_key, int64_t min_border, const int64_t *seg_size,
+                           void **d_best_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    ctx->mrg.stage = 0;
+    ctx->dmrg.stage = 0;
+    if (ctx->dnbr.stage != 2)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev or shp_dnbr_upload must come first");
+    if (!d_best_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n_cols < 0 || n_cols > MRGS_MAX_COLS) SHP_FAIL(ctx, SHP_ERR_ARG, "%d distance columns: 0 to %d wanted", n_cols, MRGS_MAX_COLS);
+    if (n_cols > 0 && !cols) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    for (int c = 0; c < n_cols; c++)
+        if (!cols[c]) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n_cols == 0 && !keys) SHP_FAIL(ctx, SHP_ERR_ARG, "the key rule needs keys");
+    if (n_rows != (int64_t)ctx->dnbr.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
+    if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
+    if (n_cols > 0 && !has_threshold && !mutual_nearest)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "no threshold: only the mutual-nearest rule does without");
+    if (n_cols > 0 && has_threshold && !(thr2 >= 0.0)) SHP_FAIL(ctx, SHP_ERR_ARG, "thr2 %g", thr2);
+    return run_dmrg_begin(ctx, cols, n_cols, has_ignore_value, ignore_value, has_threshold, thr2, mutual_nearest, keys,
+                          has_ignore_key, ignore_key, min_border, seg_size, d_best_out, dev_ms_out);
+}
+
+API int shp_dnbr_mrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dmrg.stage != 1 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no merge begun on the context's share table: shp_dnbr_mrg_begin must come first");
+    if (!counts_out || !d_pairs_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_dmrg_hook(ctx, counts_out, d_pairs_out, dev_ms_out);
+}
+
+API int shp_dnbr_mrg_number(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, int rank,
+                            uint32_t *max_group_out, void **d_hist_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dmrg.stage != 2 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no hooked merge on the context's share table: shp_dnbr_mrg_hook must come first");
+    if (!max_group_out || !d_hist_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (slot < 0 || world < 0 || rank < 0 || (slot > 0 && world > 0 && (!d_all || !counts || rank >= world)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if ((uintptr_t)d_all & 7u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
+    if (slot == 0) world = 0;
+    return run_dmrg_number(ctx, (const uint2 *)d_all, (unsigned long long)slot, (uint32_t)world, counts, (uint32_t)rank,
+                           max_group_out, d_hist_out, dev_ms_out);
+}
+
+API int shp_dnbr_mrg_records(shp_ctx *ctx, int64_t new_id_lo, int64_t new_id_hi, int64_t *counts_out, void **d_travel_out,
+                             double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->dmrg.stage != 3 || ctx->mrg.stage != 1 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no numbered merge on the context's share table: shp_dnbr_mrg_number must come first");
+    if (!counts_out || !d_travel_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (new_id_lo < 0 || new_id_hi < new_id_lo || new_id_hi > (int64_t)ctx->mrg.M + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%u", (long long)new_id_lo, (long long)new_id_hi, ctx->mrg.M);
+    return run_dmrg_records(ctx, (uint32_t)new_id_lo, (uint32_t)new_id_hi, counts_out, d_travel_out, dev_ms_out);
 }
 
 // a column shared by rows over the ranks: shp_colour_stretch in steps (colour.h)

@@ -102,6 +102,18 @@ struct MrgState {
     bool has_size = false, contracted = false;
 };
 
+// a merge over a rank's share table (dnbrmerge.h) between its steps: the link rule as shp_dnbr_mrg_begin was given
+// it (the columns lie in mrg_key / mrg_size / mrg_rec), the share table it reads, the forest pairs it sends
+struct DMrgState {
+    int stage = 0;                  // 0 none, 1 begun (columns placed, the mutual rule's best packed), 2 hooked, 3 numbered
+    int similar = 0, ncol = 0, has_key = 0, has_size = 0, has_ign = 0, has_thr = 0, mutual = 0;
+    long long ign = 0, minb = 1;
+    double thr2 = 0.0;
+    unsigned long long table_serial = 0;        // DNbrState::serial of the share table
+    unsigned long long npairs = 0;
+    double ms_records = 0.0;
+};
+
 // the member list of a merge's groups (nbragg.h): the old ids of every group in ascending order, as a CSR over the
 // new ids 0 .. M in buffers of its own (agg_*), with the list of its long rows.  serial: the groups it belongs to
 // (MrgState::serial, or a number of its own when the recode came from the host).  It lasts until the next merge.
@@ -135,13 +147,14 @@ struct shp_ctx {
         nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part,
         dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff,
         mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist,
-        mrg_rec, mrg_bestd, mrg_best,
+        mrg_rec, mrg_bestd, mrg_best, dmrg_b64, dmrg_pairs, dmrg_pcnt,
         agg_recode, agg_gsize, agg_ctr, agg_scan, agg_offs, agg_mem, agg_wcol, agg_w, agg_lrow, agg_lcoff;
     SegPointsState pts;
     NbrState nbr;
     MrgState mrg;
     AggState agg;
     DNbrState dnbr;
+    DMrgState dmrg;
     // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
     // has, new with every shp_nbr_begin, shp_nbr_upload and shp_nbr_merge_contract (kept here: run_nbr_begin resets `nbr`); the list of the
     // table's long rows (nbrr_lrow, nbrr_lcoff) belongs to the table nbrr_list_serial

@@ -50,12 +50,15 @@ static_assert(MRG_PIECE % 256u == 0u, "MRG_PIECE is a multiple of the workgroup"
 // [3] records whose border length does not fit 32 bits, [4] largest label above S met by k_mrg_recode
 enum { MRG_C_LINKS = 0, MRG_C_HALF = 1, MRG_C_REC = 2, MRG_C_WIDE = 3, MRG_C_BAD = 4, MRG_C_WORDS = 8 };
 
+// The table of the context (rows 0 .. S) or the rows of a rank's id share (dnbrmerge.h): row i is id row0 + i.
 struct MrgTable {
     const long long *offs;
     const uint32_t *ids;
     const long long *lens;
-    uint32_t ns;                // rows: S + 1
+    uint32_t ns;                // ids: S + 1
     long long nent;
+    uint32_t nrows;             // rows of offs: S + 1, or those of the share
+    uint32_t row0;              // id of row 0: 0, or the share's first id
 };
 
 // A link rule answers link(a, b, w) for an entry with a < b, both ids inside the table.
@@ -135,7 +138,7 @@ __device__ __forceinline__ uint32_t mrg_row_of(const long long *__restrict__ off
 // the rows of the first and the last entry of the workgroup's piece, into s_r[0] and s_r[1]
 __device__ __forceinline__ void mrg_piece_rows(const MrgTable &t, long long e0, long long e1, uint32_t *s_r)
 {
-    if (threadIdx.x < 2u) s_r[threadIdx.x] = mrg_row_of(t.offs, 0u, t.ns - 1u, threadIdx.x == 0u ? e0 : e1 - 1);
+    if (threadIdx.x < 2u) s_r[threadIdx.x] = mrg_row_of(t.offs, 0u, t.nrows - 1u, threadIdx.x == 0u ? e0 : e1 - 1);
     __syncthreads();
 }
 
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(256) void k_mrg_hook(MrgTable t, Rule q, uint32_t *
         const long long e = e0 + (long long)(k * 256u + threadIdx.x);
         if (e >= e1) break;
         const uint32_t b = t.ids[e];
-        const uint32_t a = mrg_row_of(t.offs, rlo, rhi, e);
+        const uint32_t a = t.row0 + mrg_row_of(t.offs, rlo, rhi, e);
         // (row 0 has no entries and no id lies past the table in a checked table: neither is relied on here)
         if (a == 0u || a >= b || b >= t.ns) continue;
         nhalf++;
@@ -243,7 +246,7 @@ __global__ __launch_bounds__(256) void k_mrgs_best(MrgTable t, MrgSimRule q, uns
         const long long e = e0 + (long long)(k * 256u + threadIdx.x);
         if (e >= e1) break;
         const uint32_t b = t.ids[e];
-        const uint32_t a = mrg_row_of(t.offs, rlo, rhi, e);
+        const uint32_t a = t.row0 + mrg_row_of(t.offs, rlo, rhi, e);
         if (a == 0u || a == b || b == 0u || b >= t.ns) continue;
         double d;
         if (!q.candidate(a, b, t.lens[e], d)) continue;
@@ -331,7 +334,7 @@ __global__ __launch_bounds__(256) void k_mrg_records(MrgTable t, const uint32_t 
         long long w = 0;
         if (e < e1) {
             const uint32_t b = t.ids[e];
-            const uint32_t a = mrg_row_of(t.offs, rlo, rhi, e);
+            const uint32_t a = t.row0 + mrg_row_of(t.offs, rlo, rhi, e);
             if (a != 0u && a < b && b < t.ns) {
                 const uint32_t ra = recode[a], rb = recode[b];
                 if (ra != 0u && rb != 0u && ra != rb) {
@@ -422,7 +425,7 @@ __global__ __launch_bounds__(256) void k_mrg_recode(const uint32_t *__restrict__
 static inline MrgTable mrg_table(shp_ctx *ctx)
 {
     return MrgTable{(const long long *)ctx->nbr_offs.p, (const uint32_t *)ctx->nbr_ids.p, (const long long *)ctx->nbr_lens.p,
-                    ctx->nbr.S + 1u, (long long)ctx->nbr.nent};
+                    ctx->nbr.S + 1u, (long long)ctx->nbr.nent, ctx->nbr.S + 1u, 0u};
 }
 
 static inline unsigned mrg_pieces(unsigned long long nent)
@@ -430,16 +433,16 @@ static inline unsigned mrg_pieces(unsigned long long nent)
     return (unsigned)((nent + MRG_PIECE - 1u) / MRG_PIECE);
 }
 
+// S, nent: the table's last id and its entries (the context's finished table, or a rank's share table).
 // The buffers of a merge, its host columns on the device (either may be NULL), zeroed counters and the parent array
 // with every id its own root: what comes before the hook of either link rule.  ev[0] is recorded in front of the
 // parent array's launch.  The groups of the merge before, and their member list (nbragg.h), end here.
-static int mrg_begin(shp_ctx *ctx, const int64_t *keys, const int64_t *seg_size)
+static int mrg_begin(shp_ctx *ctx, uint32_t S, unsigned long long nent, const int64_t *keys, const int64_t *seg_size)
 {
     hipStream_t st = ctx->stream;
     ctx->mrg = MrgState{};
     ctx->agg = AggState{};
-    const size_t ns = (size_t)ctx->nbr.S + 1;
-    const unsigned long long nent = ctx->nbr.nent;
+    const size_t ns = (size_t)S + 1;
     if (nent > (unsigned long long)MRG_PIECE * 0x7fffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "%llu entries: too many", nent);
     if (keys) CHK(buf_ensure(ctx, ctx->mrg_key, ns * 8));
     if (seg_size) CHK(buf_ensure(ctx, ctx->mrg_size, ns * 8));
@@ -460,11 +463,10 @@ static int mrg_begin(shp_ctx *ctx, const int64_t *keys, const int64_t *seg_size)
 
 // What follows the hook of either link rule: the roots flagged, scanned and numbered, the groups written.  ms_out[2]:
 // device time since ev[0] (the hook), of the renumbering.
-static int mrg_number(shp_ctx *ctx, bool has_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+static int mrg_number(shp_ctx *ctx, uint32_t S, bool has_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
 {
     MrgState &g = ctx->mrg;
     hipStream_t st = ctx->stream;
-    const uint32_t S = ctx->nbr.S;
     const size_t ns = (size_t)S + 1;
     long long *d_size = has_size ? bp<long long>(ctx->mrg_size) : nullptr;
     uint32_t *par = bp<uint32_t>(ctx->mrg_par), *root = bp<uint32_t>(ctx->mrg_root), *idx = bp<uint32_t>(ctx->mrg_idx);
@@ -524,8 +526,8 @@ static int mrg_number(shp_ctx *ctx, bool has_size, uint32_t *M_out, int64_t *cou
 static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t ign, int64_t min_border,
                          const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
 {
-    CHK(mrg_begin(ctx, keys, seg_size));
     const unsigned long long nent = ctx->nbr.nent;
+    CHK(mrg_begin(ctx, ctx->nbr.S, nent, keys, seg_size));
     if (nent) {
         const MrgLinkRule q{bp<long long>(ctx->mrg_key), seg_size ? bp<long long>(ctx->mrg_size) : nullptr, has_ign,
                             (long long)ign, (long long)min_border};
@@ -533,20 +535,15 @@ static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t
                            bp<uint32_t>(ctx->mrg_par), (unsigned long long *)ctx->mrg_ctr.p);
         KCHK(ctx);
     }
-    return mrg_number(ctx, seg_size != nullptr, M_out, counters_out, ms_out);
+    return mrg_number(ctx, ctx->nbr.S, seg_size != nullptr, M_out, counters_out, ms_out);
 }
 
-// The groups of the finished table under the similarity rule (MrgSimRule).  cols: ncol host columns of S + 1 float64;
-// keys and seg_size may be NULL.  The columns go through one staging plane into the records, in front of ev[0].
-// ms_out[3]: device time of the hook (with the two best passes of the mutual rule), of the renumbering, of the
-// records' kernels.
-static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int ncol, int has_ignv, double ignv, int has_thr,
-                                 double thr2, int mutual, const int64_t *keys, int has_ignk, int64_t ignk, int64_t min_border,
-                                 const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+// The distance columns (ncol host columns of ns float64) through one staging plane into the records of MrgSimRule,
+// ignored values marked; the mutual rule's two arrays are sized.  *ms_out: device time of the records' kernels.
+static int mrgs_place_columns(shp_ctx *ctx, const double *const *cols, int ncol, size_t ns, int has_ignv, double ignv,
+                              int mutual, double *ms_out)
 {
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)ctx->nbr.S + 1;
-    const unsigned long long nent = ctx->nbr.nent;
     CHK(buf_ensure(ctx, ctx->mrg_rec, ns * (size_t)ncol * 8));
     CHK(buf_ensure(ctx, ctx->img, ns * 8));
     if (mutual) {
@@ -570,7 +567,25 @@ static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int nc
         HIPCHK(ctx, hipEventElapsedTime(&ms1, ctx->ev[5], ctx->ev[6]));
         msr += ms1;
     }
-    CHK(mrg_begin(ctx, keys, seg_size));
+    *ms_out = msr;
+    return 0;
+}
+
+// The groups of the finished table under the similarity rule (MrgSimRule).  cols: ncol host columns of S + 1 float64;
+// keys and seg_size may be NULL.  The columns go through one staging plane into the records, in front of ev[0].
+// ms_out[3]: device time of the hook (with the two best passes of the mutual rule), of the renumbering, of the
+// records' kernels.
+static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int ncol, int has_ignv, double ignv, int has_thr,
+                                 double thr2, int mutual, const int64_t *keys, int has_ignk, int64_t ignk, int64_t min_border,
+                                 const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
+{
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)ctx->nbr.S + 1;
+    const unsigned long long nent = ctx->nbr.nent;
+    double msr = 0.0;
+    CHK(mrgs_place_columns(ctx, cols, ncol, ns, has_ignv, ignv, mutual, &msr));
+    double *rec = bp<double>(ctx->mrg_rec);
+    CHK(mrg_begin(ctx, ctx->nbr.S, nent, keys, seg_size));
     if (nent) {
         MrgSimRule q{rec, ncol, keys ? bp<long long>(ctx->mrg_key) : nullptr, seg_size ? bp<long long>(ctx->mrg_size) : nullptr,
                      has_ignk, (long long)ignk, (long long)min_border, has_thr, thr2, nullptr};
@@ -590,7 +605,7 @@ static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int nc
                            (unsigned long long *)ctx->mrg_ctr.p);
         KCHK(ctx);
     }
-    CHK(mrg_number(ctx, seg_size != nullptr, M_out, counters_out, ms_out));
+    CHK(mrg_number(ctx, ctx->nbr.S, seg_size != nullptr, M_out, counters_out, ms_out));
     if (ms_out) ms_out[2] = msr;
     return 0;
 }

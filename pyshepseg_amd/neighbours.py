@@ -403,6 +403,20 @@ class MergedSegments(object):
         return self.members[int(self.memberOffsets[group]):int(self.memberOffsets[group + 1])]
 
 
+class MergedSegmentsShare(MergedSegments):
+    """A rank's result of distributed.mergeSegmentsDistributed / mergeSimilarSegmentsDistributed.  ``recode``,
+    ``representative``, ``groupSize``, ``hist``, ``maxSegId``, ``links`` and ``recordsSorted`` are complete, the same on
+    every rank and equal to the one-GPU function's on the whole table.  ``neighbours`` is a SegmentNeighboursShare: the
+    rows of the contracted table of this rank's share of the new ids, resident on the rank's context as its share
+    table.  ``outDev``: this rank's rows of the recoded raster in device memory, (pointer, rows, columns, bytes), None
+    without rows; ``rowRange``: the image rows they are.  ``info``: this rank's figures of the exchange
+    (distributed.deviceMerge)."""
+    def __init__(self):
+        MergedSegments.__init__(self)
+        self.rowRange = None
+        self.info = {}
+
+
 def _integer(value, name):
     if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, (int, numpy.integer)):
         raise PyShepSegNeighboursError("{} must be an integer (got {!r})".format(name, value))
@@ -429,6 +443,11 @@ def _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile, outfi
     nrows = int(nb.maxSegId) + 1
     if len(nb.offsets) != nrows + 1 or len(nb.neighbours) != len(nb.borderLengths):
         raise PyShepSegNeighboursError("the table's arrays do not have the lengths of maxSegId {}".format(nb.maxSegId))
+    return _checkMergeColumns(nrows, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile, keyOptional)
+
+
+def _checkMergeColumns(nrows, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile, keyOptional=False):
+    """_checkMergeArgs for a table of ``nrows`` ids, whatever holds its rows"""
     keys = None if (keyOptional and keyColumn is None) else _integerColumn(keyColumn, 'keyColumn', nrows)
     ignore = None
     if ignoreKey is not None:
@@ -634,6 +653,25 @@ def _distanceColumns(distanceColumns, nrows):
     return out
 
 
+def _checkSimilarRule(distanceColumns, nrows, maxDistance, mutualNearest, ignoreValue):
+    """(the columns as float64, ignoreValue or None, thr2 or None) of the similarity rule for a table of ``nrows`` ids"""
+    columns = _distanceColumns(distanceColumns, nrows)
+    if isinstance(mutualNearest, (bool, numpy.bool_)) is False:
+        raise PyShepSegNeighboursError("mutualNearest must be True or False (got {!r})".format(mutualNearest))
+    ignoreV = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
+    thr2 = None
+    if maxDistance is None:
+        if not mutualNearest:
+            raise PyShepSegNeighboursError("maxDistance=None (no threshold) needs mutualNearest=True")
+    else:
+        md = numpy.float64(_number(maxDistance, 'maxDistance'))
+        if not numpy.isfinite(md) or md < 0:
+            raise PyShepSegNeighboursError("maxDistance must be finite and not negative (got {!r})".format(maxDistance))
+        with numpy.errstate(over='ignore'):
+            thr2 = float(md * md)
+    return (columns, ignoreV, thr2)
+
+
 def mergeSimilarSegments(nb, distanceColumns, maxDistance=None, mutualNearest=False, ignoreValue=None, keyColumn=None,
                          ignoreKey=None, minBorder=1, segSize=None, segfile=None, outfile=None, chunkPixels=None):
     """
@@ -665,20 +703,8 @@ def mergeSimilarSegments(nb, distanceColumns, maxDistance=None, mutualNearest=Fa
     """
     (keys, ignoreK, minBorder, sizes, raster) = _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile,
                                                                  outfile, keyOptional=True)
-    columns = _distanceColumns(distanceColumns, int(nb.maxSegId) + 1)
-    if isinstance(mutualNearest, (bool, numpy.bool_)) is False:
-        raise PyShepSegNeighboursError("mutualNearest must be True or False (got {!r})".format(mutualNearest))
-    ignoreV = None if ignoreValue is None else _number(ignoreValue, 'ignoreValue')
-    thr2 = None
-    if maxDistance is None:
-        if not mutualNearest:
-            raise PyShepSegNeighboursError("maxDistance=None (no threshold) needs mutualNearest=True")
-    else:
-        md = numpy.float64(_number(maxDistance, 'maxDistance'))
-        if not numpy.isfinite(md) or md < 0:
-            raise PyShepSegNeighboursError("maxDistance must be finite and not negative (got {!r})".format(maxDistance))
-        with numpy.errstate(over='ignore'):
-            thr2 = float(md * md)
+    (columns, ignoreV, thr2) = _checkSimilarRule(distanceColumns, int(nb.maxSegId) + 1, maxDistance, mutualNearest,
+                                                 ignoreValue)
     cols = (ctypes.c_void_p * len(columns))(*[column.ctypes.data for column in columns])
 
     def links(c, S, M, counters, ms):
@@ -775,6 +801,11 @@ def aggregateToGroups(merged, columnSelections, weights=None, ignoreValue=None, 
     there until the next merge call; on an older result ``recode`` is uploaded and the list rebuilt, with the same
     bits as the result.  The resident neighbour table is not touched.
     """
+    return _aggregateOnContext(None, merged, columnSelections, weights, ignoreValue, missingStatsValue)
+
+
+def _aggregateOnContext(ctx, merged, columnSelections, weights, ignoreValue, missingStatsValue):
+    """aggregateToGroups on the context ``ctx`` (None: the calling thread's)"""
     merged = _checkMerged(merged)
     nrows = len(merged.recode)
     (plan, ignore, missing) = _planSelections(nrows, columnSelections, ignoreValue, missingStatsValue, AGGREGATE_STATS,
@@ -785,7 +816,7 @@ def aggregateToGroups(merged, columnSelections, weights=None, ignoreValue=None, 
         if len(w) and int(w.min()) < 0:
             raise PyShepSegNeighboursError("weights holds a negative value")
     t0 = time.perf_counter()
-    c = _lib.ctx()
+    c = _lib.ctx() if ctx is None else ctx
     L = c._L
     timings = {'deviceMs': 0.0}
     _residentMembers(c, merged, timings)
