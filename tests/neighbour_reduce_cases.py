@@ -72,7 +72,15 @@ def reference_reduce(offsets, nbrs, lens, col, stats=STATS, ignoreValue=None, mi
     v = np.asarray(col).astype(np.float64)
     nrows = len(offsets) - 1
     assert len(v) == nrows and offsets[0] == 0 and offsets[-1] == len(nbrs) == len(lens)
-    assert lens.size == 0 or int(lens.max()) < 1 << 26
+    if lens.size and int(lens.max()) >= 1 << 26:
+        # _exact_products wants |w| < 2^26.  Longer lengths are as exact where the column holds integers of at most 26
+        # bits (y splits into y + 0) and no row's sum of w (1 + 2 max|v|) reaches 2^53: every product, difference and
+        # partial sum is then an integer float64 holds
+        known = v[~np.isnan(v)]
+        top = float(np.abs(known).max()) if known.size else 0.0
+        assert (known == np.rint(known)).all() and top < 1 << 26
+        assert (lens >= 0).all() and float(np.add.reduceat(lens.astype(np.float64), offsets[:-1][np.diff(offsets) > 0]).max()) \
+            * (1.0 + 2.0 * top) < 2.0 ** 53
 
     def ignored(x):
         bad = np.isnan(x)

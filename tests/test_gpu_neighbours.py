@@ -12,8 +12,10 @@ entry points refuse.  Which route every patch took, and that a block run twice
 neither lost nor doubled records, shows in ``recordsSorted``: it must EQUAL the count of the numpy model
 neighbour_cases.patch_records.
 
-Not covered: border lengths of 2^32 and more (the 64-bit sums need over 10^9 pixel pairs of one pair, which no test of
-seconds reaches) and labels of 2^31 and more in a successful table (its offsets alone are 16 GB)."""
+Border lengths of 2^32 and more (from a raster the 64-bit sums need over 10^9 pixel pairs of one pair) are reached
+through the contraction of hand-built tables: tests/test_gpu_merge_tables.py and tests/test_gpu_merge_tables_dist.py
+put non-zero high words through k_nbr_reduce, its copy in dneighbours.h and the share merge.  Not covered: labels of
+2^31 and more in a successful table (its offsets alone are 16 GB)."""
 import ctypes
 import functools
 import os
