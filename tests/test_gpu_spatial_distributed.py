@@ -114,6 +114,34 @@ def _check_split(world, dtype, nullv, span, oracle):
         assert (wf[:, S] == -9999).all() and (wi[:, S] == -9999).all()       # an id nobody holds
 
 
+@pytest.mark.parametrize('straddler', [False, True])
+def test_spatial_split_smallest_exchange(straddler):
+    """Two ranks of two rows of a 4 x 3 raster whose labels are constant within a rank's rows: no rank has a record
+    to send, so nothing is gathered (the shards above reach that at world 1 only; their empty shard is the rank
+    without records beside ranks that have some).  With ``straddler`` one more segment runs down column 0 across
+    the boundary."""
+    from pyshepseg_amd import distributed, tilingstats as ts
+    seg = np.repeat(np.array([1, 1, 2, 2], dtype=np.uint32), 3).reshape(4, 3)
+    if straddler:
+        seg[1:3, 0] = 3
+    band = (np.arange(12, dtype=np.uint16) * 7 + 1).reshape(4, 3)
+    hist = np.bincount(seg.ravel(), minlength=4).astype(np.uint32)
+    cases = _cases()
+
+    def work(c, comm, d_seg, d_band, rr):
+        return [distributed.deviceSpatialStats(c, comm, d_seg, d_band, 2, 4, 3, rr, hist, types, fn, prm, -9999, 0)
+                for (_name, fn, prm, types, _exact) in cases]
+    (results, errors) = H.runShards(seg, band, [(0, 2), (2, 4)], work, timeout=120)
+    assert not any(errors), errors
+    for (k, (name, fn, prm, types, _exact)) in enumerate(cases):
+        (wi, wf) = ts.calcPerSegmentSpatialStats(seg, band, types, fn, prm, 0, maxSegId=3)
+        for r in range(2):
+            (ic, fc, nStrad, _halo) = results[r][k]
+            assert nStrad == int(straddler), (name, prm, r)
+            assert np.array_equal(ic, wi), (name, prm, r)
+            assert np.array_equal(fc.view(np.uint32), wf.view(np.uint32)), (name, prm, r)
+
+
 def test_spatial_split_wrong_histogram_raises_everywhere():
     """a histogram that does not match the labels, too small for one id or too large for another, and a nodata
     value missing on one rank: every rank raises the same error, none hangs in a collective"""

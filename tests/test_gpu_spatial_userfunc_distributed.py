@@ -100,6 +100,34 @@ def test_userfunc_split_matches_one_gpu(world, dtype, nullv, tile):
     assert (one[0][:, 0] == 0).all() and (one[1][:, 0] == 0).all()
 
 
+@pytest.mark.parametrize('straddler', [False, True])
+def test_userfunc_split_smallest_exchange(straddler):
+    """Two ranks of two rows of a 4 x 3 raster whose labels are constant within a rank's rows: no rank has a point
+    record to send, so nothing is gathered (the shards above reach that at world 1 only; their empty shard is the
+    rank without records beside ranks that have some).  With ``straddler`` one more segment runs down column 0
+    across the boundary: its two points travel."""
+    from pyshepseg_amd import distributed, tilingstats as ts
+    seg = np.repeat(np.array([1, 1, 2, 2], dtype=np.uint32), 3).reshape(4, 3)
+    if straddler:
+        seg[1:3, 0] = 3
+    band = (np.arange(12, dtype=np.uint16) * 7 + 1).reshape(4, 3)
+    hist = np.bincount(seg.ravel(), minlength=4).astype(np.uint32)
+    fn = ts.spatialUserFunc(U.order_hash)
+
+    def work(c, comm, d_seg, d_band, rr):
+        info = {}
+        res = distributed.deviceSpatialStats(c, comm, d_seg, d_band, 2, 4, 3, rr, hist, _types(), fn, 9, -9999, 0,
+                                             tileSize=2, batchPoints=25, info=info)
+        return res, info
+    (results, errors) = H.runShards(seg, band, [(0, 2), (2, 4)], work, timeout=120)
+    assert not any(errors), errors
+    (one, nump) = _want(seg, band, 0, 2, 3, 9)
+    assert _same(one, nump)
+    for (res, info) in results:
+        assert _same(res[:2], one)
+        assert info['straddlers'] == int(straddler) and info['points_exchanged'] == 2 * int(straddler)
+
+
 def test_userfunc_shared_rows_match_one_gpu():
     """tile-sharded output rows (two ranks share rows 20..30, each holding the labels of its part, zeros elsewhere):
     no halo is needed, the points of a segment on both sides interleave by visit index"""
