@@ -656,6 +656,35 @@ int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entries_ou
                    int64_t *counters_out, double *dev_ms_out);
 int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths);
 
+/* ---- per-segment shape attributes of a label raster (shapes.calcSegmentShapes) --------------------------
+ * Per id 1 .. max_seg_id, with (r, c) a pixel's coordinates from the caller's origin: area; the sums of r, c, r^2, c^2
+ * and r c modulo 2^64; the minimum and maximum of r and of c; perimeter (the N, S, W, E sides of the id's pixels whose
+ * other side is another label, label 0 or outside the raster), outer border (those whose other side is label 0 or
+ * outside) and edge pixels (pixels with at least one such side).  Integers throughout: the result does not depend on
+ * the row blocks.  The table lives in buffers of the context's own (88 bytes per id) that are reused between calls;
+ * the neighbour table and the group lists of the context are not touched.
+ *  shp_shape_label_max_dev: *max_label_out = the largest of npix labels in device memory (4-byte aligned), 0 without
+ *    pixels; dev_ms_out (may be NULL): device time of the kernel.
+ *  shp_shape_begin: an empty table of the rows 0 .. max_seg_id; pixel (0, 0) of the raster has the coordinates
+ *    (row0, col0), both 0 .. 2^32 - 1.
+ *  shp_shape_accumulate_dev: the next block of nrows rows of ncols labels, top to bottom.  d_seg is the first row
+ *    handed over: with has_above != 0 that is the raster's row above the block, with has_below != 0 the row below the
+ *    block follows it in memory (has_above + nrows + has_below rows are readable).  Sides of the block's own pixels
+ *    count, the two extra rows are only looked at.  Coordinates of 2^32 and more are SHP_ERR_ARG.
+ *  shp_shape_finish: the extents of ids without pixels become 0.  *bad_label_out: 0, or the largest label above
+ *    max_seg_id -- such labels were never looked up, there is no result and download fails.  dev_ms_out (may be
+ *    NULL): device time of the kernels since shp_shape_begin.
+ *  shp_shape_download: max_seg_id + 1 rows of 11 uint64 to host memory: area, sum r, sum c, sum r^2, sum c^2, sum r c,
+ *    perimeter, outer border, edge pixels, rowMin | rowMax << 32, colMin | colMax << 32.
+ * Out of order the calls fail with SHP_ERR_STATE ("shp_shape_begin must come first", "shp_shape_finish must come
+ * first"). */
+int shp_shape_label_max_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, uint32_t *max_label_out, double *dev_ms_out);
+int shp_shape_begin(shp_ctx *ctx, int64_t max_seg_id, int64_t row0, int64_t col0);
+int shp_shape_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_above,
+                             int has_below);
+int shp_shape_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, uint32_t *bad_label_out, double *dev_ms_out);
+int shp_shape_download(shp_ctx *ctx, uint64_t *rows);
+
 /* ---- columns reduced over the neighbour table (neighbours.reduceOverNeighbours) ----------------------
  * The finished table stays in the context; these calls reduce per-segment columns over its rows on the device.
  * Row r has entries with neighbour id n and border length w; v is the column widened to float64.  A value is ignored

@@ -215,6 +215,11 @@ _SIGS = {
     'shp_nbr_finish': (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_uint32), _vp,
                                   _c.POINTER(_c.c_double)]),
     'shp_nbr_download': (_c.c_int, [_vp, _vp, _vp, _vp]),
+    'shp_shape_label_max_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_double)]),
+    'shp_shape_begin': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64]),
+    'shp_shape_accumulate_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
+    'shp_shape_finish': (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_double)]),
+    'shp_shape_download': (_c.c_int, [_vp, _vp]),
     'shp_nbr_upload': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),
     'shp_nbr_table_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
     'shp_nbr_reduce': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,

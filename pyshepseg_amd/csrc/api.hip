@@ -23,6 +23,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "nbragg.h"
 #include "dneighbours.h"
 #include "dnbrmerge.h"
+#include "segshape.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -116,7 +117,8 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
                  &ctx->mrg_ctr, &ctx->mrg_key, &ctx->mrg_size, &ctx->mrg_par, &ctx->mrg_root, &ctx->mrg_idx,
                  &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist, &ctx->mrg_rec, &ctx->mrg_bestd,
                  &ctx->mrg_best, &ctx->dmrg_b64, &ctx->dmrg_pairs, &ctx->dmrg_pcnt, &ctx->agg_recode, &ctx->agg_gsize, &ctx->agg_ctr, &ctx->agg_scan, &ctx->agg_offs,
-                 &ctx->agg_mem, &ctx->agg_wcol, &ctx->agg_w, &ctx->agg_lrow, &ctx->agg_lcoff};
+                 &ctx->agg_mem, &ctx->agg_wcol, &ctx->agg_w, &ctx->agg_lrow, &ctx->agg_lcoff,
+                 &ctx->shape_tab, &ctx->shape_ctr};
     *out = ctx;
     return SHP_OK;
 }
@@ -1483,6 +1485,54 @@ API int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, i
     if (ctx->nbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish must come first");
     if (!offsets || (ctx->nbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_nbr_download(ctx, offsets, neighbours, border_lengths);
+}
+
+// ---- per-segment shape attributes (segshape.h) ----------------------------------------------------------
+API int shp_shape_label_max_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix, uint32_t *max_label_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!max_label_out || npix < 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (npix > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_seg & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_shape_label_max(ctx, d_seg, (size_t)npix, max_label_out, dev_ms_out);
+}
+
+API int shp_shape_begin(shp_ctx *ctx, int64_t max_seg_id, int64_t row0, int64_t col0)
+{
+    CHK(enter(ctx));
+    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    if (row0 < 0 || col0 < 0 || row0 > 0xffffffffll || col0 > 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "origin (%lld, %lld)", (long long)row0, (long long)col0);
+    return run_shape_begin(ctx, (uint32_t)max_seg_id, (unsigned long long)row0, (unsigned long long)col0);
+}
+
+API int shp_shape_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_above,
+                                 int has_below)
+{
+    CHK(enter(ctx));
+    if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
+    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_seg & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_shape_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, has_above, has_below);
+}
+
+API int shp_shape_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, uint32_t *bad_label_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (!max_seg_id_out || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
+    CHK(run_shape_finish(ctx, max_seg_id_out, bad_label_out));
+    if (dev_ms_out) *dev_ms_out = ctx->shape.dev_ms;
+    return 0;
+}
+
+API int shp_shape_download(shp_ctx *ctx, uint64_t *rows)
+{
+    CHK(enter(ctx));
+    if (ctx->shape.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished shapes: shp_shape_finish must come first");
+    if (!rows) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_shape_download(ctx, rows);
 }
 
 // ---- columns reduced over the neighbour table (nbrreduce.h) -----------------------------------------------

@@ -126,6 +126,16 @@ struct AggState {
     double dev_ms = 0.0;
 };
 
+// the per-segment shape table between shp_shape_begin and shp_shape_download (segshape.h), in buffers of its own
+// (shape_tab: 88 bytes per id; shape_ctr), so the neighbour table and the group lists stay where they are
+struct ShapeState {
+    int stage = 0;                  // 0 none, 1 accumulating, 2 finished
+    uint32_t S = 0;
+    unsigned long long row0 = 0, col0 = 0;      // coordinates of the raster's first pixel
+    unsigned long long rows_done = 0;           // rows of the blocks so far
+    double dev_ms = 0.0;
+};
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -148,8 +158,10 @@ struct shp_ctx {
         dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff,
         mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist,
         mrg_rec, mrg_bestd, mrg_best, dmrg_b64, dmrg_pairs, dmrg_pcnt,
-        agg_recode, agg_gsize, agg_ctr, agg_scan, agg_offs, agg_mem, agg_wcol, agg_w, agg_lrow, agg_lcoff;
+        agg_recode, agg_gsize, agg_ctr, agg_scan, agg_offs, agg_mem, agg_wcol, agg_w, agg_lrow, agg_lcoff,
+        shape_tab, shape_ctr;
     SegPointsState pts;
+    ShapeState shape;
     NbrState nbr;
     MrgState mrg;
     AggState agg;
