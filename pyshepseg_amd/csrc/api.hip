@@ -99,26 +99,6 @@ static int ctx_create(int device, int high_priority, shp_ctx **out, bool shared)
     for (int i = 0; i < 16; i++) hipEventCreate(&ctx->ev[i]);
     hipEventCreateWithFlags(&ctx->evfork, hipEventDisableTiming);
     hipEventCreateWithFlags(&ctx->evjoin, hipEventDisableTiming);
-    ctx->bufs = {&ctx->img, &ctx->clus, &ctx->lab, &ctx->seg, &ctx->aux, &ctx->aux2, &ctx->stack,
-                 &ctx->scan_tmp, &ctx->sort_k0, &ctx->sort_k1, &ctx->sort_v1, &ctx->sort_hist,
-                 &ctx->pix, &ctx->segsz, &ctx->origsz, &ctx->off, &ctx->ssum, &ctx->chnext,
-                 &ctx->chtail, &ctx->mergeto, &ctx->tcount, &ctx->toff, &ctx->tfill, &ctx->tlist,
-                 &ctx->tsorted, &ctx->small, &ctx->cen, &ctx->fit_x, &ctx->fit_lab, &ctx->fit_part, &ctx->fit_lb,
-                 &ctx->big, &ctx->srclist, &ctx->tgtlist, &ctx->bigbits, &ctx->singles, &ctx->dbg, &ctx->snap,
-                 &ctx->pts_runs, &ctx->pts_off, &ctx->pts_offs, &ctx->pts_stage,
-                 &ctx->dpts_lh, &ctx->dpts_cls, &ctx->dpts_spos, &ctx->dpts_rec, &ctx->dpts_moff, &ctx->dpts_eoff,
-                 &ctx->dpts_cnt, &ctx->dpts_kpos, &ctx->dpts_mrec, &ctx->dpts_key, &ctx->dpts_idx, &ctx->dpts_k0,
-                 &ctx->dpts_k1, &ctx->dpts_v1, &ctx->dpts_pix, &ctx->vflag, &ctx->vlist, &ctx->vredo,
-                 &ctx->nbr_ctr, &ctx->nbr_rec, &ctx->nbr_key, &ctx->nbr_val, &ctx->nbr_uidx, &ctx->nbr_ua, &ctx->nbr_ub,
-                 &ctx->nbr_ucnt, &ctx->nbr_deg, &ctx->nbr_hoff, &ctx->nbr_loff, &ctx->nbr_offs, &ctx->nbr_ids,
-                 &ctx->nbr_lens, &ctx->nbrr_col, &ctx->nbrr_out, &ctx->nbrr_lrow, &ctx->nbrr_lcoff, &ctx->nbrr_part,
-                 &ctx->dnbr_blk, &ctx->dnbr_cnt, &ctx->dnbr_home, &ctx->dnbr_trav, &ctx->dnbr_mrg, &ctx->dnbr_rcnt,
-                 &ctx->dnbr_offs, &ctx->dnbr_ids, &ctx->dnbr_lens, &ctx->dnbr_lrow, &ctx->dnbr_lcoff,
-                 &ctx->mrg_ctr, &ctx->mrg_key, &ctx->mrg_size, &ctx->mrg_par, &ctx->mrg_root, &ctx->mrg_idx,
-                 &ctx->mrg_recode, &ctx->mrg_rep, &ctx->mrg_gsize, &ctx->mrg_hist, &ctx->mrg_rec, &ctx->mrg_bestd,
-                 &ctx->mrg_best, &ctx->dmrg_b64, &ctx->dmrg_pairs, &ctx->dmrg_pcnt, &ctx->agg_recode, &ctx->agg_gsize, &ctx->agg_ctr, &ctx->agg_scan, &ctx->agg_offs,
-                 &ctx->agg_mem, &ctx->agg_wcol, &ctx->agg_w, &ctx->agg_lrow, &ctx->agg_lcoff,
-                 &ctx->shape_tab, &ctx->shape_ctr};
     *out = ctx;
     return SHP_OK;
 }
@@ -1445,21 +1425,98 @@ API int shp_colour_lookup_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npix,
     return run_colour_lookup(ctx, d_seg, (size_t)npix, d_table, (uint32_t)nrows, d_out);
 }
 
+// ---- argument checks the entry points below share ---------------------------------------------------------------
+// a block of label rows in device memory (d_also: a second row pointer that must be aligned as well)
+static int chk_row_block(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, const void *d_also = nullptr)
+{
+    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_also & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return 0;
+}
+
+// lowest: -1 where "take the largest label" is an answer, 0 elsewhere
+static int chk_max_seg_id(shp_ctx *ctx, int64_t max_seg_id, int64_t lowest = 0)
+{
+    if (max_seg_id < lowest || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    return 0;
+}
+
+static int chk_id_share(shp_ctx *ctx, int64_t id_lo, int64_t id_hi, int64_t last_id)
+{
+    if (id_lo < 0 || id_hi < id_lo || id_hi > last_id + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%lld", (long long)id_lo, (long long)id_hi, (long long)last_id);
+    return 0;
+}
+
+// the three arrays of a table on the host, n_entries long where there are entries
+static int chk_table_ptrs(shp_ctx *ctx, const void *offsets, const void *neighbours, const void *border_lengths, int64_t n_entries)
+{
+    if (!offsets || (n_entries > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return 0;
+}
+static int chk_table_arrays(shp_ctx *ctx, const void *offsets, const void *neighbours, const void *border_lengths, int64_t n_entries)
+{
+    if (n_entries < 0 || n_entries >= (1ll << 40)) SHP_FAIL(ctx, SHP_ERR_ARG, "%lld entries", (long long)n_entries);
+    return chk_table_ptrs(ctx, offsets, neighbours, border_lengths, n_entries);
+}
+
+// a column of n_rows rows against the ids 0 .. S of a table (or, groups: of a member list)
+static int chk_column_rows(shp_ctx *ctx, int64_t n_rows, uint32_t S, bool groups = false)
+{
+    if (n_rows != (int64_t)S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, groups ? "a column of %lld rows for groups of %lld ids" : "a column of %lld rows for a table of %lld",
+                 (long long)n_rows, (long long)S + 1);
+    return 0;
+}
+
+// a column call: its type, its rows, the mask of nstats statistics and (outs given) a host output for every set bit
+static int chk_column_call(shp_ctx *ctx, int ctype, int64_t n_rows, uint32_t S, bool groups, uint32_t stat_mask, int nstats,
+                           void *const *outs)
+{
+    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
+    CHK(chk_column_rows(ctx, n_rows, S, groups));
+    if (stat_mask == 0u || stat_mask >= (1u << nstats)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    for (int i = 0; outs && i < nstats; i++)
+        if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
+    return 0;
+}
+
+// `world` gathered blocks of `slot` items with their counts; rank: the caller's own block (0 where it does not matter)
+static int chk_gathered(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, int rank = 0)
+{
+    if (slot < 0 || world < 0 || rank < 0 || (slot > 0 && world > 0 && (!d_all || !counts || rank >= world)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return 0;
+}
+
+static int need_table(shp_ctx *ctx)
+{
+    if (!ctx->nbr_tab.finished)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    return 0;
+}
+
+static int need_share_table(shp_ctx *ctx)
+{
+    if (!ctx->dnbr_tab.finished)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev or shp_dnbr_upload must come first");
+    return 0;
+}
+
 // ---- segment neighbours and border lengths (neighbours.h) -----------------------------------------------
 API int shp_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected)
 {
     CHK(enter(ctx));
-    if (max_seg_id < -1 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    CHK(chk_max_seg_id(ctx, max_seg_id, -1));
     return run_nbr_begin(ctx, max_seg_id, four_connected);
 }
 
 API int shp_nbr_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int has_next_row)
 {
     CHK(enter(ctx));
-    if (ctx->nbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
-    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
-    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if ((uintptr_t)d_seg & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    if (!ctx->nbr.open) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols));
     return run_nbr_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, has_next_row);
 }
 
@@ -1468,7 +1525,7 @@ API int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entrie
 {
     CHK(enter(ctx));
     if (!max_seg_id_out || !n_entries_out || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (ctx->nbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
+    if (!ctx->nbr.open) SHP_FAIL(ctx, SHP_ERR_STATE, "no table begun: shp_nbr_begin must come first");
     CHK(run_nbr_finish(ctx, max_seg_id_out, n_entries_out, bad_label_out));
     if (counters_out) {
         counters_out[0] = (int64_t)ctx->nbr.pairs;
@@ -1482,9 +1539,9 @@ API int shp_nbr_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, int64_t *n_entrie
 API int shp_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths)
 {
     CHK(enter(ctx));
-    if (ctx->nbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish must come first");
-    if (!offsets || (ctx->nbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    return run_nbr_download(ctx, offsets, neighbours, border_lengths);
+    if (!ctx->nbr_tab.finished) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish must come first");
+    CHK(chk_table_ptrs(ctx, offsets, neighbours, border_lengths, (int64_t)ctx->nbr_tab.nent));
+    return nbr_table_download(ctx, ctx->nbr_tab, offsets, neighbours, border_lengths);
 }
 
 // ---- per-segment shape attributes (segshape.h) ----------------------------------------------------------
@@ -1500,7 +1557,7 @@ API int shp_shape_label_max_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t npi
 API int shp_shape_begin(shp_ctx *ctx, int64_t max_seg_id, int64_t row0, int64_t col0)
 {
     CHK(enter(ctx));
-    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
+    CHK(chk_max_seg_id(ctx, max_seg_id));
     if (row0 < 0 || col0 < 0 || row0 > 0xffffffffll || col0 > 0xffffffffll)
         SHP_FAIL(ctx, SHP_ERR_ARG, "origin (%lld, %lld)", (long long)row0, (long long)col0);
     return run_shape_begin(ctx, (uint32_t)max_seg_id, (unsigned long long)row0, (unsigned long long)col0);
@@ -1511,9 +1568,7 @@ API int shp_shape_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nr
 {
     CHK(enter(ctx));
     if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
-    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
-    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if ((uintptr_t)d_seg & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols));
     return run_shape_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, has_above, has_below);
 }
 
@@ -1540,9 +1595,8 @@ API int shp_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *nei
                        int64_t max_seg_id, int64_t n_entries, double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
-    if (n_entries < 0 || n_entries >= (1ll << 40)) SHP_FAIL(ctx, SHP_ERR_ARG, "%lld entries", (long long)n_entries);
-    if (!offsets || (n_entries > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    CHK(chk_table_arrays(ctx, offsets, neighbours, border_lengths, n_entries));
     return run_nbr_upload(ctx, offsets, neighbours, border_lengths, (uint32_t)max_seg_id, (long long)n_entries, dev_ms_out);
 }
 
@@ -1551,8 +1605,8 @@ API int shp_nbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_o
     if (!ctx) return SHP_ERR_ARG;
     ctx->err.clear();
     if (!serial_out || !finished_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    *serial_out = ctx->nbr_serial;
-    *finished_out = ctx->nbr.stage == 2 ? 1 : 0;
+    *serial_out = ctx->nbr_tab.serial;
+    *finished_out = ctx->nbr_tab.finished ? 1 : 0;
     return 0;
 }
 
@@ -1560,15 +1614,9 @@ API int shp_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int64_t n_rows,
                        double missing_value, uint32_t stat_mask, void *const *outs, double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (ctx->nbr.stage != 2)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    CHK(need_table(ctx));
     if (!col || !outs) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
-    if (n_rows != (int64_t)ctx->nbr.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
-    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NPUBLIC)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
-    for (int i = 0; i < NBRR_NPUBLIC; i++)
-        if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
+    CHK(chk_column_call(ctx, ctype, n_rows, ctx->nbr_tab.S, false, stat_mask, NBRR_NPUBLIC, outs));
     return run_nbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
 }
 
@@ -1579,11 +1627,9 @@ API int shp_nbr_merge(shp_ctx *ctx, const int64_t *keys, int64_t n_rows, int has
 {
     CHK(enter(ctx));
     ctx->mrg.stage = 0;
-    if (ctx->nbr.stage != 2)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    CHK(need_table(ctx));
     if (!keys || !max_group_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (n_rows != (int64_t)ctx->nbr.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
+    CHK(chk_column_rows(ctx, n_rows, ctx->nbr_tab.S));
     if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
     return run_nbr_merge(ctx, keys, has_ignore, ignore_key, min_border, seg_size, max_group_out, counters_out, dev_ms_out);
 }
@@ -1600,7 +1646,7 @@ API int shp_nbr_merge_contract(shp_ctx *ctx, int64_t *n_entries_out, int64_t *re
     CHK(enter(ctx));
     if (!n_entries_out || !records_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (ctx->mrg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no groups: shp_nbr_merge must come first");
-    if (ctx->mrg.contracted || ctx->nbr.stage != 2 || ctx->nbr_serial != ctx->mrg.table_serial)
+    if (ctx->mrg.contracted || !ctx->nbr_tab.finished || ctx->nbr_tab.serial != ctx->mrg.table_serial)
         SHP_FAIL(ctx, SHP_ERR_STATE, "the table the groups were found in is no longer the context's finished table");
     return run_nbr_merge_contract(ctx, n_entries_out, records_out, dev_ms_out);
 }
@@ -1624,14 +1670,12 @@ API int shp_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int n_col
 {
     CHK(enter(ctx));
     ctx->mrg.stage = 0;
-    if (ctx->nbr.stage != 2)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "no finished table: shp_nbr_finish or shp_nbr_upload must come first");
+    CHK(need_table(ctx));
     if (!cols || !max_group_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (n_cols < 1 || n_cols > MRGS_MAX_COLS) SHP_FAIL(ctx, SHP_ERR_ARG, "%d distance columns: 1 to %d wanted", n_cols, MRGS_MAX_COLS);
     for (int c = 0; c < n_cols; c++)
         if (!cols[c]) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (n_rows != (int64_t)ctx->nbr.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->nbr.S + 1);
+    CHK(chk_column_rows(ctx, n_rows, ctx->nbr_tab.S));
     if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
     if (!has_threshold && !mutual_nearest) SHP_FAIL(ctx, SHP_ERR_ARG, "no threshold: only the mutual-nearest rule does without");
     if (has_threshold && !(thr2 >= 0.0)) SHP_FAIL(ctx, SHP_ERR_ARG, "thr2 %g", thr2);
@@ -1684,12 +1728,7 @@ API int shp_nbr_aggregate(shp_ctx *ctx, const void *col, int ctype, int64_t n_ro
     CHK(enter(ctx));
     if (ctx->agg.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no member list: shp_nbr_members_build must come first");
     if (!col || !outs) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
-    if (n_rows != (int64_t)ctx->agg.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for groups of %lld ids", (long long)n_rows, (long long)ctx->agg.S + 1);
-    if (stat_mask == 0u || stat_mask >= (1u << AGG_NSTATS)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
-    for (int i = 0; i < AGG_NSTATS; i++)
-        if (((stat_mask >> i) & 1u) && !outs[i]) SHP_FAIL(ctx, SHP_ERR_ARG, "no output for statistic %d", i);
+    CHK(chk_column_call(ctx, ctype, n_rows, ctx->agg.S, true, stat_mask, AGG_NSTATS, outs));
     return run_agg(ctx, col, ctype, weights, has_ignore, ignore_value, missing_value, stat_mask, outs, dev_ms_out);
 }
 
@@ -1700,12 +1739,9 @@ API int shp_dnbr_local_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, i
 {
     CHK(enter(ctx));
     if (!max_label_out || !counts_out || !d_travel_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
-    if (id_lo < 0 || id_hi < id_lo || id_hi > max_seg_id + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%lld", (long long)id_lo, (long long)id_hi, (long long)max_seg_id);
-    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
-    if (nrows > 0 && ncols > 0 && !d_seg) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (((uintptr_t)d_seg & 3u) || ((uintptr_t)d_halo_row & 3u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    CHK(chk_id_share(ctx, id_lo, id_hi, max_seg_id));
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols, d_halo_row));
     CHK(run_dnbr_local(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, nrows > 0 ? d_halo_row : nullptr, (uint32_t)max_seg_id,
                        four_connected, (uint32_t)id_lo, (uint32_t)id_hi, max_label_out, counts_out, d_travel_out));
     if (dev_ms_out) *dev_ms_out = ctx->dnbr.dev_ms;
@@ -1718,7 +1754,7 @@ API int shp_dnbr_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int wo
     CHK(enter(ctx));
     if (ctx->dnbr.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no local step: shp_dnbr_local_dev must come first");
     if (!d_cols || !n_picked_out || !n_entries_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (slot < 0 || world < 0 || (slot > 0 && world > 0 && (!d_all || !counts))) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(chk_gathered(ctx, d_all, slot, world, counts));
     if (((uintptr_t)d_all & 15u) || ((uintptr_t)d_cols & 7u)) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
     if (slot == 0) world = 0;
     CHK(run_dnbr_merge(ctx, (const uint4 *)d_all, (unsigned long long)slot, (uint32_t)world, counts, (long long *)d_cols,
@@ -1730,20 +1766,18 @@ API int shp_dnbr_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int wo
 API int shp_dnbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *neighbours, int64_t *border_lengths)
 {
     CHK(enter(ctx));
-    if (ctx->dnbr.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev must come first");
-    if (!offsets || (ctx->dnbr.nent > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    return run_dnbr_download(ctx, offsets, neighbours, border_lengths);
+    if (!ctx->dnbr_tab.finished) SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev must come first");
+    CHK(chk_table_ptrs(ctx, offsets, neighbours, border_lengths, (int64_t)ctx->dnbr_tab.nent));
+    return nbr_table_download(ctx, ctx->dnbr_tab, offsets, neighbours, border_lengths);
 }
 
 API int shp_dnbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *neighbours, const int64_t *border_lengths,
                         int64_t max_seg_id, int64_t id_lo, int64_t id_hi, int64_t n_entries)
 {
     CHK(enter(ctx));
-    if (max_seg_id < 0 || max_seg_id >= 0xfffffffell) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id %lld", (long long)max_seg_id);
-    if (id_lo < 0 || id_hi < id_lo || id_hi > max_seg_id + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%lld", (long long)id_lo, (long long)id_hi, (long long)max_seg_id);
-    if (n_entries < 0 || n_entries >= (1ll << 40)) SHP_FAIL(ctx, SHP_ERR_ARG, "%lld entries", (long long)n_entries);
-    if (!offsets || (n_entries > 0 && (!neighbours || !border_lengths))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    CHK(chk_id_share(ctx, id_lo, id_hi, max_seg_id));
+    CHK(chk_table_arrays(ctx, offsets, neighbours, border_lengths, n_entries));
     if (offsets[0] != 0 || offsets[id_hi - id_lo] != n_entries)
         SHP_FAIL(ctx, SHP_ERR_ARG, "not a share table: the offsets must run from 0 to the number of entries");
     return run_dnbr_upload(ctx, offsets, neighbours, border_lengths, (uint32_t)max_seg_id, (uint32_t)id_lo, (uint32_t)id_hi,
@@ -1755,8 +1789,8 @@ API int shp_dnbr_table_serial(shp_ctx *ctx, uint64_t *serial_out, int *finished_
     if (!ctx) return SHP_ERR_ARG;
     ctx->err.clear();
     if (!serial_out || !finished_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    *serial_out = ctx->dnbr.serial;
-    *finished_out = ctx->dnbr.stage == 2 ? 1 : 0;
+    *serial_out = ctx->dnbr_tab.serial;
+    *finished_out = ctx->dnbr_tab.finished ? 1 : 0;
     return 0;
 }
 
@@ -1764,14 +1798,10 @@ API int shp_dnbr_reduce_dev(shp_ctx *ctx, const void *col, int ctype, int64_t n_
                             double missing_value, uint32_t stat_mask, void *d_out, double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (ctx->dnbr.stage != 2)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev or shp_dnbr_upload must come first");
+    CHK(need_share_table(ctx));
     if (!col || !d_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if ((uintptr_t)d_out & 7u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
-    if (ctype != COL_F64 && ctype != COL_F32 && ctype != COL_I64) SHP_FAIL(ctx, SHP_ERR_ARG, "unknown column type %d", ctype);
-    if (n_rows != (int64_t)ctx->dnbr.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
-    if (stat_mask == 0u || stat_mask >= (1u << NBRR_NPUBLIC)) SHP_FAIL(ctx, SHP_ERR_ARG, "statistics mask %#x", stat_mask);
+    CHK(chk_column_call(ctx, ctype, n_rows, ctx->dnbr_tab.S, false, stat_mask, NBRR_NPUBLIC, nullptr));
     return run_dnbr_reduce(ctx, col, ctype, has_ignore, ignore_value, missing_value, stat_mask, d_out, dev_ms_out);
 }
 
@@ -1784,16 +1814,14 @@ API int shp_dnbr_mrg_begin(shp_ctx *ctx, const double *const *cols, int n_cols, 
     CHK(enter(ctx));
     ctx->mrg.stage = 0;
     ctx->dmrg.stage = 0;
-    if (ctx->dnbr.stage != 2)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "no share table: shp_dnbr_merge_dev or shp_dnbr_upload must come first");
+    CHK(need_share_table(ctx));
     if (!d_best_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (n_cols < 0 || n_cols > MRGS_MAX_COLS) SHP_FAIL(ctx, SHP_ERR_ARG, "%d distance columns: 0 to %d wanted", n_cols, MRGS_MAX_COLS);
     if (n_cols > 0 && !cols) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     for (int c = 0; c < n_cols; c++)
         if (!cols[c]) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (n_cols == 0 && !keys) SHP_FAIL(ctx, SHP_ERR_ARG, "the key rule needs keys");
-    if (n_rows != (int64_t)ctx->dnbr.S + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "a column of %lld rows for a table of %lld", (long long)n_rows, (long long)ctx->dnbr.S + 1);
+    CHK(chk_column_rows(ctx, n_rows, ctx->dnbr_tab.S));
     if (min_border < 1) SHP_FAIL(ctx, SHP_ERR_ARG, "min_border %lld", (long long)min_border);
     if (n_cols > 0 && !has_threshold && !mutual_nearest)
         SHP_FAIL(ctx, SHP_ERR_ARG, "no threshold: only the mutual-nearest rule does without");
@@ -1805,7 +1833,7 @@ API int shp_dnbr_mrg_begin(shp_ctx *ctx, const double *const *cols, int n_cols, 
 API int shp_dnbr_mrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (ctx->dmrg.stage != 1 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+    if (ctx->dmrg.stage != 1 || !ctx->dnbr_tab.finished || ctx->dnbr_tab.serial != ctx->dmrg.table_serial)
         SHP_FAIL(ctx, SHP_ERR_STATE, "no merge begun on the context's share table: shp_dnbr_mrg_begin must come first");
     if (!counts_out || !d_pairs_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_dmrg_hook(ctx, counts_out, d_pairs_out, dev_ms_out);
@@ -1815,11 +1843,10 @@ API int shp_dnbr_mrg_number(shp_ctx *ctx, const void *d_all, int64_t slot, int w
                             uint32_t *max_group_out, void **d_hist_out, double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (ctx->dmrg.stage != 2 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+    if (ctx->dmrg.stage != 2 || !ctx->dnbr_tab.finished || ctx->dnbr_tab.serial != ctx->dmrg.table_serial)
         SHP_FAIL(ctx, SHP_ERR_STATE, "no hooked merge on the context's share table: shp_dnbr_mrg_hook must come first");
     if (!max_group_out || !d_hist_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (slot < 0 || world < 0 || rank < 0 || (slot > 0 && world > 0 && (!d_all || !counts || rank >= world)))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(chk_gathered(ctx, d_all, slot, world, counts, rank));
     if ((uintptr_t)d_all & 7u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
     if (slot == 0) world = 0;
     return run_dmrg_number(ctx, (const uint2 *)d_all, (unsigned long long)slot, (uint32_t)world, counts, (uint32_t)rank,
@@ -1830,11 +1857,10 @@ API int shp_dnbr_mrg_records(shp_ctx *ctx, int64_t new_id_lo, int64_t new_id_hi,
                              double *dev_ms_out)
 {
     CHK(enter(ctx));
-    if (ctx->dmrg.stage != 3 || ctx->mrg.stage != 1 || ctx->dnbr.stage != 2 || ctx->dnbr.serial != ctx->dmrg.table_serial)
+    if (ctx->dmrg.stage != 3 || ctx->mrg.stage != 1 || !ctx->dnbr_tab.finished || ctx->dnbr_tab.serial != ctx->dmrg.table_serial)
         SHP_FAIL(ctx, SHP_ERR_STATE, "no numbered merge on the context's share table: shp_dnbr_mrg_number must come first");
     if (!counts_out || !d_travel_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (new_id_lo < 0 || new_id_hi < new_id_lo || new_id_hi > (int64_t)ctx->mrg.M + 1)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "id share %lld..%lld of 0..%u", (long long)new_id_lo, (long long)new_id_hi, ctx->mrg.M);
+    CHK(chk_id_share(ctx, new_id_lo, new_id_hi, (int64_t)ctx->mrg.M));
     return run_dmrg_records(ctx, (uint32_t)new_id_lo, (uint32_t)new_id_hi, counts_out, d_travel_out, dev_ms_out);
 }
 

@@ -63,30 +63,59 @@ struct DColourState {
     double gamma[2] = {}, lo = 0.0, hi = 0.0, dev_ms = 0.0;
 };
 
-// a segment-adjacency table between shp_nbr_begin and shp_nbr_download (neighbours.h).  The records and the
-// finished table live in buffers of their own (nbr_*), so transfers and other calls may come between the steps.
+// the rows of a CSR that the reduction kernels treat as long (nbrreduce.h: more than NBRR_LONG entries) and their
+// chunks: lrow[k] the k-th long row, lcoff[k] the chunks of the long rows before it.  serial: the table or member
+// list it was built for (0: none); nbrr_long_ensure builds it again only for another serial.
+struct NbrLongList {
+    DevBuf lrow, lcoff;
+    uint32_t nlong = 0, nchunks = 0;
+    unsigned long long serial = 0;
+};
+
+// A resident CSR neighbour table: rows row0 .. row0 + nrows - 1 of the ids 0 .. S, whole rows.  The one-GPU table
+// (neighbours.h) is the share [0, S + 1); the share table of a row-sharded raster (dneighbours.h) holds the rows of
+// distributed.idRange.  serial: a number no other table of the process has (nbr_next_serial); whoever remembers it
+// and the context can tell whether the buffers still hold that table.  S, row0 and nrows are known from the step
+// that begins a table; nent and finished once it stands.
+struct NbrTable {
+    DevBuf offs, ids, lens;         // nrows + 1 int64, nent uint32, nent int64
+    uint32_t S = 0, row0 = 0, nrows = 0;
+    unsigned long long nent = 0, serial = 0;
+    bool finished = false;
+    NbrLongList longs;
+};
+// the table is gone (its buffers and the list of its long rows stay allocated)
+static inline void nbr_table_end(NbrTable &t)
+{
+    t.S = t.row0 = t.nrows = 0u;
+    t.nent = t.serial = 0ull;
+    t.finished = false;
+}
+static inline void nbr_long_bufs(NbrLongList &l, std::vector<DevBuf *> &out) { out.push_back(&l.lrow); out.push_back(&l.lcoff); }
+static inline void nbr_table_bufs(NbrTable &t, std::vector<DevBuf *> &out)
+{
+    out.push_back(&t.offs); out.push_back(&t.ids); out.push_back(&t.lens);
+    nbr_long_bufs(t.longs, out);
+}
+
+// the records of a one-GPU table between shp_nbr_begin and shp_nbr_finish (neighbours.h), in a buffer of their own
+// (nbr_rec), so transfers and other calls may come between the steps.  The table they become is shp_ctx::nbr_tab.
 struct NbrState {
-    int stage = 0;                  // 0 none, 1 accumulating, 2 finished
+    bool open = false;              // accumulating
     int eight = 0;
     int64_t given = -1;             // the caller's max_seg_id, -1: take the largest label
     unsigned long long cap = 0, used = 0, last_block = 0;      // records: room, stored, of the last block
     unsigned long long pairs = 0;   // differing pixel pairs met
     unsigned long long reruns = 0;  // row blocks that did not fit and ran a second time
-    unsigned long long nent = 0;    // entries of the finished table
-    uint32_t max_label = 0, S = 0;
+    uint32_t max_label = 0;
     double dev_ms = 0.0;
 };
 
-// the neighbour table of this rank's id share [id_lo, id_hi) of a row-sharded raster (dneighbours.h): rows
-// id_hi - id_lo, in dnbr_offs / dnbr_ids / dnbr_lens -- buffers of its own, so the one-GPU table (nbr_*) and the share
-// table do not displace each other.  serial: from the numbering of nbr_serial, new with every local step and
-// upload; list_serial: the share table whose long rows dnbr_lrow / dnbr_lcoff list.
+// the exchange that builds a rank's share table (dneighbours.h, shp_ctx::dnbr_tab) between its local step and its
+// merge: the share itself (S, row0, nrows) waits in the table
 struct DNbrState {
-    int stage = 0;                  // 0 none, 1 local step done (home and travelling records packed), 2 share table built
-    uint32_t S = 0, id_lo = 0, id_hi = 0;
-    unsigned long long nlocal = 0, nhome = 0, ntrav = 0, nent = 0;
-    unsigned long long serial = 0, list_serial = 0;
-    uint32_t nlong = 0, nchunks = 0;
+    int stage = 0;                  // 0 none, 1 local step done (home and travelling records packed)
+    unsigned long long nlocal = 0, nhome = 0, ntrav = 0;
     double dev_ms = 0.0;
 };
 
@@ -98,7 +127,7 @@ struct MrgState {
     uint32_t S = 0, M = 0;
     unsigned long long links = 0, half = 0;     // links; entries with a < b
     unsigned long long table_serial = 0;
-    unsigned long long serial = 0;  // of these groups, from the numbering of nbr_serial: new with every merge
+    unsigned long long serial = 0;  // of these groups, from the numbering of the tables: new with every merge
     bool has_size = false, contracted = false;
 };
 
@@ -109,20 +138,20 @@ struct DMrgState {
     int similar = 0, ncol = 0, has_key = 0, has_size = 0, has_ign = 0, has_thr = 0, mutual = 0;
     long long ign = 0, minb = 1;
     double thr2 = 0.0;
-    unsigned long long table_serial = 0;        // DNbrState::serial of the share table
+    unsigned long long table_serial = 0;        // NbrTable::serial of the share table
     unsigned long long npairs = 0;
     double ms_records = 0.0;
 };
 
 // the member list of a merge's groups (nbragg.h): the old ids of every group in ascending order, as a CSR over the
-// new ids 0 .. M in buffers of its own (agg_*), with the list of its long rows.  serial: the groups it belongs to
-// (MrgState::serial, or a number of its own when the recode came from the host).  It lasts until the next merge.
+// new ids 0 .. M in buffers of its own (agg_*); the list of its long rows is shp_ctx::agg_longs, which this state's
+// resets leave alone.  serial: the groups it belongs to (MrgState::serial, or a number of its own when the recode
+// came from the host).  It lasts until the next merge.
 struct AggState {
     int stage = 0;                  // 0 none, 1 built
     uint32_t S = 0, M = 0;
     unsigned long long serial = 0, nmem = 0;
     const uint32_t *recode = nullptr;   // the device recode it was built from: mrg_recode or agg_recode
-    uint32_t nlong = 0, nchunks = 0;
     double dev_ms = 0.0;
 };
 
@@ -136,6 +165,22 @@ struct ShapeState {
     double dev_ms = 0.0;
 };
 
+// The context's named workspace buffers (grow-only), each named HERE ONLY: the list makes the members of shp_ctx and
+// the entries of shp_ctx::bufs, which is what buf_ensure's regrow log indexes and shp_ctx_destroy frees.
+#define SHP_CTX_BUFS(X) \
+    X(img) X(clus) X(lab) X(seg) X(aux) X(aux2) X(stack) X(scan_tmp) X(sort_k0) X(sort_k1) X(sort_v1) \
+    X(sort_hist) X(pix) X(segsz) X(origsz) X(off) X(ssum) X(chnext) X(chtail) X(mergeto) X(tcount) X(toff) \
+    X(tfill) X(tlist) X(tsorted) X(small) X(cen) X(fit_x) X(fit_lab) X(fit_part) X(fit_lb) X(big) X(srclist) \
+    X(tgtlist) X(bigbits) X(singles) X(dbg) X(snap) X(pts_runs) X(pts_off) X(pts_offs) X(pts_stage) X(dpts_lh) \
+    X(dpts_cls) X(dpts_spos) X(dpts_rec) X(dpts_moff) X(dpts_eoff) X(dpts_cnt) X(dpts_kpos) X(dpts_mrec) \
+    X(dpts_key) X(dpts_idx) X(dpts_k0) X(dpts_k1) X(dpts_v1) X(dpts_pix) X(vflag) X(vlist) X(vredo) X(nbr_ctr) \
+    X(nbr_rec) X(nbr_key) X(nbr_val) X(nbr_uidx) X(nbr_ua) X(nbr_ub) X(nbr_ucnt) X(nbr_deg) X(nbr_hoff) \
+    X(nbr_loff) X(nbrr_col) X(nbrr_out) X(nbrr_part) X(dnbr_blk) X(dnbr_cnt) X(dnbr_home) X(dnbr_trav) \
+    X(dnbr_mrg) X(dnbr_rcnt) X(mrg_ctr) X(mrg_key) X(mrg_size) X(mrg_par) X(mrg_root) X(mrg_idx) X(mrg_recode) \
+    X(mrg_rep) X(mrg_gsize) X(mrg_hist) X(mrg_rec) X(mrg_bestd) X(mrg_best) X(dmrg_b64) X(dmrg_pairs) \
+    X(dmrg_pcnt) X(agg_recode) X(agg_gsize) X(agg_ctr) X(agg_scan) X(agg_offs) X(agg_mem) X(agg_wcol) X(agg_w) \
+    X(shape_tab) X(shape_ctr)
+
 struct shp_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -144,22 +189,20 @@ struct shp_ctx {
     hipEvent_t evfork = nullptr, evjoin = nullptr;
     std::string err;
     std::vector<DevBuf *> bufs;
-    // named workspace buffers (grow-only)
-    DevBuf img, clus, lab, seg, aux, aux2, stack, scan_tmp, sort_k0, sort_k1, sort_v1, sort_hist,
-        pix, segsz, origsz, off, ssum, chnext, chtail, mergeto, tcount, toff, tfill, tlist, tsorted,
-        small, cen, fit_x, fit_lab, fit_part, fit_lb, big, srclist, tgtlist, bigbits, singles, dbg, snap,
-        pts_runs, pts_off, pts_offs, pts_stage,
-        dpts_lh, dpts_cls, dpts_spos, dpts_rec, dpts_moff, dpts_eoff, dpts_cnt, dpts_kpos, dpts_mrec, dpts_key,
-        dpts_idx, dpts_k0, dpts_k1, dpts_v1, dpts_pix,
-        vflag, vlist, vredo,
-        nbr_ctr, nbr_rec, nbr_key, nbr_val, nbr_uidx, nbr_ua, nbr_ub, nbr_ucnt, nbr_deg, nbr_hoff, nbr_loff, nbr_offs,
-        nbr_ids, nbr_lens,
-        nbrr_col, nbrr_out, nbrr_lrow, nbrr_lcoff, nbrr_part,
-        dnbr_blk, dnbr_cnt, dnbr_home, dnbr_trav, dnbr_mrg, dnbr_rcnt, dnbr_offs, dnbr_ids, dnbr_lens, dnbr_lrow, dnbr_lcoff,
-        mrg_ctr, mrg_key, mrg_size, mrg_par, mrg_root, mrg_idx, mrg_recode, mrg_rep, mrg_gsize, mrg_hist,
-        mrg_rec, mrg_bestd, mrg_best, dmrg_b64, dmrg_pairs, dmrg_pcnt,
-        agg_recode, agg_gsize, agg_ctr, agg_scan, agg_offs, agg_mem, agg_wcol, agg_w, agg_lrow, agg_lcoff,
-        shape_tab, shape_ctr;
+#define X(name) DevBuf name;
+    SHP_CTX_BUFS(X)
+#undef X
+    NbrTable nbr_tab, dnbr_tab;        // the one-GPU table and the rank's share table: neither displaces the other
+    NbrLongList agg_longs;             // the long rows of the member list (nbragg.h)
+    shp_ctx()
+    {
+#define X(name) bufs.push_back(&name);
+        SHP_CTX_BUFS(X)
+#undef X
+        nbr_table_bufs(nbr_tab, bufs);
+        nbr_table_bufs(dnbr_tab, bufs);
+        nbr_long_bufs(agg_longs, bufs);
+    }
     SegPointsState pts;
     ShapeState shape;
     NbrState nbr;
@@ -167,11 +210,6 @@ struct shp_ctx {
     AggState agg;
     DNbrState dnbr;
     DMrgState dmrg;
-    // the table in nbr_offs / nbr_ids / nbr_lens (nbrreduce.h).  nbr_serial: a number no other table of the process
-    // has, new with every shp_nbr_begin, shp_nbr_upload and shp_nbr_merge_contract (kept here: run_nbr_begin resets `nbr`); the list of the
-    // table's long rows (nbrr_lrow, nbrr_lcoff) belongs to the table nbrr_list_serial
-    unsigned long long nbr_serial = 0, nbrr_list_serial = 0;
-    uint32_t nbrr_nlong = 0, nbrr_nchunks = 0;
     DSegPointsState dpts;
     DColourState dcol;
     uint32_t *h_pinned = nullptr;   // SHP_PINNED_BYTES of pinned host staging (small transfers)

@@ -6,7 +6,8 @@
 // except d2 of the similarity rule, which is a function of the two ids' records alone; so nothing depends on which
 // rank holds an entry, or on the order of the atomics.
 //
-//  1. run_dmrg_begin / run_dmrg_hook.  Row i of the share table is id id_lo + i (MrgTable::row0), so the entries
+//  1. run_dmrg_begin / run_dmrg_hook.  Row i of the share table is id id_lo + i (NbrTable::row0; mrg_table of
+//     nbrmerge.h makes the kernels' view of either table), so the entries
 //     a < b of a rank's rows are owned by that rank alone and every such entry of the whole table has one owner.
 //     k_mrg_hook and k_mrgs_best run over them as they run over the one-GPU table, into a parent array of ALL ids
 //     (S + 1) from the full key / size / distance columns.  The mutual rule needs best[b] of ids of other shares:
@@ -24,9 +25,10 @@
 //  3. run_dmrg_number: mrg_number unchanged, redundantly on every rank; the groups lie where shp_nbr_merge leaves
 //     them (ctx->mrg, mrg_recode / mrg_rep / mrg_gsize / mrg_hist), so the calls that read them serve as they are.
 //  4. run_dmrg_records: k_mrg_records over the share's entries a < b; the records are sorted and reduced to distinct
-//     pairs (dnbr_sort_reduce) and split by k_dnbr_pack into home and travelling records against the NEW share of
-//     the ids 0 .. M.  That is the state run_dnbr_local leaves (DNbrState, stage 1), so the caller's all-gather and
-//     run_dnbr_merge build the new share table and its two columns as they build the first one.
+//     pairs (nbr_sort_reduce) and split into home and travelling records against the NEW share of the ids 0 .. M
+//     (dnbr_pack), the two routines of run_dnbr_local.  That is the state run_dnbr_local leaves (DNbrState stage 1,
+//     the new share waiting in shp_ctx::dnbr_tab), so the caller's all-gather and run_dnbr_merge build the new share
+//     table and its two columns as they build the first one.
 #pragma once
 #include "common.h"
 #include "nbrmerge.h"
@@ -110,13 +112,6 @@ __global__ __launch_bounds__(256) void k_dmrg_hook_pairs(const uint2 *__restrict
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
-static inline MrgTable dmrg_table(shp_ctx *ctx)
-{
-    const DNbrState &d = ctx->dnbr;
-    return MrgTable{(const long long *)ctx->dnbr_offs.p, (const uint32_t *)ctx->dnbr_ids.p, (const long long *)ctx->dnbr_lens.p,
-                    d.S + 1u, (long long)d.nent, d.id_hi - d.id_lo, d.id_lo};
-}
-
 static inline MrgSimRule dmrg_sim_rule(shp_ctx *ctx, const uint32_t *best)
 {
     const DMrgState &m = ctx->dmrg;
@@ -124,16 +119,16 @@ static inline MrgSimRule dmrg_sim_rule(shp_ctx *ctx, const uint32_t *best)
                       m.has_size ? bp<long long>(ctx->mrg_size) : nullptr, m.has_ign, m.ign, m.minb, m.has_thr, m.thr2, best};
 }
 
-// Step 1, up to the mutual rule's exchange.  The share table must be the context's (DNbrState stage 2).  ncol 0: the
+// Step 1, up to the mutual rule's exchange.  The share table must be the context's finished one.  ncol 0: the
 // key rule (keys given).  *d_best_out: with `mutual` the int64 column of S + 1 values for the all-reduce (context
 // memory), otherwise NULL.  ms_out[2]: device time of the records' kernels, of the best passes.
 static int run_dmrg_begin(shp_ctx *ctx, const double *const *cols, int ncol, int has_ignv, double ignv, int has_thr,
                           double thr2, int mutual, const int64_t *keys, int has_ignk, int64_t ignk, int64_t min_border,
                           const int64_t *seg_size, void **d_best_out, double *ms_out)
 {
-    const DNbrState &d = ctx->dnbr;
+    const NbrTable &d = ctx->dnbr_tab;
     hipStream_t st = ctx->stream;
-    const uint32_t S = d.S, nsh = d.id_hi - d.id_lo;
+    const uint32_t S = d.S, nsh = d.nrows;
     const size_t ns = (size_t)S + 1;
     ctx->dmrg = DMrgState{};
     *d_best_out = nullptr;
@@ -166,13 +161,13 @@ static int run_dmrg_begin(shp_ctx *ctx, const double *const *cols, int ncol, int
         if (d.nent) {
             const MrgSimRule q = dmrg_sim_rule(ctx, nullptr);
             const dim3 grid(mrg_pieces(d.nent));
-            hipLaunchKernelGGL(k_mrgs_best<0>, grid, dim3(256), 0, st, dmrg_table(ctx), q, bestd, best);
+            hipLaunchKernelGGL(k_mrgs_best<0>, grid, dim3(256), 0, st, mrg_table(d), q, bestd, best);
             KCHK(ctx);
-            hipLaunchKernelGGL(k_mrgs_best<1>, grid, dim3(256), 0, st, dmrg_table(ctx), q, bestd, best);
+            hipLaunchKernelGGL(k_mrgs_best<1>, grid, dim3(256), 0, st, mrg_table(d), q, bestd, best);
             KCHK(ctx);
         }
         if (nsh) {
-            hipLaunchKernelGGL(k_dmrg_pack_best, dim3(grid_for(nsh, 256)), dim3(256), 0, st, (const uint32_t *)best, d.id_lo,
+            hipLaunchKernelGGL(k_dmrg_pack_best, dim3(grid_for(nsh, 256)), dim3(256), 0, st, (const uint32_t *)best, d.row0,
                                nsh, b64);
             KCHK(ctx);
         }
@@ -192,7 +187,7 @@ static int run_dmrg_begin(shp_ctx *ctx, const double *const *cols, int ncol, int
 // context memory).  ms_out[2]: device time of the hook, of the flatten and the pairs' compaction.
 static int run_dmrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, double *ms_out)
 {
-    const DNbrState &d = ctx->dnbr;
+    const NbrTable &d = ctx->dnbr_tab;
     DMrgState &m = ctx->dmrg;
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)d.S + 1;
@@ -211,11 +206,11 @@ static int run_dmrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, 
         const dim3 grid(mrg_pieces(d.nent));
         if (m.similar) {
             const MrgSimRule q = dmrg_sim_rule(ctx, m.mutual ? bp<uint32_t>(ctx->mrg_best) : nullptr);
-            hipLaunchKernelGGL(k_mrg_hook<MrgSimRule>, grid, dim3(256), 0, st, dmrg_table(ctx), q, par, ctr);
+            hipLaunchKernelGGL(k_mrg_hook<MrgSimRule>, grid, dim3(256), 0, st, mrg_table(d), q, par, ctr);
         } else {
             const MrgLinkRule q{bp<long long>(ctx->mrg_key), m.has_size ? bp<long long>(ctx->mrg_size) : nullptr, m.has_ign,
                                 m.ign, m.minb};
-            hipLaunchKernelGGL(k_mrg_hook<MrgLinkRule>, grid, dim3(256), 0, st, dmrg_table(ctx), q, par, ctr);
+            hipLaunchKernelGGL(k_mrg_hook<MrgLinkRule>, grid, dim3(256), 0, st, mrg_table(d), q, par, ctr);
         }
         KCHK(ctx);
     }
@@ -259,7 +254,7 @@ static int run_dmrg_hook(shp_ctx *ctx, int64_t *counts_out, void **d_pairs_out, 
 static int run_dmrg_number(shp_ctx *ctx, const uint2 *d_all, unsigned long long slot, uint32_t world, const uint32_t *counts,
                            uint32_t rank, uint32_t *M_out, void **d_hist_out, double *ms_out)
 {
-    const DNbrState &d = ctx->dnbr;
+    const NbrTable &d = ctx->dnbr_tab;
     DMrgState &m = ctx->dmrg;
     hipStream_t st = ctx->stream;
     const size_t ns = (size_t)d.S + 1;
@@ -297,7 +292,8 @@ static int run_dmrg_number(shp_ctx *ctx, const uint2 *d_all, unsigned long long 
 static int run_dmrg_records(shp_ctx *ctx, uint32_t new_lo, uint32_t new_hi, int64_t *counts_out, void **d_trav_out,
                             double *ms_out)
 {
-    DNbrState &d = ctx->dnbr;
+    DNbrState &x = ctx->dnbr;
+    const NbrTable &d = ctx->dnbr_tab;
     DMrgState &m = ctx->dmrg;
     MrgState &g = ctx->mrg;
     hipStream_t st = ctx->stream;
@@ -307,14 +303,14 @@ static int run_dmrg_records(shp_ctx *ctx, uint32_t new_lo, uint32_t new_hi, int6
     *d_trav_out = nullptr;
     m.stage = 0;
     if (g.half > NBR_MAX_REC) SHP_FAIL(ctx, SHP_ERR_NOMEM, "%llu neighbour records: more than the sort indexes", g.half);
-    if (ctx->nbr.stage == 1) ctx->nbr.stage = 0;            // (the record buffer is the one-GPU accumulation's)
+    ctx->nbr.open = false;                                  // (the record buffer is the one-GPU accumulation's)
     CHK(buf_ensure(ctx, ctx->nbr_rec, (size_t)(g.half ? g.half : 1) * 16));
     CHK(buf_ensure(ctx, ctx->nbr_ctr, NBR_C_WORDS * 8));
     const unsigned long long cap = ctx->nbr_rec.cap / 16;
     HIPCHK(ctx, hipMemsetAsync(&ctr[MRG_C_REC], 0, 16, st));        // (MRG_C_REC and MRG_C_WIDE)
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
     if (d.nent) {
-        hipLaunchKernelGGL(k_mrg_records, dim3(mrg_pieces(d.nent)), dim3(256), 0, st, dmrg_table(ctx),
+        hipLaunchKernelGGL(k_mrg_records, dim3(mrg_pieces(d.nent)), dim3(256), 0, st, mrg_table(d),
                            (const uint32_t *)ctx->mrg_recode.p, (uint4 *)ctx->nbr_rec.p, cap, ctr);
         KCHK(ctx);
     }
@@ -325,45 +321,23 @@ static int run_dmrg_records(shp_ctx *ctx, uint32_t new_lo, uint32_t new_hi, int6
     counts_out[0] = (int64_t)n;
     counts_out[4] = (int64_t)wide;
     if (wide) return 0;
-    // from here on the share table the groups were found in is gone
-    const unsigned long long list_serial = d.list_serial;
+    // from here on the share table the groups were found in is gone: the share of the new ids waits in its place
     const uint32_t M = g.M;
-    d = DNbrState{};
-    d.list_serial = list_serial;
-    d.serial = nbr_next_serial();
+    x = DNbrState{};
+    dnbr_begin_share(ctx, M, new_lo, new_hi);
     uint32_t U = 0;
-    CHK(dnbr_sort_reduce(ctx, (const uint4 *)ctx->nbr_rec.p, (uint32_t)n, bits_for(M), &U));
-    unsigned long long *nctr = (unsigned long long *)ctx->nbr_ctr.p;
-    pin[0] = pin[1] = 0ull;
-    if (U) {
-        CHK(buf_ensure(ctx, ctx->dnbr_home, (size_t)U * 16));
-        CHK(buf_ensure(ctx, ctx->dnbr_trav, (size_t)U * 16));
-        HIPCHK(ctx, hipMemsetAsync(nctr, 0, 16, st));
-        hipLaunchKernelGGL(k_dnbr_pack, dim3(grid_for(U, 256)), dim3(256), 0, st, (const uint32_t *)ctx->nbr_ua.p,
-                           (const uint32_t *)ctx->nbr_ub.p, (const unsigned long long *)ctx->nbr_ucnt.p, U, new_lo, new_hi,
-                           (uint4 *)ctx->dnbr_home.p, (uint4 *)ctx->dnbr_trav.p, nctr);
-        KCHK(ctx);
-        HIPCHK(ctx, hipMemcpyAsync(pin, nctr, 16, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+    CHK(nbr_sort_reduce<unsigned long long>(ctx, (const uint4 *)ctx->nbr_rec.p, (uint32_t)n, bits_for(M), &U));
+    CHK(dnbr_pack(ctx, U, new_lo, new_hi, &x.nhome, &x.ntrav));
     float ms = 0.f;
     HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    if (pin[0] + pin[1] != (unsigned long long)U)
-        SHP_FAIL(ctx, SHP_ERR_STATE, "%llu home and %llu travelling records for %u pairs", pin[0], pin[1], U);
-    d.S = M;
-    d.id_lo = new_lo;
-    d.id_hi = new_hi;
-    d.nlocal = U;
-    d.nhome = pin[0];
-    d.ntrav = pin[1];
-    d.dev_ms = ms;
-    d.stage = 1;
+    x.nlocal = U;
+    x.dev_ms = ms;
+    x.stage = 1;
     g.contracted = true;
     counts_out[1] = (int64_t)U;
-    counts_out[2] = (int64_t)d.nhome;
-    counts_out[3] = (int64_t)d.ntrav;
-    *d_trav_out = d.ntrav ? ctx->dnbr_trav.p : nullptr;
+    counts_out[2] = (int64_t)x.nhome;
+    counts_out[3] = (int64_t)x.ntrav;
+    *d_trav_out = x.ntrav ? ctx->dnbr_trav.p : nullptr;
     if (ms_out) *ms_out = ms;
     return 0;
 }

@@ -8,7 +8,8 @@
 //   offsets   their exclusive scan (scan.h), widened to the int64 offsets the reduction kernels read;
 //   members   the ids 0 .. S sorted by their new id with the stable radix sort of sort.h (value = index): within a
 //             group the ids stay ascending; the ids that recode to 0 come first and are left out.
-// It is built once per merge result and kept, with the list of its long rows, until the next merge.
+// It is built once per merge result and kept, with the list of its long rows (shp_ctx::agg_longs, an NbrLongList
+// under the member list's serial), until the next merge.
 //
 // THE AGGREGATION runs the reduction kernels of nbrreduce.h over that CSR: a group is a "row", its members are the
 // "neighbour ids" and the weight of a member is the "border length" (k_agg_weights lays the weights out by entry).
@@ -123,8 +124,8 @@ static int run_agg_build(shp_ctx *ctx, const uint32_t *h_recode, uint32_t S, uin
     CHK(sort_pairs(ctx, d_recode, nullptr, (uint32_t)ns, bits_for(M), nullptr, &sorted));
     CHK(buf_ensure(ctx, ctx->agg_mem, nmem * 4));
     if (nmem) HIPCHK(ctx, hipMemcpyAsync(ctx->agg_mem.p, sorted + (ns - nmem), nmem * 4, hipMemcpyDeviceToDevice, st));
-    CHK(nbrr_long_list_of(ctx, (const long long *)ctx->agg_offs.p, (uint32_t)nm, ctx->agg_lrow, ctx->agg_lcoff, &a.nlong,
-                          &a.nchunks));
+    const unsigned long long serial = h_recode ? nbr_next_serial() : ctx->mrg.serial;
+    CHK(nbrr_long_ensure(ctx, ctx->agg_longs, (const long long *)ctx->agg_offs.p, (uint32_t)nm, serial));
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     HIPCHK(ctx, hipStreamSynchronize(st));
     float ms = 0.f;
@@ -134,7 +135,7 @@ static int run_agg_build(shp_ctx *ctx, const uint32_t *h_recode, uint32_t S, uin
     a.M = M;
     a.nmem = nmem;
     a.recode = d_recode;
-    a.serial = h_recode ? nbr_next_serial() : ctx->mrg.serial;
+    a.serial = serial;
     a.stage = 1;
     return 0;
 }
@@ -161,47 +162,20 @@ static int run_agg(shp_ctx *ctx, const void *col, int ctype, const int64_t *weig
     static const int slot_of[AGG_NSTATS] = {NBRR_COUNT, NBRR_BORDER, NBRR_MIN, NBRR_MAX, NBRR_SUM, NBRR_MEAN, NBRR_BORDERMEAN};
     int nsel = 0;
     for (int i = 0; i < AGG_NSTATS; i++) nsel += (mask >> i) & 1u;
-    CHK(buf_ensure(ctx, ctx->nbrr_col, ns * 8));
     CHK(buf_ensure(ctx, ctx->nbrr_out, (size_t)nsel * nm * 8));
     CHK(buf_ensure(ctx, ctx->agg_w, (size_t)a.nmem * 8));
-    double *d_col = bp<double>(ctx->nbrr_col);
-    const void *d_raw = nullptr;
-    if (ctype == COL_F64) {
-        HIPCHK(ctx, hipMemcpyAsync(d_col, col, ns * 8, hipMemcpyHostToDevice, st));
-    } else {
-        const size_t bytes = ns * (ctype == COL_F32 ? 4 : 8);
-        CHK(buf_ensure(ctx, ctx->img, bytes));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->img.p, col, bytes, hipMemcpyHostToDevice, st));
-        d_raw = ctx->img.p;
-    }
     const long long *d_wcol = nullptr;
     if (weights) {
         CHK(buf_ensure(ctx, ctx->agg_wcol, ns * 8));
         HIPCHK(ctx, hipMemcpyAsync(ctx->agg_wcol.p, weights, ns * 8, hipMemcpyHostToDevice, st));
         d_wcol = (const long long *)ctx->agg_wcol.p;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    if (ctype == COL_F32) {
-        hipLaunchKernelGGL(k_col_from_f32, dim3(colour_grid(ns, 256)), dim3(256), 0, st, (const float *)d_raw, ns, d_col);
-        KCHK(ctx);
-    } else if (ctype == COL_I64) {
-        hipLaunchKernelGGL(k_nbrr_from_i64, dim3(colour_grid(ns, 256)), dim3(256), 0, st, (const long long *)d_raw, ns, d_col);
-        KCHK(ctx);
-    }
+    const void *d_raw = nullptr;
+    CHK(nbrr_stage_column(ctx, col, ctype, ns, &d_raw));
     hipLaunchKernelGGL(k_agg_weights, dim3(grid_for(a.nmem, 256, 2048u)), dim3(256), 0, st, (const uint32_t *)ctx->agg_mem.p,
                        (size_t)a.nmem, d_wcol, bp<long long>(ctx->agg_w));
     KCHK(ctx);
-    NbrrParams p;
-    p.offs = (const long long *)ctx->agg_offs.p;
-    p.ids = (const uint32_t *)ctx->agg_mem.p;
-    p.lens = (const long long *)ctx->agg_w.p;
-    p.col = d_col;
-    p.ns = (uint32_t)nm;
-    p.row0 = 0u;
-    p.has_ign = has_ign;
-    p.ign = ign;
-    p.missing = missing;
-    for (int i = 0; i < NBRR_NSTATS; i++) p.out[i] = nullptr;
+    NbrrParams p = nbrr_params(ctx, ctx->agg_offs.p, ctx->agg_mem.p, ctx->agg_w.p, (uint32_t)nm, 0u, has_ign, ign, missing);
     void *d_out[AGG_NSTATS];
     int slot = 0;
     bool any = false;
@@ -209,7 +183,7 @@ static int run_agg(shp_ctx *ctx, const void *col, int ctype, const int64_t *weig
         d_out[i] = ((mask >> i) & 1u) ? (void *)((char *)ctx->nbrr_out.p + (size_t)(slot++) * nm * 8) : nullptr;
         if (d_out[i] && !(i == AGG_SUM && isum)) { p.out[slot_of[i]] = d_out[i]; any = true; }
     }
-    if (any) CHK(nbrr_launch(ctx, p, bp<uint32_t>(ctx->agg_lrow), bp<uint32_t>(ctx->agg_lcoff), a.nlong, a.nchunks));
+    if (any) CHK(nbrr_launch(ctx, p, ctx->agg_longs));
     if (isum) {
         HIPCHK(ctx, hipMemsetAsync(d_out[AGG_SUM], 0, nm * 8, st));
         hipLaunchKernelGGL(k_agg_isum, dim3(grid_for(ns, 256)), dim3(256), 0, st, (const long long *)d_raw, a.recode,
@@ -220,10 +194,5 @@ static int run_agg(shp_ctx *ctx, const void *col, int ctype, const int64_t *weig
     for (int i = 0; i < AGG_NSTATS; i++)
         if (d_out[i]) HIPCHK(ctx, hipMemcpyAsync(outs[i], d_out[i], nm * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    if (dev_ms_out) {
-        float ms = 0.f;
-        HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        *dev_ms_out = ms;
-    }
-    return 0;
+    return nbrr_dev_ms(ctx, dev_ms_out);
 }

@@ -50,7 +50,8 @@ static_assert(MRG_PIECE % 256u == 0u, "MRG_PIECE is a multiple of the workgroup"
 // [3] records whose border length does not fit 32 bits, [4] largest label above S met by k_mrg_recode
 enum { MRG_C_LINKS = 0, MRG_C_HALF = 1, MRG_C_REC = 2, MRG_C_WIDE = 3, MRG_C_BAD = 4, MRG_C_WORDS = 8 };
 
-// The table of the context (rows 0 .. S) or the rows of a rank's id share (dnbrmerge.h): row i is id row0 + i.
+// What the merge's kernels read of an NbrTable (mrg_table): the one-GPU table (rows 0 .. S) or the rows of a rank's id
+// share (dnbrmerge.h); row i is id row0 + i.
 struct MrgTable {
     const long long *offs;
     const uint32_t *ids;
@@ -422,10 +423,10 @@ __global__ __launch_bounds__(256) void k_mrg_recode(const uint32_t *__restrict__
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
-static inline MrgTable mrg_table(shp_ctx *ctx)
+static inline MrgTable mrg_table(const NbrTable &t)
 {
-    return MrgTable{(const long long *)ctx->nbr_offs.p, (const uint32_t *)ctx->nbr_ids.p, (const long long *)ctx->nbr_lens.p,
-                    ctx->nbr.S + 1u, (long long)ctx->nbr.nent, ctx->nbr.S + 1u, 0u};
+    return MrgTable{(const long long *)t.offs.p, (const uint32_t *)t.ids.p, (const long long *)t.lens.p, t.S + 1u,
+                    (long long)t.nent, t.nrows, t.row0};
 }
 
 static inline unsigned mrg_pieces(unsigned long long nent)
@@ -510,7 +511,7 @@ static int mrg_number(shp_ctx *ctx, uint32_t S, bool has_size, uint32_t *M_out, 
     g.links = pin[MRG_C_LINKS];
     g.half = pin[MRG_C_HALF];
     g.has_size = has_size;
-    g.table_serial = ctx->nbr_serial;
+    g.table_serial = ctx->nbr_tab.serial;
     g.serial = nbr_next_serial();
     g.stage = 1;
     *M_out = M;
@@ -526,16 +527,17 @@ static int mrg_number(shp_ctx *ctx, uint32_t S, bool has_size, uint32_t *M_out, 
 static int run_nbr_merge(shp_ctx *ctx, const int64_t *keys, int has_ign, int64_t ign, int64_t min_border,
                          const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
 {
-    const unsigned long long nent = ctx->nbr.nent;
-    CHK(mrg_begin(ctx, ctx->nbr.S, nent, keys, seg_size));
+    const NbrTable &t = ctx->nbr_tab;
+    const unsigned long long nent = t.nent;
+    CHK(mrg_begin(ctx, t.S, nent, keys, seg_size));
     if (nent) {
         const MrgLinkRule q{bp<long long>(ctx->mrg_key), seg_size ? bp<long long>(ctx->mrg_size) : nullptr, has_ign,
                             (long long)ign, (long long)min_border};
-        hipLaunchKernelGGL(k_mrg_hook<MrgLinkRule>, dim3(mrg_pieces(nent)), dim3(256), 0, ctx->stream, mrg_table(ctx), q,
+        hipLaunchKernelGGL(k_mrg_hook<MrgLinkRule>, dim3(mrg_pieces(nent)), dim3(256), 0, ctx->stream, mrg_table(t), q,
                            bp<uint32_t>(ctx->mrg_par), (unsigned long long *)ctx->mrg_ctr.p);
         KCHK(ctx);
     }
-    return mrg_number(ctx, ctx->nbr.S, seg_size != nullptr, M_out, counters_out, ms_out);
+    return mrg_number(ctx, t.S, seg_size != nullptr, M_out, counters_out, ms_out);
 }
 
 // The distance columns (ncol host columns of ns float64) through one staging plane into the records of MrgSimRule,
@@ -580,12 +582,13 @@ static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int nc
                                  const int64_t *seg_size, uint32_t *M_out, int64_t *counters_out, double *ms_out)
 {
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)ctx->nbr.S + 1;
-    const unsigned long long nent = ctx->nbr.nent;
+    const NbrTable &t = ctx->nbr_tab;
+    const size_t ns = (size_t)t.S + 1;
+    const unsigned long long nent = t.nent;
     double msr = 0.0;
     CHK(mrgs_place_columns(ctx, cols, ncol, ns, has_ignv, ignv, mutual, &msr));
     double *rec = bp<double>(ctx->mrg_rec);
-    CHK(mrg_begin(ctx, ctx->nbr.S, nent, keys, seg_size));
+    CHK(mrg_begin(ctx, t.S, nent, keys, seg_size));
     if (nent) {
         MrgSimRule q{rec, ncol, keys ? bp<long long>(ctx->mrg_key) : nullptr, seg_size ? bp<long long>(ctx->mrg_size) : nullptr,
                      has_ignk, (long long)ignk, (long long)min_border, has_thr, thr2, nullptr};
@@ -595,17 +598,17 @@ static int run_nbr_merge_similar(shp_ctx *ctx, const double *const *cols, int nc
             uint32_t *best = bp<uint32_t>(ctx->mrg_best);
             HIPCHK(ctx, hipMemsetAsync(bestd, 0xff, ns * 8, st));
             HIPCHK(ctx, hipMemsetAsync(best, 0xff, ns * 4, st));
-            hipLaunchKernelGGL(k_mrgs_best<0>, grid, dim3(256), 0, st, mrg_table(ctx), q, bestd, best);
+            hipLaunchKernelGGL(k_mrgs_best<0>, grid, dim3(256), 0, st, mrg_table(t), q, bestd, best);
             KCHK(ctx);
-            hipLaunchKernelGGL(k_mrgs_best<1>, grid, dim3(256), 0, st, mrg_table(ctx), q, bestd, best);
+            hipLaunchKernelGGL(k_mrgs_best<1>, grid, dim3(256), 0, st, mrg_table(t), q, bestd, best);
             KCHK(ctx);
             q.best = best;
         }
-        hipLaunchKernelGGL(k_mrg_hook<MrgSimRule>, grid, dim3(256), 0, st, mrg_table(ctx), q, bp<uint32_t>(ctx->mrg_par),
+        hipLaunchKernelGGL(k_mrg_hook<MrgSimRule>, grid, dim3(256), 0, st, mrg_table(t), q, bp<uint32_t>(ctx->mrg_par),
                            (unsigned long long *)ctx->mrg_ctr.p);
         KCHK(ctx);
     }
-    CHK(mrg_number(ctx, ctx->nbr.S, seg_size != nullptr, M_out, counters_out, ms_out));
+    CHK(mrg_number(ctx, t.S, seg_size != nullptr, M_out, counters_out, ms_out));
     if (ms_out) ms_out[2] = msr;
     return 0;
 }
@@ -633,7 +636,7 @@ static int run_nbr_merge_contract(shp_ctx *ctx, int64_t *nent_out, int64_t *reco
 {
     MrgState &g = ctx->mrg;
     hipStream_t st = ctx->stream;
-    const unsigned long long nent = ctx->nbr.nent;
+    const unsigned long long nent = ctx->nbr_tab.nent;
     unsigned long long *ctr = (unsigned long long *)ctx->mrg_ctr.p;
     unsigned long long *pin = (unsigned long long *)ctx->h_pinned;
     if (g.half > NBR_MAX_REC) SHP_FAIL(ctx, SHP_ERR_NOMEM, "%llu neighbour records: more than the sort indexes", g.half);
@@ -642,7 +645,7 @@ static int run_nbr_merge_contract(shp_ctx *ctx, int64_t *nent_out, int64_t *reco
     float ms = 0.f;
     if (nent) {
         HIPCHK(ctx, hipEventRecord(ctx->ev[2], st));
-        hipLaunchKernelGGL(k_mrg_records, dim3(mrg_pieces(nent)), dim3(256), 0, st, mrg_table(ctx),
+        hipLaunchKernelGGL(k_mrg_records, dim3(mrg_pieces(nent)), dim3(256), 0, st, mrg_table(ctx->nbr_tab),
                            (const uint32_t *)ctx->mrg_recode.p, (uint4 *)ctx->nbr_rec.p, cap, ctr);
         KCHK(ctx);
         HIPCHK(ctx, hipEventRecord(ctx->ev[3], st));
@@ -655,12 +658,13 @@ static int run_nbr_merge_contract(shp_ctx *ctx, int64_t *nent_out, int64_t *reco
     if (n > g.half || n > cap) SHP_FAIL(ctx, SHP_ERR_STATE, "%llu records of %llu entries", n, g.half);
     // from here on the table the groups were found in is gone
     ctx->nbr = NbrState{};
-    ctx->nbr_serial = nbr_next_serial();
+    nbr_table_end(ctx->nbr_tab);
+    ctx->nbr_tab.serial = nbr_next_serial();
     ctx->nbr.cap = cap;
     ctx->nbr.used = n;
     g.contracted = true;
     CHK(nbr_build_table(ctx, g.M, (uint32_t)n));
-    *nent_out = (int64_t)ctx->nbr.nent;
+    *nent_out = (int64_t)ctx->nbr_tab.nent;
     *records_out = (int64_t)n;
     if (dev_ms_out) *dev_ms_out = (double)ms + ctx->nbr.dev_ms;
     return 0;

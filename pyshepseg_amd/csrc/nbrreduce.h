@@ -33,11 +33,15 @@
 //     conflicts there are left as they fall.
 //  k_nbrr_long: a wavefront per chunk of a long row, partial results to a record per chunk; k_nbrr_long_combine: a
 //     thread per long row adds the chunks' records in chunk order.  The long rows and their chunks are listed once
-//     per table (a flag scan, a fill, a scan of the chunk counts: scan.h) and kept while the table is resident.
+//     per table (a flag scan, a fill, a scan of the chunk counts: scan.h) and kept while the table is resident:
+//     NbrLongList (common.h) and nbrr_long_ensure, for the one-GPU table, a rank's share table and the member list of
+//     nbragg.h alike.
 //  k_nbrr_validate: the rules of an uploaded table (below), one launch.
 // The three reduction kernels take a row base (NbrrParams::row0): the table's row i is id row0 + i.  The one-GPU
 // table has row0 = 0; the share table of a row-sharded raster (dneighbours.h) holds the whole rows of the ids
 // row0 .. row0 + ns - 1, and since a row's order above depends on nothing but the row, its results are the same bits.
+// Host side, shared by the three reductions (run_nbr_reduce here, run_dnbr_reduce, run_agg): nbrr_stage_column puts
+// the host column on the device, nbrr_params / nbrr_table_params fill the kernels' parameters, nbrr_launch runs them.
 #pragma once
 #include "common.h"
 #include "scan.h"
@@ -346,30 +350,26 @@ static const char *nbrr_rule_text(int rule)
     }
 }
 
-// A host table into nbr_offs / nbr_ids / nbr_lens.  A table that breaks a rule leaves no finished table.
+// A host table into the context's one-GPU table.  A table that breaks a rule leaves no finished table.
 static int run_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *nbrs, const int64_t *lens, uint32_t S,
                           long long nent, double *dev_ms_out)
 {
     NbrState &s = ctx->nbr;
+    NbrTable &t = ctx->nbr_tab;
     hipStream_t st = ctx->stream;
     s = NbrState{};
-    ctx->nbr_serial = nbr_next_serial();
-    const size_t ns = (size_t)S + 1;
-    CHK(buf_ensure(ctx, ctx->nbr_offs, (ns + 1) * 8));
-    CHK(buf_ensure(ctx, ctx->nbr_ids, (size_t)nent * 4));
-    CHK(buf_ensure(ctx, ctx->nbr_lens, (size_t)nent * 8));
+    nbr_table_end(t);
+    t.serial = nbr_next_serial();
+    t.S = S;
+    t.nrows = S + 1u;
     CHK(buf_ensure(ctx, ctx->nbr_ctr, NBR_C_WORDS * 8));
     unsigned long long *first = (unsigned long long *)ctx->nbr_ctr.p;
     unsigned long long *pin = (unsigned long long *)ctx->h_pinned;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->nbr_offs.p, offsets, (ns + 1) * 8, hipMemcpyHostToDevice, st));
-    if (nent) {
-        HIPCHK(ctx, hipMemcpyAsync(ctx->nbr_ids.p, nbrs, (size_t)nent * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->nbr_lens.p, lens, (size_t)nent * 8, hipMemcpyHostToDevice, st));
-    }
+    CHK(nbr_table_upload_arrays(ctx, t, offsets, nbrs, lens, (unsigned long long)nent));
     HIPCHK(ctx, hipMemsetAsync(first, 0xff, 8, st));
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    hipLaunchKernelGGL(k_nbrr_validate, dim3(grid_for(ns, 256)), dim3(256), 0, st, (const long long *)ctx->nbr_offs.p,
-                       (const uint32_t *)ctx->nbr_ids.p, (const long long *)ctx->nbr_lens.p, (uint32_t)ns, nent, first);
+    hipLaunchKernelGGL(k_nbrr_validate, dim3(grid_for(t.nrows, 256)), dim3(256), 0, st, (const long long *)t.offs.p,
+                       (const uint32_t *)t.ids.p, (const long long *)t.lens.p, t.nrows, nent, first);
     KCHK(ctx);
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     HIPCHK(ctx, hipMemcpyAsync(pin, first, 8, hipMemcpyDeviceToHost, st));
@@ -383,96 +383,80 @@ static int run_nbr_upload(shp_ctx *ctx, const int64_t *offsets, const uint32_t *
         SHP_FAIL(ctx, SHP_ERR_ARG, "not a neighbour table: %s %lld: %s", (key >> 60) ? "entry" : "offset", pos,
                  nbrr_rule_text(rule));
     }
-    s.S = S;
-    s.nent = (unsigned long long)nent;
-    s.stage = 2;
+    t.nent = (unsigned long long)nent;
+    t.finished = true;
     return 0;
 }
 
-// the long rows of a table of ns rows (offsets offs) and their chunks, into lrow / lcoff
-static int nbrr_long_list_of(shp_ctx *ctx, const long long *offs, uint32_t ns, DevBuf &b_lrow, DevBuf &b_lcoff,
-                             uint32_t *nlong_out, uint32_t *nchunks_out)
+// The long rows of a CSR of nrows rows (offsets offs) and their chunks into `list`, unless it holds those of `serial`
+// already: once per table or member list, whichever of them the list belongs to.
+static int nbrr_long_ensure(shp_ctx *ctx, NbrLongList &list, const long long *offs, uint32_t nrows, unsigned long long serial)
 {
+    if (list.serial == serial) return 0;
     hipStream_t st = ctx->stream;
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
-    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns)));
-    CHK(buf_ensure(ctx, ctx->nbr_deg, (size_t)ns * 4));
+    list.serial = 0;
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(nrows)));
+    CHK(buf_ensure(ctx, ctx->nbr_deg, (size_t)nrows * 4));
     uint32_t *lidx = bp<uint32_t>(ctx->nbr_deg);
     NbrrLongFn lf{offs};
-    CHK(scan_exclusive(ctx, lf, ns, lidx, nullptr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir));
+    CHK(scan_exclusive(ctx, lf, nrows, lidx, nullptr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir));
     HIPCHK(ctx, hipStreamSynchronize(st));
     const uint32_t nlong = *(volatile uint32_t *)mir;
     uint32_t nchunks = 0;
     if (nlong) {
-        CHK(buf_ensure(ctx, b_lrow, (size_t)nlong * 4));
-        CHK(buf_ensure(ctx, b_lcoff, ((size_t)nlong + 1) * 4));
-        hipLaunchKernelGGL(k_nbrr_long_fill, dim3(grid_for(ns, 256)), dim3(256), 0, st, offs, ns, (const uint32_t *)lidx,
-                           bp<uint32_t>(b_lrow));
+        CHK(buf_ensure(ctx, list.lrow, (size_t)nlong * 4));
+        CHK(buf_ensure(ctx, list.lcoff, ((size_t)nlong + 1) * 4));
+        hipLaunchKernelGGL(k_nbrr_long_fill, dim3(grid_for(nrows, 256)), dim3(256), 0, st, offs, nrows, (const uint32_t *)lidx,
+                           bp<uint32_t>(list.lrow));
         KCHK(ctx);
-        NbrrChunksFn cf{offs, bp<uint32_t>(b_lrow)};
-        uint32_t *lcoff = bp<uint32_t>(b_lcoff);
+        NbrrChunksFn cf{offs, bp<uint32_t>(list.lrow)};
+        uint32_t *lcoff = bp<uint32_t>(list.lcoff);
         CHK(scan_exclusive(ctx, cf, nlong, lcoff, lcoff + nlong, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 1));
         HIPCHK(ctx, hipStreamSynchronize(st));
         nchunks = *(volatile uint32_t *)(mir + 1);
         if (nchunks < nlong) SHP_FAIL(ctx, SHP_ERR_STATE, "%u chunks for %u long rows", nchunks, nlong);
     }
-    *nlong_out = nlong;
-    *nchunks_out = nchunks;
+    list.nlong = nlong;
+    list.nchunks = nchunks;
+    list.serial = serial;
     return 0;
 }
 
-// the long rows of the resident table and their chunks, once per table
-static int nbrr_long_list(shp_ctx *ctx)
-{
-    if (ctx->nbrr_list_serial == ctx->nbr_serial) return 0;
-    CHK(nbrr_long_list_of(ctx, (const long long *)ctx->nbr_offs.p, ctx->nbr.S + 1u, ctx->nbrr_lrow, ctx->nbrr_lcoff,
-                          &ctx->nbrr_nlong, &ctx->nbrr_nchunks));
-    ctx->nbrr_list_serial = ctx->nbr_serial;
-    return 0;
-}
-
-// the reduction's kernels over the table of p, its long rows listed in lrow / lcoff
-static int nbrr_launch(shp_ctx *ctx, const NbrrParams &p, const uint32_t *lrow, const uint32_t *lcoff, uint32_t nlong,
-                       uint32_t nchunks)
+// the reduction's kernels over the CSR of p, its long rows listed in `list`
+static int nbrr_launch(shp_ctx *ctx, const NbrrParams &p, const NbrLongList &list)
 {
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_nbrr_short, dim3(grid_for(p.ns, NBRR_ROWS)), dim3(256), 0, st, p);
     KCHK(ctx);
-    if (nlong) {
-        CHK(buf_ensure(ctx, ctx->nbrr_part, (size_t)nchunks * sizeof(NbrrPart)));
-        hipLaunchKernelGGL(k_nbrr_long, dim3(grid_for(nchunks, 4)), dim3(256), 0, st, p, lrow, lcoff, nlong, nchunks,
-                           (NbrrPart *)ctx->nbrr_part.p);
+    if (list.nlong) {
+        const uint32_t *lrow = (const uint32_t *)list.lrow.p, *lcoff = (const uint32_t *)list.lcoff.p;
+        CHK(buf_ensure(ctx, ctx->nbrr_part, (size_t)list.nchunks * sizeof(NbrrPart)));
+        hipLaunchKernelGGL(k_nbrr_long, dim3(grid_for(list.nchunks, 4)), dim3(256), 0, st, p, lrow, lcoff, list.nlong,
+                           list.nchunks, (NbrrPart *)ctx->nbrr_part.p);
         KCHK(ctx);
-        hipLaunchKernelGGL(k_nbrr_long_combine, dim3(grid_for(nlong, 256)), dim3(256), 0, st, p, lrow, lcoff, nlong,
+        hipLaunchKernelGGL(k_nbrr_long_combine, dim3(grid_for(list.nlong, 256)), dim3(256), 0, st, p, lrow, lcoff, list.nlong,
                            (const NbrrPart *)ctx->nbrr_part.p);
         KCHK(ctx);
     }
     return 0;
 }
 
-// One column over the resident table.  outs[i]: host memory of S + 1 rows for statistic i of the mask.
-static int run_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int has_ign, double ign, double missing,
-                          uint32_t mask, void *const *outs, double *dev_ms_out)
+// One host column of ns values (ctype: COL_F64 / COL_F32 / COL_I64) as float64 in nbrr_col: float64 is copied there,
+// float32 and int64 go to ctx->img and through a conversion kernel.  ev[0] is recorded between the copy and the
+// conversion: the caller's device time starts there.  *raw_out: the column as the host gave it, on the device.
+static int nbrr_stage_column(shp_ctx *ctx, const void *col, int ctype, size_t ns, const void **raw_out)
 {
-    const NbrState &s = ctx->nbr;
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)s.S + 1;
-    int nsel = 0;
-    for (int i = 0; i < NBRR_NSTATS; i++) nsel += (mask >> i) & 1u;
     CHK(buf_ensure(ctx, ctx->nbrr_col, ns * 8));
-    CHK(buf_ensure(ctx, ctx->nbrr_out, (size_t)nsel * ns * 8));
     double *d_col = bp<double>(ctx->nbrr_col);
-    const void *d_raw = nullptr;
-    if (ctype == COL_F64) {
-        HIPCHK(ctx, hipMemcpyAsync(d_col, col, ns * 8, hipMemcpyHostToDevice, st));
-    } else {
-        const size_t bytes = ns * (ctype == COL_F32 ? 4 : 8);
-        CHK(buf_ensure(ctx, ctx->img, bytes));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->img.p, col, bytes, hipMemcpyHostToDevice, st));
+    const void *d_raw = d_col;
+    if (ctype != COL_F64) {
+        CHK(buf_ensure(ctx, ctx->img, ns * (ctype == COL_F32 ? 4 : 8)));
         d_raw = ctx->img.p;
     }
+    HIPCHK(ctx, hipMemcpyAsync((void *)d_raw, col, ns * (ctype == COL_F32 ? 4 : 8), hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    CHK(nbrr_long_list(ctx));
     if (ctype == COL_F32) {
         hipLaunchKernelGGL(k_col_from_f32, dim3(colour_grid(ns, 256)), dim3(256), 0, st, (const float *)d_raw, ns, d_col);
         KCHK(ctx);
@@ -480,29 +464,73 @@ static int run_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int has_ign,
         hipLaunchKernelGGL(k_nbrr_from_i64, dim3(colour_grid(ns, 256)), dim3(256), 0, st, (const long long *)d_raw, ns, d_col);
         KCHK(ctx);
     }
+    if (raw_out) *raw_out = d_raw;
+    return 0;
+}
+
+// the kernels' parameters over a CSR of nrows rows whose row 0 is id row0, the column staged in nbrr_col; no outputs yet
+static NbrrParams nbrr_params(shp_ctx *ctx, const void *offs, const void *ids, const void *lens, uint32_t nrows, uint32_t row0,
+                              int has_ign, double ign, double missing)
+{
     NbrrParams p;
-    p.offs = (const long long *)ctx->nbr_offs.p;
-    p.ids = (const uint32_t *)ctx->nbr_ids.p;
-    p.lens = (const long long *)ctx->nbr_lens.p;
-    p.col = d_col;
-    p.ns = (uint32_t)ns;
-    p.row0 = 0u;
+    p.offs = (const long long *)offs;
+    p.ids = (const uint32_t *)ids;
+    p.lens = (const long long *)lens;
+    p.col = bp<double>(ctx->nbrr_col);
+    p.ns = nrows;
+    p.row0 = row0;
     p.has_ign = has_ign;
     p.ign = ign;
     p.missing = missing;
+    for (int i = 0; i < NBRR_NSTATS; i++) p.out[i] = nullptr;
+    return p;
+}
+
+// ... over a table, the statistics of `mask` written to consecutive columns of S + 1 rows from d_out, in the order of
+// their bits
+static NbrrParams nbrr_table_params(shp_ctx *ctx, const NbrTable &t, int has_ign, double ign, double missing, void *d_out,
+                                    uint32_t mask)
+{
+    NbrrParams p = nbrr_params(ctx, t.offs.p, t.ids.p, t.lens.p, t.nrows, t.row0, has_ign, ign, missing);
     int slot = 0;
     for (int i = 0; i < NBRR_NSTATS; i++)
-        p.out[i] = ((mask >> i) & 1u) ? (void *)((char *)ctx->nbrr_out.p + (size_t)(slot++) * ns * 8) : nullptr;
-    CHK(nbrr_launch(ctx, p, bp<uint32_t>(ctx->nbrr_lrow), bp<uint32_t>(ctx->nbrr_lcoff), ctx->nbrr_nlong,
-                    ctx->nbrr_nchunks));
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-    for (int i = 0; i < NBRR_NSTATS; i++)
-        if (p.out[i]) HIPCHK(ctx, hipMemcpyAsync(outs[i], p.out[i], ns * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
+        if ((mask >> i) & 1u) p.out[i] = (char *)d_out + (size_t)(slot++) * ((size_t)t.S + 1) * 8;
+    return p;
+}
+
+static int nbrr_mask_count(uint32_t mask)
+{
+    int nsel = 0;
+    for (int i = 0; i < NBRR_NSTATS; i++) nsel += (mask >> i) & 1u;
+    return nsel;
+}
+
+// device time between ev[0] and ev[1] (the stream is synchronised)
+static int nbrr_dev_ms(shp_ctx *ctx, double *dev_ms_out)
+{
     if (dev_ms_out) {
         float ms = 0.f;
         HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
         *dev_ms_out = ms;
     }
     return 0;
+}
+
+// One column over the one-GPU table.  outs[i]: host memory of S + 1 rows for statistic i of the mask.
+static int run_nbr_reduce(shp_ctx *ctx, const void *col, int ctype, int has_ign, double ign, double missing,
+                          uint32_t mask, void *const *outs, double *dev_ms_out)
+{
+    NbrTable &t = ctx->nbr_tab;
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)t.S + 1;
+    CHK(buf_ensure(ctx, ctx->nbrr_out, (size_t)nbrr_mask_count(mask) * ns * 8));
+    CHK(nbrr_stage_column(ctx, col, ctype, ns, nullptr));
+    CHK(nbrr_long_ensure(ctx, t.longs, (const long long *)t.offs.p, t.nrows, t.serial));
+    const NbrrParams p = nbrr_table_params(ctx, t, has_ign, ign, missing, ctx->nbrr_out.p, mask);
+    CHK(nbrr_launch(ctx, p, t.longs));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    for (int i = 0; i < NBRR_NSTATS; i++)
+        if (p.out[i]) HIPCHK(ctx, hipMemcpyAsync(outs[i], p.out[i], ns * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    return nbrr_dev_ms(ctx, dev_ms_out);
 }

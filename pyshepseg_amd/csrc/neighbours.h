@@ -20,12 +20,18 @@
 //     The record buffer grows between blocks: every patch reserves its records with one atomic add and stores only
 //     what fits; when a block did not fit, the reserved total is exactly what it needs, the buffer is regrown
 //     (records of earlier blocks kept) and the block runs again.  Device memory is bounded by records.
-//  2. run_nbr_finish: the records are sorted by the 64-bit key (a, b) -- two stable passes of sort.h's 32-bit sort,
-//     by b then by a, over the significant bits of the largest label -- and run-length reduced with 64-bit sums.
-//  3. CSR.  Row r holds its neighbours below r (reduced pairs (a, r)), then those above ((r, b)).  The second part
-//     lies in the reduced order already; the first is the reduced pairs in a stable sort by b, which keeps the a's
-//     ascending.  The degree of both ends is counted (runs of one id add once), scanned, and both parts are filled:
-//     every row ascending.
+//  2. nbr_sort_reduce: the records are sorted by the 64-bit key (a, b) -- two stable passes of sort.h's 32-bit sort,
+//     by b then by a, over the significant bits of the largest label -- and run-length reduced with 64-bit sums.  A
+//     template over the width of the count a record carries: 32 bits here (what the patch kernel wrote), 64 bits
+//     where the records are sums already (dneighbours.h, dnbrmerge.h).
+//  3. nbr_build_csr.  Row r holds its neighbours below r (reduced pairs (a, r)), then those above ((r, b)).  The
+//     second part lies in the reduced order already; the first is the reduced pairs in a stable sort by b, which keeps
+//     the a's ascending.  The degree of both ends is counted (runs of one id add once), scanned, and both parts are
+//     filled: every row ascending.  A template over whole table / id share: the share table of dneighbours.h is the
+//     same build over the rows [id_lo, id_hi), the one-GPU table is the share [0, S + 1) and reads neither the range
+//     nor the shares' entry offsets.
+// The table itself is an NbrTable (common.h): shp_ctx::nbr_tab here, shp_ctx::dnbr_tab for a rank's share.  Download
+// and the copy half of an upload (nbr_table_download, nbr_table_upload_arrays) serve both.
 #pragma once
 #include "common.h"
 #include "scan.h"
@@ -192,16 +198,26 @@ __global__ __launch_bounds__(256) void k_nbr_field(const uint4 *__restrict__ rec
     if (idx_copy) idx_copy[j] = i;
 }
 
+// the count of a record as the run-length reduction reads it: the one-GPU finish takes the 32-bit count the patch
+// kernel wrote (word 2), the share tables the 64-bit count of a record that is itself a sum (words 2 and 3)
+template <typename CNT> __device__ __forceinline__ CNT nbr_rec_count(const uint4 &r);
+template <> __device__ __forceinline__ uint32_t nbr_rec_count<uint32_t>(const uint4 &r) { return r.z; }
+template <> __device__ __forceinline__ unsigned long long nbr_rec_count<unsigned long long>(const uint4 &r)
+{
+    return ((unsigned long long)r.w << 32) | r.z;
+}
+
 // b and count of every record in sorted order (one 16-byte gather instead of two of 4)
+template <typename CNT>
 __global__ __launch_bounds__(256) void k_nbr_gather(const uint4 *__restrict__ rec, uint32_t n,
                                                     const uint32_t *__restrict__ idx, uint32_t *__restrict__ sb,
-                                                    uint32_t *__restrict__ sc)
+                                                    CNT *__restrict__ sc)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
     const uint4 r = rec[idx[j]];
     sb[j] = r.x;
-    sc[j] = r.z;
+    sc[j] = nbr_rec_count<CNT>(r);
 }
 
 // 1 where sorted record j starts a new (a, b)
@@ -213,10 +229,11 @@ struct NbrHeadFn {
     }
 };
 
-// run-length reduction: entry e = (heads before j) + head(j) - 1 gets (a, b) from its head and the sum of its
-// records' counts; the records of an entry that share a wavefront add once
+// run-length reduction: entry e = (heads before j) + head(j) - 1 gets (a, b) from its head and the 64-bit sum of its
+// records' counts (CNT: as read, 32 or 64 bits); the records of an entry that share a wavefront add once
+template <typename CNT>
 __global__ __launch_bounds__(256) void k_nbr_reduce(const uint32_t *__restrict__ sa, const uint32_t *__restrict__ sb,
-                                                    const uint32_t *__restrict__ sc, const uint32_t *__restrict__ uidx,
+                                                    const CNT *__restrict__ sc, const uint32_t *__restrict__ uidx,
                                                     uint32_t n, uint32_t *__restrict__ ua, uint32_t *__restrict__ ub,
                                                     unsigned long long *__restrict__ ucnt)
 {
@@ -244,9 +261,15 @@ __global__ __launch_bounds__(256) void k_nbr_reduce(const uint32_t *__restrict__
     if (bd) atomicAdd(&ucnt[e], (((unsigned long long)lhi << 32) | llo) - (incl - own));
 }
 
-// cnt[key] += how often key occurs in the SORTED keys: a run inside a wavefront adds once
-__global__ __launch_bounds__(256) void k_nbr_degree(const uint32_t *__restrict__ keys, uint32_t n,
-                                                    uint32_t *__restrict__ cnt)
+// The three CSR kernels run over the rows lo .. hi - 1 (row i is id lo + i).  SHARE = false is the whole table: lo = 0,
+// every key has a row and the reduced entries of the rows start at 0, so neither the range nor first[] is read.
+// SHARE = true is a rank's id share (dneighbours.h): keys outside [lo, hi) have no row here, and the entries with a in
+// the share start at first[0] of the (a, b) order, those with b in the share at first[1] of the order by b.
+
+// cnt[key - lo] += how often key occurs in the SORTED keys: a run inside a wavefront adds once
+template <bool SHARE>
+__global__ __launch_bounds__(256) void k_nbr_degree(const uint32_t *__restrict__ keys, uint32_t n, uint32_t lo,
+                                                    uint32_t hi, uint32_t *__restrict__ cnt)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     const unsigned lane = lane_id();
@@ -255,9 +278,23 @@ __global__ __launch_bounds__(256) void k_nbr_degree(const uint32_t *__restrict__
     const uint32_t pk = __shfl_up(k, 1, 64);
     const bool bd = lane == 0u || k != pk;
     const unsigned long long bound = __ballot(bd);
-    if (!in || !bd) return;
+    if (!in || !bd || (SHARE && (k < lo || k >= hi))) return;
     const unsigned long long rest = lane == 63u ? 0ull : (bound >> (lane + 1u));
-    atomicAdd(&cnt[k], rest ? (uint32_t)__builtin_ctzll(rest) + 1u : 64u - lane);
+    atomicAdd(&cnt[SHARE ? k - lo : k], rest ? (uint32_t)__builtin_ctzll(rest) + 1u : 64u - lane);
+}
+
+// first[0] / first[1]: how many of the sorted keys ka / kb (n each) are below lo (share tables only)
+__global__ void k_dnbr_bounds(const uint32_t *__restrict__ ka, const uint32_t *__restrict__ kb, uint32_t n, uint32_t lo,
+                              uint32_t *__restrict__ first)
+{
+    if (blockIdx.x != 0u || threadIdx.x >= 2u) return;
+    const uint32_t *k = threadIdx.x == 0u ? ka : kb;
+    uint32_t a = 0u, b = n;
+    while (a < b) {
+        const uint32_t mid = a + (b - a) / 2u;
+        if (k[mid] < lo) a = mid + 1u; else b = mid;
+    }
+    first[threadIdx.x] = a;
 }
 
 __global__ __launch_bounds__(256) void k_nbr_offsets(const uint32_t *__restrict__ hoff, const uint32_t *__restrict__ loff,
@@ -267,40 +304,47 @@ __global__ __launch_bounds__(256) void k_nbr_offsets(const uint32_t *__restrict_
     if (i < n) offs[i] = (long long)hoff[i] + (long long)loff[i];
 }
 
-// Row r starts at hoff[r] + loff[r] (the entries above / below the diagonal of all smaller ids) and holds its
-// lcnt[r] smaller neighbours first.  Reduced entry j = (a, b), a < b, is the (j - hoff[a])-th larger neighbour of a:
-// place hoff[a] + loff[a] + lcnt[a] + j - hoff[a] = loff[a + 1] + j.
+// Row i starts at hoff[i] + loff[i] (the entries above / below the diagonal of the rows before it) and holds its
+// lcnt[i] smaller neighbours first.  Reduced entry j = (a, b), a < b, is the (j - first[0] - hoff[i])-th larger
+// neighbour of row i = a - lo: place hoff[i] + loff[i] + lcnt[i] + j - first[0] - hoff[i] = loff[i + 1] + j - first[0].
+template <bool SHARE>
 __global__ __launch_bounds__(256) void k_nbr_fill_high(const uint32_t *__restrict__ ua, const uint32_t *__restrict__ ub,
                                                        const unsigned long long *__restrict__ ucnt, uint32_t U,
+                                                       uint32_t lo, uint32_t hi, const uint32_t *__restrict__ first,
                                                        const uint32_t *__restrict__ loff, uint32_t *__restrict__ nbrs,
                                                        long long *__restrict__ lens)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= U) return;
-    const size_t p = (size_t)loff[ua[j] + 1u] + j;
+    const uint32_t a = ua[j];
+    if (SHARE && (a < lo || a >= hi)) return;
+    const size_t p = SHARE ? (size_t)loff[a - lo + 1u] + (j - first[0]) : (size_t)loff[a + 1u] + j;
     nbrs[p] = ub[j];
     lens[p] = (long long)ucnt[j];
 }
 
-// The q-th entry in the stable order by b (entry order[q], its b = skb[q]) is the (q - loff[b])-th smaller neighbour
-// of b: place hoff[b] + loff[b] + q - loff[b] = hoff[b] + q.
+// The q-th entry in the stable order by b (entry order[q], its b = skb[q]) is the (q - first[1] - loff[i])-th smaller
+// neighbour of row i = b - lo: place hoff[i] + loff[i] + q - first[1] - loff[i] = hoff[i] + q - first[1].
+template <bool SHARE>
 __global__ __launch_bounds__(256) void k_nbr_fill_low(const uint32_t *__restrict__ skb, const uint32_t *__restrict__ order,
                                                       const uint32_t *__restrict__ ua,
                                                       const unsigned long long *__restrict__ ucnt, uint32_t U,
+                                                      uint32_t lo, uint32_t hi, const uint32_t *__restrict__ first,
                                                       const uint32_t *__restrict__ hoff, uint32_t *__restrict__ nbrs,
                                                       long long *__restrict__ lens)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q >= U) return;
+    const uint32_t b = skb[q];
+    if (SHARE && (b < lo || b >= hi)) return;
     const uint32_t j = order[q];
-    const size_t p = (size_t)hoff[skb[q]] + q;
+    const size_t p = SHARE ? (size_t)hoff[b - lo] + (q - first[1]) : (size_t)hoff[b] + q;
     nbrs[p] = ua[j];
     lens[p] = (long long)ucnt[j];
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
-// a number for the next table of the process: whoever remembers a table's serial (and its context) can tell
-// whether nbr_offs / nbr_ids / nbr_lens still hold that table
+// a number for the next table of the process (NbrTable::serial)
 static inline unsigned long long nbr_next_serial()
 {
     static std::atomic<unsigned long long> serial{0};
@@ -343,14 +387,15 @@ static int run_nbr_begin(shp_ctx *ctx, int64_t max_seg_id, int four_connected)
 {
     NbrState &s = ctx->nbr;
     s = NbrState{};
-    ctx->nbr_serial = nbr_next_serial();        // (the table of an earlier serial is gone from here on)
+    nbr_table_end(ctx->nbr_tab);                // (the table of an earlier serial is gone from here on)
+    ctx->nbr_tab.serial = nbr_next_serial();
     CHK(buf_ensure(ctx, ctx->nbr_ctr, NBR_C_WORDS * 8));
     HIPCHK(ctx, hipMemsetAsync(ctx->nbr_ctr.p, 0, NBR_C_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     s.cap = ctx->nbr_rec.cap / 16;          // (a buffer of an earlier table is reused)
     s.given = max_seg_id;
     s.eight = four_connected ? 0 : 1;
-    s.stage = 1;
+    s.open = true;
     return 0;
 }
 
@@ -398,106 +443,153 @@ static int run_nbr_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrow
     SHP_FAIL(ctx, SHP_ERR_STATE, "a row block's records did not fit the buffer sized for them");
 }
 
-// The table over the ids 0 .. S of the first n records of nbr_rec (ids 1 .. S, a < b): steps 2 and 3 of the header.
-// Offsets (S + 2 int64), neighbours and lengths (2 U entries) stay in the context's nbr_offs / nbr_ids / nbr_lens;
-// the state becomes a finished table.  (nbrmerge.h builds the table of merged segments through it.)
-static int nbr_build_table(shp_ctx *ctx, uint32_t S, uint32_t n)
+// n records (b, a, count: CNT as nbr_rec_count reads it) sorted by the 64-bit key (a, b) -- two stable passes of
+// sort.h's 32-bit sort, by b then by a, over `bits` significant bits -- and run-length reduced with 64-bit sums:
+// *U_out distinct pairs in nbr_ua / nbr_ub / nbr_ucnt.  The host reads the distinct-pair count mid-way (one
+// synchronisation).  Step 2 of the header for every table of the library.
+template <typename CNT>
+static int nbr_sort_reduce(shp_ctx *ctx, const uint4 *rec, uint32_t n, int bits, uint32_t *U_out)
 {
-    NbrState &s = ctx->nbr;
     hipStream_t st = ctx->stream;
-    const size_t ns = (size_t)S + 1;
-    const int bits = bits_for(S);
+    *U_out = 0u;
+    if (n == 0u) return 0;
     uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
-    HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    uint32_t U = 0;
-    uint32_t *ua = nullptr, *ub = nullptr;
-    unsigned long long *ucnt = nullptr;
-    if (n) {
-        CHK(buf_ensure(ctx, ctx->nbr_key, (size_t)n * 4));
-        CHK(buf_ensure(ctx, ctx->nbr_val, (size_t)n * 4));
-        CHK(buf_ensure(ctx, ctx->nbr_uidx, (size_t)n * 4));
-        CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(n > ns + 1 ? n : ns + 1)));
-        const uint4 *rec = (const uint4 *)ctx->nbr_rec.p;
-        uint32_t *key = bp<uint32_t>(ctx->nbr_key), *val = bp<uint32_t>(ctx->nbr_val), *uidx = bp<uint32_t>(ctx->nbr_uidx);
-        const unsigned gn = grid_for(n, 256);
-        // stable by b, then stable by a: sorted by (a, b)
-        uint32_t *ord = nullptr, *sa = nullptr;
-        hipLaunchKernelGGL(k_nbr_field, dim3(gn), dim3(256), 0, st, rec, n, 0, (const uint32_t *)nullptr, key,
-                           (uint32_t *)nullptr);
-        KCHK(ctx);
-        CHK(sort_pairs(ctx, key, nullptr, n, bits, nullptr, &ord, true));
-        hipLaunchKernelGGL(k_nbr_field, dim3(gn), dim3(256), 0, st, rec, n, 1, (const uint32_t *)ord, key, val);
-        KCHK(ctx);
-        CHK(sort_pairs(ctx, key, val, n, bits, &sa, &ord, true));
-        uint32_t *sb = key, *sc = val;          // (the sort has read both)
-        hipLaunchKernelGGL(k_nbr_gather, dim3(gn), dim3(256), 0, st, rec, n, (const uint32_t *)ord, sb, sc);
-        KCHK(ctx);
-        NbrHeadFn hf{sa, sb};
-        CHK(scan_exclusive(ctx, hf, n, uidx, nullptr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        U = *(volatile uint32_t *)mir;
-        if (U < 1u || U > n) SHP_FAIL(ctx, SHP_ERR_STATE, "%u distinct pairs out of %u records", U, n);
-        CHK(buf_ensure(ctx, ctx->nbr_ua, (size_t)U * 4));
-        CHK(buf_ensure(ctx, ctx->nbr_ub, (size_t)U * 4));
-        CHK(buf_ensure(ctx, ctx->nbr_ucnt, (size_t)U * 8));
-        ua = bp<uint32_t>(ctx->nbr_ua);
-        ub = bp<uint32_t>(ctx->nbr_ub);
-        ucnt = (unsigned long long *)ctx->nbr_ucnt.p;
-        HIPCHK(ctx, hipMemsetAsync(ucnt, 0, (size_t)U * 8, st));
-        hipLaunchKernelGGL(k_nbr_reduce, dim3(gn), dim3(256), 0, st, (const uint32_t *)sa, (const uint32_t *)sb,
-                           (const uint32_t *)sc, (const uint32_t *)uidx, n, ua, ub, ucnt);
-        KCHK(ctx);
-    } else {
-        CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(ns + 1)));
-    }
-    // degrees of both ends, their scans, the two fills
-    CHK(buf_ensure(ctx, ctx->nbr_deg, 2 * ns * 4));
-    CHK(buf_ensure(ctx, ctx->nbr_hoff, (ns + 1) * 4));
-    CHK(buf_ensure(ctx, ctx->nbr_loff, (ns + 1) * 4));
-    CHK(buf_ensure(ctx, ctx->nbr_offs, (ns + 1) * 8));
-    CHK(buf_ensure(ctx, ctx->nbr_ids, (size_t)2 * U * 4));
-    CHK(buf_ensure(ctx, ctx->nbr_lens, (size_t)2 * U * 8));
-    uint32_t *hcnt = bp<uint32_t>(ctx->nbr_deg), *lcnt = hcnt + ns;
-    uint32_t *hoff = bp<uint32_t>(ctx->nbr_hoff), *loff = bp<uint32_t>(ctx->nbr_loff);
-    HIPCHK(ctx, hipMemsetAsync(hcnt, 0, 2 * ns * 4, st));
-    uint32_t *skb = nullptr, *ordb = nullptr;
-    if (U) {
-        const unsigned gu = grid_for(U, 256);
-        hipLaunchKernelGGL(k_nbr_degree, dim3(gu), dim3(256), 0, st, (const uint32_t *)ua, U, hcnt);
-        KCHK(ctx);
-        CHK(sort_pairs(ctx, ub, nullptr, U, bits, &skb, &ordb, true));
-        hipLaunchKernelGGL(k_nbr_degree, dim3(gu), dim3(256), 0, st, (const uint32_t *)skb, U, lcnt);
-        KCHK(ctx);
-    }
-    ArrFn fh{hcnt}, fl{lcnt};
-    CHK(scan_exclusive(ctx, fh, (uint32_t)ns, hoff, hoff + ns, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 1));
-    CHK(scan_exclusive(ctx, fl, (uint32_t)ns, loff, loff + ns, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 2));
-    hipLaunchKernelGGL(k_nbr_offsets, dim3(grid_for(ns + 1, 256)), dim3(256), 0, st, (const uint32_t *)hoff,
-                       (const uint32_t *)loff, (uint32_t)(ns + 1), (long long *)ctx->nbr_offs.p);
+    CHK(buf_ensure(ctx, ctx->nbr_key, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_val, (size_t)n * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_uidx, (size_t)n * 4));
+    if (sizeof(CNT) == 8) CHK(buf_ensure(ctx, ctx->dnbr_cnt, (size_t)n * 8));
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(n)));
+    uint32_t *key = bp<uint32_t>(ctx->nbr_key), *val = bp<uint32_t>(ctx->nbr_val), *uidx = bp<uint32_t>(ctx->nbr_uidx);
+    const unsigned gn = grid_for(n, 256);
+    // stable by b, then stable by a: sorted by (a, b)
+    uint32_t *ord = nullptr, *sa = nullptr;
+    hipLaunchKernelGGL(k_nbr_field, dim3(gn), dim3(256), 0, st, rec, n, 0, (const uint32_t *)nullptr, key, (uint32_t *)nullptr);
     KCHK(ctx);
-    if (U) {
-        const unsigned gu = grid_for(U, 256);
-        hipLaunchKernelGGL(k_nbr_fill_high, dim3(gu), dim3(256), 0, st, (const uint32_t *)ua, (const uint32_t *)ub,
-                           (const unsigned long long *)ucnt, U, (const uint32_t *)loff, bp<uint32_t>(ctx->nbr_ids),
-                           (long long *)ctx->nbr_lens.p);
-        KCHK(ctx);
-        hipLaunchKernelGGL(k_nbr_fill_low, dim3(gu), dim3(256), 0, st, (const uint32_t *)skb, (const uint32_t *)ordb,
-                           (const uint32_t *)ua, (const unsigned long long *)ucnt, U, (const uint32_t *)hoff,
-                           bp<uint32_t>(ctx->nbr_ids), (long long *)ctx->nbr_lens.p);
-        KCHK(ctx);
-    }
-    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    CHK(sort_pairs(ctx, key, nullptr, n, bits, nullptr, &ord, true));
+    hipLaunchKernelGGL(k_nbr_field, dim3(gn), dim3(256), 0, st, rec, n, 1, (const uint32_t *)ord, key, val);
+    KCHK(ctx);
+    CHK(sort_pairs(ctx, key, val, n, bits, &sa, &ord, true));
+    // (the sort has read key and val: b goes where key was, and a 32-bit count where val was)
+    uint32_t *sb = key;
+    CNT *sc = sizeof(CNT) == 8 ? (CNT *)ctx->dnbr_cnt.p : (CNT *)val;
+    hipLaunchKernelGGL(k_nbr_gather<CNT>, dim3(gn), dim3(256), 0, st, rec, n, (const uint32_t *)ord, sb, sc);
+    KCHK(ctx);
+    NbrHeadFn hf{sa, sb};
+    CHK(scan_exclusive(ctx, hf, n, uidx, nullptr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    nbr_ms(ctx);
-    const uint32_t th = *(volatile uint32_t *)(mir + 1), tl = *(volatile uint32_t *)(mir + 2);
-    if (th != U || tl != U) SHP_FAIL(ctx, SHP_ERR_STATE, "degrees sum to %u and %u for %u pairs", th, tl, U);
-    s.S = S;
-    s.nent = 2ull * U;
-    s.stage = 2;
+    const uint32_t U = *(volatile uint32_t *)mir;
+    if (U < 1u || U > n) SHP_FAIL(ctx, SHP_ERR_STATE, "%u distinct pairs out of %u records", U, n);
+    CHK(buf_ensure(ctx, ctx->nbr_ua, (size_t)U * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_ub, (size_t)U * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_ucnt, (size_t)U * 8));
+    HIPCHK(ctx, hipMemsetAsync(ctx->nbr_ucnt.p, 0, (size_t)U * 8, st));
+    hipLaunchKernelGGL(k_nbr_reduce<CNT>, dim3(gn), dim3(256), 0, st, (const uint32_t *)sa, (const uint32_t *)sb,
+                       (const CNT *)sc, (const uint32_t *)uidx, n, bp<uint32_t>(ctx->nbr_ua), bp<uint32_t>(ctx->nbr_ub),
+                       (unsigned long long *)ctx->nbr_ucnt.p);
+    KCHK(ctx);
+    *U_out = U;
     return 0;
 }
 
-// The table of everything accumulated, for run_nbr_download.  *bad_out: 0, or the largest label above a given
+// Step 3 of the header: the CSR of the U reduced pairs (nbr_ua / nbr_ub / nbr_ucnt) over the rows of t (t.row0, t.nrows
+// are set) into t.offs / t.ids / t.lens; t.nent is set.  The degrees of both ends are counted, scanned, and both
+// parts of every row filled.
+//   SHARE = false, the whole table (row0 = 0, nrows = S + 1): every pair has both its rows here, so nent = 2 U is
+//     known up front and nothing is read back -- the caller synchronises and checks mir[1] == mir[2] == U.
+//   SHARE = true, a rank's id share: k_dnbr_bounds finds where the share's entries start in the two orders, and the
+//     host reads the two degree totals (one synchronisation) to size the entries: each is at most U.
+template <bool SHARE>
+static int nbr_build_csr(shp_ctx *ctx, NbrTable &t, uint32_t U, int bits)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t lo = t.row0, nr = t.nrows, hi = lo + nr;
+    uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
+    uint32_t *ua = bp<uint32_t>(ctx->nbr_ua), *ub = bp<uint32_t>(ctx->nbr_ub);
+    const unsigned long long *ucnt = (const unsigned long long *)ctx->nbr_ucnt.p;
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes((size_t)nr + 1)));
+    CHK(buf_ensure(ctx, ctx->nbr_deg, (size_t)2 * nr * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_hoff, ((size_t)nr + 1) * 4));
+    CHK(buf_ensure(ctx, ctx->nbr_loff, ((size_t)nr + 1) * 4));
+    CHK(buf_ensure(ctx, t.offs, ((size_t)nr + 1) * 8));
+    unsigned long long nent = 2ull * U;
+    if (!SHARE) {
+        CHK(buf_ensure(ctx, t.ids, (size_t)nent * 4));
+        CHK(buf_ensure(ctx, t.lens, (size_t)nent * 8));
+    }
+    uint32_t *hcnt = bp<uint32_t>(ctx->nbr_deg), *lcnt = hcnt + nr;
+    uint32_t *hoff = bp<uint32_t>(ctx->nbr_hoff), *loff = bp<uint32_t>(ctx->nbr_loff);
+    uint32_t *first = SHARE ? (uint32_t *)((unsigned long long *)ctx->nbr_ctr.p + 2) : nullptr;
+    if (nr) HIPCHK(ctx, hipMemsetAsync(hcnt, 0, (size_t)2 * nr * 4, st));
+    uint32_t *skb = nullptr, *ordb = nullptr;
+    const unsigned gu = grid_for(U, 256);
+    if (U && nr) {
+        hipLaunchKernelGGL(k_nbr_degree<SHARE>, dim3(gu), dim3(256), 0, st, (const uint32_t *)ua, U, lo, hi, hcnt);
+        KCHK(ctx);
+        CHK(sort_pairs(ctx, ub, nullptr, U, bits, &skb, &ordb, true));
+        hipLaunchKernelGGL(k_nbr_degree<SHARE>, dim3(gu), dim3(256), 0, st, (const uint32_t *)skb, U, lo, hi, lcnt);
+        KCHK(ctx);
+        if (SHARE) {
+            hipLaunchKernelGGL(k_dnbr_bounds, dim3(1), dim3(64), 0, st, (const uint32_t *)ua, (const uint32_t *)skb, U, lo, first);
+            KCHK(ctx);
+        }
+    }
+    ArrFn fh{hcnt}, fl{lcnt};
+    CHK(scan_exclusive(ctx, fh, nr, hoff, hoff + nr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 1));
+    CHK(scan_exclusive(ctx, fl, nr, loff, loff + nr, bp<uint32_t>(ctx->scan_tmp), nullptr, mir + 2));
+    hipLaunchKernelGGL(k_nbr_offsets, dim3(grid_for((size_t)nr + 1, 256)), dim3(256), 0, st, (const uint32_t *)hoff,
+                       (const uint32_t *)loff, nr + 1u, (long long *)t.offs.p);
+    KCHK(ctx);
+    if (SHARE) {
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        const uint32_t th = *(volatile uint32_t *)(mir + 1), tl = *(volatile uint32_t *)(mir + 2);
+        if (th > U || tl > U) SHP_FAIL(ctx, SHP_ERR_STATE, "degrees sum to %u and %u for %u pairs", th, tl, U);
+        nent = (unsigned long long)th + tl;
+        CHK(buf_ensure(ctx, t.ids, (size_t)nent * 4));
+        CHK(buf_ensure(ctx, t.lens, (size_t)nent * 8));
+    }
+    if (nent) {
+        hipLaunchKernelGGL(k_nbr_fill_high<SHARE>, dim3(gu), dim3(256), 0, st, (const uint32_t *)ua, (const uint32_t *)ub, ucnt,
+                           U, lo, hi, (const uint32_t *)first, (const uint32_t *)loff, bp<uint32_t>(t.ids), (long long *)t.lens.p);
+        KCHK(ctx);
+        hipLaunchKernelGGL(k_nbr_fill_low<SHARE>, dim3(gu), dim3(256), 0, st, (const uint32_t *)skb, (const uint32_t *)ordb,
+                           (const uint32_t *)ua, ucnt, U, lo, hi, (const uint32_t *)first, (const uint32_t *)hoff,
+                           bp<uint32_t>(t.ids), (long long *)t.lens.p);
+        KCHK(ctx);
+    }
+    t.nent = nent;
+    return 0;
+}
+
+// The table over the ids 0 .. S of the first n records of nbr_rec (ids 1 .. S, a < b, 32-bit counts): steps 2 and 3 of
+// the header into the context's one-GPU table, which becomes a finished table.  (nbrmerge.h builds the table of
+// merged segments through it.)
+static int nbr_build_table(shp_ctx *ctx, uint32_t S, uint32_t n)
+{
+    NbrTable &t = ctx->nbr_tab;
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)S + 1;
+    const int bits = bits_for(S);
+    const uint32_t *mir = ctx->h_pinned + PIN_MIRROR + MIR_NBR;
+    HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
+    // (room for the longer of the two halves' scans at once: no buffer grows between them)
+    CHK(buf_ensure(ctx, ctx->scan_tmp, scan_tmp_bytes(n > ns + 1 ? n : ns + 1)));
+    uint32_t U = 0;
+    CHK(nbr_sort_reduce<uint32_t>(ctx, (const uint4 *)ctx->nbr_rec.p, n, bits, &U));
+    t.S = S;
+    t.row0 = 0u;
+    t.nrows = (uint32_t)ns;
+    CHK(nbr_build_csr<false>(ctx, t, U, bits));
+    HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    nbr_ms(ctx);
+    const uint32_t th = *(volatile const uint32_t *)(mir + 1), tl = *(volatile const uint32_t *)(mir + 2);
+    if (th != U || tl != U) SHP_FAIL(ctx, SHP_ERR_STATE, "degrees sum to %u and %u for %u pairs", th, tl, U);
+    ctx->nbr.open = false;
+    t.finished = true;
+    return 0;
+}
+
+// The table of everything accumulated, for nbr_table_download.  *bad_out: 0, or the largest label above a given
 // max_seg_id (then nothing is built).
 static int run_nbr_finish(shp_ctx *ctx, uint32_t *S_out, int64_t *nent_out, uint32_t *bad_out)
 {
@@ -512,19 +604,37 @@ static int run_nbr_finish(shp_ctx *ctx, uint32_t *S_out, int64_t *nent_out, uint
     if (S >= 0xfffffffeu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
     *S_out = S;
     CHK(nbr_build_table(ctx, S, (uint32_t)s.used));
-    *nent_out = (int64_t)s.nent;
+    *nent_out = (int64_t)ctx->nbr_tab.nent;
     return 0;
 }
 
-static int run_nbr_download(shp_ctx *ctx, int64_t *offsets, uint32_t *nbrs, int64_t *lens)
+// a finished table (either of the context's two) to host memory
+static int nbr_table_download(shp_ctx *ctx, const NbrTable &t, int64_t *offsets, uint32_t *nbrs, int64_t *lens)
 {
-    const NbrState &s = ctx->nbr;
     hipStream_t st = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(offsets, ctx->nbr_offs.p, ((size_t)s.S + 2) * 8, hipMemcpyDeviceToHost, st));
-    if (s.nent) {
-        HIPCHK(ctx, hipMemcpyAsync(nbrs, ctx->nbr_ids.p, (size_t)s.nent * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipMemcpyAsync(lens, ctx->nbr_lens.p, (size_t)s.nent * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(offsets, t.offs.p, ((size_t)t.nrows + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (t.nent) {
+        HIPCHK(ctx, hipMemcpyAsync(nbrs, t.ids.p, (size_t)t.nent * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipMemcpyAsync(lens, t.lens.p, (size_t)t.nent * 8, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+// The arrays of a host table into t's buffers (t.nrows is set; the copies are queued, not awaited).  What makes them
+// a table -- the device validation of shp_nbr_upload, the host check of shp_dnbr_upload -- is the caller's.
+static int nbr_table_upload_arrays(shp_ctx *ctx, NbrTable &t, const int64_t *offsets, const uint32_t *nbrs, const int64_t *lens,
+                                   unsigned long long nent)
+{
+    hipStream_t st = ctx->stream;
+    const size_t nr = t.nrows;
+    CHK(buf_ensure(ctx, t.offs, (nr + 1) * 8));
+    CHK(buf_ensure(ctx, t.ids, (size_t)nent * 4));
+    CHK(buf_ensure(ctx, t.lens, (size_t)nent * 8));
+    HIPCHK(ctx, hipMemcpyAsync(t.offs.p, offsets, (nr + 1) * 8, hipMemcpyHostToDevice, st));
+    if (nent) {
+        HIPCHK(ctx, hipMemcpyAsync(t.ids.p, nbrs, (size_t)nent * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipMemcpyAsync(t.lens.p, lens, (size_t)nent * 8, hipMemcpyHostToDevice, st));
+    }
     return 0;
 }

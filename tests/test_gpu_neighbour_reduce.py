@@ -18,8 +18,10 @@ import functools
 import numpy as np
 import pytest
 
+import aggregate_cases as ac
 import neighbour_cases as nc
 import neighbour_reduce_cases as rc
+import table_cases as tc
 from test_gpu_neighbours import find, in_fresh_context, real_raster, real_reference
 
 pytestmark = pytest.mark.gpu
@@ -320,6 +322,89 @@ def test_a_row_in_two_tables():
     for stat in rc.STATS:
         assert a[stat][keep].tobytes() == b[stat][keep].tobytes(), stat
     assert not all(a[stat].tobytes() == b[stat].tobytes() for stat in FLOAT_SUMS)
+
+
+# ---- 5b: three owners of a list of long rows in one context -----------------------------------------------------
+LISTS_S = rc.LONG + 3
+LISTS_STATS = ('mean', 'bordermean', 'nearest')
+
+
+@functools.lru_cache(maxsize=None)
+def list_tables():
+    """(T1, T2, T3) over the ids 0 .. LONG + 3: a star of LONG + 2 leaves around id 1, the same star around the last
+    id, and a chain; lengths 1 .. 9"""
+    S = LISTS_S
+    leaves = np.arange(2, S + 1, dtype=np.int64)
+    w = 1 + np.arange(len(leaves)) % 9
+    t1 = tc.table_from_edges(S, np.ones(len(leaves), dtype=np.int64), leaves, w)
+    t2 = tc.table_from_edges(S, leaves - 1, np.full(len(leaves), S, dtype=np.int64), w)
+    i = np.arange(1, S, dtype=np.int64)
+    t3 = tc.table_from_edges(S, i, i + 1, 1 + i % 9)
+    return (t1, t2, t3)
+
+
+def long_rows(table):
+    return np.flatnonzero(np.diff(table[0]) > rc.LONG).tolist()
+
+
+def test_list_tables_have_their_long_rows():
+    """no GPU: one row above NBRR_LONG in T1 and in T2, at different indices, none in T3; the share of T2 that holds
+    the hub lists it at another index again; one chunk each"""
+    (t1, t2, t3) = list_tables()
+    assert (long_rows(t1), long_rows(t2), long_rows(t3)) == ([1], [LISTS_S], [])
+    assert int(np.diff(t1[0]).max()) == int(np.diff(t2[0]).max()) == rc.LONG + 2 <= rc.CHUNK
+    share = tc.share_of(t2, 1, 2)
+    (lo, hi) = share.idRange
+    assert lo > 1 and hi == LISTS_S + 1 and long_rows((share.offsets,)) == [LISTS_S - lo]
+
+
+def test_long_row_lists_of_two_tables_and_a_member_list_interleaved():
+    """One context, one thread: reductions over T1, T2, T3 (each upload a new table), over the share of T2 that holds
+    the hub, an aggregation over a member list with one long row, then T1 and the share again.  Each owner of a list
+    of long rows must use its own, rebuilt exactly when its table changed: every result equals the numpy model bit
+    for bit (integer columns: exact in any order)."""
+    import types
+    from pyshepseg_amd import _lib, distributed, neighbours
+    from pyshepseg_amd import comm as shpcomm
+    tables = list_tables()
+    col = rc.integer_column(LISTS_S + 1, 1 << 20, 41)
+    selection = [(s, s) for s in LISTS_STATS]
+    want = [rc.reference_reduce(*t, col, stats=LISTS_STATS) for t in tables]
+    recode = np.ones(LISTS_S + 1, dtype=np.uint32)
+    recode[0] = 0
+    assert long_rows(ac.member_csr(recode, 1)) == [1]
+    aggStats = [(s, s) for s in ac.STATS]
+    aggWant = ac.reference_aggregate(recode, 1, col)
+
+    def same_bits(got, model, rows=slice(None)):
+        assert sorted(got) == sorted(LISTS_STATS)
+        for name in LISTS_STATS:
+            assert got[name].dtype == model[name].dtype, name
+            assert got[name][rows].tobytes() == model[name][rows].tobytes(), name
+
+    def steps():
+        c = _lib.ctx()
+        (engine, comm) = (types.SimpleNamespace(c=c), shpcomm.LocalComm())
+        whole = [tc.whole_of(t) for t in tables]
+        for k in (0, 1, 2):                                                            # steps 1 to 3
+            same_bits(reduce(whole[k], col, selection), want[k])
+            assert whole[k].reduceTimings['uploaded']
+        share = tc.share_of(tables[1], 1, 2)
+        rows = slice(*share.idRange)
+        got = distributed.reduceOverNeighboursDistributed(engine, comm, share, [(col, selection)])       # step 4
+        assert share.reduceTimings['uploaded']
+        same_bits(got, want[1], rows)
+        byHand = neighbours.MergedSegments()                                            # step 5
+        (byHand.recode, byHand.maxSegId) = (recode, 1)
+        agg = neighbours.aggregateToGroups(byHand, [(col, aggStats)])
+        for name in ac.STATS:
+            assert agg[name].dtype == aggWant[name].dtype and np.array_equal(agg[name], aggWant[name]), name
+        same_bits(reduce(whole[0], col, selection), want[0])                            # step 6
+        assert whole[0].reduceTimings['uploaded']
+        got = distributed.reduceOverNeighboursDistributed(engine, comm, share, [(col, selection)])       # step 7
+        assert not share.reduceTimings['uploaded']
+        same_bits(got, want[1], rows)
+    in_fresh_context(steps)
 
 
 # ---- 6: several columns, shared output ---------------------------------------------------------------------------

@@ -14,7 +14,7 @@ neighbour_cases.patch_records.
 
 Border lengths of 2^32 and more (from a raster the 64-bit sums need over 10^9 pixel pairs of one pair) are reached
 through the contraction of hand-built tables: tests/test_gpu_merge_tables.py and tests/test_gpu_merge_tables_dist.py
-put non-zero high words through k_nbr_reduce, its copy in dneighbours.h and the share merge.  Not covered: labels of
+put non-zero high words through k_nbr_reduce (its 64-bit instantiation, which the share tables use) and the share merge.  Not covered: labels of
 2^31 and more in a successful table (its offsets alone are 16 GB)."""
 import ctypes
 import functools
