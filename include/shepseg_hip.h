@@ -880,6 +880,33 @@ int shp_dnbr_mrg_number(shp_ctx *ctx, const void *d_all, int64_t slot, int world
 int shp_dnbr_mrg_records(shp_ctx *ctx, int64_t new_id_lo, int64_t new_id_hi, int64_t *counts_out, void **d_travel_out,
                          double *dev_ms_out);
 
+/* ---- the shared prefix sum and radix sort on their own (csrc/prims.h; for the tests) -------------------------
+ * csrc/scan.h's scan_exclusive and csrc/sort.h's sort_pairs, called as the product's forty call sites call them, on
+ * buffers of the caller's in device memory (shp_dev_alloc; 4-byte aligned is enough, and a pointer that is not 16-byte
+ * aligned makes the kernels take their 4-byte loads and stores).  No product path uses these two: they let a test
+ * choose n, alignment and flags.  Both use the context's scan and sort workspaces (and the first words of its small
+ * scratch block), so neither may come between the steps of a call sequence that keeps state in the workspace
+ * (shp_segpoints_*, shp_dsegpoints_*, shp_dcolour_*); shp_dev_* transfers may come before and after.  n of 2^32 or
+ * more and NULL pointers are SHP_ERR_ARG.
+ *  shp_prim_scan: d_out[i] = sum of d_in[0 .. i - 1] modulo 2^32 for n words.  flags bit 0: read d_in through a
+ *    functor without the 16-byte load (get4); bit 1: ask for the lazy add-back -- d_out is then left without the
+ *    per-block offsets, which go to d_boff_out (device, ceil(n / 8192) words) with their count in *nboff_out (0 when
+ *    the scan had one block and handed back no offsets).  Without bit 1 d_boff_out and nboff_out may be NULL.
+ *    *total_dev_out: the total as the scan's device word holds it; *total_mirror_out: as the word of the pinned
+ *    block holds it after the stream's synchronisation.  Both words hold 0xA5A5A5A5 before the scan.
+ *  shp_prim_sort: sorts n (key, value) pairs stably by the low 8 * max(1, ceil(bits / 8)) key bits (sort_pairs sorts
+ *    whole bytes), bits 0 .. 32.  d_vals NULL: the values are the indices 0 .. n - 1.  flags bit 0: the staged
+ *    scatter.  d_keys_out NULL: sort_pairs is told the keys are not wanted (its last pass writes none).  The result
+ *    is copied out of the library's ping-pong buffers, so d_keys_out / d_vals_out must not be those.
+ *    digit_starts_out (host, 257 words, may be NULL): when the sort took one pass (bits <= 8), entry d is
+ *    sort_digit_start(d) read on the device from the pass's scanned histogram as the k-means fit reads it -- the
+ *    position of the first key whose low byte is d, and n for d = 256; all zero for n = 0; untouched for more
+ *    passes. */
+int shp_prim_scan(shp_ctx *ctx, const uint32_t *d_in, uint64_t n, uint32_t *d_out, int flags, uint32_t *total_dev_out,
+                  uint32_t *total_mirror_out, uint32_t *d_boff_out, uint32_t *nboff_out);
+int shp_prim_sort(shp_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, uint64_t n, int bits, int flags,
+                  uint32_t *d_keys_out, uint32_t *d_vals_out, uint32_t *digit_starts_out);
+
 /* ---- multi-GPU exchange -----------------------------------------------------------------
  * One process per GPU.  The reference ships whole pickled tile results to one process over a
  * multiprocessing.managers TCP channel (NetworkDataChannel, tiling.py:1799-1912; SegmentationResultCache

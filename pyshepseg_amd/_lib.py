@@ -79,6 +79,9 @@ _SIGS = {
     'shp_host_free': (_c.c_int, [_vp, _vp]),
     'shp_dev_copy': (_c.c_int, [_vp, _vp, _vp, _c.c_size_t]),
     'shp_sync': (_c.c_int, [_vp]),
+    'shp_prim_scan': (_c.c_int, [_vp, _vp, _c.c_uint64, _vp, _c.c_int, _c.POINTER(_c.c_uint32),
+                                 _c.POINTER(_c.c_uint32), _vp, _c.POINTER(_c.c_uint32)]),
+    'shp_prim_sort': (_c.c_int, [_vp, _vp, _vp, _c.c_uint64, _c.c_int, _c.c_int, _vp, _vp, _vp]),
     'shp_dev_synthimg': (_c.c_int, [_vp, _c.c_uint64, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int,
                                     _c.c_int, _vp]),
     'shp_dev_block_labels': (_c.c_int, [_vp, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _vp,

@@ -4,6 +4,7 @@
 #include <utility>
 #include "scan.h"
 #include "sort.h"
+#include "prims.h"
 #include "kmeans.h"
 #include "clump.h"
 #include "elim_single.h"
@@ -595,6 +596,26 @@ API int shp_dev_memset(shp_ctx *ctx, void *dst_dev, int value, size_t bytes)
     if (bytes) HIPCHK(ctx, hipMemsetAsync(dst_dev, value, bytes, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+// ---- the shared primitives on their own (prims.h; for the tests) -------------------------------
+API int shp_prim_scan(shp_ctx *ctx, const uint32_t *d_in, uint64_t n, uint32_t *d_out, int flags,
+                      uint32_t *total_dev_out, uint32_t *total_mirror_out, uint32_t *d_boff_out, uint32_t *nboff_out)
+{
+    CHK(enter(ctx));
+    if (!d_in || !d_out || !total_dev_out || !total_mirror_out || ((flags & 2) && (!d_boff_out || !nboff_out)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n >= 0x100000000ull || (flags & ~3)) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_prim_scan(ctx, d_in, (uint32_t)n, d_out, flags, total_dev_out, total_mirror_out, d_boff_out, nboff_out);
+}
+
+API int shp_prim_sort(shp_ctx *ctx, const uint32_t *d_keys, const uint32_t *d_vals, uint64_t n, int bits, int flags,
+                      uint32_t *d_keys_out, uint32_t *d_vals_out, uint32_t *digit_starts_out)
+{
+    CHK(enter(ctx));
+    if (!d_keys || !d_vals_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (n >= 0x100000000ull || bits < 0 || bits > 32 || (flags & ~1)) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_prim_sort(ctx, d_keys, d_vals, (uint32_t)n, bits, flags, d_keys_out, d_vals_out, digit_starts_out);
 }
 
 API int shp_dev_synthimg(shp_ctx *ctx, uint64_t seed, int nbands, int64_t y0, int64_t x0, int nrows,

@@ -24,7 +24,7 @@
 // pinned block) instead of by a copy command queued behind it -- under load every command on a
 // stream costs 40-80 us, and there were ten such copies per tile.
 #define PIN_MIRROR (SHP_PINNED_BYTES / 4u - 64u)
-enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5, MIR_PTS = 8, MIR_NBR = 16 };     // (MIR_PTS: 8 words, segpoints.h; MIR_NBR: 3, neighbours.h)
+enum { MIR_NBIG = 0, MIR_RELABEL = 4, MIR_RUNS = 5, MIR_PTS = 8, MIR_NBR = 16, MIR_PRIM = 32 };     // (MIR_PTS: 8 words, segpoints.h; MIR_NBR: 3, neighbours.h; MIR_PRIM: 1, prims.h)
 #define MIRROR_STORE(ptr, v) __hip_atomic_store((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
 
 struct DevBuf {

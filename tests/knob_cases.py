@@ -6,6 +6,7 @@ is the GPU side of a case, expected() the oracle's; both return dicts of arrays 
 import numpy as np
 
 import clump_shape_cases
+import prim_cases
 import segtable_cases
 from seg_cases import (STATS_SEL, cut_components, fixed_centres, many_sources_one_target, oracle_tiled,
                        stats_band, synth_tile, uniform_region)
@@ -22,9 +23,9 @@ MANY_BIG = ('clump_many_big',)
 # (name, environment of the child, cases that reach the code the setting changes)
 MATRIX = [
     ('scan_two_launch', {'SHEPSEG_SCAN_ONE': '0'},
-     ('tile', 'tiled4', 'stats_sort_int32', 'stats_sort_uint8', 'subset', 'tables')),
+     ('tile', 'tiled4', 'stats_sort_int32', 'stats_sort_uint8', 'subset', 'tables', 'prim_scan', 'prim_sort')),
     ('csr_pixel_sort', {'SHEPSEG_CSR_RUNS': '0'}, ('tables',)),
-    ('sort_wide', {'SHEPSEG_SORT_WIDE': '1'}, tuple('stats_sort_' + d for d in STATS_DTYPES)),
+    ('sort_wide', {'SHEPSEG_SORT_WIDE': '1'}, tuple('stats_sort_' + d for d in STATS_DTYPES) + ('prim_sort',)),
     ('small_no_lists', {'SHEPSEG_SMALL_LISTS': '0'}, SMALL),
     ('small_one_level_barrier', {'SHEPSEG_SMALL_BAR2': '0'}, SMALL),
     ('small_blocks_1', {'SHEPSEG_SMALL_BLOCKS': '1'}, SMALL),
@@ -159,6 +160,10 @@ def run_case(name, oracle, tmpdir):
         return {'seg': seg, 'next': np.array([nxt])}
     if name == 'tables':
         return device_tables(*segtable_cases.make(*TABLES_CASE))
+    if name == 'prim_scan':
+        return prim_cases.knob_scan_run()
+    if name == 'prim_sort':
+        return prim_cases.knob_sort_run()
     raise KeyError(name)
 
 
@@ -193,6 +198,10 @@ def expected(name, oracle):
         return {'seg': seg, 'next': np.array([nxt])}
     if name == 'tables':
         return expected_tables(*segtable_cases.make(*TABLES_CASE), oracle)
+    if name == 'prim_scan':             # the numpy models of tests/prim_cases.py: no oracle
+        return prim_cases.knob_scan_expected()
+    if name == 'prim_sort':
+        return prim_cases.knob_sort_expected()
     raise KeyError(name)
 
 
