@@ -685,6 +685,36 @@ int shp_shape_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows,
 int shp_shape_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, uint32_t *bad_label_out, double *dev_ms_out);
 int shp_shape_download(shp_ctx *ctx, uint64_t *rows);
 
+/* ---- the shape table of a raster sharded by rows over the ranks (dist_shapes.deviceShapes) ---------------
+ * A rank begins a table of all ids with row0 = its first image row (shp_shape_begin), accumulates its rows, hands the
+ * rows of the segments that straddle a cut to the ranks that own their ids and ends with a table in which every id's
+ * row is non-zero on at most one rank: an integer all-reduce of the (max_seg_id + 1) x 11 words then completes it.
+ *  shp_shape_accumulate_halo_dev: shp_shape_accumulate_dev with the two extra rows wherever they lie: d_seg is the
+ *    block's own first row, d_above / d_below the raster's row before / after the block (ncols labels each, in device
+ *    memory, only looked at), NULL where the raster ends.  A rank's gigabytes of labels need not be copied to stand
+ *    between their halo rows.
+ *  shp_dshape_local_dev: after the accumulation.  d_hist: the whole raster's pixel count per id, n_hist = max_seg_id
+ *    + 1 uint32 in device memory.  *max_label_out: 0, or the largest label above max_seg_id in this rank's rows --
+ *    then nothing else is done and the table is gone.  Otherwise, with l an id's area here: l == hist[id] keeps the
+ *    row; 0 < l < hist[id] packs it as a record of 96 bytes (the id as uint64, then the row's 11 words) and empties
+ *    it; counts_out[0] = such records, at *d_records_out in device memory until the context's next shape call
+ *    (NULL without records); counts_out[1] = ids with l > hist[id] (the histogram is not these labels').
+ *  shp_dshape_merge_dev: d_all holds `world` blocks of `slot` records (16-byte aligned), the first counts[r] of block
+ *    r valid (slot 0: no rank sent any, d_all is not read).  Records with an id in [id_lo, id_hi) are folded into
+ *    that id's row (sums and counts add, extents combine by min / max); then the extents of ids without pixels
+ *    become 0 and the table is finished (shp_shape_download).  counts_out[0] = records folded, [1] = distinct ids
+ *    folded, [2] = ids of the share whose area is neither 0 nor d_hist's.  *d_table_out: the table in device memory,
+ *    for the all-reduce; it is what shp_shape_download copies.
+ * dev_ms_out (may be NULL): device time of the kernels since shp_shape_begin.  Out of order: SHP_ERR_STATE
+ * ("shp_shape_begin must come first", "shp_dshape_local_dev must come first"). */
+int shp_shape_accumulate_halo_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, const uint32_t *d_above,
+                                  const uint32_t *d_below);
+int shp_dshape_local_dev(shp_ctx *ctx, const uint32_t *d_hist, int64_t n_hist, uint32_t *max_label_out, int64_t *counts_out,
+                         void **d_records_out, double *dev_ms_out);
+int shp_dshape_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, const uint32_t *d_hist,
+                         int64_t n_hist, int64_t id_lo, int64_t id_hi, int64_t *counts_out, void **d_table_out,
+                         double *dev_ms_out);
+
 /* ---- columns reduced over the neighbour table (neighbours.reduceOverNeighbours) ----------------------
  * The finished table stays in the context; these calls reduce per-segment columns over its rows on the device.
  * Row r has entries with neighbour id n and border length w; v is the column widened to float64.  A value is ignored

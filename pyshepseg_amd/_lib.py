@@ -223,6 +223,11 @@ _SIGS = {
     'shp_shape_accumulate_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int]),
     'shp_shape_finish': (_c.c_int, [_vp, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_double)]),
     'shp_shape_download': (_c.c_int, [_vp, _vp]),
+    'shp_shape_accumulate_halo_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _vp, _vp]),
+    'shp_dshape_local_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.POINTER(_c.c_uint32), _vp, _c.POINTER(_vp),
+                                        _c.POINTER(_c.c_double)]),
+    'shp_dshape_merge_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _vp,
+                                        _c.POINTER(_vp), _c.POINTER(_c.c_double)]),
     'shp_nbr_upload': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),
     'shp_nbr_table_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
     'shp_nbr_reduce': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,

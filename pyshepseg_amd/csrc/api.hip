@@ -25,6 +25,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "dneighbours.h"
 #include "dnbrmerge.h"
 #include "segshape.h"
+#include "dsegshape.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1590,7 +1591,54 @@ API int shp_shape_accumulate_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nr
     CHK(enter(ctx));
     if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
     CHK(chk_row_block(ctx, d_seg, nrows, ncols));
-    return run_shape_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, has_above, has_below);
+    const uint32_t *first = d_seg + (has_above ? (size_t)ncols : 0);
+    return run_shape_accumulate(ctx, first, (uint32_t)nrows, (uint32_t)ncols, has_above ? first - ncols : nullptr,
+                                has_below ? first + (size_t)nrows * (size_t)ncols : nullptr);
+}
+
+API int shp_shape_accumulate_halo_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, const uint32_t *d_above,
+                                      const uint32_t *d_below)
+{
+    CHK(enter(ctx));
+    if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols, d_above));
+    if ((uintptr_t)d_below & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned raster");
+    return run_shape_accumulate(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, d_above, d_below);
+}
+
+// ---- the shape table of a row-sharded raster (dsegshape.h) -------------------------------------------------
+API int shp_dshape_local_dev(shp_ctx *ctx, const uint32_t *d_hist, int64_t n_hist, uint32_t *max_label_out, int64_t *counts_out,
+                             void **d_records_out, double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->shape.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no shapes begun: shp_shape_begin must come first");
+    if (!d_hist || !max_label_out || !counts_out || !d_records_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_hist & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned histogram");
+    if (n_hist != (int64_t)ctx->shape.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a histogram of %lld rows for a table of %lld", (long long)n_hist, (long long)ctx->shape.S + 1);
+    CHK(run_dshape_local(ctx, d_hist, max_label_out, counts_out, d_records_out));
+    if (dev_ms_out) *dev_ms_out = ctx->shape.dev_ms;
+    return 0;
+}
+
+API int shp_dshape_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int world, const uint32_t *counts, const uint32_t *d_hist,
+                             int64_t n_hist, int64_t id_lo, int64_t id_hi, int64_t *counts_out, void **d_table_out,
+                             double *dev_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->shape.stage != 3) SHP_FAIL(ctx, SHP_ERR_STATE, "no local step: shp_dshape_local_dev must come first");
+    if (!d_hist || !counts_out || !d_table_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if ((uintptr_t)d_hist & 3u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned histogram");
+    if (n_hist != (int64_t)ctx->shape.S + 1)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a histogram of %lld rows for a table of %lld", (long long)n_hist, (long long)ctx->shape.S + 1);
+    CHK(chk_id_share(ctx, id_lo, id_hi, (int64_t)ctx->shape.S));
+    CHK(chk_gathered(ctx, d_all, slot, world, counts));
+    if ((uintptr_t)d_all & 15u) SHP_FAIL(ctx, SHP_ERR_ARG, "unaligned buffer");
+    if (slot == 0) world = 0;
+    CHK(run_dshape_merge(ctx, (const unsigned long long *)d_all, (unsigned long long)slot, (uint32_t)world, counts, d_hist,
+                         (uint32_t)id_lo, (uint32_t)id_hi, counts_out, d_table_out));
+    if (dev_ms_out) *dev_ms_out = ctx->shape.dev_ms;
+    return 0;
 }
 
 API int shp_shape_finish(shp_ctx *ctx, uint32_t *max_seg_id_out, uint32_t *bad_label_out, double *dev_ms_out)

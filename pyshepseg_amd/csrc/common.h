@@ -157,9 +157,12 @@ struct AggState {
 
 // the per-segment shape table between shp_shape_begin and shp_shape_download (segshape.h), in buffers of its own
 // (shape_tab: 88 bytes per id; shape_ctr), so the neighbour table and the group lists stay where they are
+// A rank's rows of a sharded raster (dsegshape.h) go 1 -> 3 -> 2: the straddlers' rows leave the table as records
+// (dshape_rec, 96 bytes each; dshape_ctr, dshape_rcnt) before the ranks' records are folded into it.
 struct ShapeState {
-    int stage = 0;                  // 0 none, 1 accumulating, 2 finished
+    int stage = 0;                  // 0 none, 1 accumulating, 2 finished, 3 classified: the straddlers' records packed
     uint32_t S = 0;
+    unsigned long long nrec = 0;    // records packed by the classification
     unsigned long long row0 = 0, col0 = 0;      // coordinates of the raster's first pixel
     unsigned long long rows_done = 0;           // rows of the blocks so far
     double dev_ms = 0.0;
@@ -179,7 +182,7 @@ struct ShapeState {
     X(dnbr_mrg) X(dnbr_rcnt) X(mrg_ctr) X(mrg_key) X(mrg_size) X(mrg_par) X(mrg_root) X(mrg_idx) X(mrg_recode) \
     X(mrg_rep) X(mrg_gsize) X(mrg_hist) X(mrg_rec) X(mrg_bestd) X(mrg_best) X(dmrg_b64) X(dmrg_pairs) \
     X(dmrg_pcnt) X(agg_recode) X(agg_gsize) X(agg_ctr) X(agg_scan) X(agg_offs) X(agg_mem) X(agg_wcol) X(agg_w) \
-    X(shape_tab) X(shape_ctr)
+    X(shape_tab) X(shape_ctr) X(dshape_rec) X(dshape_ctr) X(dshape_rcnt)
 
 struct shp_ctx {
     int device = 0;

@@ -9,6 +9,9 @@
 //
 // The labels come in row blocks, top to bottom, each with the row above and the row below it where the raster has
 // them: a side belongs to the block of its own pixel and looks at the neighbouring block's row without counting it.
+// The two rows are given by pointers of their own (ShapeGeom::rowAbove, rowBelow; null where the raster ends): next to
+// the block in memory for the one-GPU calls, in the halo gather's buffer for a rank's rows of a sharded raster
+// (dsegshape.h), whose gigabytes of labels are then not copied to stand between their halo rows.
 //  1. k_shape_patch: one workgroup per 32 x 64 patch (k_nbr_patch's patches) plus a one-pixel rim on all four sides,
 //     a wavefront per image row.  Lanes that hold one label side by side form a run and the run's first lane acts for
 //     it (nbr_rows' ballot and count-trailing-zeros idiom): its length is the area, the column sums are closed forms of
@@ -62,7 +65,7 @@ struct ShapeGeom {
     const uint32_t *seg;        // the block's first row
     uint32_t nrows, ncols;      // of the block
     uint32_t pcols;             // patches per patch row
-    int above, below;           // a row of the raster lies before seg / after the block's last row
+    const uint32_t *rowAbove, *rowBelow;    // the raster's row before the block / after its last row; null: the raster ends
     uint32_t S;                 // the table's last row
     unsigned long long R0, C0;  // coordinates of the block's first pixel
 };
@@ -177,13 +180,16 @@ __global__ __launch_bounds__(256) void k_shape_patch(ShapeGeom g, unsigned long 
     }
     if (threadIdx.x == 0) { s_over = 0u; s_nlist = 0u; }
     // the patch and its rim; 0 (no segment) wherever the raster, or what may be read of it, ends
-    const long long ylo = g.above ? -1ll : 0ll, yhi = (long long)g.nrows + (g.below ? 1ll : 0ll);
     uint32_t mx = 0u;
     for (uint32_t i = threadIdx.x; i < (SHAPE_PH + 2u) * SHAPE_TW; i += 256u) {
         const uint32_t r = i / SHAPE_TW, c = i - r * SHAPE_TW;
         const long long gy = (long long)y0 + r - 1, gx = (long long)x0 + c - 1;
         uint32_t v = 0u;
-        if (gy >= ylo && gy < yhi && gx >= 0 && gx < (long long)g.ncols) v = g.seg[gy * (long long)g.ncols + gx];
+        if (gx >= 0 && gx < (long long)g.ncols) {
+            if (gy >= 0 && gy < (long long)g.nrows) v = g.seg[gy * (long long)g.ncols + gx];
+            else if (gy == -1) v = g.rowAbove ? g.rowAbove[gx] : 0u;
+            else if (gy == (long long)g.nrows) v = g.rowBelow ? g.rowBelow[gx] : 0u;
+        }
         tile[r][c] = v;
         mx = max(mx, v);
     }
@@ -314,9 +320,9 @@ static int run_shape_begin(shp_ctx *ctx, uint32_t S, unsigned long long row0, un
     return 0;
 }
 
-// d_seg: the first row handed over, which is the row above the block when has_above
-static int run_shape_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrows, uint32_t ncols, int has_above,
-                                int has_below)
+// d_seg: the block's first row; d_above / d_below: the raster's row before / after the block, null where it ends
+static int run_shape_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrows, uint32_t ncols, const uint32_t *d_above,
+                                const uint32_t *d_below)
 {
     ShapeState &s = ctx->shape;
     hipStream_t st = ctx->stream;
@@ -325,8 +331,7 @@ static int run_shape_accumulate(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nr
         SHP_FAIL(ctx, SHP_ERR_ARG, "coordinates of 2^32 and more");
     const uint32_t pcols = (ncols + SHAPE_PW - 1u) / SHAPE_PW, prows = (nrows + SHAPE_PH - 1u) / SHAPE_PH;
     if ((unsigned long long)pcols * prows > 0x7fffffffull) SHP_FAIL(ctx, SHP_ERR_ARG, "row block too large");
-    ShapeGeom g{d_seg + (has_above ? (size_t)ncols : 0), nrows, ncols, pcols, has_above ? 1 : 0, has_below ? 1 : 0, s.S,
-                s.row0 + s.rows_done, s.col0};
+    ShapeGeom g{d_seg, nrows, ncols, pcols, d_above, d_below, s.S, s.row0 + s.rows_done, s.col0};
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
     hipLaunchKernelGGL(k_shape_patch, dim3(pcols * prows), dim3(256), 0, st, g, (unsigned long long *)ctx->shape_tab.p,
                        bp<uint32_t>(ctx->shape_ctr));

@@ -80,6 +80,7 @@ Each has a module of its own, built on the steps of distdev.py, and asks the eng
       reduceOverNeighboursDistributed and aggregateToGroupsDistributed need only the engine's context ``c``.
   dist_colour: writeColorTableFromRatColumnsDistributed, renderColourTableDistributed -- colourTableOnDevice,
       renderOnDevice.
+  dist_shapes: calcSegmentShapesDistributed -- shapesOnDevice (a merge's recoded rows need only ``c`` and ``nCols``).
 Their names are importable from here as before.
 """
 import collections
@@ -109,6 +110,7 @@ from .dist_neighbours import (deviceNeighbours, findSegmentNeighboursDistributed
 from .dist_colour import (RENDER_BLOCK_PIXELS, RENDER_GROUP_BLOCKS, colourShares, deviceColourTable,  # noqa: F401
                           writeColorTableFromRatColumnsDistributed, _NpyRgbaPatchWriter, deviceRender,
                           renderColourTableDistributed)
+from .dist_shapes import SHAPE_RECORD_BYTES, deviceShapes, calcSegmentShapesDistributed  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------
@@ -987,6 +989,11 @@ class HipEngine(object):
         """findSegmentNeighboursDistributed's path for this rank's output rows (deviceNeighbours)."""
         return deviceNeighbours(self.c, comm, self._heldOut(), None, self.nCols, (self.outLo, self.outHi), maxSegId,
                                 fourConnected=fourConnected, info=info)
+
+    def shapesOnDevice(self, comm, maxSegId, hist, missingStatsValue=-9999, info=None):
+        """calcSegmentShapesDistributed's path for this rank's output rows (deviceShapes)."""
+        return deviceShapes(self.c, comm, self._heldOut(), None, self.nCols, (self.outLo, self.outHi), maxSegId, hist,
+                            missingStatsValue=missingStatsValue, info=info)
 
     def mergeOnDevice(self, comm, share, rule, nRows, outfile=None, info=None):
         """mergeSegmentsDistributed's path with this rank's output rows recoded (deviceMerge)."""

@@ -16,7 +16,9 @@ outerBorder``, and ``nb.columns['borderLength'] / perimeter`` is the segment's r
 ``sums``: the sums of r, c, r^2, c^2 and r c over the id's pixels modulo 2^64 (numpy's wrap).
 
 There is no CPU fallback: without a GPU the call fails as every entry point of this package does.  The multi-rank
-form on row-sharded labels does not exist yet; ``origin`` is the piece it needs.
+form on row-sharded labels is dist_shapes.calcSegmentShapesDistributed (distributed.calcSegmentShapesDistributed): every
+rank accumulates its rows with its first row as the row origin and a halo row on either side, only the segments that
+straddle a cut travel, and the result is this function's on the whole mosaic, bit for bit.
 """
 import ctypes
 import time
@@ -212,6 +214,15 @@ def calcSegmentShapes(segfile, maxSegId=None, origin=(0, 0), chunkPixels=None, m
     finally:
         src.close()
     t1 = time.perf_counter()
+    (columns, sums) = columnsFromTable(table, missing)
+    timings['derive'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    return SegmentShapes(S.value, columns, sums, origin, timings=timings, deviceMs=deviceMs)
+
+
+def columnsFromTable(table, missingStatsValue=-9999):
+    """(columns, sums) of a SegmentShapes from the downloaded device table (maxSegId + 1 rows of _TABLE_WORDS uint64,
+    csrc/segshape.h): what calcSegmentShapes and dist_shapes.deviceShapes both end with"""
     columns = {name: table[:, w].astype(numpy.int64) for (name, w) in _COUNT_WORD.items()}
     lo = numpy.uint64(0xFFFFFFFF)
     sh = numpy.uint64(32)
@@ -221,7 +232,5 @@ def calcSegmentShapes(segfile, maxSegId=None, origin=(0, 0), chunkPixels=None, m
     columns['colMax'] = (table[:, 10] >> sh).astype(numpy.int64)
     sums = {name: numpy.ascontiguousarray(table[:, w]) for (name, w) in _SUM_WORD.items()}
     columns = {name: columns[name] for name in COUNT_COLUMNS}
-    columns.update(shapeColumnsFromSums(columns, sums, missing))
-    timings['derive'] = time.perf_counter() - t1
-    timings['total'] = time.perf_counter() - t0
-    return SegmentShapes(S.value, columns, sums, origin, timings=timings, deviceMs=deviceMs)
+    columns.update(shapeColumnsFromSums(columns, sums, missingStatsValue))
+    return columns, sums
