@@ -715,6 +715,43 @@ int shp_dshape_merge_dev(shp_ctx *ctx, const void *d_all, int64_t slot, int worl
                          int64_t n_hist, int64_t id_lo, int64_t id_hi, int64_t *counts_out, void **d_table_out,
                          double *dev_ms_out);
 
+/* ---- segment outlines as vertex rings, traced from the label raster (outlines.traceSegmentOutlines) ----
+ * Pixel (y, x) covers [y, y + 1] x [x, x + 1]; corners are (row, col) pairs; label 0 is no segment.  A side of a pixel
+ * of id A is an edge of A when the label across it is not A (another id, label 0, outside the raster: the perimeter of
+ * the shape table).  Edges are directed with A's pixel on the right of travel (N eastwards, E southwards, S westwards,
+ * W northwards) and ordered by the key (y, x, side) with N, E, S, W = 0 .. 3.  At its end corner an edge turns right
+ * when the pixel right-ahead is not A, goes straight when it is and the pixel left-ahead is not, turns left when both
+ * are; where only the pixel left-ahead is A (A touches itself diagonally) it turns right for four-connected segments
+ * and left for eight-connected ones.  The cycles of that successor map are the rings.  A ring's vertices are the start
+ * corners of its edges whose predecessor has another side, in cycle order from the one of the smallest key; rings are
+ * ordered by (id, that key); ringArea2 = sum of c_i r_(i+1) - c_(i+1) r_i is positive for an outer ring, negative for a
+ * hole, twice the pixels enclosed.  Integers throughout: the result does not depend on the launches or on the number
+ * of doubling rounds.  The whole raster is in device memory (4-byte aligned, at most 2^32 - 8192 pixels and as many
+ * edges); the work arrays live in buffers of the context's own that are reused between calls, and the neighbour
+ * table, the group lists and the shape table of the context are not touched.
+ *  shp_outline_need: *need_out = the bytes those buffers still have to grow by, *free_out = the device's free bytes.
+ *    edges < 0: for shp_outline_edges_dev on npix pixels (5 bytes a pixel); edges >= 0: for shp_outline_trace on that
+ *    many edges (37 bytes an edge, and room for as many vertices at 16 bytes and a quarter as many rings at 52).
+ *  shp_outline_edges_dev: finds the edges of nrows x ncols labels and gives every one its index.  *edges_out: their
+ *    number; *bad_label_out: 0, or the largest label above max_seg_id.  With such a label, or with more than 2^32 -
+ *    8192 edges, there is nothing to trace and shp_outline_trace fails.  Otherwise d_seg must stay in place until
+ *    shp_outline_trace returns.
+ *  shp_outline_trace: successors, then pointer-doubling rounds launched one by one from the host until a round changes
+ *    no window minimum (at most ceil(log2(edges)) + 2: beyond that the call fails with SHP_ERR_STATE and does not
+ *    loop), then rings, vertices (row0 and col0, both 0 .. 2^32 - 1, added) and areas.  counts_out[3]: rings, vertices,
+ *    rounds run.  steps_ms_out (may be NULL) [4]: device time of shp_outline_edges_dev's kernels, of the successors, of
+ *    the rounds, of the rest.
+ *  shp_outline_download: to host memory, all int64: ring_offsets (max_seg_id + 2: the rings of id i are
+ *    ring_offsets[i] .. ring_offsets[i + 1]), vertex_offsets (rings + 1), vertices (vertices x 2, row then col),
+ *    ring_area2 (rings); the last two may be NULL without rings.
+ * Out of order the calls fail with SHP_ERR_STATE ("shp_outline_edges_dev must come first", "shp_outline_trace must come
+ * first"). */
+int shp_outline_need(shp_ctx *ctx, int64_t npix, int64_t edges, int64_t *need_out, int64_t *free_out);
+int shp_outline_edges_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t max_seg_id,
+                          int four_connected, int64_t *edges_out, uint32_t *bad_label_out);
+int shp_outline_trace(shp_ctx *ctx, int64_t row0, int64_t col0, int64_t *counts_out, double *steps_ms_out);
+int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2);
+
 /* ---- columns reduced over the neighbour table (neighbours.reduceOverNeighbours) ----------------------
  * The finished table stays in the context; these calls reduce per-segment columns over its rows on the device.
  * Row r has entries with neighbour id n and border length w; v is the column widened to float64.  A value is ignored

@@ -26,6 +26,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "dnbrmerge.h"
 #include "segshape.h"
 #include "dsegshape.h"
+#include "outline.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1657,6 +1658,56 @@ API int shp_shape_download(shp_ctx *ctx, uint64_t *rows)
     if (ctx->shape.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no finished shapes: shp_shape_finish must come first");
     if (!rows) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_shape_download(ctx, rows);
+}
+
+// ---- segment outlines as vertex rings (outline.h) ---------------------------------------------------------
+API int shp_outline_need(shp_ctx *ctx, int64_t npix, int64_t edges, int64_t *need_out, int64_t *free_out)
+{
+    CHK(enter(ctx));
+    if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (npix < 0 || npix > (int64_t)OL_MAX_ITEMS || edges > (int64_t)OL_MAX_ITEMS) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_outline_need(ctx, (unsigned long long)npix, (long long)edges, (long long *)need_out, (long long *)free_out);
+}
+
+API int shp_outline_edges_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t max_seg_id,
+                              int four_connected, int64_t *edges_out, uint32_t *bad_label_out)
+{
+    CHK(enter(ctx));
+    if (!edges_out || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols));
+    if (nrows == 0 || ncols == 0) nrows = ncols = 0;
+    if (nrows * ncols > (int64_t)OL_MAX_ITEMS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a raster of %lld pixels: more than %u", (long long)(nrows * ncols), OL_MAX_ITEMS);
+    long long edges = 0;
+    CHK(run_outline_edges(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, (uint32_t)max_seg_id, four_connected ? 0 : 1, &edges,
+                          bad_label_out));
+    *edges_out = (int64_t)edges;
+    return 0;
+}
+
+API int shp_outline_trace(shp_ctx *ctx, int64_t row0, int64_t col0, int64_t *counts_out, double *steps_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->outline.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no edges counted: shp_outline_edges_dev must come first");
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (row0 < 0 || col0 < 0 || row0 > 0xffffffffll || col0 > 0xffffffffll)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "origin (%lld, %lld)", (long long)row0, (long long)col0);
+    CHK(run_outline_trace(ctx, (long long)row0, (long long)col0));
+    counts_out[0] = (int64_t)ctx->outline.rings;
+    counts_out[1] = (int64_t)ctx->outline.verts;
+    counts_out[2] = (int64_t)ctx->outline.rounds;
+    if (steps_ms_out)
+        for (int i = 0; i < 4; i++) steps_ms_out[i] = ctx->outline.ms[i];
+    return 0;
+}
+
+API int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2)
+{
+    CHK(enter(ctx));
+    if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+    if (!ring_offsets || !vertex_offsets || (ctx->outline.rings && (!vertices || !ring_area2))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_outline_download(ctx, ring_offsets, vertex_offsets, vertices, ring_area2);
 }
 
 // ---- columns reduced over the neighbour table (nbrreduce.h) -----------------------------------------------

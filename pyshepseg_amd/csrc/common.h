@@ -168,6 +168,19 @@ struct ShapeState {
     double dev_ms = 0.0;
 };
 
+// the outlines between shp_outline_edges_dev, shp_outline_trace and shp_outline_download (outline.h), in buffers of
+// their own (ol_*), so the neighbour table, the group lists and the shape table stay where they are.  seg: the
+// caller's labels, which must stay in place from the first call to the second.
+struct OutlineState {
+    int stage = 0;                  // 0 none, 1 edges counted, 2 traced
+    const uint32_t *seg = nullptr;
+    uint32_t nrows = 0, ncols = 0, S = 0;
+    int eight = 0;
+    uint32_t edges = 0, rings = 0, verts = 0, rounds = 0;
+    size_t voff64_at = 0, area_at = 0;          // where the int64 vertex offsets and the ring areas lie in ol_ring
+    double ms[4] = {};              // device time: sides and scan, successors, doubling rounds, rings and vertices
+};
+
 // The context's named workspace buffers (grow-only), each named HERE ONLY: the list makes the members of shp_ctx and
 // the entries of shp_ctx::bufs, which is what buf_ensure's regrow log indexes and shp_ctx_destroy frees.
 #define SHP_CTX_BUFS(X) \
@@ -182,7 +195,8 @@ struct ShapeState {
     X(dnbr_mrg) X(dnbr_rcnt) X(mrg_ctr) X(mrg_key) X(mrg_size) X(mrg_par) X(mrg_root) X(mrg_idx) X(mrg_recode) \
     X(mrg_rep) X(mrg_gsize) X(mrg_hist) X(mrg_rec) X(mrg_bestd) X(mrg_best) X(dmrg_b64) X(dmrg_pairs) \
     X(dmrg_pcnt) X(agg_recode) X(agg_gsize) X(agg_ctr) X(agg_scan) X(agg_offs) X(agg_mem) X(agg_wcol) X(agg_w) \
-    X(shape_tab) X(shape_ctr) X(dshape_rec) X(dshape_ctr) X(dshape_rcnt)
+    X(shape_tab) X(shape_ctr) X(dshape_rec) X(dshape_ctr) X(dshape_rcnt) X(ol_ctr) X(ol_mask) X(ol_off) X(ol_epix) \
+    X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff)
 
 struct shp_ctx {
     int device = 0;
@@ -208,6 +222,7 @@ struct shp_ctx {
     }
     SegPointsState pts;
     ShapeState shape;
+    OutlineState outline;
     NbrState nbr;
     MrgState mrg;
     AggState agg;

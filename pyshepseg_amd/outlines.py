@@ -1,0 +1,298 @@
+"""Segment outlines as rings of vertices, traced on the GPU from the label raster.
+
+Object-based work ends in polygons: a layer to lay over the imagery, to edit, to join to the per-segment columns.
+``traceSegmentOutlines`` gives every segment's outline as vertex rings from the label raster alone (csrc/outline.h):
+the boundary sides that shapes.calcSegmentShapes counts as ``perimeter`` are put in order here.
+
+Definitions.  Pixel (y, x) covers [y, y + 1] x [x, x + 1]; corners are integer (row, col) pairs; label 0 is no segment.
+A side of a pixel of id A is an edge of A when the label across it differs from A: another id, label 0 and outside the
+raster all count.  Edges are directed with A's pixel on the right of travel:
+
+    side 0 (N): (y, x) -> (y, x + 1)            side 2 (S): (y + 1, x + 1) -> (y + 1, x)
+    side 1 (E): (y, x + 1) -> (y + 1, x + 1)    side 3 (W): (y + 1, x) -> (y, x)
+
+An edge's key is (y, x, side).  An edge arrives at its end corner; with R = the pixel right-ahead is A and L = the pixel
+left-ahead is A its successor is: not R, the next side of the same pixel (a right turn); R and not L, the same side of
+the pixel right-ahead (straight on); R and L, side - 1 of the pixel left-ahead (a left turn).  At a saddle (not R, L: A
+touches itself diagonally) ``fourConnected=True`` turns right and the two pixels stay apart, ``fourConnected=False``
+turns left and they are joined.  A turn edge is an edge whose predecessor has another side number; its start corner
+is a vertex.  A ring is one cycle of the successor map: the start corners of its turn edges in cycle order, beginning
+with the turn edge of the smallest key.  ``ringArea2`` = sum(c_i r_(i+1) - c_(i+1) r_i) is positive for an outer ring
+(clockwise on screen) and negative for a hole; half its magnitude is the pixels enclosed.  Rings are ordered by (id,
+key of the first turn edge), so every id's first ring is an outer ring.
+
+A ring may touch itself at a saddle corner (with ``fourConnected=False`` an outer ring passes such a corner twice, with
+``fourConnected=True`` a hole may), as the rings of ``gdal_polygonize`` do: the rings are valid boundaries of the pixel
+sets, not always simple polygons in the OGC sense.
+
+The labels are whole in HBM for this function: a host array or ``.npy`` file is uploaded once, resident labels are
+read in place.  The working set is 9 bytes a pixel (labels included), 37 bytes an edge, 16 a vertex and about 52 a
+ring; when the free HBM does not hold it the call raises before anything is allocated.  There is no CPU fallback.
+Streaming in row blocks and a multi-rank form do not exist yet.
+"""
+import ctypes
+import json
+import time
+
+import numpy
+
+from . import _lib
+from . import shapes
+from . import tilingstats
+
+
+class PyShepSegOutlinesError(Exception):
+    pass
+
+
+COLUMNS = ('numParts', 'numHoles', 'numVertices', 'holeArea')
+# pixels, and edges, one call can take (csrc/outline.h: OL_MAX_ITEMS)
+MAX_ITEMS = 2 ** 32 - 8192
+
+
+def _segmentSums(values, offsets):
+    """sum of values[offsets[i]:offsets[i + 1]] for every i, int64"""
+    cs = numpy.zeros(len(values) + 1, dtype=numpy.int64)
+    numpy.cumsum(values, out=cs[1:])
+    return cs[offsets[1:]] - cs[offsets[:-1]]
+
+
+def columnsFromRings(ringOffsets, vertexOffsets, ringArea2):
+    """The int64 columns COLUMNS, one row per id: ``numParts`` the id's outer rings, ``numHoles`` its holes,
+    ``numVertices`` the vertices of all its rings, ``holeArea`` the pixels its holes enclose."""
+    outer = (ringArea2 > 0).astype(numpy.int64)
+    hole = (ringArea2 < 0).astype(numpy.int64)
+    return {'numParts': _segmentSums(outer, ringOffsets),
+            'numHoles': _segmentSums(hole, ringOffsets),
+            'numVertices': _segmentSums(numpy.diff(vertexOffsets), ringOffsets),
+            'holeArea': _segmentSums(numpy.where(ringArea2 < 0, -ringArea2, 0) // 2, ringOffsets)}
+
+
+class SegmentOutlines(object):
+    """The result of traceSegmentOutlines, for the ids 0 .. ``maxSegId`` (S = maxSegId + 1 rows).
+
+    ``ringOffsets``: int64, S + 1 long, the rings of id i are ``ringOffsets[i]:ringOffsets[i + 1]``;
+    ``vertexOffsets``: int64, rings + 1 long; ``vertices``: int64 (n, 2) as (row, col), ``origin`` added;
+    ``ringArea2``: int64, positive for outer rings, negative for holes; ``columns``: the int64 columns COLUMNS as the
+    statistics' column dictionaries hold them; ``rounds``: pointer-doubling rounds run; ``edges``: boundary sides;
+    ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels, ``deviceStepsMs`` its split."""
+    def __init__(self, maxSegId, ringOffsets, vertexOffsets, vertices, ringArea2, origin=(0, 0), fourConnected=True,
+                 rounds=0, edges=None, timings=None, deviceMs=None, deviceStepsMs=None):
+        self.maxSegId = maxSegId
+        self.ringOffsets = ringOffsets
+        self.vertexOffsets = vertexOffsets
+        self.vertices = vertices
+        self.ringArea2 = ringArea2
+        self.origin = origin
+        self.fourConnected = fourConnected
+        self.rounds = rounds
+        self.edges = edges
+        self.timings = timings if timings is not None else {}
+        self.deviceMs = deviceMs
+        self.deviceStepsMs = deviceStepsMs if deviceStepsMs is not None else {}
+        self.columns = columnsFromRings(ringOffsets, vertexOffsets, ringArea2)
+
+    def _ringRange(self, segId):
+        if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
+            raise PyShepSegOutlinesError("segment id must be an integer 0 .. {} (got {!r})".format(self.maxSegId, segId))
+        return range(int(self.ringOffsets[segId]), int(self.ringOffsets[segId + 1]))
+
+    def ring(self, r):
+        return self.vertices[int(self.vertexOffsets[r]):int(self.vertexOffsets[r + 1])]
+
+    def ringsOf(self, segId):
+        """the id's rings, outer rings and holes in ring order: a list of (k, 2) arrays (views of ``vertices``)"""
+        return [self.ring(r) for r in self._ringRange(segId)]
+
+    def polygonsOf(self, segId):
+        """The id's polygons: a list of [shell, hole, ...], the shells in ring order and every hole with its shell.
+
+        An id with one outer ring owns all its holes.  With several, a hole goes to the enclosing shell of the
+        smallest area, decided on the host: the centre of the pixel of the hole's first edge (the pixel right-ahead of
+        vertex 0 heading to vertex 1, a pixel of the id) lies strictly inside every shell that encloses the hole."""
+        rings = list(self._ringRange(segId))
+        shells = [r for r in rings if self.ringArea2[r] > 0]
+        polys = {r: [self.ring(r)] for r in shells}
+        for r in rings:
+            if self.ringArea2[r] > 0:
+                continue
+            if len(shells) == 1:
+                polys[shells[0]].append(self.ring(r))
+                continue
+            v = self.ring(r)
+            d = numpy.sign(v[1] - v[0])                 # direction of travel (drow, dcol); the pixel lies to its right
+            centre = v[0] + 0.5 * d + 0.5 * numpy.array([d[1], -d[0]])
+            inside = [s for s in shells if _contains(self.ring(s), centre)]
+            if not inside:
+                raise PyShepSegOutlinesError("a hole of segment {} lies in none of its outer rings".format(segId))
+            polys[min(inside, key=lambda s: self.ringArea2[s])].append(self.ring(r))
+        return [polys[r] for r in shells]
+
+
+def _contains(ring, point):
+    """point (row, col), with half-integer coordinates, strictly inside the rectilinear ring: a ray towards
+    increasing col crosses an odd number of its vertical segments"""
+    nxt = numpy.roll(ring, -1, axis=0)
+    vertical = ring[:, 1] == nxt[:, 1]
+    lo = numpy.minimum(ring[:, 0], nxt[:, 0])
+    hi = numpy.maximum(ring[:, 0], nxt[:, 0])
+    crossed = vertical & (ring[:, 1] > point[1]) & (lo < point[0]) & (point[0] < hi)
+    return bool(numpy.count_nonzero(crossed) & 1)
+
+
+def _xy(ring, transform):
+    """a ring's (x, y) pairs, closed: without a transform x = col and y = row, with a GDAL six-tuple applied to (col,
+    row)"""
+    col = ring[:, 1].astype(numpy.float64)
+    row = ring[:, 0].astype(numpy.float64)
+    if transform is None:
+        (x, y) = (col, row)
+    else:
+        t = [float(v) for v in transform]
+        if len(t) != 6:
+            raise PyShepSegOutlinesError("transform must be a GDAL geotransform of six numbers")
+        x = t[0] + col * t[1] + row * t[2]
+        y = t[3] + col * t[4] + row * t[5]
+    pts = [[float(a), float(b)] for (a, b) in zip(x.tolist(), y.tolist())]
+    return pts + pts[:1]
+
+
+def _num(v):
+    return repr(int(v)) if float(v).is_integer() else repr(float(v))
+
+
+def toWKT(o, segId, transform=None):
+    """The id's outline as a WKT MULTIPOLYGON (``MULTIPOLYGON EMPTY`` for an id without pixels), rings closed.
+    ``transform`` is a GDAL six-tuple applied to (col, row); without one x = col and y = row.
+
+    Plain Python, for looking at results and exporting chosen ids; not meant for millions of features."""
+    polys = o.polygonsOf(segId)
+    if not polys:
+        return 'MULTIPOLYGON EMPTY'
+    return 'MULTIPOLYGON (' + ', '.join(
+        '(' + ', '.join('(' + ', '.join(_num(x) + ' ' + _num(y) for (x, y) in _xy(ring, transform)) + ')' for ring in poly) + ')'
+        for poly in polys) + ')'
+
+
+def writeGeoJSON(o, path, ids=None, transform=None, columns=None):
+    """Write a GeoJSON FeatureCollection of MultiPolygons to ``path``: one feature per id of ``ids`` (default: every
+    id with a ring), with the property ``segId`` and one property per entry of ``columns`` (a dictionary of
+    per-segment columns, maxSegId + 1 rows each).  ``transform`` as in toWKT.  Returns the number of features.
+
+    Plain Python, for looking at results and exporting chosen ids; not meant for millions of features."""
+    if ids is None:
+        ids = numpy.flatnonzero(numpy.diff(o.ringOffsets) > 0)
+    columns = dict(columns) if columns is not None else {}
+    for (name, col) in columns.items():
+        if len(col) != o.maxSegId + 1:
+            raise PyShepSegOutlinesError("column {!r} has {} rows, not maxSegId + 1 = {}".format(name, len(col), o.maxSegId + 1))
+    features = []
+    for i in ids:
+        i = int(i)
+        props = {'segId': i}
+        for (name, col) in columns.items():
+            v = col[i]
+            props[name] = v.item() if isinstance(v, numpy.generic) else v
+        coords = [[_xy(ring, transform) for ring in poly] for poly in o.polygonsOf(i)]
+        features.append({'type': 'Feature', 'properties': props, 'geometry': {'type': 'MultiPolygon', 'coordinates': coords}})
+    with open(path, 'w') as f:
+        json.dump({'type': 'FeatureCollection', 'features': features}, f)
+    return len(features)
+
+
+def _checkArgs(segfile, maxSegId, origin):
+    """(host labels or None, device labels or None, rows, columns, maxSegId or None, (row0, col0)): everything that
+    can be refused before the GPU is touched; the argument checks are those of shapes.calcSegmentShapes"""
+    try:
+        (seg, devSeg, nrows, ncols, maxSegId, origin, _chunk, _missing) = shapes._checkArgs(segfile, maxSegId, origin, None, -9999)
+    except shapes.PyShepSegShapesError as e:
+        raise PyShepSegOutlinesError(str(e))
+    if nrows * ncols > MAX_ITEMS:
+        raise PyShepSegOutlinesError("a raster of {} pixels: more than the {} one call can take".format(nrows * ncols, MAX_ITEMS))
+    return (seg, devSeg, nrows, ncols, maxSegId, origin)
+
+
+def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0)):
+    """
+    The outline of every segment of a label raster as vertex rings, on the GPU: a SegmentOutlines.
+
+    ``segfile`` is what shapes.calcSegmentShapes takes -- a 2-D uint32 array, a ``.npy`` path, a
+    TiledSegmentationResult (its ``segimg``), a result whose labels are in HBM (``outDev``, read in place) or a
+    MergedSegments (its ``outDev`` if it has one, else its ``segimg``).  A host raster is uploaded once, whole.
+
+    ``fourConnected`` decides the saddle corners (module docstring).  ``maxSegId`` is the last row of every column and
+    of ``ringOffsets``; None takes the ``maxSegId`` of a result object that carries one, otherwise the largest label,
+    found by a reduction on the GPU.  A label above a given ``maxSegId`` raises PyShepSegOutlinesError with the largest
+    such label.  ``origin`` = (row0, col0), non-negative integers, is added to the vertex coordinates and changes
+    nothing else.
+
+    The raster has at most 2^32 - 8192 pixels and as many edges, and the working set (module docstring) must fit the
+    free HBM: otherwise PyShepSegOutlinesError names the bytes needed, before anything is allocated.
+    """
+    (seg, devSeg, nrows, ncols, maxSegId, origin) = _checkArgs(segfile, maxSegId, origin)
+    t0 = time.perf_counter()
+    c = _lib.ctx()
+    L = c._L
+    npix = nrows * ncols
+    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
+    timings = {}
+    (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
+    ms = ctypes.c_double(0)
+    deviceMs = 0.0
+    try:
+        c.check(L.shp_outline_need(c.handle, npix, -1, ctypes.byref(need), ctypes.byref(free)))
+        want = need.value + (4 * npix if devSeg is None else 0)
+        if want > free.value:
+            raise PyShepSegOutlinesError("the labels and per-pixel arrays of {} x {} pixels need {} bytes of device memory, {} are "
+                                         "free".format(nrows, ncols, want, free.value))
+        dseg = src.chunk(0, nrows)[0] if npix else None
+        timings['upload'] = time.perf_counter() - t0
+        if maxSegId is None:
+            t1 = time.perf_counter()
+            top = ctypes.c_uint32(0)
+            if npix:
+                c.check(L.shp_shape_label_max_dev(c.handle, dseg, npix, ctypes.byref(top), ctypes.byref(ms)))
+                deviceMs += ms.value
+            if top.value >= 0xFFFFFFFE:
+                raise PyShepSegOutlinesError("label {} is too large".format(top.value))
+            maxSegId = top.value
+            timings['labelMax'] = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        (edges, bad) = (ctypes.c_int64(0), ctypes.c_uint32(0))
+        c.check(L.shp_outline_edges_dev(c.handle, dseg, nrows, ncols, maxSegId, int(bool(fourConnected)), ctypes.byref(edges),
+                                        ctypes.byref(bad)))
+        if bad.value:
+            raise PyShepSegOutlinesError("segment id {} is above maxSegId {}".format(bad.value, maxSegId))
+        if edges.value > MAX_ITEMS:
+            raise PyShepSegOutlinesError("{} edges: more than the {} one call can take".format(edges.value, MAX_ITEMS))
+        c.check(L.shp_outline_need(c.handle, npix, edges.value, ctypes.byref(need), ctypes.byref(free)))
+        if need.value > free.value:
+            raise PyShepSegOutlinesError("the per-edge arrays of {} edges need {} bytes of device memory, {} are "
+                                         "free".format(edges.value, need.value, free.value))
+        timings['edges'] = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        counts = numpy.zeros(3, dtype=numpy.int64)
+        steps = numpy.zeros(4, dtype=numpy.float64)
+        c.check(L.shp_outline_trace(c.handle, origin[0], origin[1], _lib.ptr(counts), _lib.ptr(steps)))
+        timings['trace'] = time.perf_counter() - t1
+        t1 = time.perf_counter()
+        (nrings, nverts, rounds) = (int(v) for v in counts)
+        ringOffsets = numpy.empty(maxSegId + 2, dtype=numpy.int64)
+        vertexOffsets = numpy.empty(nrings + 1, dtype=numpy.int64)
+        vertices = numpy.empty((nverts, 2), dtype=numpy.int64)
+        ringArea2 = numpy.empty(nrings, dtype=numpy.int64)
+        c.check(L.shp_outline_download(c.handle, _lib.ptr(ringOffsets), _lib.ptr(vertexOffsets), _lib.ptr(vertices),
+                                       _lib.ptr(ringArea2)))
+        timings['download'] = time.perf_counter() - t1
+    finally:
+        src.close()
+    deviceStepsMs = dict(zip(('edges', 'successors', 'rounds', 'rings'), steps.tolist()))
+    deviceMs += float(steps.sum())
+    t1 = time.perf_counter()
+    out = SegmentOutlines(maxSegId, ringOffsets, vertexOffsets, vertices, ringArea2, origin=origin,
+                          fourConnected=bool(fourConnected), rounds=rounds, edges=int(edges.value), deviceMs=deviceMs,
+                          deviceStepsMs=deviceStepsMs)
+    timings['columns'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    out.timings = timings
+    return out
