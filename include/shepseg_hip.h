@@ -412,7 +412,8 @@ int shp_dstats_merge_bands_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, const v
  * inverted -- the row gather that copySubsettedSegmentsToNew (:232-266) applies to every RAT
  * column and the optional origSegIdColName column (:207-226); hist_out[new id] = pixel count
  * (histogramDict).  orig_out / hist_out hold cap rows (n + 1 are written); *n_new_out = n.
- * Error "Requested subset is not within input image" as subset.py:86-88. */
+ * Error "Requested subset is not within input image" as subset.py:86-88; max_seg_id = 0xffffffff is
+ * refused ("max_seg_id too large"): max_seg_id + 1 ids are counted in 32 bits. */
 int shp_subset_recode(shp_ctx *ctx, const uint32_t *seg, int64_t img_rows, int64_t img_cols,
                       int64_t tlx, int64_t tly, int64_t xs, int64_t ys, const uint8_t *mask,
                       int tile_size, uint32_t max_seg_id, uint32_t *out, uint32_t *orig_out,

@@ -1308,7 +1308,7 @@ API int shp_dstats_merge_bands_dev(shp_ctx *ctx, const uint32_t *d_pair_seg, con
 
 // ---- subset ---------------------------------------------------------------------
 static int subset_check(shp_ctx *ctx, int64_t img_rows, int64_t img_cols, int64_t tlx, int64_t tly,
-                        int64_t xs, int64_t ys, int tile_size)
+                        int64_t xs, int64_t ys, int tile_size, uint32_t max_seg_id)
 {
     if (img_rows < 0 || img_cols < 0 || tlx < 0 || tly < 0 || xs < 0 || ys < 0 || tile_size < 1)
         SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
@@ -1316,6 +1316,8 @@ static int subset_check(shp_ctx *ctx, int64_t img_rows, int64_t img_cols, int64_
         SHP_FAIL(ctx, SHP_ERR_ARG, "Requested subset is not within input image");      // subset.py:86-88
     if ((uint64_t)xs * (uint64_t)ys >= 0xffffffffull || img_cols >= 0xffffffffll)
         SHP_FAIL(ctx, SHP_ERR_ARG, "subset too large");
+    // max_seg_id + 1 ids are scanned as a 32-bit count
+    if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
     return 0;
 }
 
@@ -1327,7 +1329,7 @@ API int shp_subset_recode_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t img_r
     CHK(enter(ctx));
     if (!d_seg || !d_out || !orig_out || !hist_out || !n_new_out || cap < 1)
         SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    CHK(subset_check(ctx, img_rows, img_cols, tlx, tly, xs, ys, tile_size));
+    CHK(subset_check(ctx, img_rows, img_cols, tlx, tly, xs, ys, tile_size, max_seg_id));
     return run_subset_recode(ctx, d_seg, (uint32_t)img_cols, (uint32_t)tlx, (uint32_t)tly, (uint32_t)xs,
                              (uint32_t)ys, d_mask, (uint32_t)tile_size, max_seg_id, d_out, orig_out,
                              hist_out, cap, n_new_out);
@@ -1341,7 +1343,7 @@ API int shp_subset_recode(shp_ctx *ctx, const uint32_t *seg, int64_t img_rows, i
     CHK(enter(ctx));
     if (!seg || !out || !orig_out || !hist_out || !n_new_out || cap < 1)
         SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    CHK(subset_check(ctx, img_rows, img_cols, tlx, tly, xs, ys, tile_size));
+    CHK(subset_check(ctx, img_rows, img_cols, tlx, tly, xs, ys, tile_size, max_seg_id));
     const size_t n = (size_t)xs * (size_t)ys;
     *n_new_out = 0;
     if (n == 0) return 0;

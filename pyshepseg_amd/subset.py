@@ -66,6 +66,7 @@ def subsetImage(inname, outname, tlx, tly, newXsize, newYsize, outformat=None, c
     if valid.size == 0:
         raise PyShepSegSubsetError('No valid data found in subset')
     maxId = int(valid.max())
+    checkMaxId(maxId)
     cap = min(maxId, win.size) + 1
     out = numpy.empty((newYsize, newXsize), dtype=shepseg.SegIdType)
     orig = numpy.zeros(cap, dtype=numpy.uint32)
@@ -103,6 +104,12 @@ def loadMask(maskImage, newXsize, newYsize):
     if mask.shape != (newYsize, newXsize):
         raise PyShepSegSubsetError('mask should match requested subset size if supplied')
     return numpy.ascontiguousarray(mask != 0, dtype=numpy.uint8)
+
+
+def checkMaxId(maxId):
+    "the recode counts the ids 0..maxId in 32 bits, so the largest label a window may hold is 2^32 - 2"
+    if maxId >= 0xffffffff:
+        raise PyShepSegSubsetError('segment id %d in the subset is too large (at most %d)' % (maxId, 0xfffffffe))
 
 
 def checkOutname(outname):

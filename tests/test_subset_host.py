@@ -16,3 +16,32 @@ def test_subset_errors():
     seg[:] = 7
     with pytest.raises(subset.PyShepSegSubsetError, match='No valid data'):
         subset.subsetImage(seg, None, 0, 0, 20, 10, maskImage=np.zeros((10, 20), np.uint8))
+
+
+def test_subset_refuses_the_largest_label(monkeypatch):
+    """the recode counts the ids 0..max in 32 bits: a window holding the label 0xffffffff is refused by the wrapper
+    before it asks for a context; the same label outside the window or under the mask does not count"""
+    from pyshepseg_amd import subset, _lib
+
+    class Reached(Exception):
+        pass
+
+    def ctx():
+        raise Reached()
+    monkeypatch.setattr(_lib, 'ctx', ctx)
+    seg = np.full((4, 6), 3, dtype=np.uint32)
+    seg[2, 4] = 0xffffffff
+    mask = np.ones((3, 3), np.uint8)
+    mask[1, 2] = 0
+    with pytest.raises(subset.PyShepSegSubsetError, match='4294967295 in the subset is too large'):
+        subset.subsetImage(seg, None, 2, 1, 3, 3)
+    with pytest.raises(subset.PyShepSegSubsetError, match='too large'):
+        subset.subsetImage(seg, None, 0, 0, 6, 4, maskImage=np.ones((4, 6), np.uint8))
+    subset.checkMaxId(0xfffffffe)
+    with pytest.raises(subset.PyShepSegSubsetError, match='too large'):
+        subset.checkMaxId(0xffffffff)
+    # where the label does not count, the wrapper goes on to the device
+    with pytest.raises(Reached):
+        subset.subsetImage(seg, None, 0, 0, 4, 4)
+    with pytest.raises(Reached):
+        subset.subsetImage(seg, None, 2, 1, 3, 3, maskImage=mask)
