@@ -191,12 +191,22 @@ static float ev_ms(shp_ctx *ctx, int a, int b)
 // ---- k-means --------------------------------------------------------------------------------
 API int shp_last_fit_path(const shp_ctx *ctx) { return ctx ? ctx->fit_path : -1; }
 
+// what the four shp_kmeans_fit* entry points check alike (pixels: the sample has a pixel type `dtype`, else it is
+// float64; init may be NULL in the planar forms only)
+static int check_fit_args(shp_ctx *ctx, const void *xsample, bool pixels, int dtype, const double *init_centres,
+                          bool need_init, const double *centres_out)
+{
+    if (!xsample || (need_init && !init_centres) || !centres_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (pixels && dtype_size(dtype) == 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad pixel type %d", dtype);
+    return 0;
+}
+
 API int shp_kmeans_fit(shp_ctx *ctx, const double *xsample, int64_t nrows, int nbands, int k,
                        const double *init_centres, int max_iter, double tol_rel,
                        double *centres_out, int32_t *labels_out, int *n_iter_out)
 {
     CHK(enter(ctx));
-    if (!xsample || !init_centres || !centres_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(check_fit_args(ctx, xsample, false, FIT_DT_F64, init_centres, true, centres_out));
     return run_kmeans_fit(ctx, xsample, FIT_DT_F64, nrows, nbands, k, init_centres, max_iter, tol_rel,
                           centres_out, labels_out, n_iter_out);
 }
@@ -207,8 +217,7 @@ API int shp_kmeans_fit_typed(shp_ctx *ctx, const void *xsample, int dtype, int64
                              double *centres_out, int32_t *labels_out, int *n_iter_out)
 {
     CHK(enter(ctx));
-    if (!xsample || !init_centres || !centres_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (dtype_size(dtype) == 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad pixel type %d", dtype);
+    CHK(check_fit_args(ctx, xsample, true, dtype, init_centres, true, centres_out));
     return run_kmeans_fit(ctx, xsample, dtype, nrows, nbands, k, init_centres, max_iter, tol_rel,
                           centres_out, labels_out, n_iter_out);
 }
@@ -217,30 +226,16 @@ API int shp_kmeans_fit_typed(shp_ctx *ctx, const void *xsample, int dtype, int64
 // planes of npix pixels.  Rows with the null value in any band are dropped, the initial centres are
 // diagonalClusterCentres of what is left (init_centres == NULL) or given; *nrows_out = rows fitted
 // (labels_out, optional, holds that many).  Same arithmetic as shp_kmeans_fit_typed on the
-// transposed rows, prepared by one host thread per band.
-API int shp_kmeans_fit_planar(shp_ctx *ctx, const void *planes, int dtype, int64_t npix, int nbands,
-                              int has_null, int64_t null_val, int k, const double *init_centres,
-                              int max_iter, double tol_rel, double *centres_out, int32_t *labels_out,
-                              int *n_iter_out, int64_t *nrows_out)
-{
-    CHK(enter(ctx));
-    if (!planes || !centres_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (dtype_size(dtype) == 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad pixel type %d", dtype);
-    if (nrows_out) *nrows_out = 0;
-    return run_kmeans_fit(ctx, planes, dtype, npix, nbands, k, init_centres, max_iter, tol_rel, centres_out,
-                          labels_out, n_iter_out, true, has_null, (long long)null_val, nrows_out);
-}
-
-// the same with the E-step sharded by sample rows over the ranks of a communicator: every rank passes the SAME
-// sample and gets the same model (fit_elkan.h: FitShard); cm == NULL: shp_kmeans_fit_planar
+// transposed rows, prepared by one host thread per band (kmeans.h: fit_prepare).
+// cm with more than one rank: the E-step sharded by sample rows over the ranks of the communicator: every rank
+// passes the SAME sample and gets the same model (fit_elkan.h: FitShard)
 API int shp_kmeans_fit_planar_dist(shp_ctx *ctx, shp_comm *cm, const void *planes, int dtype, int64_t npix, int nbands,
                                    int has_null, int64_t null_val, int k, const double *init_centres,
                                    int max_iter, double tol_rel, double *centres_out, int32_t *labels_out,
                                    int *n_iter_out, int64_t *nrows_out)
 {
     CHK(enter(ctx));
-    if (!planes || !centres_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (dtype_size(dtype) == 0) SHP_FAIL(ctx, SHP_ERR_ARG, "bad pixel type %d", dtype);
+    CHK(check_fit_args(ctx, planes, true, dtype, init_centres, false, centres_out));
     if (nrows_out) *nrows_out = 0;
     FitShard sh;
     if (cm && cm->world > 1) {
@@ -249,6 +244,15 @@ API int shp_kmeans_fit_planar_dist(shp_ctx *ctx, shp_comm *cm, const void *plane
     }
     return run_kmeans_fit(ctx, planes, dtype, npix, nbands, k, init_centres, max_iter, tol_rel, centres_out,
                           labels_out, n_iter_out, true, has_null, (long long)null_val, nrows_out, sh);
+}
+
+API int shp_kmeans_fit_planar(shp_ctx *ctx, const void *planes, int dtype, int64_t npix, int nbands,
+                              int has_null, int64_t null_val, int k, const double *init_centres,
+                              int max_iter, double tol_rel, double *centres_out, int32_t *labels_out,
+                              int *n_iter_out, int64_t *nrows_out)
+{
+    return shp_kmeans_fit_planar_dist(ctx, nullptr, planes, dtype, npix, nbands, has_null, null_val, k, init_centres,
+                                      max_iter, tol_rel, centres_out, labels_out, n_iter_out, nrows_out);
 }
 
 API int shp_kmeans_assign(shp_ctx *ctx, const void *img, int dtype, int nbands, int nrows, int ncols,

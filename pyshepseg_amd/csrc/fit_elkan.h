@@ -26,9 +26,16 @@
 //    orc_kmeans_fit_elkan, i.e. to the reference with OMP_NUM_THREADS=1 (with more threads sklearn
 //    adds per-thread partial sums in the order the threads finish: not reproducible run to run).
 // Shared by both: empty-cluster relocation as numpy evaluates it (pairwise row sums, np.argpartition's
-// introselect), center_shift_tot as numpy's pairwise sum.
+// introselect), center_shift_tot as numpy's pairwise sum; the M-step's enqueue (fit_enqueue_mstep); the
+// environment's knobs, read once per call (fit_knobs); every buffer's carving (fit_layout.h).
+// The host side of this path, top down: run_fit_elkan (the batch loop and the three stop codes) over
+// elk_plan (the form: lazy or table, sharded or not, fused or not, grids, LDS) and ElkFit's steps (carve,
+// upload, enqueue_init, enqueue_iteration = enqueue_estep over for_each_shard + the M-step, trace,
+// finish_empty_cluster).
 #pragma once
 #include "comm.h"        // the row-sharded E-step all-gathers its labels with RCCL (FitShard)
+#include "fit_layout.h"  // every buffer of the fit carved in one place
+static_assert(FIT_PIN_STAGE_BYTES == PIN_MIRROR * 4u, "fit_layout.h: FIT_PIN_STAGE_BYTES");
 
 #define FIT_TIE_EPS 1e-12
 
@@ -625,6 +632,7 @@ struct ElkCtl {
     uint32_t nd[2];     // labels changed by the E-step of iteration it: nd[it & 1]
     double shift_tot;
 };
+static_assert(sizeof(ElkCtl) == ELK_CTL_BYTES, "fit_layout.h: ELK_CTL_BYTES");
 
 struct ElkEpilogue {
     ElkCtl *ctl;                    // nullptr: no epilogue
@@ -879,6 +887,96 @@ __global__ __launch_bounds__(1024) void k_elk_update(double *__restrict__ S, con
 #define ELK_BATCH 8                 // iterations enqueued between two host synchronisations
 #endif
 
+// The environment's knobs of one fit call, read once at its top (the tests set and unset them between calls
+// of one process, so nothing here is cached) and passed down.
+enum { FIT_ALGO_AUTO = 0, FIT_ALGO_LLOYD = 1, FIT_ALGO_ELKAN = 2 };
+struct FitKnobs {
+    int algo;                   // SHEPSEG_FIT_ALGO: auto | lloyd | elkan (kmeans.h: run_kmeans_fit)
+    bool elk_table;             // SHEPSEG_ELK_TABLE=1: the exact table of lower bounds also where k <= 64
+    bool elk_unfused;           // SHEPSEG_ELK_UNFUSED=1: the iteration's tail as a kernel of its own
+    bool check_digits;          // SHEPSEG_FIT_CHECK_DIGITS=1: elk_check_digits every iteration, one per batch
+    bool trace, timing;         // SHEPSEG_FIT_TRACE, SHEPSEG_FIT_TIMING: a line per batch on stderr
+    int shards, shard_only;     // SHEPSEG_FIT_SHARDS / _SHARD_ONLY: the one-process rehearsal (elk_shard)
+};
+static FitKnobs fit_knobs()
+{
+    auto on = [](const char *v) { return v && atoi(v) != 0; };
+    const char *algo = getenv("SHEPSEG_FIT_ALGO"), *sh = getenv("SHEPSEG_FIT_SHARDS"), *only = getenv("SHEPSEG_FIT_SHARD_ONLY");
+    FitKnobs kb;
+    kb.algo = algo && !strcmp(algo, "lloyd") ? FIT_ALGO_LLOYD : algo && !strcmp(algo, "elkan") ? FIT_ALGO_ELKAN : FIT_ALGO_AUTO;
+    kb.elk_table = on(getenv("SHEPSEG_ELK_TABLE"));
+    kb.elk_unfused = on(getenv("SHEPSEG_ELK_UNFUSED"));
+    kb.check_digits = on(getenv("SHEPSEG_FIT_CHECK_DIGITS"));
+    kb.trace = getenv("SHEPSEG_FIT_TRACE") != nullptr;
+    kb.timing = getenv("SHEPSEG_FIT_TIMING") != nullptr;
+    kb.shards = sh ? atoi(sh) : 0;
+    kb.shard_only = only ? atoi(only) : -1;
+    return kb;
+}
+
+// The M-step's enqueue for one iteration, shared by the Lloyd loop (kmeans.h) and the Elkan loop: the row
+// numbers sorted stably by label, the clusters' ranges of that list, the row-order sums per (cluster, band).
+// digits: with one radix pass (k <= 256) the ranges are read off the sort's own scanned histogram and no
+// search kernel runs (the caller's tail then zeroes the next E-step's counter); else k_elk_offsets finds them
+// and zeroes *zero.  check_stop_seen: SHEPSEG_FIT_CHECK_DIGITS (elk_check_digits), with the digits only.
+struct FitMstep {
+    const double *X;            // n rows of nb
+    uint32_t n;
+    int nb, k;
+    const int32_t *lab;
+    uint32_t *off, *zero;       // k + 1 list offsets; the counter k_elk_offsets zeroes
+    const uint32_t *stop;
+    double *S, *cnt;            // k x nb sums, k counts as float64
+};
+static int elk_check_digits(shp_ctx *ctx, const FitDigits &dg, const FitMstep &m, uint32_t stop_seen);
+static int fit_enqueue_mstep(shp_ctx *ctx, const FitMstep &m, bool digits, const ElkEpilogue &ep,
+                             const uint32_t *check_stop_seen)
+{
+    hipStream_t st = ctx->stream;
+    uint32_t *ks = nullptr, *rows = nullptr;
+    SortDigits sd;
+    CHK(sort_pairs(ctx, (const uint32_t *)m.lab, nullptr, m.n, bits_for((uint32_t)(m.k - 1)), &ks, &rows, false, &sd));
+    FitDigits dg{nullptr, nullptr, 0u, m.n};
+    if (digits && sd.passes == 1) {
+        dg.hscan = sd.hscan; dg.boff = sd.boff; dg.nblk = sd.nblk;
+        if (check_stop_seen) CHK(elk_check_digits(ctx, dg, m, *check_stop_seen));
+    } else {
+        hipLaunchKernelGGL(k_elk_offsets, dim3(grid_for((size_t)m.k + 1, 256)), dim3(256), 0, st, ks, m.n, m.k, m.off,
+                           m.zero, m.stop); KCHK(ctx);
+    }
+    if (m.nb <= 64)
+        hipLaunchKernelGGL(k_fit_sum_lists_staged, dim3(m.k), dim3(FIT_SUM_THREADS), 0, st, m.X, m.nb, rows, m.off, m.S,
+                           m.cnt, m.stop, dg, ep);
+    else
+        hipLaunchKernelGGL(k_fit_sum_lists, dim3(m.k, (m.nb + 63) / 64), dim3(64), 0, st, m.X, m.nb, rows, m.off, m.S,
+                           m.cnt, m.stop, dg);
+    KCHK(ctx);
+    return 0;
+}
+
+// SHEPSEG_FIT_CHECK_DIGITS: the ranges read off the sort's scanned histogram against a count of the labels
+// themselves (stop_seen: the batch before raised ctl->stop, so this iteration did not really run)
+static int elk_check_digits(shp_ctx *ctx, const FitDigits &dg, const FitMstep &m, uint32_t stop_seen)
+{
+    hipStream_t st = ctx->stream;
+    const int k = m.k;
+    std::vector<uint32_t> got((size_t)k + 1);
+    std::vector<int32_t> hl(m.n);
+    hipLaunchKernelGGL(k_fit_digit_starts, dim3(1), dim3(256), 0, st, dg, k, m.off); KCHK(ctx);
+    HIPCHK(ctx, hipMemcpyAsync(got.data(), m.off, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hl.data(), m.lab, (size_t)m.n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (stop_seen != 0u) return 0;
+    std::vector<uint32_t> want((size_t)k + 1, 0u);
+    for (uint32_t i = 0; i < m.n; i++) if ((uint32_t)hl[i] < (uint32_t)k) want[(size_t)hl[i] + 1]++;
+    for (int j = 0; j < k; j++) want[(size_t)j + 1] += want[j];
+    for (int j = 0; j <= k; j++)
+        if (got[j] != want[j])
+            SHP_FAIL(ctx, SHP_ERR_STATE, "fit: cluster %d's row list starts at %u in the sort's histogram, %u by count "
+                     "(the layout sort_digit_start assumes has changed)", j, got[j], want[j]);
+    return 0;
+}
+
 // The E-step sharded by sample rows over the ranks of a communicator (the one part of the fit that
 // shards; sklearn's fit itself is one process, shepseg.py:305-312).  Rank r runs init / filter / visit on rows
 // [r ns, (r + 1) ns) -- its own bounds, stamps, upper bounds; nothing of them ever leaves the rank -- then the
@@ -886,6 +984,9 @@ __global__ __launch_bounds__(1024) void k_elk_update(double *__restrict__ S, con
 // trip), and every rank runs the M-step on the full label array: the same sort, the same row-order sums, the
 // same tail on the same bits, so the centres agree without a broadcast.  The count of changed labels comes
 // from comparing the gathered labels with the previous iteration's, on every rank alike.
+//   The gather writes world * ns words, ns = ceil(n / world): up to world - 1 words past the n labels.  The
+// label buffer must have room for them (fit_layout.h: FIT_LAB_GAP, FitLayout::lab_words); run_fit_elkan is told
+// the room there is and refuses a sharding that does not fit, before anything is enqueued.
 //   nc == nullptr with world > 1: ONE process plays all the ranks in turn (tests of the shard arithmetic on a
 // one-GPU box: SHEPSEG_FIT_SHARDS); only == r: it plays rank r alone (the timing of one rank's share:
 // SHEPSEG_FIT_SHARD_ONLY; the other shards' labels go stale, the result is not a fit).
@@ -894,6 +995,33 @@ struct FitShard {
     void *nc = nullptr;             // ncclComm_t
     int only = -1;
 };
+// The sharding a fit really runs with: the rehearsal's where the caller brought none; none where the form has no
+// sharded E-step (the exact-table form: every rank runs it whole), no previous-label buffer, or too many ranks
+static FitShard elk_shard(FitShard shard, const FitKnobs &knobs, uint32_t n, bool lazy, bool have_prev)
+{
+    if (shard.world == 1 && knobs.shards > 1) {
+        shard.world = knobs.shards;
+        shard.only = knobs.shard_only;
+        if (shard.world > FIT_SHARD_MAX || (size_t)shard.world > (size_t)n) shard = FitShard();
+    }
+    if (shard.world > 1 && (!lazy || !have_prev || shard.world > FIT_SHARD_MAX)) shard = FitShard();
+    return shard;
+}
+// fn(i0, m) for every run of rows [i0, i0 + m) this process plays (a shard = the same kernels on pointers moved
+// to the shard's first row); unsharded: fn(0, n)
+template <class Fn>
+static int for_each_shard(const FitShard &shard, uint32_t n, Fn fn)
+{
+    const bool sharded = shard.world > 1;
+    const uint32_t ns = sharded ? fit_shard_rows(n, shard.world) : n;
+    for (int r = 0; r < shard.world; r++) {
+        if (sharded && ((shard.nc && r != shard.rank) || (shard.only >= 0 && r != shard.only))) continue;
+        const uint32_t i0 = sharded ? (uint32_t)r * ns : 0u;
+        if (i0 >= n) continue;
+        CHK(fn(i0, sharded ? (n - i0 < ns ? n - i0 : ns) : n));
+    }
+    return 0;
+}
 __global__ __launch_bounds__(256) void k_fit_count_diff(const int32_t *__restrict__ a, const int32_t *__restrict__ b,
                                                         uint32_t n, uint32_t *count, const uint32_t *stop)
 {
@@ -904,99 +1032,47 @@ __global__ __launch_bounds__(256) void k_fit_count_diff(const int32_t *__restric
     if (lane_id() == 0 && c) atomicAdd(count, c);
 }
 
-// The faithful path.  dX: the centred sample on the device (n rows of nb); X: the same on the host
-// through Xat; C: the centred initial centres in, the final centred centres out; dlab: n labels out.
-// Iterations run in batches of ELK_BATCH without a host round trip (k_elk_update owns the convergence
-// tests; once it raises ctl->stop the kernels still queued behind it return at once); an iteration that
-// leaves a cluster empty is finished on the host.
-template <class XAt>
-static int run_fit_elkan(shp_ctx *ctx, const double *dX, XAt Xat, uint32_t n, int nb, int k,
-                         std::vector<double> &C, int max_iter, double tol, int32_t *dlab, double *ddist,
-                         int *n_iter_out, FitShard shard = FitShard(), int32_t *dlab_prev = nullptr)
-{
-    const int kn = k * nb;
-    hipStream_t st = ctx->stream;
-    // k <= 64: no table of exact bounds (fit_bounds.h): n x k float32 brackets + n x k 2-byte stamps + the upper
-    // bounds, and the history of shifts / their running sums / centres per iteration.  SHEPSEG_ELK_TABLE=1: the
-    // round-3 form (the exact table, cluster-major), which k > 64 always takes.
-    const bool lazy = k <= 64 && nb <= 64 && max_iter < 65000 &&
-                      !(getenv("SHEPSEG_ELK_TABLE") && atoi(getenv("SHEPSEG_ELK_TABLE")) != 0);
-    if (shard.world > 1 && (!lazy || !dlab_prev || shard.world > 64)) shard = FitShard();    // (the exact-table form is not sharded: every rank runs it whole)
-    const bool sharded = shard.world > 1;
-    const uint32_t ns = sharded ? (n + (uint32_t)shard.world - 1u) / (uint32_t)shard.world : n;      // rows per rank
-    const size_t hist_rows = (size_t)max_iter + 3;
-    const size_t hist_doubles = lazy ? hist_rows * ((size_t)3 * k + kn) : 0;
-    if (lazy) CHK(buf_ensure(ctx, ctx->fit_lb, (size_t)n * k * 6 + 512 + (size_t)n * 8 * 3 + hist_doubles * 8 + 64));
-    else CHK(buf_ensure(ctx, ctx->fit_lb, ((size_t)k * n + n) * 8));
-    // small device block: C | cshift | half | next | S | cnt | scratch (2k) | ctl | off (k + 1)
-    const size_t small_doubles = (size_t)kn + k + (size_t)k * k + k + kn + k + 3 * (size_t)k;
-    CHK(buf_ensure(ctx, ctx->fit_part, small_doubles * 8 + sizeof(ElkCtl) + ((size_t)k + 4) * 4 + 64));
-    double *dlb = bp<double>(ctx->fit_lb), *dub = dlb + (size_t)k * n;
-    float *dA = nullptr;
-    uint16_t *dstamps = nullptr;
-    ElkHist hist{nullptr, nullptr, nullptr, nullptr, 0u};
-    unsigned long long *ddiag = nullptr, *dcmask = nullptr, *dmmask = nullptr;
-    if (lazy) {
-        // ub | cmask | mmask | hist (cs, cum, cen) | diag | A | stamps
-        dub = bp<double>(ctx->fit_lb);
-        dcmask = (unsigned long long *)(dub + n);
-        dmmask = dcmask + n;
-        hist.cs = (double *)(dmmask + n);
-        hist.cum = hist.cs + hist_rows * k;
-        hist.cen = hist.cum + hist_rows * k;
-        hist.csT = hist.cen + hist_rows * kn;
-        hist.rows = (uint32_t)hist_rows;
-        ddiag = (unsigned long long *)(hist.csT + hist_rows * k);
-        dA = (float *)(((uintptr_t)(ddiag + 8) + 255u) & ~(uintptr_t)255u);
-        dstamps = (uint16_t *)(dA + (size_t)n * k);
-        dlb = nullptr;
-    }
-    double *dC = bp<double>(ctx->fit_part), *dcshift = dC + kn, *dhalf = dcshift + k, *dnext = dhalf + (size_t)k * k;
-    double *dS = dnext + k, *dcnt = dS + kn, *dscr = dcnt + k;
-    ElkCtl *dctl = (ElkCtl *)(dscr + 3 * (size_t)k);
-    uint32_t *doff = (uint32_t *)(dctl + 1);
-    uint32_t *dstop = &dctl->stop;
-    // host staging (pinned when it fits the context's block): C | cshift | half | next up, S | cnt down, ctl
-    const size_t up_doubles = (size_t)kn + k + (size_t)k * k + k, dn_doubles = (size_t)kn + k;
-    std::vector<double> pageable;
-    double *stage = (double *)ctx->h_pinned;
-    const bool pinned = (up_doubles + dn_doubles) * 8 + sizeof(ElkCtl) + 256 <= (size_t)PIN_MIRROR * 4u;
-    if (!pinned) { pageable.resize(up_doubles + dn_doubles + 8); stage = pageable.data(); }
-    double *h_up = stage, *h_dn = stage + up_doubles;
-    ElkCtl *h_ctl = (ElkCtl *)(h_dn + dn_doubles);
-    std::vector<double> half((size_t)k * k), next(k), cshift(k, 0.0), Cn(kn), w(k);
-    auto upload = [&]() -> int {                    // (the stream is idle whenever this runs)
-        memcpy(h_up, C.data(), (size_t)kn * 8);
-        memcpy(h_up + kn, cshift.data(), (size_t)k * 8);
-        memcpy(h_up + kn + k, half.data(), (size_t)k * k * 8);
-        memcpy(h_up + kn + k + (size_t)k * k, next.data(), (size_t)k * 8);
-        HIPCHK(ctx, hipMemcpyAsync(dC, h_up, up_doubles * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        return 0;
-    };
-    auto upload_ctl = [&](uint32_t iters, uint32_t nd0, uint32_t nd1) -> int {
-        memset(h_ctl, 0, sizeof(ElkCtl));
-        h_ctl->iters = iters; h_ctl->nd[0] = nd0; h_ctl->nd[1] = nd1;
-        HIPCHK(ctx, hipMemcpyAsync(dctl, h_ctl, sizeof(ElkCtl), hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        return 0;
-    };
-    HIPCHK(ctx, hipStreamSynchronize(st));          // earlier users of the pinned block are done
-    elk_half_distances(C.data(), k, nb, half.data(), next.data());
-    CHK(upload());                                  // (cshift = 0: the first E-step's bounds update changes nothing)
-    CHK(upload_ctl(0, 0, 0));
-    const unsigned g = grid_for(n, 256);
-    const bool want_diag = lazy && getenv("SHEPSEG_FIT_TRACE");
+// The form one Elkan fit takes, decided once from the shapes and the knobs
+typedef decltype(&k_elk2_visit<0>) ElkVisitFn;
+struct ElkPlan {
+    // lazy (k <= 64): no table of exact bounds (fit_bounds.h): n x k float32 brackets + n x k 2-byte stamps + the
+    // upper bounds, and the history of shifts / their running sums / centres per iteration.  Else the round-3
+    // form (the exact table, cluster-major), which k > 64 always takes.
+    bool lazy;
+    FitShard shard;
+    bool sharded;
+    uint32_t ns;                // rows per rank
+    // the end of an iteration: the last workgroup of the staged sums (fused: nb <= 64, tables in its LDS), else
+    // k_elk_update with its tables in LDS (upd_lds) or in device scratch
+    bool fused, upd_lds;
+    bool want_diag;             // the visit kernel counts rows read / samples visited / exact comparisons
     // k_elk2_filter: shifts, nearest-centre distances (float64) and the half distances (float32) in LDS;
     // k_elk2_visit: the half distances and the centres (float64), the shifts' running sums, the list of a chunk's visits
-    const size_t lds_f = (size_t)2 * k * 8 + (size_t)k * k * 4, lds2 = ((size_t)k * k + kn + k) * 8 + ELK2_VCHUNK * 4;
-    // the pixel-band count as a template parameter where it is small (the sample row then lives in registers)
-    auto visit2 = nb == 1 ? k_elk2_visit<1> : nb == 2 ? k_elk2_visit<2> : nb == 3 ? k_elk2_visit<3> : nb == 4 ? k_elk2_visit<4> :
-                  nb == 5 ? k_elk2_visit<5> : nb == 6 ? k_elk2_visit<6> : nb == 7 ? k_elk2_visit<7> : nb == 8 ? k_elk2_visit<8> :
-                  nb == 10 ? k_elk2_visit<10> : nb == 12 ? k_elk2_visit<12> : k_elk2_visit<0>;
-    unsigned g2 = g, gf = g, gv = (unsigned)grid_for(n, ELK2_VCHUNK);
-    if (lazy) {
-        // workgroups stride over chunks of samples: as many as stay resident
+    size_t lds_f, lds_v, lds_i;
+    ElkVisitFn visit;           // the pixel-band count as a template parameter where it is small (the sample row then lives in registers)
+    unsigned g;                 // a thread per sample
+    unsigned g2, gf, gv;        // init / filter / visit: workgroups stride over chunks of samples, as many as stay resident
+};
+static ElkPlan elk_plan(uint32_t n, int nb, int k, int max_iter, const FitKnobs &knobs, const FitShard &shard, bool have_prev)
+{
+    const int kn = k * nb;
+    ElkPlan p;
+    p.lazy = k <= 64 && nb <= 64 && max_iter < 65000 && !knobs.elk_table;
+    p.shard = elk_shard(shard, knobs, n, p.lazy, have_prev);
+    p.sharded = p.shard.world > 1;
+    p.ns = p.sharded ? fit_shard_rows(n, p.shard.world) : n;
+    p.upd_lds = ELK_UPDATE_LDS_DOUBLES(k, nb) * 8 <= 64 * 1024;
+    p.fused = nb <= 64 && ELK_UPDATE_LDS_DOUBLES(k, nb) <= 2u * (FIT_STAGE_DOUBLES + 4u * 64u) && !knobs.elk_unfused;
+    p.want_diag = p.lazy && knobs.trace;
+    p.lds_f = (size_t)2 * k * 8 + (size_t)k * k * 4;
+    p.lds_v = ((size_t)k * k + kn + k) * 8 + ELK2_VCHUNK * 4;
+    p.lds_i = ((size_t)k * k + kn) * 8;
+    p.visit = nb == 1 ? k_elk2_visit<1> : nb == 2 ? k_elk2_visit<2> : nb == 3 ? k_elk2_visit<3> : nb == 4 ? k_elk2_visit<4> :
+              nb == 5 ? k_elk2_visit<5> : nb == 6 ? k_elk2_visit<6> : nb == 7 ? k_elk2_visit<7> : nb == 8 ? k_elk2_visit<8> :
+              nb == 10 ? k_elk2_visit<10> : nb == 12 ? k_elk2_visit<12> : k_elk2_visit<0>;
+    p.g = grid_for(n, 256);
+    p.g2 = p.g; p.gf = p.g; p.gv = (unsigned)grid_for(n, ELK2_VCHUNK);
+    if (p.lazy) {
         int dev = 0, ncu = 256;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1008,198 +1084,290 @@ static int run_fit_elkan(shp_ctx *ctx, const double *dX, XAt Xat, uint32_t n, in
             }
             return (unsigned)(ncu * per_cu);
         };
-        const unsigned cap_f = resident((const void *)k_elk2_filter<0>, lds_f), cap_v = resident((const void *)visit2, lds2);
-        const unsigned cap_i = resident((const void *)k_elk2_init, ((size_t)k * k + kn) * 8);
-        if (gf > cap_f) gf = cap_f;
-        if (gv > cap_v) gv = cap_v;
-        if (g2 > cap_i) g2 = cap_i;
-        // cum[1] = 0; cen[1] = the initial centres (dC, uploaded above)
+        const unsigned cap_f = resident((const void *)k_elk2_filter<0>, p.lds_f), cap_v = resident((const void *)p.visit, p.lds_v);
+        const unsigned cap_i = resident((const void *)k_elk2_init, p.lds_i);
+        if (p.gf > cap_f) p.gf = cap_f;
+        if (p.gv > cap_v) p.gv = cap_v;
+        if (p.g2 > cap_i) p.g2 = cap_i;
+    }
+    return p;
+}
+
+// One Elkan fit: its inputs, its plan, every device and staging pointer at its elk_layout offset, and the host's
+// copies of what goes up with the centres
+struct ElkFit {
+    shp_ctx *ctx;
+    hipStream_t st;
+    const double *dX;           // the centred sample on the device (n rows of nb)
+    uint32_t n;
+    int nb, k, kn;
+    double tol;
+    int32_t *dlab, *dlab_prev;
+    double *ddist;
+    ElkPlan p;
+    ElkLayout L;
+    double *dlb, *dub;
+    float *dA;
+    uint16_t *dstamps;
+    ElkHist hist;
+    unsigned long long *ddiag, *dcmask, *dmmask;
+    double *dC, *dcshift, *dhalf, *dnext, *dS, *dcnt, *dscr;
+    ElkCtl *dctl;
+    uint32_t *doff, *ddone;
+    std::vector<double> pageable;       // the staging block where it does not fit the context's pinned one
+    double *h_up, *h_dn;
+    ElkCtl *h_ctl;
+    std::vector<double> half, next, cshift;
+
+    int carve()
+    {
+        CHK(buf_ensure(ctx, ctx->fit_lb, L.lb_total));
+        CHK(buf_ensure(ctx, ctx->fit_part, L.part_total));
+        void *lb = ctx->fit_lb.p, *part = ctx->fit_part.p;
+        dub = fit_at<double>(lb, L.ub);
+        hist = ElkHist{nullptr, nullptr, nullptr, nullptr, 0u};
+        if (L.lazy) {
+            dlb = nullptr;
+            dcmask = fit_at<unsigned long long>(lb, L.cmask); dmmask = fit_at<unsigned long long>(lb, L.mmask);
+            hist = ElkHist{fit_at<double>(lb, L.cs), fit_at<double>(lb, L.cum), fit_at<double>(lb, L.cen),
+                           fit_at<double>(lb, L.csT), (uint32_t)L.hist_rows};
+            ddiag = fit_at<unsigned long long>(lb, L.diag);
+            dA = fit_at<float>(lb, L.A); dstamps = fit_at<uint16_t>(lb, L.stamps);
+        } else {
+            dlb = fit_at<double>(lb, L.lb);
+            dcmask = dmmask = ddiag = nullptr; dA = nullptr; dstamps = nullptr;
+        }
+        dC = fit_at<double>(part, L.C); dcshift = fit_at<double>(part, L.cshift); dhalf = fit_at<double>(part, L.half);
+        dnext = fit_at<double>(part, L.next); dS = fit_at<double>(part, L.S); dcnt = fit_at<double>(part, L.cnt);
+        dscr = fit_at<double>(part, L.scratch); dctl = fit_at<ElkCtl>(part, L.ctl);
+        doff = fit_at<uint32_t>(part, L.off); ddone = fit_at<uint32_t>(part, L.done);
+        void *stage = ctx->h_pinned;
+        if (!L.stage_pinned) { pageable.resize(L.stage_doubles); stage = pageable.data(); }
+        h_up = fit_at<double>(stage, L.up); h_dn = fit_at<double>(stage, L.down); h_ctl = fit_at<ElkCtl>(stage, L.stage_ctl);
+        return 0;
+    }
+
+    // C | cshift | half | next to the device (the stream is idle whenever this runs)
+    int upload(const std::vector<double> &C)
+    {
+        memcpy(h_up, C.data(), (size_t)kn * 8);
+        memcpy(h_up + kn, cshift.data(), (size_t)k * 8);
+        memcpy(h_up + kn + k, half.data(), (size_t)k * k * 8);
+        memcpy(h_up + kn + k + (size_t)k * k, next.data(), (size_t)k * 8);
+        HIPCHK(ctx, hipMemcpyAsync(dC, h_up, L.up.bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        return 0;
+    }
+    int upload_ctl(uint32_t iters, uint32_t nd0, uint32_t nd1)
+    {
+        memset(h_ctl, 0, sizeof(ElkCtl));
+        h_ctl->iters = iters; h_ctl->nd[0] = nd0; h_ctl->nd[1] = nd1;
+        HIPCHK(ctx, hipMemcpyAsync(dctl, h_ctl, sizeof(ElkCtl), hipMemcpyHostToDevice, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        return 0;
+    }
+
+    // the bounds and labels of the initial centres (dC, uploaded before)
+    int enqueue_init()
+    {
+        if (!p.lazy) {
+            HIPCHK(ctx, hipMemsetAsync(dlb, 0, (size_t)k * n * 8, st));
+            hipLaunchKernelGGL(k_elk_init, dim3(p.g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dlab, dub, dlb); KCHK(ctx);
+            return 0;
+        }
+        // cum[1] = 0; cen[1] = the initial centres
         HIPCHK(ctx, hipMemsetAsync(hist.cum, 0, (size_t)2 * k * 8, st));
         HIPCHK(ctx, hipMemsetAsync(ddiag, 0, 64, st));
         HIPCHK(ctx, hipMemcpyAsync(hist.cen + kn, dC, (size_t)kn * 8, hipMemcpyDeviceToDevice, st));
-        // (a shard = the same kernels on pointers moved to the shard's first row)
-        for (int r = 0; r < shard.world; r++) {
-            if (sharded && ((shard.nc && r != shard.rank) || (shard.only >= 0 && r != shard.only))) continue;
-            const uint32_t i0 = sharded ? (uint32_t)r * ns : 0u;
-            if (i0 >= n) continue;
-            const uint32_t m = sharded ? (n - i0 < ns ? n - i0 : ns) : n;
-            hipLaunchKernelGGL(k_elk2_init, dim3(g2), dim3(256), ((size_t)k * k + kn) * 8, st, dX + (size_t)i0 * nb, m, nb, dC, k, dhalf,
+        CHK(for_each_shard(p.shard, n, [&](uint32_t i0, uint32_t m) -> int {
+            hipLaunchKernelGGL(k_elk2_init, dim3(p.g2), dim3(256), p.lds_i, st, dX + (size_t)i0 * nb, m, nb, dC, k, dhalf,
                                dlab + i0, dub + i0, dA + (size_t)i0 * k, dstamps + (size_t)i0 * k); KCHK(ctx);
-        }
-        if (sharded) HIPCHK(ctx, hipMemcpyAsync(dlab_prev, dlab, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    } else {
-        HIPCHK(ctx, hipMemsetAsync(dlb, 0, (size_t)k * n * 8, st));
-        hipLaunchKernelGGL(k_elk_init, dim3(g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dlab, dub, dlb); KCHK(ctx);
+            return 0;
+        }));
+        if (p.sharded) HIPCHK(ctx, hipMemcpyAsync(dlab_prev, dlab, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        return 0;
     }
-    auto estep = [&](uint32_t *nd, const uint32_t *stop, int it) -> int {
-        if (lazy) {
+
+    // the E-step of iteration `it`; nd: the counter of changed labels it adds to
+    int enqueue_estep(uint32_t *nd, const uint32_t *stop, int it)
+    {
+        if (p.lazy) {
             const double *csp = it > 1 ? hist.cs + (size_t)(it - 1) * k : (const double *)nullptr;
-            for (int r = 0; r < shard.world; r++) {
-                if (sharded && ((shard.nc && r != shard.rank) || (shard.only >= 0 && r != shard.only))) continue;
-                const uint32_t i0 = sharded ? (uint32_t)r * ns : 0u;
-                if (i0 >= n) continue;
-                const uint32_t m = sharded ? (n - i0 < ns ? n - i0 : ns) : n;
+            CHK(for_each_shard(p.shard, n, [&](uint32_t i0, uint32_t m) -> int {
                 unsigned gfr = (unsigned)grid_for(m, 256), gvr = (unsigned)grid_for(m, ELK2_VCHUNK);
-                if (gfr > gf) gfr = gf;
-                if (gvr > gv) gvr = gv;
-                hipLaunchKernelGGL(k_elk2_filter<0>, dim3(gfr), dim3(256), lds_f, st, m, k, dhalf, dnext, csp, hist.cum + (size_t)it * k,
+                if (gfr > p.gf) gfr = p.gf;
+                if (gvr > p.gv) gvr = p.gv;
+                hipLaunchKernelGGL(k_elk2_filter<0>, dim3(gfr), dim3(256), p.lds_f, st, m, k, dhalf, dnext, csp, hist.cum + (size_t)it * k,
                                    dlab + i0, dub + i0, dA + (size_t)i0 * k, dcmask + i0, dmmask + i0, stop); KCHK(ctx);
-                hipLaunchKernelGGL(visit2, dim3(gvr), dim3(256), lds2, st, dX + (size_t)i0 * nb, m, nb, hist.cen + (size_t)it * kn, k, dhalf,
+                hipLaunchKernelGGL(p.visit, dim3(gvr), dim3(256), p.lds_v, st, dX + (size_t)i0 * nb, m, nb, hist.cen + (size_t)it * kn, k, dhalf,
                                    hist.cum + (size_t)it * k, dlab + i0, dub + i0, dA + (size_t)i0 * k, dstamps + (size_t)i0 * k,
-                                   dcmask + i0, dmmask + i0, hist, (uint32_t)it, sharded ? (uint32_t *)(ddiag + 6) : nd, stop,
-                                   want_diag ? ddiag : (unsigned long long *)nullptr);
-            }
-            if (sharded) {
-                // every rank's labels on every rank (in place, on this stream), then the changed-label count from the
-                // labels themselves -- the same on all ranks
-                if (shard.nc)
-                    NCCLCHK(ctx, ncclAllGather(dlab + (size_t)shard.rank * ns, dlab, ns, ncclInt32, (ncclComm_t)shard.nc, st));
+                                   dcmask + i0, dmmask + i0, hist, (uint32_t)it, p.sharded ? (uint32_t *)(ddiag + 6) : nd, stop,
+                                   p.want_diag ? ddiag : (unsigned long long *)nullptr);
+                return 0;
+            }));
+            if (p.sharded) {
+                // every rank's labels on every rank (in place, on this stream: world * ns words from dlab, see FitShard),
+                // then the changed-label count from the labels themselves -- the same on all ranks
+                if (p.shard.nc)
+                    NCCLCHK(ctx, ncclAllGather(dlab + (size_t)p.shard.rank * p.ns, dlab, p.ns, ncclInt32, (ncclComm_t)p.shard.nc, st));
                 hipLaunchKernelGGL(k_fit_count_diff, dim3(256), dim3(256), 0, st, dlab, dlab_prev, n, nd, stop); KCHK(ctx);
                 HIPCHK(ctx, hipMemcpyAsync(dlab_prev, dlab, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
             }
         }
         else if (k <= 64)
-            hipLaunchKernelGGL(k_elk_estep64, dim3(g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dnext, dcshift, dlab,
+            hipLaunchKernelGGL(k_elk_estep64, dim3(p.g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dnext, dcshift, dlab,
                                dub, dlb, nd, stop);
         else
-            hipLaunchKernelGGL(k_elk_estep, dim3(g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dnext, dcshift, dlab,
+            hipLaunchKernelGGL(k_elk_estep, dim3(p.g), dim3(256), 0, st, dX, n, nb, dC, k, dhalf, dnext, dcshift, dlab,
                                dub, dlb, nd, stop);
         KCHK(ctx);
         return 0;
-    };
-    // the end of an iteration: the last workgroup of the staged sums (nb <= 64, tables in its LDS), else k_elk_update
-    const bool upd_lds = ELK_UPDATE_LDS_DOUBLES(k, nb) * 8 <= 64 * 1024;
-    const bool fused = nb <= 64 && ELK_UPDATE_LDS_DOUBLES(k, nb) <= 2u * (FIT_STAGE_DOUBLES + 4u * 64u) &&
-                       !(getenv("SHEPSEG_ELK_UNFUSED") && atoi(getenv("SHEPSEG_ELK_UNFUSED")) != 0);
-    uint32_t *ddone = doff + (size_t)k + 1;
-    HIPCHK(ctx, hipMemsetAsync(ddone, 0, 4, st));
-    auto ep_of = [&](int it, bool on) -> ElkEpilogue {
-        ElkEpilogue ep;
-        ep.ctl = on ? dctl : nullptr; ep.done = ddone; ep.C = dC; ep.cshift = dcshift; ep.half = dhalf; ep.next = dnext;
-        ep.scratch = (fused || upd_lds) ? nullptr : dscr; ep.tol = tol; ep.it = (uint32_t)it; ep.hist = hist;
-        return ep;
-    };
-    const bool check_digits = getenv("SHEPSEG_FIT_CHECK_DIGITS") && atoi(getenv("SHEPSEG_FIT_CHECK_DIGITS")) != 0;
-    uint32_t h_ctl_stop_seen = 0u;          // (the check above only judges iterations that really ran)
-    bool strict = false, finished = false;
-    int it_done = 0;
-    while (it_done < max_iter && !finished) {
-        const int b_end = check_digits ? it_done + 1 : (it_done + ELK_BATCH < max_iter ? it_done + ELK_BATCH : max_iter);
-        for (int it = it_done + 1; it <= b_end; it++) {
-            CHK(estep(&dctl->nd[it & 1], dstop, it));
-            // row lists: the row numbers sorted stably by label
-            uint32_t *ks = nullptr, *rows = nullptr;
-            SortDigits sd;
-            CHK(sort_pairs(ctx, (const uint32_t *)dlab, nullptr, n, bits_for((uint32_t)(k - 1)), &ks, &rows, false, &sd));
-            // with one radix pass (k <= 256) the clusters' ranges are in the sort's own scanned histogram:
-            // no search kernel (k_elk_update zeroes the next E-step's counter)
-            FitDigits dg{nullptr, nullptr, 0u, n};
-            if (sd.passes == 1) { dg.hscan = sd.hscan; dg.boff = sd.boff; dg.nblk = sd.nblk; }
-            else {
-                hipLaunchKernelGGL(k_elk_offsets, dim3(grid_for((size_t)k + 1, 256)), dim3(256), 0, st, ks, n, k, doff,
-                                   &dctl->nd[(it + 1) & 1], dstop); KCHK(ctx);
-            }
-            if (sd.passes == 1 && check_digits) {
-                // the ranges read off the sort's scanned histogram against a count of the labels themselves
-                std::vector<uint32_t> got((size_t)k + 1);
-                std::vector<int32_t> hl(n);
-                hipLaunchKernelGGL(k_fit_digit_starts, dim3(1), dim3(256), 0, st, dg, k, doff); KCHK(ctx);
-                HIPCHK(ctx, hipMemcpyAsync(got.data(), doff, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipMemcpyAsync(hl.data(), dlab, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipStreamSynchronize(st));
-                if (h_ctl_stop_seen == 0u) {
-                    std::vector<uint32_t> want((size_t)k + 1, 0u);
-                    for (uint32_t i = 0; i < n; i++) if ((uint32_t)hl[i] < (uint32_t)k) want[(size_t)hl[i] + 1]++;
-                    for (int j = 0; j < k; j++) want[(size_t)j + 1] += want[j];
-                    for (int j = 0; j <= k; j++)
-                        if (got[j] != want[j])
-                            SHP_FAIL(ctx, SHP_ERR_STATE, "fit: cluster %d's row list starts at %u in the sort's histogram, %u by count "
-                                     "(the layout sort_digit_start assumes has changed)", j, got[j], want[j]);
-                }
-            }
-            if (nb <= 64)
-                hipLaunchKernelGGL(k_fit_sum_lists_staged, dim3(k), dim3(FIT_SUM_THREADS), 0, st, dX, nb, rows, doff, dS, dcnt, dstop, dg,
-                                   ep_of(it, fused));
-            else
-                hipLaunchKernelGGL(k_fit_sum_lists, dim3(k, (nb + 63) / 64), dim3(64), 0, st, dX, nb, rows, doff, dS, dcnt,
-                                   dstop, dg);
-            KCHK(ctx);
-            if (!fused) {
-                hipLaunchKernelGGL(k_elk_update, dim3(1), dim3(1024), upd_lds ? ELK_UPDATE_LDS_DOUBLES(k, nb) * 8 : 0, st, dS, dcnt, k, nb,
-                                   ep_of(it, true)); KCHK(ctx);
-            }
+    }
+
+    // iteration `it`: E-step, M-step sums, and the iteration's tail (in the sums' last workgroup when fused)
+    int enqueue_iteration(int it, const uint32_t *check_stop_seen)
+    {
+        const uint32_t *dstop = &dctl->stop;
+        auto ep_of = [&](bool on) -> ElkEpilogue {
+            ElkEpilogue ep;
+            ep.ctl = on ? dctl : nullptr; ep.done = ddone; ep.C = dC; ep.cshift = dcshift; ep.half = dhalf; ep.next = dnext;
+            ep.scratch = (p.fused || p.upd_lds) ? nullptr : dscr; ep.tol = tol; ep.it = (uint32_t)it; ep.hist = hist;
+            return ep;
+        };
+        CHK(enqueue_estep(&dctl->nd[it & 1], dstop, it));
+        const FitMstep ms{dX, n, nb, k, dlab, doff, &dctl->nd[(it + 1) & 1], dstop, dS, dcnt};
+        CHK(fit_enqueue_mstep(ctx, ms, true, ep_of(p.fused), check_stop_seen));
+        if (!p.fused) {
+            hipLaunchKernelGGL(k_elk_update, dim3(1), dim3(1024), p.upd_lds ? ELK_UPDATE_LDS_DOUBLES(k, nb) * 8 : 0, st,
+                               dS, dcnt, k, nb, ep_of(true)); KCHK(ctx);
         }
-        HIPCHK(ctx, hipMemcpyAsync(h_ctl, dctl, sizeof(ElkCtl), hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+
+    // SHEPSEG_FIT_TRACE: a line per batch (h_ctl holds the batch's ElkCtl)
+    int trace(int b_end)
+    {
+        std::vector<double> hs(k);
+        HIPCHK(ctx, hipMemcpyAsync(hs.data(), dcshift, (size_t)k * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
-        const uint32_t stop = h_ctl->stop;
-        h_ctl_stop_seen = stop;
-        if (getenv("SHEPSEG_FIT_TRACE")) {
-            std::vector<double> hs(k);
-            HIPCHK(ctx, hipMemcpyAsync(hs.data(), dcshift, (size_t)k * 8, hipMemcpyDeviceToHost, st));
+        int nz = 0;
+        for (int j = 0; j < k; j++) nz += hs[j] == 0.0;
+        fprintf(stderr, "elkan batch to %d: stop %u iters %u labels changed %u / %u shift %.17g, %d of %d centres did not move\n",
+                b_end, h_ctl->stop, h_ctl->iters, h_ctl->nd[0], h_ctl->nd[1], h_ctl->shift_tot, nz, k);
+        if (p.want_diag) {
+            unsigned long long hd[3];
+            HIPCHK(ctx, hipMemcpyAsync(hd, ddiag, sizeof(hd), hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
-            int nz = 0;
-            for (int j = 0; j < k; j++) nz += hs[j] == 0.0;
-            fprintf(stderr, "elkan batch to %d: stop %u iters %u labels changed %u / %u shift %.17g, %d of %d centres did not move\n",
-                    b_end, stop, h_ctl->iters, h_ctl->nd[0], h_ctl->nd[1], h_ctl->shift_tot, nz, k);
-            if (want_diag) {
-                unsigned long long hd[3];
-                HIPCHK(ctx, hipMemcpyAsync(hd, ddiag, sizeof(hd), hipMemcpyDeviceToHost, st));
-                HIPCHK(ctx, hipStreamSynchronize(st));
-                fprintf(stderr, "   since the start: %llu rows read, %llu samples visited, %llu comparisons recomputed exactly (n = %u)\n",
-                        hd[0], hd[1], hd[2], n);
-            }
+            fprintf(stderr, "   since the start: %llu rows read, %llu samples visited, %llu comparisons recomputed exactly (n = %u)\n",
+                    hd[0], hd[1], hd[2], n);
         }
-        if (stop == 0u) { it_done = b_end; continue; }
-        if (stop == 1u || stop == 3u) {
-            it_done = (int)h_ctl->iters;
-            strict = stop == 1u;
-            finished = true;
-            break;
-        }
-        // stop == 2: iteration `it` left a cluster empty after its E-step and sums; the host finishes it
-        const int it = (int)h_ctl->iters + 1;
+        return 0;
+    }
+
+    // Iteration `it` left a cluster empty after its E-step and sums (stop == 2): the host finishes it as the
+    // reference does (fit_mstep_tail), and puts the device where k_elk_update would have left it.
+    // C: the centres the iteration started from in, its new centres out.
+    template <class XAt>
+    int finish_empty_cluster(XAt Xat, std::vector<double> &C, int it, double *shift_tot)
+    {
         const uint32_t nd = h_ctl->nd[it & 1], nd_other = h_ctl->nd[(it + 1) & 1];
-        HIPCHK(ctx, hipMemcpyAsync(h_dn, dS, dn_doubles * 8, hipMemcpyDeviceToHost, st));
+        std::vector<double> Cn(kn), w(k);
+        HIPCHK(ctx, hipMemcpyAsync(h_dn, dS, L.down.bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(h_up, dC, (size_t)kn * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipStreamSynchronize(st));
         memcpy(Cn.data(), h_dn, (size_t)kn * 8);
         memcpy(w.data(), h_dn + kn, (size_t)k * 8);
-        memcpy(C.data(), h_up, (size_t)kn * 8);             // the centres this iteration started from
-        double shift_tot = 0.0;
+        memcpy(C.data(), h_up, (size_t)kn * 8);
         auto fetch = [&](std::vector<double> &dist, std::vector<int32_t> &hl) -> int {
-            hipLaunchKernelGGL(k_fit_dist, dim3(g), dim3(256), 0, st, dX, n, nb, dlab, dC, ddist); KCHK(ctx);
+            hipLaunchKernelGGL(k_fit_dist, dim3(p.g), dim3(256), 0, st, dX, n, nb, dlab, dC, ddist); KCHK(ctx);
             dist.resize(n); hl.resize(n);
             HIPCHK(ctx, hipMemcpyAsync(dist.data(), ddist, (size_t)n * 8, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipMemcpyAsync(hl.data(), dlab, (size_t)n * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
             return 0;
         };
-        CHK(fit_mstep_tail(k, nb, n, Cn, w, C, Xat, fetch, cshift, &shift_tot));
+        *shift_tot = 0.0;
+        CHK(fit_mstep_tail(k, nb, n, Cn, w, C, Xat, fetch, cshift, shift_tot));
         elk_half_distances(Cn.data(), k, nb, half.data(), next.data());
         C = Cn;
-        CHK(upload());
-        if (lazy) {             // this iteration's shifts, their running sums and the next E-step's centres (k_elk_update's part)
+        CHK(upload(C));
+        if (p.lazy) {             // this iteration's shifts, their running sums and the next E-step's centres (k_elk_update's part)
             std::vector<double> row(k);
             HIPCHK(ctx, hipMemcpyAsync(row.data(), hist.cum + (size_t)it * k, (size_t)k * 8, hipMemcpyDeviceToHost, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
             for (int j = 0; j < k; j++) row[j] = row[j] + cshift[j];
             HIPCHK(ctx, hipMemcpyAsync(hist.cum + ((size_t)it + 1) * k, row.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
             HIPCHK(ctx, hipMemcpyAsync(hist.cs + (size_t)it * k, cshift.data(), (size_t)k * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(ctx, hipMemcpy2DAsync(hist.csT + it, hist_rows * 8, cshift.data(), 8, 8, (size_t)k, hipMemcpyHostToDevice, st));
+            HIPCHK(ctx, hipMemcpy2DAsync(hist.csT + it, L.hist_rows * 8, cshift.data(), 8, 8, (size_t)k, hipMemcpyHostToDevice, st));
             HIPCHK(ctx, hipMemcpyAsync(hist.cen + ((size_t)it + 1) * kn, C.data(), (size_t)kn * 8, hipMemcpyHostToDevice, st));
             HIPCHK(ctx, hipStreamSynchronize(st));
         }
         // (the counter the next E-step adds to was zeroed by this iteration's k_elk_offsets)
         CHK(upload_ctl((uint32_t)it, (it & 1) ? nd_other : nd, (it & 1) ? nd : nd_other));
+        return 0;
+    }
+};
+
+// The faithful path.  dX: the centred sample on the device (n rows of nb); X: the same on the host
+// through Xat; C: the centred initial centres in, the final centred centres out; dlab: n labels out, in a
+// buffer with room for lab_words words (the sharded E-step's all-gather: FitShard); dlab_prev: n more.
+// Iterations run in batches of ELK_BATCH without a host round trip (k_elk_update owns the convergence
+// tests; once it raises ctl->stop the kernels still queued behind it return at once); an iteration that
+// leaves a cluster empty is finished on the host.
+template <class XAt>
+static int run_fit_elkan(shp_ctx *ctx, const double *dX, XAt Xat, uint32_t n, int nb, int k,
+                         std::vector<double> &C, int max_iter, double tol, int32_t *dlab, double *ddist,
+                         int *n_iter_out, const FitKnobs &knobs, FitShard shard, int32_t *dlab_prev, size_t lab_words)
+{
+    hipStream_t st = ctx->stream;
+    ElkFit f;
+    f.ctx = ctx; f.st = st; f.dX = dX; f.n = n; f.nb = nb; f.k = k; f.kn = k * nb; f.tol = tol;
+    f.dlab = dlab; f.dlab_prev = dlab_prev; f.ddist = ddist;
+    f.p = elk_plan(n, nb, k, max_iter, knobs, shard, dlab_prev != nullptr);
+    if (f.p.sharded && (size_t)f.p.shard.world * f.p.ns > lab_words)
+        SHP_FAIL(ctx, SHP_ERR_STATE, "fit: %d ranks x %u labels do not fit the label buffer's %zu words", f.p.shard.world,
+                 f.p.ns, lab_words);
+    f.L = elk_layout(n, nb, k, max_iter, f.p.lazy);
+    CHK(f.carve());
+    f.half.assign((size_t)k * k, 0.0); f.next.assign(k, 0.0); f.cshift.assign(k, 0.0);
+    HIPCHK(ctx, hipStreamSynchronize(st));          // earlier users of the pinned block are done
+    elk_half_distances(C.data(), k, nb, f.half.data(), f.next.data());
+    CHK(f.upload(C));                               // (cshift = 0: the first E-step's bounds update changes nothing)
+    CHK(f.upload_ctl(0, 0, 0));
+    CHK(f.enqueue_init());
+    HIPCHK(ctx, hipMemsetAsync(f.ddone, 0, 4, st));
+    uint32_t stop_seen = 0u;                // (elk_check_digits only judges iterations that really ran)
+    bool strict = false, finished = false;
+    int it_done = 0;
+    while (it_done < max_iter && !finished) {
+        const int b_end = knobs.check_digits ? it_done + 1 : (it_done + ELK_BATCH < max_iter ? it_done + ELK_BATCH : max_iter);
+        for (int it = it_done + 1; it <= b_end; it++)
+            CHK(f.enqueue_iteration(it, knobs.check_digits ? &stop_seen : (const uint32_t *)nullptr));
+        HIPCHK(ctx, hipMemcpyAsync(f.h_ctl, f.dctl, sizeof(ElkCtl), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        const uint32_t stop = stop_seen = f.h_ctl->stop;
+        if (knobs.trace) CHK(f.trace(b_end));
+        if (stop == 0u) { it_done = b_end; continue; }
+        if (stop == 1u || stop == 3u) {
+            it_done = (int)f.h_ctl->iters;
+            strict = stop == 1u;
+            finished = true;
+            break;
+        }
+        // stop == 2: an empty cluster in iteration iters + 1; the host finishes it and applies the same tests
+        const int it = (int)f.h_ctl->iters + 1;
+        const uint32_t nd = f.h_ctl->nd[it & 1];
+        double shift_tot = 0.0;
+        CHK(f.finish_empty_cluster(Xat, C, it, &shift_tot));
         it_done = it;
         if (it >= 2 && nd == 0u) { strict = true; finished = true; }
         else if (shift_tot <= tol) finished = true;
     }
-    if (!strict) CHK(estep(&dctl->nd[0], nullptr, it_done + 1));
+    if (!strict) CHK(f.enqueue_estep(&f.dctl->nd[0], nullptr, it_done + 1));
     // the final centres
-    HIPCHK(ctx, hipMemcpyAsync(h_up, dC, (size_t)kn * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(f.h_up, f.dC, (size_t)k * nb * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
-    memcpy(C.data(), h_up, (size_t)kn * 8);
+    memcpy(C.data(), f.h_up, (size_t)k * nb * 8);
     *n_iter_out = it_done;
     return 0;
 }

@@ -14,6 +14,7 @@
 // SGPRs (uniform scalar loads); bytes are nB*sizeof(px) in + 2 B (uint16 label) out.
 #pragma once
 #include "common.h"
+#include "fit_layout.h"
 #include <algorithm>
 #include <chrono>
 #include <thread>
@@ -245,6 +246,7 @@ struct FitCtl {
     uint32_t near;      // E-steps that met a sample with two centres within FIT_TIE_EPS (fit_elkan.h)
     double shift;
 };
+static_assert(sizeof(FitCtl) == FIT_CTL_BYTES, "fit_layout.h: FIT_CTL_BYTES");
 
 #include "fit_elkan.h"
 
@@ -558,9 +560,232 @@ __global__ __launch_bounds__(256) void k_fit_transpose(const double *__restrict_
 }
 
 #define FIT_DT_F64 100        // xin holds float64 rows (shp_kmeans_fit); else one of the SHP_* pixel types
-// planar: xin_any holds nb planes of nrows pixels (a pixel type, not FIT_DT_F64); rows with a null in
-// any band are dropped when has_null; init == nullptr: diagonalClusterCentres of the kept rows;
-// *nrows_kept_out = rows the model was fitted on (labels_out holds that many).
+// the sample's element type as ST inside the statement (DISPATCH_DTYPE's pixel types and FIT_DT_F64)
+#define DISPATCH_SAMPLE(ctx, xdtype, ...)                                      \
+    switch (xdtype) {                                                          \
+    case FIT_DT_F64: { typedef double ST; __VA_ARGS__; } break;                \
+    case SHP_U8: { typedef uint8_t ST; __VA_ARGS__; } break;                   \
+    case SHP_I16: { typedef int16_t ST; __VA_ARGS__; } break;                  \
+    case SHP_U16: { typedef uint16_t ST; __VA_ARGS__; } break;                 \
+    case SHP_I32: { typedef int32_t ST; __VA_ARGS__; } break;                  \
+    case SHP_U32: { typedef uint32_t ST; __VA_ARGS__; } break;                 \
+    default: SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad sample type %d", xdtype); \
+    }
+
+// What fit_prepare leaves: the centred sample in the context's pinned ctx->h_fit and these
+struct FitPrep {
+    uint32_t n = 0;                     // rows kept (non-null)
+    bool planar = false;                // h_fit holds nb planes of n values (else n rows of nb)
+    std::vector<double> mu, var_sum;    // per band: mean, sum of squared deviations of the centred column
+    std::vector<double> init;           // k x nb initial centres, given or diagonalClusterCentres of the kept rows
+};
+
+// X lives in a pinned, grow-only buffer of the context: no page faults after the first call and the
+// upload runs at full PCIe speed.
+static int fit_host_sample(shp_ctx *ctx, size_t xbytes)
+{
+    if (ctx->h_fit_cap >= xbytes) return 0;
+    if (ctx->h_fit) hipHostFree(ctx->h_fit);
+    ctx->h_fit = nullptr; ctx->h_fit_cap = 0;
+    if (hipHostMalloc((void **)&ctx->h_fit, xbytes + xbytes / 8, hipHostMallocDefault) != hipSuccess)
+        SHP_FAIL(ctx, SHP_ERR_NOMEM, "hipHostMalloc(%zu) failed", xbytes);
+    ctx->h_fit_cap = xbytes + xbytes / 8;
+    return 0;
+}
+
+// Sample preparation on the host for elements of type T.  planar: xin holds nb planes of nrows pixels (a pixel
+// type, not float64); rows with a null in any band are dropped when has_null; init == nullptr:
+// diagonalClusterCentres of the kept rows.  Else rows: sklearn's X -= X.mean(axis=0), rows outer / bands inner,
+// which keeps each band's additions in row order while nb independent chains are in flight.
+template <class T>
+static int fit_prepare(shp_ctx *ctx, const T *xin, int64_t nrows, int nb, int k, const double *init, bool planar,
+                       int has_null, long long null_val, FitPrep &fp)
+{
+    constexpr bool pixel = std::is_integral<T>::value;
+    if (planar && !pixel) SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad sample type %d", FIT_DT_F64);
+    uint32_t n = (uint32_t)nrows;
+    std::vector<uint32_t> keep_idx;
+    fp.planar = planar;
+    fp.n = n;
+    if constexpr (pixel) {
+        if (planar) {
+            // rows kept first (the buffers are sized by them)
+            if (has_null) { planar_keep(xin, (size_t)nrows, nb, null_val, keep_idx); n = (uint32_t)keep_idx.size(); }
+            fp.n = n;
+            if ((int64_t)n < (int64_t)k) SHP_FAIL(ctx, SHP_ERR_ARG, "n_samples=%lld should be >= n_clusters=%d",
+                                                  (long long)n, k);
+        }
+    }
+    CHK(fit_host_sample(ctx, (size_t)n * nb * 8));
+    double *X = ctx->h_fit;
+    fp.mu.assign(nb, 0.0); fp.var_sum.assign(nb, 0.0);
+    if constexpr (pixel) {
+        if (planar) {
+            const uint32_t *ix = has_null ? keep_idx.data() : (const uint32_t *)nullptr;
+            PlanarPrep pp;
+            pp.n = n;
+            pp.mu.assign(nb, 0.0); pp.var_sum.assign(nb, 0.0); pp.vmin.assign(nb, 0); pp.vmax.assign(nb, 0);
+            std::vector<std::thread> th;
+            for (int b = 0; b < nb; b++)
+                th.emplace_back([&, b] {
+                    planar_band(xin + (size_t)b * (size_t)nrows, ix, n, X + (size_t)b * n, &pp.mu[b], &pp.var_sum[b],
+                                &pp.vmin[b], &pp.vmax[b]);
+                });
+            for (auto &t : th) t.join();
+            fp.mu = pp.mu; fp.var_sum = pp.var_sum;
+            if (!init) {
+                fp.init.resize((size_t)k * nb);
+                planar_diag_init<T>(pp, nb, k, fp.init.data());
+            }
+        }
+    }
+    if (!planar) {
+        std::vector<double> acc(nb, 0.0);
+        fit_centre_rows(xin, n, nb, X, fp.mu, acc);
+        for (int b = 0; b < nb; b++) acc[b] /= (double)n;
+        for (uint32_t i = 0; i < n; i++)
+            for (int b = 0; b < nb; b++) { const double d = X[(size_t)i * nb + b] - acc[b]; fp.var_sum[b] += d * d; }
+    }
+    if (init) fp.init.assign(init, init + (size_t)k * nb);
+    if (fp.init.empty()) SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: no initial centres");
+    return 0;
+}
+
+// The device and pinned pointers of run_kmeans_fit, each at its fit_layout offset
+struct FitDev {
+    double *X, *dist;
+    int32_t *labA, *labB;
+    FitCtl *ctl;
+    double *m2c, *cnorm, *C;
+    double *sums, *cntd, *S, *w;
+    uint32_t *counts, *off;
+    FitCtl *pin_ctl;
+    double *pin_up;
+};
+
+static int fit_carve(shp_ctx *ctx, const FitLayout &L, FitDev &d)
+{
+    CHK(buf_ensure(ctx, ctx->fit_x, L.x_total));
+    CHK(buf_ensure(ctx, ctx->fit_lab, L.lab_total));
+    CHK(buf_ensure(ctx, ctx->fit_part, L.part_total));
+    CHK(buf_ensure(ctx, ctx->cen, L.cen_total));
+    d.X = fit_at<double>(ctx->fit_x.p, L.x); d.dist = fit_at<double>(ctx->fit_x.p, L.dist);
+    d.labA = fit_at<int32_t>(ctx->fit_lab.p, L.labA); d.labB = fit_at<int32_t>(ctx->fit_lab.p, L.labB);
+    d.ctl = fit_at<FitCtl>(ctx->fit_lab.p, L.ctl);
+    d.m2c = fit_at<double>(ctx->cen.p, L.m2c); d.cnorm = fit_at<double>(ctx->cen.p, L.cnorm);
+    d.C = fit_at<double>(ctx->cen.p, L.C);
+    d.sums = fit_at<double>(ctx->fit_part.p, L.sums); d.cntd = fit_at<double>(ctx->fit_part.p, L.cntd);
+    d.S = fit_at<double>(ctx->fit_part.p, L.S); d.w = fit_at<double>(ctx->fit_part.p, L.w);
+    d.counts = fit_at<uint32_t>(ctx->fit_part.p, L.counts); d.off = fit_at<uint32_t>(ctx->fit_part.p, L.off);
+    d.pin_ctl = fit_at<FitCtl>(ctx->h_pinned, L.pin_ctl); d.pin_up = fit_at<double>(ctx->h_pinned, L.pin_up);
+    return 0;
+}
+
+// the centred sample to the device as rows (the planar form is transposed there); labels_old = -1
+static int fit_upload_sample(shp_ctx *ctx, const FitDev &d, const FitPrep &fp, int nb)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = fp.n;
+    const size_t xbytes = (size_t)n * nb * 8;
+    HIPCHK(ctx, hipStreamSynchronize(st));           // earlier users of the staging area are done
+    if (fp.planar) {
+        CHK(buf_ensure(ctx, ctx->aux, xbytes));
+        HIPCHK(ctx, hipMemcpyAsync(ctx->aux.p, ctx->h_fit, xbytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_fit_transpose, dim3(grid_for((size_t)n * nb, 256)), dim3(256), 0, st,
+                           bp<double>(ctx->aux), n, nb, d.X); KCHK(ctx);
+    } else {
+        HIPCHK(ctx, hipMemcpyAsync(d.X, ctx->h_fit, xbytes, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(ctx, hipMemsetAsync(d.labB, 0xff, (size_t)n * 4, st));
+    return 0;
+}
+
+// the E-step operands of centres cc (m2c | cnorm | C, adjacent on the device) and a cleared FitCtl
+static int fit_upload_centres(shp_ctx *ctx, const FitDev &d, const std::vector<double> &cc, int k, int nb)
+{
+    const int kn = k * nb;
+    kmeans_prepare_host(cc.data(), k, nb, d.pin_up, d.pin_up + kn);
+    memcpy(d.pin_up + kn + k, cc.data(), (size_t)kn * 8);
+    HIPCHK(ctx, hipMemcpyAsync(d.m2c, d.pin_up, (size_t)(2 * kn + k) * 8, hipMemcpyHostToDevice, ctx->stream));
+    memset(d.pin_ctl, 0, sizeof(FitCtl));
+    HIPCHK(ctx, hipMemcpyAsync(d.ctl, d.pin_ctl, sizeof(FitCtl), hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+
+// The Lloyd iterations run in batches of FIT_BATCH without a host round trip: the last kernel of an
+// iteration (k_fit_update) owns the convergence tests and, once it raises ctl->stop, the kernels still
+// queued behind it return at once.  Iteration `it` writes its labels to buffer A when it is odd, B when
+// even, and compares them with the other buffer (labels_old).
+struct LloydResult {
+    int it_done = 0;
+    bool strict = false;        // stopped on unchanged labels: they match the final centres
+    bool finished = false;
+    bool need_elkan = false;    // a (near) tie decided a label, or a cluster came out empty: fit_elkan.h
+};
+static int fit_lloyd_loop(shp_ctx *ctx, const FitDev &d, uint32_t n, int nb, int k, int max_iter, double tol,
+                          bool force_lloyd, const FitKnobs &knobs, LloydResult &r)
+{
+    hipStream_t st = ctx->stream;
+    const unsigned g = grid_for(n, 256u * FIT_RPT);
+    while (r.it_done < max_iter && !r.finished) {
+        // (the first batch is ONE iteration: where the tie guard fires at all -- integer-valued initial centres on
+        //  integer imagery -- it fires in the very first E-step, and seven more iterations would be thrown away)
+        const int batch = r.it_done == 0 ? 1 : FIT_BATCH;
+        const int b_end = r.it_done + batch < max_iter ? r.it_done + batch : max_iter;
+        for (int it = r.it_done + 1; it <= b_end; it++) {
+            int32_t *dlab = (it & 1) ? d.labA : d.labB, *dlab_old = (it & 1) ? d.labB : d.labA;
+            launch_fit_assign(ctx, g, d.X, n, nb, d.m2c, d.cnorm, k, dlab, dlab_old, d.ctl); KCHK(ctx);
+            const FitMstep ms{d.X, n, nb, k, dlab, d.off, d.off + k + 1, &d.ctl->stop, d.sums, d.cntd};
+            CHK(fit_enqueue_mstep(ctx, ms, false, ElkEpilogue{}, nullptr));
+            hipLaunchKernelGGL(k_fit_counts, dim3(grid_for((size_t)k, 256)), dim3(256), 0, st, d.off, k, d.counts,
+                               &d.ctl->stop); KCHK(ctx);
+            hipLaunchKernelGGL(k_fit_update, dim3(1), dim3(256), 0, st, d.sums, d.counts, 1u, k, nb, d.S, d.w,
+                               d.C, d.m2c, d.cnorm, d.ctl, tol, (uint32_t)it); KCHK(ctx);
+        }
+        HIPCHK(ctx, hipMemcpyAsync(d.pin_ctl, d.ctl, sizeof(FitCtl), hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        const FitCtl &c = *d.pin_ctl;
+        if (knobs.timing)
+            fprintf(stderr, "kmeans fit: batch to %d: stop %u iters %u ndiff %u near %u shift %.17g tol %.17g\n", b_end, c.stop,
+                    c.iters, c.ndiff, c.near, c.shift, tol);
+        if (c.near != 0u && !force_lloyd) { r.need_elkan = true; return 0; }    // a (near) tie decided a label
+        if (c.stop == 0u) { r.it_done = b_end; continue; }
+        if (c.stop == 1u || c.stop == 3u) {
+            r.it_done = (int)c.iters;
+            r.strict = c.stop == 1u;
+            r.finished = true;
+            return 0;
+        }
+        // stop == 2: an iteration found an empty cluster.  Relocations are the reference algorithm's
+        // business (which samples move where depends on its distances and on numpy's partition order,
+        // and what follows on Elkan's bounds): start over on that path (fit_elkan.h)
+        if (force_lloyd && k > 1) SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: an empty cluster needs SHEPSEG_FIT_ALGO=auto or elkan");
+        r.need_elkan = true;
+        return 0;
+    }
+    return 0;
+}
+
+// the final centres (plus the sample's mean) and labels to the caller
+static int fit_download(shp_ctx *ctx, const FitDev &d, const int32_t *dlab, const FitPrep &fp, int k, int nb,
+                        double *centres_out, int32_t *labels_out)
+{
+    hipStream_t st = ctx->stream;
+    const int kn = k * nb;
+    HIPCHK(ctx, hipMemcpyAsync(d.pin_up, d.C, (size_t)kn * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    for (int t = 0; t < kn; t++) centres_out[t] = d.pin_up[t] + fp.mu[t % nb];
+    if (labels_out) {       // via the pinned sample buffer (X is no longer needed): see shp_dev_subsample
+        HIPCHK(ctx, hipMemcpyAsync(ctx->h_fit, dlab, (size_t)fp.n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(ctx, hipStreamSynchronize(st));
+        memcpy(labels_out, ctx->h_fit, (size_t)fp.n * 4);
+    }
+    return 0;
+}
+
+// The fit: prepare, layout, upload, Lloyd loop, Elkan if the loop says so, labels and centres out.
+// planar: xin_any holds nb planes of nrows pixels (fit_prepare); *nrows_kept_out = rows the model was fitted on
+// (labels_out holds that many).
 static int run_kmeans_fit(shp_ctx *ctx, const void *xin_any, int xdtype, int64_t nrows, int nb, int k,
                           const double *init, int max_iter, double tol_rel, double *centres_out,
                           int32_t *labels_out, int *n_iter_out, bool planar = false, int has_null = 0,
@@ -570,238 +795,59 @@ static int run_kmeans_fit(shp_ctx *ctx, const void *xin_any, int xdtype, int64_t
         SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad shape");
     if (!planar && nrows < k) SHP_FAIL(ctx, SHP_ERR_ARG, "n_samples=%lld should be >= n_clusters=%d",
                                        (long long)nrows, k);
-    uint32_t n = (uint32_t)nrows;
+    const FitKnobs knobs = fit_knobs();
     const int kn = k * nb;
     const auto t_begin = std::chrono::steady_clock::now();
-    PlanarPrep pp;
-    std::vector<uint32_t> keep_idx;
-    std::vector<double> init_diag;
-    if (planar) {
-        // rows kept first (the buffers below are sized by them)
-        if (has_null) {
-            switch (xdtype) {
-            case SHP_U8: planar_keep((const uint8_t *)xin_any, (size_t)nrows, nb, null_val, keep_idx); break;
-            case SHP_I16: planar_keep((const int16_t *)xin_any, (size_t)nrows, nb, null_val, keep_idx); break;
-            case SHP_U16: planar_keep((const uint16_t *)xin_any, (size_t)nrows, nb, null_val, keep_idx); break;
-            case SHP_I32: planar_keep((const int32_t *)xin_any, (size_t)nrows, nb, null_val, keep_idx); break;
-            case SHP_U32: planar_keep((const uint32_t *)xin_any, (size_t)nrows, nb, null_val, keep_idx); break;
-            default: SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad sample type %d", xdtype);
-            }
-            n = (uint32_t)keep_idx.size();
-        }
-        if (nrows_kept_out) *nrows_kept_out = (int64_t)n;
-        if ((int64_t)n < (int64_t)k) SHP_FAIL(ctx, SHP_ERR_ARG, "n_samples=%lld should be >= n_clusters=%d",
-                                              (long long)n, k);
-    }
-    // centre the data on the host (sklearn: X -= X.mean(axis=0)); rows outer / bands inner keeps
-    // each band's additions in row order while nb independent chains are in flight.  X lives in
-    // a pinned, grow-only buffer of the context: no page faults after the first call and the
-    // upload runs at full PCIe speed.
-    const size_t xbytes = (size_t)n * nb * 8;
-    if (ctx->h_fit_cap < xbytes) {
-        if (ctx->h_fit) hipHostFree(ctx->h_fit);
-        ctx->h_fit = nullptr; ctx->h_fit_cap = 0;
-        if (hipHostMalloc((void **)&ctx->h_fit, xbytes + xbytes / 8, hipHostMallocDefault) != hipSuccess)
-            SHP_FAIL(ctx, SHP_ERR_NOMEM, "hipHostMalloc(%zu) failed", xbytes);
-        ctx->h_fit_cap = xbytes + xbytes / 8;
-    }
-    double *X = ctx->h_fit;
-    std::vector<double> mu(nb, 0.0), acc(nb, 0.0), acc2(nb, 0.0);
-    if (planar) {
-        const uint32_t *ix = has_null ? keep_idx.data() : (const uint32_t *)nullptr;
-        pp.n = n;
-        pp.mu.assign(nb, 0.0); pp.var_sum.assign(nb, 0.0); pp.vmin.assign(nb, 0); pp.vmax.assign(nb, 0);
-        std::vector<std::thread> th;
-#define PLANAR_BANDS(T)                                                                              \
-        for (int b = 0; b < nb; b++)                                                                     \
-            th.emplace_back([&, b] {                                                                     \
-                planar_band((const T *)xin_any + (size_t)b * (size_t)nrows, ix, n, X + (size_t)b * n,   \
-                            &pp.mu[b], &pp.var_sum[b], &pp.vmin[b], &pp.vmax[b]);                        \
-            })
-        switch (xdtype) {
-        case SHP_U8: PLANAR_BANDS(uint8_t); break;
-        case SHP_I16: PLANAR_BANDS(int16_t); break;
-        case SHP_U16: PLANAR_BANDS(uint16_t); break;
-        case SHP_I32: PLANAR_BANDS(int32_t); break;
-        case SHP_U32: PLANAR_BANDS(uint32_t); break;
-        default: SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad sample type %d", xdtype);
-        }
-#undef PLANAR_BANDS
-        for (auto &t : th) t.join();
-        for (int b = 0; b < nb; b++) { mu[b] = pp.mu[b]; acc2[b] = pp.var_sum[b]; }
-        if (!init) {
-            init_diag.resize(kn);
-            switch (xdtype) {
-            case SHP_U8: planar_diag_init<uint8_t>(pp, nb, k, init_diag.data()); break;
-            case SHP_I16: planar_diag_init<int16_t>(pp, nb, k, init_diag.data()); break;
-            case SHP_U16: planar_diag_init<uint16_t>(pp, nb, k, init_diag.data()); break;
-            case SHP_I32: planar_diag_init<int32_t>(pp, nb, k, init_diag.data()); break;
-            default: planar_diag_init<uint32_t>(pp, nb, k, init_diag.data()); break;
-            }
-            init = init_diag.data();
-        }
-    } else {
-        switch (xdtype) {
-        case FIT_DT_F64: fit_centre_rows((const double *)xin_any, n, nb, X, mu, acc); break;
-        case SHP_U8: fit_centre_rows((const uint8_t *)xin_any, n, nb, X, mu, acc); break;
-        case SHP_I16: fit_centre_rows((const int16_t *)xin_any, n, nb, X, mu, acc); break;
-        case SHP_U16: fit_centre_rows((const uint16_t *)xin_any, n, nb, X, mu, acc); break;
-        case SHP_I32: fit_centre_rows((const int32_t *)xin_any, n, nb, X, mu, acc); break;
-        case SHP_U32: fit_centre_rows((const uint32_t *)xin_any, n, nb, X, mu, acc); break;
-        default: SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: bad sample type %d", xdtype);
-        }
-        for (int b = 0; b < nb; b++) acc[b] /= (double)n;
-        for (uint32_t i = 0; i < n; i++)
-            for (int b = 0; b < nb; b++) { const double d = X[(size_t)i * nb + b] - acc[b]; acc2[b] += d * d; }
-    }
-    if (!init) SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: no initial centres");
-    // (host X is row-major, or band-planar in the planar form)
+    FitPrep fp;
+    DISPATCH_SAMPLE(ctx, xdtype, {
+        const int rc = fit_prepare(ctx, (const ST *)xin_any, nrows, nb, k, init, planar, has_null, null_val, fp);
+        if (planar && nrows_kept_out) *nrows_kept_out = (int64_t)fp.n;
+        CHK(rc);
+    });
+    const uint32_t n = fp.n;
+    const double *X = ctx->h_fit;
     auto Xat = [&](uint32_t i, int b) -> double { return planar ? X[(size_t)b * n + i] : X[(size_t)i * nb + b]; };
     double tol = 0.0;
-    for (int b = 0; b < nb; b++) tol += acc2[b] / (double)n;
+    for (int b = 0; b < nb; b++) tol += fp.var_sum[b] / (double)n;
     tol = tol / nb * tol_rel;
     std::vector<double> C(kn);
-    for (int t = 0; t < kn; t++) C[t] = init[t] - mu[t % nb];
+    for (int t = 0; t < kn; t++) C[t] = fp.init[t] - fp.mu[t % nb];
 
-    if ((size_t)(2 * kn + 2 * k + 8) * 8 > SHP_PINNED_BYTES)
+    const FitLayout L = fit_layout(n, nb, k);
+    if (L.pin_total > SHP_PINNED_BYTES)
         SHP_FAIL(ctx, SHP_ERR_ARG, "k * nbands too large for the k-means fit (%d x %d)", k, nb);
-    CHK(buf_ensure(ctx, ctx->fit_x, (size_t)n * nb * 8 + (size_t)n * 8));
-    CHK(buf_ensure(ctx, ctx->fit_lab, (size_t)n * 4 * 2 + 64 + 1024));        // (128 words between the two label arrays: the
-                                                                               //  sharded E-step's all-gather pads the first)
-    CHK(buf_ensure(ctx, ctx->fit_part, (size_t)(kn + k) * 8 * 3 + ((size_t)2 * k + 4) * 4 + 512));
-    CHK(buf_ensure(ctx, ctx->cen, (size_t)(kn + k) * 8 * 2));
-    double *dX = bp<double>(ctx->fit_x), *ddist = dX + (size_t)n * nb;
-    int32_t *dlabA = bp<int32_t>(ctx->fit_lab), *dlabB = dlabA + n + 128;
-    FitCtl *dctl = (FitCtl *)(dlabB + n);
-    // row-order sums | their counts as float64 (unused here) | S | w | counts | list offsets (k + 1) + a spare word
-    double *dpart2 = bp<double>(ctx->fit_part), *dcntd = dpart2 + kn;
-    double *dS = dcntd + k, *dw = dS + kn;
-    uint32_t *dpc2 = (uint32_t *)(dw + k + 2);
-    uint32_t *doff = dpc2 + k;
-    double *dm2c = bp<double>(ctx->cen), *dcn = dm2c + kn, *dC = dcn + k;
-    hipStream_t st = ctx->stream;
-    // pinned staging: [0..] FitCtl, then m2c|cnorm|C (2kn+k doubles)
-    FitCtl *pin_ctl = (FitCtl *)ctx->h_pinned;
-    double *pin_up = (double *)(ctx->h_pinned + 16);
-    HIPCHK(ctx, hipStreamSynchronize(st));           // earlier users of the staging area are done
-    if (planar) {
-        CHK(buf_ensure(ctx, ctx->aux, xbytes));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->aux.p, X, xbytes, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_fit_transpose, dim3(grid_for((size_t)n * nb, 256)), dim3(256), 0, st,
-                           bp<double>(ctx->aux), n, nb, dX); KCHK(ctx);
-    } else {
-        HIPCHK(ctx, hipMemcpyAsync(dX, X, xbytes, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(ctx, hipMemsetAsync(dlabB, 0xff, (size_t)n * 4, st));        // labels_old = -1
-    const unsigned g = grid_for(n, 256u * FIT_RPT);
-    auto upload_centres = [&](const std::vector<double> &cc) -> int {
-        kmeans_prepare_host(cc.data(), k, nb, pin_up, pin_up + kn);        // m2c | cnorm
-        memcpy(pin_up + kn + k, cc.data(), (size_t)kn * 8);              // C  (dC follows dcn)
-        HIPCHK(ctx, hipMemcpyAsync(dm2c, pin_up, (size_t)(2 * kn + k) * 8, hipMemcpyHostToDevice, st));
-        return 0;
-    };
-    auto upload_ctl = [&](uint32_t iters) -> int {
-        memset(pin_ctl, 0, sizeof(FitCtl));
-        pin_ctl->iters = iters;
-        HIPCHK(ctx, hipMemcpyAsync(dctl, pin_ctl, sizeof(FitCtl), hipMemcpyHostToDevice, st));
-        return 0;
-    };
-    // The iterations run in batches of FIT_BATCH without a host round trip: the last kernel of an
-    // iteration (k_fit_update) owns the convergence tests and, once it raises ctl->stop, the
-    // kernels still queued behind it return at once.  Iteration `it` writes its labels to buffer
-    // A when it is odd, B when even, and compares them with the other buffer (labels_old).
+    FitDev d;
+    CHK(fit_carve(ctx, L, d));
+    CHK(fit_upload_sample(ctx, d, fp, nb));
     const auto t_prep = std::chrono::steady_clock::now();
-    bool strict = false, finished = false;
-    int it_done = 0;
+    ctx->fit_path = 0;
+    CHK(fit_upload_centres(ctx, d, C, k, nb));
+
     // SHEPSEG_FIT_ALGO: auto (the fast path unless its tie guard fires; sklearn runs Lloyd for k == 1),
     // lloyd (never leave the fast path), elkan (always the reference's algorithm): fit_elkan.h
-    const char *algo_env = getenv("SHEPSEG_FIT_ALGO");
-    const bool force_lloyd = k == 1 || (algo_env && !strcmp(algo_env, "lloyd"));
-    bool elkan = k > 1 && !force_lloyd && algo_env && !strcmp(algo_env, "elkan");
-    const std::vector<double> C0 = C;
-    ctx->fit_path = 0;
-    CHK(upload_centres(C));
-    CHK(upload_ctl(0));
-    while (it_done < max_iter && !finished && !elkan) {
-        // (the first batch is ONE iteration: where the tie guard fires at all -- integer-valued initial centres on
-        //  integer imagery -- it fires in the very first E-step, and seven more iterations would be thrown away)
-        const int batch = it_done == 0 ? 1 : FIT_BATCH;
-        const int b_end = it_done + batch < max_iter ? it_done + batch : max_iter;
-        for (int it = it_done + 1; it <= b_end; it++) {
-            int32_t *dlab = (it & 1) ? dlabA : dlabB, *dlab_old = (it & 1) ? dlabB : dlabA;
-            launch_fit_assign(ctx, g, dX, n, nb, dm2c, dcn, k, dlab, dlab_old, dctl); KCHK(ctx);
-            {
-                uint32_t *ks = nullptr, *rows = nullptr;
-                CHK(sort_pairs(ctx, (const uint32_t *)dlab, nullptr, n, bits_for((uint32_t)(k - 1)), &ks, &rows));
-                hipLaunchKernelGGL(k_elk_offsets, dim3(grid_for((size_t)k + 1, 256)), dim3(256), 0, st, ks, n, k, doff,
-                                   doff + k + 1, &dctl->stop); KCHK(ctx);
-                if (nb <= 64)
-                    hipLaunchKernelGGL(k_fit_sum_lists_staged, dim3(k), dim3(FIT_SUM_THREADS), 0, st, dX, nb, rows, doff, dpart2,
-                                       dcntd, &dctl->stop, FitDigits{nullptr, nullptr, 0u, n}, ElkEpilogue{});
-                else
-                    hipLaunchKernelGGL(k_fit_sum_lists, dim3(k, (nb + 63) / 64), dim3(64), 0, st, dX, nb, rows, doff,
-                                       dpart2, dcntd, &dctl->stop, FitDigits{nullptr, nullptr, 0u, n});
-                KCHK(ctx);
-                hipLaunchKernelGGL(k_fit_counts, dim3(grid_for((size_t)k, 256)), dim3(256), 0, st, doff, k, dpc2,
-                                   &dctl->stop); KCHK(ctx);
-            }
-            hipLaunchKernelGGL(k_fit_update, dim3(1), dim3(256), 0, st, dpart2, dpc2, 1u, k, nb, dS, dw,
-                               dC, dm2c, dcn, dctl, tol, (uint32_t)it); KCHK(ctx);
-        }
-        HIPCHK(ctx, hipMemcpyAsync(pin_ctl, dctl, sizeof(FitCtl), hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        const uint32_t stop = pin_ctl->stop;
-        if (getenv("SHEPSEG_FIT_TIMING"))
-            fprintf(stderr, "kmeans fit: batch to %d: stop %u iters %u ndiff %u near %u shift %.17g tol %.17g\n", b_end, stop,
-                    pin_ctl->iters, pin_ctl->ndiff, pin_ctl->near, pin_ctl->shift, tol);
-        if (pin_ctl->near != 0u && !force_lloyd) { elkan = true; break; }    // a (near) tie decided a label
-        if (stop == 0u) { it_done = b_end; continue; }
-        if (stop == 1u || stop == 3u) {
-            it_done = (int)pin_ctl->iters;
-            strict = stop == 1u;
-            finished = true;
-            break;
-        }
-        // stop == 2: an iteration found an empty cluster.  Relocations are the reference algorithm's
-        // business (which samples move where depends on its distances and on numpy's partition order,
-        // and what follows on Elkan's bounds): start over on that path (fit_elkan.h)
-        if (force_lloyd && k > 1) SHP_FAIL(ctx, SHP_ERR_ARG, "kmeans_fit: an empty cluster needs SHEPSEG_FIT_ALGO=auto or elkan");
-        elkan = true;
-        break;
-    }
-    int it = it_done;
-    int32_t *dlab = (it_done & 1) ? dlabA : dlabB;
-    if (it_done == 0) dlab = dlabA;                  // max_iter < 1: labels of the initial centres
-    if (elkan) {
+    const bool force_lloyd = k == 1 || knobs.algo == FIT_ALGO_LLOYD;
+    LloydResult lr;
+    lr.need_elkan = !force_lloyd && knobs.algo == FIT_ALGO_ELKAN;
+    if (!lr.need_elkan) CHK(fit_lloyd_loop(ctx, d, n, nb, k, max_iter, tol, force_lloyd, knobs, lr));
+    int it = lr.it_done;
+    int32_t *dlab = (it & 1) ? d.labA : d.labB;
+    if (it == 0) dlab = d.labA;                      // max_iter < 1: labels of the initial centres
+    if (lr.need_elkan) {
         // the reference's algorithm from the initial centres (whatever the fast path did is dropped)
-        C = C0;
-        dlab = dlabA;
-        if (shard.world == 1 && getenv("SHEPSEG_FIT_SHARDS") && atoi(getenv("SHEPSEG_FIT_SHARDS")) > 1) {
-            // one process plays every rank in turn (or, SHEPSEG_FIT_SHARD_ONLY=r, rank r alone): fit_elkan.h FitShard
-            shard.world = atoi(getenv("SHEPSEG_FIT_SHARDS"));
-            shard.only = getenv("SHEPSEG_FIT_SHARD_ONLY") ? atoi(getenv("SHEPSEG_FIT_SHARD_ONLY")) : -1;
-            if (shard.world > 64 || (size_t)shard.world > (size_t)n) shard = FitShard();
-        }
-        CHK(run_fit_elkan(ctx, dX, Xat, n, nb, k, C, max_iter, tol, dlab, ddist, &it, shard, dlabB));
+        dlab = d.labA;
+        CHK(run_fit_elkan(ctx, d.X, Xat, n, nb, k, C, max_iter, tol, dlab, d.dist, &it, knobs, shard, d.labB, L.lab_words));
         ctx->fit_path = 1;
-        HIPCHK(ctx, hipMemcpyAsync(dC, C.data(), (size_t)kn * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-    } else if (!strict) {
+        HIPCHK(ctx, hipMemcpyAsync(d.C, C.data(), (size_t)kn * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    } else if (!lr.strict) {
         // extra E-step so that the labels match the final centres (the device already holds their
         // m2c | cnorm; either label buffer will do)
-        launch_fit_assign(ctx, g, dX, n, nb, dm2c, dcn, k, dlab, (const int32_t *)nullptr, (FitCtl *)nullptr); KCHK(ctx);
+        launch_fit_assign(ctx, grid_for(n, 256u * FIT_RPT), d.X, n, nb, d.m2c, d.cnorm, k, dlab, (const int32_t *)nullptr,
+                          (FitCtl *)nullptr); KCHK(ctx);
     }
-    HIPCHK(ctx, hipMemcpyAsync(pin_up, dC, (size_t)kn * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));
-    for (int t = 0; t < kn; t++) C[t] = pin_up[t];
-    if (labels_out) {       // via the pinned sample buffer (X is no longer needed): see shp_dev_subsample
-        HIPCHK(ctx, hipMemcpyAsync(ctx->h_fit, dlab, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        memcpy(labels_out, ctx->h_fit, (size_t)n * 4);
-    }
-    for (int t = 0; t < kn; t++) centres_out[t] = C[t] + mu[t % nb];
+    CHK(fit_download(ctx, d, dlab, fp, k, nb, centres_out, labels_out));
     if (n_iter_out) *n_iter_out = it;
-    if (getenv("SHEPSEG_FIT_TIMING")) {
+    if (knobs.timing) {
         const auto t_end = std::chrono::steady_clock::now();
         fprintf(stderr, "kmeans fit: n=%u k=%d iterations=%d  host prep + upload %.2f ms  Lloyd %.2f ms\n", n, k, it,
                 std::chrono::duration<double, std::milli>(t_prep - t_begin).count(),
