@@ -752,6 +752,50 @@ int shp_outline_edges_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, in
                           int four_connected, int64_t *edges_out, uint32_t *bad_label_out);
 int shp_outline_trace(shp_ctx *ctx, int64_t row0, int64_t col0, int64_t *counts_out, double *steps_ms_out);
 int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2);
+/* shp_outline_serial: *calls_out = the shp_outline_edges_dev calls this context has had (every one replaces the
+ * outlines it holds, whatever becomes of it); *serial_out = the value of that count the traced outlines in the
+ * context's buffers belong to, 0 when there are none.  A caller that counts its own calls can so tell, without a call
+ * of its own at trace time, whether the outlines it once traced are still the resident ones.  No device work. */
+int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_out);
+
+/* ---- convex hulls of the outline rings: solidity and Feret diameters (outlines.calcSegmentHulls) ----
+ * The strict convex hull of all vertices of each id's rings: no repeated points, no three consecutive collinear points,
+ * oriented like an outer ring (positive under ringArea2's formula), from the hull vertex of the smallest (row, col).
+ * hull_reach of the hull edge from point k to its successor = the largest cross product |e x (q - p_k)| over the hull's
+ * points q (twice the area of the largest triangle on that edge); hull_area2 = the ring formula over the hull;
+ * feret_max2 = the largest squared distance between two hull points.  Integers throughout: the result does not depend on
+ * the launches, the atomics' order or the one size threshold (csrc/hull.h: lists of more than 64 points are walked by
+ * one lane).  With H and W the row and column spans of all vertices the caller guarantees H W <= 2^32 and max(H, W) <
+ * 2^31 (shp_hull_build refuses other spans): every cross product then stays within 2^33 and every squared distance fits
+ * int64.  Memory and work follow the vertices, rings and ids, never a bounding box.  The work arrays live in buffers of
+ * the context's own (hl_*): the outlines (a later shp_outline_download), the neighbour table, the group lists and the
+ * shape table of the context are not touched.
+ *  shp_hull_need: *need_out = the bytes the buffers still have to grow by for n_vertices vertices in n_rings rings of the
+ *    ids 0 .. max_seg_id, at the bounds candidates <= vertices and hull points <= vertices (64 bytes a vertex, 40 an id;
+ *    with upload != 0 16 a vertex, 16 a ring and 8 an id more); *free_out = the device's free bytes.
+ *  shp_hull_source: the rings to hull.  All four arrays NULL: the context's traced outlines, read in place (the counts
+ *    are ignored; SHP_ERR_STATE without traced outlines).  Otherwise host arrays as shp_outline_download fills them
+ *    (ring_offsets max_seg_id + 2, vertex_offsets n_rings + 1, vertices n_vertices x 2, ring_area2 n_rings), uploaded
+ *    once; only the ends of the two offset arrays are checked here, that they ascend is the caller's to see to (no
+ *    kernel indexes by them).  *upload_ms_out (may be NULL): device time of the copies.
+ *  shp_hull_build: (row_base, col_base) = the smallest row and column of all vertices, (row_span, col_span) = H and W.
+ *    convex_only != 0: only the left-turn vertices of rings with ring_area2 > 0 are candidates, which holds the hull
+ *    vertices of traced rings but not of arbitrary ones.  counts_out[3]: hull points, candidates, points kept after
+ *    the column filter.  steps_ms_out (may be NULL) [5]: device time of the candidates, the order, the chains, the
+ *    points, the reach.  SHP_ERR_STATE when the traced outlines a resident source named have been replaced.
+ *  shp_hull_download: to host memory, all int64: hull_offsets (max_seg_id + 2), hull_points (hull points x 2, row then
+ *    col), hull_reach (hull points), hull_area2 and feret_max2 (max_seg_id + 1 each, 0 for an id without rings); the
+ *    points and the reach may be NULL without hull points.
+ * Out of order the calls fail with SHP_ERR_STATE ("shp_hull_source must come first", "shp_hull_build must come
+ * first"). */
+int shp_hull_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int64_t max_seg_id, int upload, int64_t *need_out,
+                  int64_t *free_out);
+int shp_hull_source(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t *vertex_offsets, const int64_t *vertices,
+                    const int64_t *ring_area2, int64_t max_seg_id, int64_t n_rings, int64_t n_vertices, double *upload_ms_out);
+int shp_hull_build(shp_ctx *ctx, int64_t row_base, int64_t col_base, int64_t row_span, int64_t col_span, int convex_only,
+                   int64_t *counts_out, double *steps_ms_out);
+int shp_hull_download(shp_ctx *ctx, int64_t *hull_offsets, int64_t *hull_points, int64_t *hull_reach, int64_t *hull_area2,
+                      int64_t *feret_max2);
 
 /* ---- columns reduced over the neighbour table (neighbours.reduceOverNeighbours) ----------------------
  * The finished table stays in the context; these calls reduce per-segment columns over its rows on the device.

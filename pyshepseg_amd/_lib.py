@@ -233,6 +233,12 @@ _SIGS = {
                                          _c.POINTER(_c.c_uint32)]),
     'shp_outline_trace': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _vp, _vp]),
     'shp_outline_download': (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    'shp_outline_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    'shp_hull_need': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64),
+                                 _c.POINTER(_c.c_int64)]),
+    'shp_hull_source': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),
+    'shp_hull_build': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _vp, _vp]),
+    'shp_hull_download': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     'shp_nbr_upload': (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),
     'shp_nbr_table_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
     'shp_nbr_reduce': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_double, _c.c_double, _c.c_uint32,

@@ -27,6 +27,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "segshape.h"
 #include "dsegshape.h"
 #include "outline.h"
+#include "hull.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1678,6 +1679,7 @@ API int shp_outline_need(shp_ctx *ctx, int64_t npix, int64_t edges, int64_t *nee
 API int shp_outline_edges_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int64_t max_seg_id,
                               int four_connected, int64_t *edges_out, uint32_t *bad_label_out)
 {
+    if (ctx) ctx->outline_calls++;              // (counted whatever becomes of the call: shp_outline_serial)
     CHK(enter(ctx));
     if (!edges_out || !bad_label_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     CHK(chk_max_seg_id(ctx, max_seg_id));
@@ -1714,6 +1716,82 @@ API int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *verte
     if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
     if (!ring_offsets || !vertex_offsets || (ctx->outline.rings && (!vertices || !ring_area2))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_outline_download(ctx, ring_offsets, vertex_offsets, vertices, ring_area2);
+}
+
+API int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_out)
+{
+    if (!ctx) return SHP_ERR_ARG;
+    ctx->err.clear();
+    if (!calls_out || !serial_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    *calls_out = ctx->outline_calls;
+    *serial_out = ctx->outline.stage == 2 ? ctx->outline.serial : 0ull;
+    return 0;
+}
+
+// ---- convex hulls of the outline rings (hull.h) ------------------------------------------------------------
+API int shp_hull_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int64_t max_seg_id, int upload, int64_t *need_out,
+                      int64_t *free_out)
+{
+    CHK(enter(ctx));
+    if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (n_vertices < 0 || n_vertices > (int64_t)OL_MAX_ITEMS || n_rings < 0 || n_rings > (int64_t)OL_MAX_ITEMS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_hull_need(ctx, (size_t)n_vertices, (size_t)n_rings, (size_t)max_seg_id, upload, (long long *)need_out,
+                         (long long *)free_out);
+}
+
+API int shp_hull_source(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t *vertex_offsets, const int64_t *vertices,
+                        const int64_t *ring_area2, int64_t max_seg_id, int64_t n_rings, int64_t n_vertices, double *upload_ms_out)
+{
+    CHK(enter(ctx));
+    ctx->hull.stage = 0;
+    if (upload_ms_out) *upload_ms_out = 0.0;
+    if (!ring_offsets && !vertex_offsets && !vertices && !ring_area2) {
+        if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+        return run_hull_source(ctx, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr);
+    }
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (n_vertices < 0 || n_vertices > (int64_t)OL_MAX_ITEMS || n_rings < 0 || n_rings > (int64_t)OL_MAX_ITEMS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "%lld vertices in %lld rings: more than %u", (long long)n_vertices, (long long)n_rings, OL_MAX_ITEMS);
+    if (!ring_offsets || !vertex_offsets || (n_rings && !ring_area2) || (n_vertices && !vertices)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ring_offsets[0] != 0 || ring_offsets[max_seg_id + 1] != n_rings || vertex_offsets[0] != 0 || vertex_offsets[n_rings] != n_vertices)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "the offsets do not span %lld rings and %lld vertices", (long long)n_rings, (long long)n_vertices);
+    return run_hull_source(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, (uint32_t)max_seg_id, (uint32_t)n_rings,
+                           (uint32_t)n_vertices, upload_ms_out);
+}
+
+API int shp_hull_build(shp_ctx *ctx, int64_t row_base, int64_t col_base, int64_t row_span, int64_t col_span, int convex_only,
+                       int64_t *counts_out, double *steps_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->hull.stage < 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no rings to hull: shp_hull_source must come first");
+    if (ctx->hull.resident && (ctx->outline.stage != 2 || ctx->outline.serial != ctx->hull.outline_serial)) {
+        ctx->hull.stage = 0;
+        SHP_FAIL(ctx, SHP_ERR_STATE, "the traced outlines have been replaced: shp_hull_source must come first");
+    }
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (row_span < 0 || col_span < 0 || row_span > 0x7fffffffll || col_span > 0x7fffffffll ||
+        (unsigned long long)row_span * (unsigned long long)col_span > (1ull << 32))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "spans (%lld, %lld)", (long long)row_span, (long long)col_span);
+    if (row_base < -(1ll << 62) || row_base > (1ll << 62) || col_base < -(1ll << 62) || col_base > (1ll << 62))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "base (%lld, %lld)", (long long)row_base, (long long)col_base);
+    CHK(run_hull_build(ctx, (long long)row_base, (long long)col_base, (uint32_t)row_span, (uint32_t)col_span, convex_only ? 1 : 0));
+    counts_out[0] = (int64_t)ctx->hull.nh;
+    counts_out[1] = (int64_t)ctx->hull.ncand;
+    counts_out[2] = (int64_t)ctx->hull.nkept;
+    if (steps_ms_out)
+        for (int i = 0; i < 5; i++) steps_ms_out[i] = ctx->hull.ms[i];
+    return 0;
+}
+
+API int shp_hull_download(shp_ctx *ctx, int64_t *hull_offsets, int64_t *hull_points, int64_t *hull_reach, int64_t *hull_area2,
+                          int64_t *feret_max2)
+{
+    CHK(enter(ctx));
+    if (ctx->hull.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no hulls built: shp_hull_build must come first");
+    if (!hull_offsets || !hull_area2 || !feret_max2 || (ctx->hull.nh && (!hull_points || !hull_reach))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_hull_download(ctx, hull_offsets, hull_points, hull_reach, hull_area2, feret_max2);
 }
 
 // ---- columns reduced over the neighbour table (nbrreduce.h) -----------------------------------------------

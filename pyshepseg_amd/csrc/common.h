@@ -179,6 +179,20 @@ struct OutlineState {
     uint32_t edges = 0, rings = 0, verts = 0, rounds = 0;
     size_t voff64_at = 0, area_at = 0;          // where the int64 vertex offsets and the ring areas lie in ol_ring
     double ms[4] = {};              // device time: sides and scan, successors, doubling rounds, rings and vertices
+    unsigned long long serial = 0;  // shp_ctx::outline_calls when these edges were counted: which outlines these are
+};
+
+// the hulls of the outline rings between shp_hull_source, shp_hull_build and shp_hull_download (hull.h), in buffers
+// of their own (hl_*): the outline state, the neighbour table, the group lists and the shape table stay where they
+// are.  resident: the rings are read in place from the outline buffers, which must still hold outline_serial.
+struct HullState {
+    int stage = 0;                  // 0 none, 1 rings known, 2 hulls built
+    bool resident = false;
+    unsigned long long outline_serial = 0;
+    uint32_t S = 0, nr = 0, nv = 0;
+    uint32_t ncand = 0, nkept = 0, nh = 0;      // candidates, points kept of them, hull points
+    size_t hoff64_at = 0, area_at = 0, feret_at = 0;    // where the int64 offsets, areas and diameters lie in hl_id
+    double ms[5] = {};              // device time: candidates, order, chains, points, reach
 };
 
 // The context's named workspace buffers (grow-only), each named HERE ONLY: the list makes the members of shp_ctx and
@@ -196,7 +210,8 @@ struct OutlineState {
     X(mrg_rep) X(mrg_gsize) X(mrg_hist) X(mrg_rec) X(mrg_bestd) X(mrg_best) X(dmrg_b64) X(dmrg_pairs) \
     X(dmrg_pcnt) X(agg_recode) X(agg_gsize) X(agg_ctr) X(agg_scan) X(agg_offs) X(agg_mem) X(agg_wcol) X(agg_w) \
     X(shape_tab) X(shape_ctr) X(dshape_rec) X(dshape_ctr) X(dshape_rcnt) X(ol_ctr) X(ol_mask) X(ol_off) X(ol_epix) \
-    X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff)
+    X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff) X(hl_vtx) X(hl_voff) X(hl_roff) X(hl_area) X(hl_pos) \
+    X(hl_cid) X(hl_ccol) X(hl_crow) X(hl_k) X(hl_v) X(hl_id) X(hl_pts) X(hl_reach) X(hl_ctr)
 
 struct shp_ctx {
     int device = 0;
@@ -223,6 +238,8 @@ struct shp_ctx {
     SegPointsState pts;
     ShapeState shape;
     OutlineState outline;
+    unsigned long long outline_calls = 0;       // shp_outline_edges_dev calls of this context: each replaces the outlines
+    HullState hull;
     NbrState nbr;
     MrgState mrg;
     AggState agg;

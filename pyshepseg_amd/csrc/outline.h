@@ -344,6 +344,7 @@ static int run_outline_edges(shp_ctx *ctx, const uint32_t *d_seg, uint32_t nrows
     OutlineState &o = ctx->outline;
     hipStream_t st = ctx->stream;
     o = OutlineState{};
+    o.serial = ctx->outline_calls;
     const uint32_t npix = nrows * ncols;
     CHK(buf_ensure(ctx, ctx->ol_ctr, OL_CTR_WORDS * 4));
     CHK(buf_ensure(ctx, ctx->ol_mask, npix));

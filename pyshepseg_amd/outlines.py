@@ -29,6 +29,9 @@ The labels are whole in HBM for this function: a host array or ``.npy`` file is 
 read in place.  The working set is 9 bytes a pixel (labels included), 37 bytes an edge, 16 a vertex and about 52 a
 ring; when the free HBM does not hold it the call raises before anything is allocated.  There is no CPU fallback.
 Streaming in row blocks and a multi-rank form do not exist yet.
+
+``calcSegmentHulls`` takes every segment's convex hull from the rings (csrc/hull.h), in place while they are still in
+HBM, and with it the hull-based shape attributes: ``solidity``, ``convexity``, ``feretMin``, ``feretMax``.
 """
 import ctypes
 import json
@@ -91,6 +94,10 @@ class SegmentOutlines(object):
         self.deviceMs = deviceMs
         self.deviceStepsMs = deviceStepsMs if deviceStepsMs is not None else {}
         self.columns = columnsFromRings(ringOffsets, vertexOffsets, ringArea2)
+        # which outlines of which context these are (residentOutlineSerial); None for rings built by hand
+        self.residentSerial = None
+        self._residentCtx = None
+        self.hulls = None           # a SegmentHulls after traceSegmentOutlines(hulls=True)
 
     def _ringRange(self, segId):
         if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
@@ -212,9 +219,10 @@ def _checkArgs(segfile, maxSegId, origin):
     return (seg, devSeg, nrows, ncols, maxSegId, origin)
 
 
-def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0)):
+def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0), hulls=False):
     """
-    The outline of every segment of a label raster as vertex rings, on the GPU: a SegmentOutlines.
+    The outline of every segment of a label raster as vertex rings, on the GPU: a SegmentOutlines.  With ``hulls=True``
+    its ``hulls`` is the SegmentHulls of calcSegmentHulls, taken while the rings are still in HBM.
 
     ``segfile`` is what shapes.calcSegmentShapes takes -- a 2-D uint32 array, a ``.npy`` path, a
     TiledSegmentationResult (its ``segimg``), a result whose labels are in HBM (``outDev``, read in place) or a
@@ -233,6 +241,8 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
+    if hulls:
+        _outlineSerial(c)
     npix = nrows * ncols
     src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     timings = {}
@@ -259,6 +269,7 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
             timings['labelMax'] = time.perf_counter() - t1
         t1 = time.perf_counter()
         (edges, bad) = (ctypes.c_int64(0), ctypes.c_uint32(0))
+        serial = c._outlineEdgeCalls = getattr(c, '_outlineEdgeCalls', 0) + 1
         c.check(L.shp_outline_edges_dev(c.handle, dseg, nrows, ncols, maxSegId, int(bool(fourConnected)), ctypes.byref(edges),
                                         ctypes.byref(bad)))
         if bad.value:
@@ -293,6 +304,251 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
                           fourConnected=bool(fourConnected), rounds=rounds, edges=int(edges.value), deviceMs=deviceMs,
                           deviceStepsMs=deviceStepsMs)
     timings['columns'] = time.perf_counter() - t1
+    (out.residentSerial, out._residentCtx) = (serial, c.handle.value)
+    if hulls:
+        t1 = time.perf_counter()
+        out.hulls = calcSegmentHulls(out)
+        timings['hulls'] = time.perf_counter() - t1
     timings['total'] = time.perf_counter() - t0
     out.timings = timings
     return out
+
+
+# ---- convex hulls of the rings: solidity and Feret diameters (csrc/hull.h) ----------------------------------------------
+HULL_SUMS = ('numHullVertices', 'hullArea2', 'feretMax2')
+HULL_DERIVED = ('hullArea', 'solidity', 'hullPerimeter', 'convexity', 'feretMax', 'feretMin', 'feretRatio')
+HULL_STEPS = ('candidates', 'order', 'chains', 'points', 'reach')
+
+
+def _outlineSerial(c):
+    """The serial of the traced outlines context ``c`` holds on the device, None without any.  The serial is the count
+    of the context's shp_outline_edges_dev calls at the trace; traceSegmentOutlines counts its own calls on the context
+    object instead of asking (a trace makes the calls it always made), and every question brings that count up to the
+    library's, so a count that calls from elsewhere have left behind can only make outlines look replaced."""
+    (calls, serial) = (ctypes.c_uint64(0), ctypes.c_uint64(0))
+    c.check(c._L.shp_outline_serial(c.handle, ctypes.byref(calls), ctypes.byref(serial)))
+    c._outlineEdgeCalls = calls.value
+    return serial.value if serial.value else None
+
+
+def residentOutlineSerial():
+    """The serial of the traced outlines the calling thread's context holds on the device, None without any: a
+    SegmentOutlines whose ``residentSerial`` it is still has its rings in HBM, and calcSegmentHulls reads them there."""
+    return _outlineSerial(_lib.ctx())
+
+
+def _perId(values, offsets, ufunc, empty):
+    """ufunc.reduce over values[offsets[i]:offsets[i + 1]] for every i, ``empty`` where the range is empty"""
+    out = numpy.full(len(offsets) - 1, empty, dtype=numpy.float64)
+    has = numpy.flatnonzero(numpy.diff(offsets) > 0)
+    if len(has):
+        out[has] = ufunc.reduceat(values, offsets[:-1][has])
+    return out
+
+
+def hullColumnsFromSums(sums, hullOffsets, hullPoints, hullReach, ringArea2Sum, perimeter, missing=-9999):
+    """
+    The float64 columns HULL_DERIVED from the integers of the GPU, as a dictionary: ``sums`` the int64 columns HULL_SUMS,
+    the hulls' offsets, points and per-edge reach, ``ringArea2Sum`` the sum of the id's ringArea2 (twice its pixels)
+    and ``perimeter`` the sum of its rings' lengths (the shape table's ``perimeter``).
+
+    ``hullArea`` = hullArea2 / 2; ``solidity`` = ringArea2Sum / hullArea2; ``hullPerimeter`` = the sum of the hull
+    edges' lengths; ``convexity`` = hullPerimeter / perimeter; ``feretMax`` = sqrt(feretMax2); ``feretMin`` = the
+    minimum over the hull's edges of hullReach / sqrt(squared edge length), the width between the edge's line and the
+    parallel support line; ``feretRatio`` = feretMin / feretMax.  Rows without hull points, and ratios whose
+    denominator is 0, hold ``missing``.
+
+    The minimum over the edges is taken here, in float64, and not on the GPU: comparing reach^2 / length^2 of two
+    edges exactly takes more than 128 bits at the coordinate limits, while every edge's reach and squared length are
+    exact integers and the hulls have far fewer points than the rings.
+    """
+    n = len(hullOffsets) - 1
+    out = {name: numpy.full(n, float(missing), dtype=numpy.float64) for name in HULL_DERIVED}
+    has = numpy.asarray(sums['numHullVertices']) > 0
+    if not has.any():
+        return out
+    ho = numpy.asarray(hullOffsets)
+    pts = numpy.asarray(hullPoints)
+    nxt = numpy.arange(len(pts), dtype=numpy.int64) + 1
+    idOf = numpy.repeat(numpy.arange(n), numpy.diff(ho))
+    last = nxt == ho[1:][idOf]
+    nxt[last] = ho[:-1][idOf][last]
+    d = pts[nxt] - pts
+    len2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]            # exact: below 2^63 within the limits
+    length = numpy.sqrt(len2.astype(numpy.float64))
+    with numpy.errstate(divide='ignore', invalid='ignore'):
+        width = numpy.where(len2 > 0, numpy.asarray(hullReach).astype(numpy.float64) / length, 0.0)
+    a2 = numpy.asarray(sums['hullArea2']).astype(numpy.float64)
+    f2 = numpy.asarray(sums['feretMax2']).astype(numpy.float64)
+    hullPerimeter = _perId(length, ho, numpy.add, 0.0)
+    feretMin = _perId(width, ho, numpy.minimum, 0.0)
+    feretMax = numpy.sqrt(f2)
+    per = numpy.asarray(perimeter).astype(numpy.float64)
+    out['hullArea'][has] = a2[has] / 2.0
+    out['hullPerimeter'][has] = hullPerimeter[has]
+    out['feretMax'][has] = feretMax[has]
+    out['feretMin'][has] = feretMin[has]
+    for (name, num, den) in (('solidity', numpy.asarray(ringArea2Sum).astype(numpy.float64), a2), ('convexity', hullPerimeter, per),
+                             ('feretRatio', feretMin, feretMax)):
+        ok = has & (den > 0)
+        out[name][ok] = num[ok] / den[ok]
+    return out
+
+
+class SegmentHulls(object):
+    """The result of calcSegmentHulls, for the ids 0 .. ``maxSegId`` (S = maxSegId + 1 rows).
+
+    ``hullOffsets``: int64, S + 1 long, the hull of id i is ``hullPoints[hullOffsets[i]:hullOffsets[i + 1]]`` (empty
+    for an id without rings); ``hullPoints``: int64 (n, 2) as (row, col), the outlines' origin included: the strict
+    convex hull of all vertices of the id's rings, without repeated points or three consecutive collinear points,
+    oriented like an outer ring and starting at the hull vertex of the smallest (row, col); ``hullReach``: int64 (n),
+    for the hull edge from point k to its successor the largest cross product with the hull's points; ``sums``: the
+    int64 columns HULL_SUMS (all 0 for an id without rings); ``columns``: those and the float64 columns HULL_DERIVED of
+    hullColumnsFromSums; ``timings``: seconds per step, ``timings['uploaded']`` whether the rings had to go up;
+    ``deviceMs``: GPU time of the kernels, ``deviceStepsMs`` its split into HULL_STEPS."""
+    def __init__(self, maxSegId, hullOffsets, hullPoints, hullReach, sums, columns, timings=None, deviceMs=None,
+                 deviceStepsMs=None, candidates=None, kept=None):
+        self.maxSegId = maxSegId
+        self.hullOffsets = hullOffsets
+        self.hullPoints = hullPoints
+        self.hullReach = hullReach
+        self.sums = sums
+        self.columns = columns
+        self.timings = timings if timings is not None else {}
+        self.deviceMs = deviceMs
+        self.deviceStepsMs = deviceStepsMs if deviceStepsMs is not None else {}
+        self.candidates = candidates
+        self.kept = kept
+
+    def hullOf(self, segId):
+        """the id's hull: a (k, 2) array (a view of ``hullPoints``)"""
+        if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
+            raise PyShepSegOutlinesError("segment id must be an integer 0 .. {} (got {!r})".format(self.maxSegId, segId))
+        return self.hullPoints[int(self.hullOffsets[segId]):int(self.hullOffsets[segId + 1])]
+
+
+def _ringLengths(vertexOffsets, vertices):
+    """the length of every ring, float64 (whole numbers for rectilinear rings)"""
+    vo = numpy.asarray(vertexOffsets)
+    v = numpy.asarray(vertices)
+    if len(v) == 0:
+        return numpy.zeros(len(vo) - 1, dtype=numpy.float64)
+    d = numpy.empty(v.shape, dtype=numpy.float64)       # from every vertex to the next one, of a ring's last to its first
+    d[:-1] = v[1:] - v[:-1]
+    has = numpy.flatnonzero(numpy.diff(vo) > 0)
+    d[vo[1:][has] - 1] = v[vo[:-1][has]] - v[vo[1:][has] - 1]
+    return _perId(numpy.hypot(d[:, 0], d[:, 1]), vo, numpy.add, 0.0)
+
+
+def _checkRings(o):
+    """(ringOffsets, vertexOffsets, vertices, ringArea2 as contiguous int64 arrays, (row base, col base), (H, W)):
+    everything that can be refused before the GPU is touched"""
+    S = o.maxSegId
+    if isinstance(S, (bool, numpy.bool_)) or not isinstance(S, (int, numpy.integer)) or not 0 <= S < 0xFFFFFFFE:
+        raise PyShepSegOutlinesError("maxSegId must be an integer 0 .. 2^32 - 3 (got {!r})".format(S))
+    arrays = []
+    for (name, ndim) in (('ringOffsets', 1), ('vertexOffsets', 1), ('vertices', 2), ('ringArea2', 1)):
+        a = numpy.asarray(getattr(o, name))
+        if a.dtype != numpy.int64 or a.ndim != ndim:
+            raise PyShepSegOutlinesError("{} must be an int64 array of {} dimension(s)".format(name, ndim))
+        arrays.append(numpy.ascontiguousarray(a))
+    (ro, vo, v, a2) = arrays
+    if v.shape[1:] != (2,):
+        raise PyShepSegOutlinesError("vertices must have the shape (n, 2)")
+    if len(ro) != S + 2 or len(vo) != len(a2) + 1:
+        raise PyShepSegOutlinesError("ringOffsets must have maxSegId + 2 entries and vertexOffsets one more than ringArea2")
+    for (name, off, n) in (('ringOffsets', ro, len(a2)), ('vertexOffsets', vo, len(v))):
+        if off[0] != 0 or off[-1] != n or numpy.any(numpy.diff(off) < 0):
+            raise PyShepSegOutlinesError("{} must ascend from 0 to {}".format(name, n))
+    if len(v) > MAX_ITEMS or len(a2) > MAX_ITEMS:
+        raise PyShepSegOutlinesError("{} vertices in {} rings: more than the {} one call can take".format(len(v), len(a2), MAX_ITEMS))
+    (base, span) = ((0, 0), (0, 0))
+    if len(v):
+        lo = [int(x) for x in v.min(axis=0)]
+        hi = [int(x) for x in v.max(axis=0)]
+        if min(lo) < -2 ** 62 or max(hi) > 2 ** 62:
+            raise PyShepSegOutlinesError("vertex coordinates beyond +-2^62")
+        (H, W) = (hi[0] - lo[0], hi[1] - lo[1])
+        if H * W > 2 ** 32 or max(H, W) >= 2 ** 31:
+            raise PyShepSegOutlinesError("the vertices span {} rows and {} columns: the hulls take spans H, W with H W <= 2^32 and "
+                                         "max(H, W) < 2^31".format(H, W))
+        (base, span) = ((lo[0], lo[1]), (H, W))
+    return (ro, vo, v, a2, base, span)
+
+
+def calcSegmentHulls(o, missing=-9999):
+    """
+    The convex hull of every segment of a SegmentOutlines ``o``, on the GPU: a SegmentHulls, with the hull-based shape
+    attributes ``solidity`` (area over hull area: ragged against smooth, where compactness cannot tell),
+    ``convexity``, and the Feret diameters ``feretMin``, ``feretMax`` (width and length independent of the axes).
+
+    If ``o``'s rings are still the ones its trace left in HBM (``o.residentSerial`` is residentOutlineSerial() of the
+    same context) they are read in place; otherwise ``vertices``, ``vertexOffsets``, ``ringOffsets`` and ``ringArea2``
+    are uploaded once, which also allows rings that no raster produced (any SegmentOutlines built by hand).  All parts
+    of an id form one hull, and holes cannot matter.  Everything up to the final square roots is integer arithmetic on
+    the GPU (csrc/hull.h); ``missing`` fills the float columns of ids without rings.
+
+    The minimum width is the one comparison left to the host: comparing reach^2 / length^2 of two hull edges exactly
+    takes more than 128 bits at the coordinate limits, so the GPU returns every hull edge's exact ``hullReach`` and
+    hullColumnsFromSums takes the minimum of reach / length in float64 over the hull, which has far fewer points than
+    the rings.
+
+    Limits, checked before the GPU is touched: with H and W the row and column spans of all vertices, H W <= 2^32 and
+    max(H, W) < 2^31 (every cross product then stays within 2^33, every squared distance fits int64); traced outlines
+    always satisfy this.  The working set is sized from the vertices, rings and ids alone, never from a bounding box;
+    when the free HBM does not hold it PyShepSegOutlinesError names the bytes before anything is allocated.
+    """
+    t0 = time.perf_counter()
+    (ro, vo, v, a2, base, span) = _checkRings(o)
+    (S, nrings, nverts) = (int(o.maxSegId), len(a2), len(v))
+    c = _lib.ctx()
+    L = c._L
+    timings = {}
+    serial = _outlineSerial(c)
+    resident = (serial is not None and getattr(o, 'residentSerial', None) == serial and
+                getattr(o, '_residentCtx', None) == c.handle.value)
+    (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
+    c.check(L.shp_hull_need(c.handle, nverts, nrings, S, 0 if resident else 1, ctypes.byref(need), ctypes.byref(free)))
+    if need.value > free.value:
+        raise PyShepSegOutlinesError("the hull arrays of {} vertices, {} rings and {} ids need {} bytes of device memory, {} are "
+                                     "free".format(nverts, nrings, S + 1, need.value, free.value))
+    timings['need'] = time.perf_counter() - t0          # (with the checks: two passes over the vertices for their extent)
+    t1 = time.perf_counter()
+    ms = ctypes.c_double(0)
+    if resident:
+        c.check(L.shp_hull_source(c.handle, None, None, None, None, S, nrings, nverts, ctypes.byref(ms)))
+    else:
+        c.check(L.shp_hull_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(v), _lib.ptr(a2), S, nrings, nverts,
+                                  ctypes.byref(ms)))
+    timings['upload'] = time.perf_counter() - t1
+    timings['uploaded'] = not resident
+    timings['uploadDeviceMs'] = ms.value
+    t1 = time.perf_counter()
+    counts = numpy.zeros(3, dtype=numpy.int64)
+    steps = numpy.zeros(5, dtype=numpy.float64)
+    # only the trace's own rings are known to have their hull vertices among the convex corners of the outer rings
+    c.check(L.shp_hull_build(c.handle, base[0], base[1], span[0], span[1], 1 if resident else 0, _lib.ptr(counts), _lib.ptr(steps)))
+    timings['build'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    nh = int(counts[0])
+    hullOffsets = numpy.empty(S + 2, dtype=numpy.int64)
+    hullPoints = numpy.empty((nh, 2), dtype=numpy.int64)
+    hullReach = numpy.empty(nh, dtype=numpy.int64)
+    hullArea2 = numpy.empty(S + 1, dtype=numpy.int64)
+    feretMax2 = numpy.empty(S + 1, dtype=numpy.int64)
+    c.check(L.shp_hull_download(c.handle, _lib.ptr(hullOffsets), _lib.ptr(hullPoints), _lib.ptr(hullReach), _lib.ptr(hullArea2),
+                                _lib.ptr(feretMax2)))
+    timings['download'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    sums = {'numHullVertices': numpy.diff(hullOffsets), 'hullArea2': hullArea2, 'feretMax2': feretMax2}
+    columns = dict(sums)
+    columns.update(hullColumnsFromSums(sums, hullOffsets, hullPoints, hullReach, _segmentSums(a2, ro),
+                                       _segmentSums_f(_ringLengths(vo, v), ro), missing))
+    timings['columns'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    return SegmentHulls(S, hullOffsets, hullPoints, hullReach, sums, columns, timings=timings, deviceMs=float(steps.sum()),
+                        deviceStepsMs=dict(zip(HULL_STEPS, steps.tolist())), candidates=int(counts[1]), kept=int(counts[2]))
+
+
+def _segmentSums_f(values, offsets):
+    return _perId(values, offsets, numpy.add, 0.0)
