@@ -758,6 +758,63 @@ int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_of
  * of its own at trace time, whether the outlines it once traced are still the resident ones.  No device work. */
 int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_out);
 
+/* The junction switch of the trace.  Labels outside the raster read as 0; of the four pixels a b / c d round a corner the
+ * pairs (a, b), (b, d), (c, d), (a, c) that differ number its degree, and a corner of degree >= 3 is a junction (three or
+ * more segments meet, or two at a saddle), whatever four_connected.
+ *  shp_outline_junctions: between shp_outline_edges_dev and shp_outline_trace (SHP_ERR_STATE elsewhere); on != 0: every
+ *    edge whose start corner is a junction is a vertex edge like a turn edge, so a ring that runs straight through such a
+ *    corner gets a collinear vertex there; a ring then starts at its vertex edge of the smallest key.  Ring order, areas
+ *    and the rings' number are the plain trace's.  Every shp_outline_edges_dev clears the switch; asked after it and
+ *    before shp_outline_need, that call's bytes include the flags (a byte a vertex).
+ *  shp_outline_download_junction: junction[vertices], 1 where the vertex's corner is a junction; SHP_ERR_STATE unless the
+ *    outlines were traced with the switch on. */
+int shp_outline_junctions(shp_ctx *ctx, int on);
+int shp_outline_download_junction(shp_ctx *ctx, uint8_t *junction);
+
+/* ---- Douglas-Peucker simplification of the outline rings, shared borders staying shared (outlines.simplifySegmentOutlines) ----
+ * Input: rings as shp_outline_download fills them and a junction flag per vertex.  A ring's anchors are its flagged
+ * vertices; a ring without any takes its vertex of the smallest (row, col) (the first of equal ones).  An arc runs from
+ * one anchor to the next in ring order, cyclically, both included (closed with one anchor).  Both ends of an arc are kept.
+ * Between kept a and b: m(q) = |(b - a) x (q - a)| if a != b, |q - a|^2 if a = b; the candidate is the point of the largest
+ * m, ties to the smallest (row, col), then to the first in arc order; it exceeds when m^2 65536 > tolerance2q |b - a|^2
+ * (a != b) or m 65536 > tolerance2q (a = b), in 128-bit integers; if it exceeds it is kept and both halves are treated
+ * the same way.  Every quantity is symmetric in the direction of travel, so the two rings along a border keep the same
+ * vertices of it.  A ring's vertices are its kept source vertices in source order; it is dropped when fewer than three
+ * remain or when its new ring_area2 is 0 or differs in sign from its source ring's; the others keep their order.
+ * Integers throughout: the result does not depend on the launches, the atomics' order, the path or the rounds.  The
+ * caller guarantees the coordinate spans of shp_hull_build.  The work arrays live in buffers of the context's own (sp_*):
+ * the outlines, the hulls, the neighbour table, the group lists and the shape table of the context are not touched.
+ *  shp_simplify_need: *need_out = the bytes the buffers still have to grow by for n_vertices (at most 2^31 - 8192)
+ *    vertices in n_rings rings of the ids 0 .. max_seg_id, at the bounds arcs <= vertices and points of the global class <=
+ *    2 vertices (13 bytes a vertex, 24 an arc, 40 a point, 40 a ring, the result 24 a vertex, 24 a ring and 8 an id; with
+ *    upload != 0 17 a vertex, 16 a ring and 8 an id more); *free_out = the device's free bytes.
+ *  shp_simplify_source: all five arrays NULL: the context's traced outlines and flags, read in place (the counts are
+ *    ignored; SHP_ERR_STATE without traced outlines or without the junction switch).  Otherwise host arrays, uploaded
+ *    once; both offset arrays must ascend from 0 to their counts (the kernels index by them).
+ *  shp_simplify_build: tolerance2q = floor(tolerance^2 65536) <= 2^46; path 0 auto, 1 short, 2 group, 3 global: an arc of
+ *    up to 64 points is taken by one wavefront, of up to 1024 by one workgroup (both in LDS with the round loop in the
+ *    kernel), a longer one in global arrays with one round per set of launches from the host; 2 puts every arc up to
+ *    1024 points into the group class, 3 every arc into the global one.  Bases and spans as shp_hull_build.  A round
+ *    splits every open interval whose candidate exceeds; more rounds than the longest arc has points is SHP_ERR_STATE,
+ *    never a loop.  counts_out[10]: rings, vertices, rounds that split (the recursion's depth), arcs, points of the
+ *    longest arc, arcs of the short, group and global class, vertices kept before the drop rule, 0.  steps_ms_out (may
+ *    be NULL) [4]: device time of anchors and arcs, the rounds, areas and drop rule, the emission.  SHP_ERR_STATE when
+ *    the traced outlines a resident source named have been replaced.
+ *  shp_simplify_download: to host memory, all int64: ring_offsets (max_seg_id + 2), vertex_offsets (rings + 1), vertices
+ *    (vertices x 2), ring_area2, source_ring (rings: the ring's index in the source), kept_vertex (vertices: the vertex's
+ *    index in the source); arrays of no entries may be NULL.
+ * Out of order the calls fail with SHP_ERR_STATE ("shp_simplify_source must come first", "shp_simplify_build must come
+ * first"). */
+int shp_simplify_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int64_t max_seg_id, int upload, int64_t *need_out,
+                      int64_t *free_out);
+int shp_simplify_source(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t *vertex_offsets, const int64_t *vertices,
+                        const int64_t *ring_area2, const uint8_t *junction, int64_t max_seg_id, int64_t n_rings,
+                        int64_t n_vertices, double *upload_ms_out);
+int shp_simplify_build(shp_ctx *ctx, uint64_t tolerance2q, int path, int64_t row_base, int64_t col_base, int64_t row_span,
+                       int64_t col_span, int64_t *counts_out, double *steps_ms_out);
+int shp_simplify_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2,
+                          int64_t *source_ring, int64_t *kept_vertex);
+
 /* ---- convex hulls of the outline rings: solidity and Feret diameters (outlines.calcSegmentHulls) ----
  * The strict convex hull of all vertices of each id's rings: no repeated points, no three consecutive collinear points,
  * oriented like an outer ring (positive under ringArea2's formula), from the hull vertex of the smallest (row, col).

@@ -234,6 +234,13 @@ _SIGS = {
     'shp_outline_trace': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _vp, _vp]),
     'shp_outline_download': (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     'shp_outline_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    'shp_outline_junctions': (_c.c_int, [_vp, _c.c_int]),
+    'shp_outline_download_junction': (_c.c_int, [_vp, _vp]),
+    'shp_simplify_need': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64),
+                                     _c.POINTER(_c.c_int64)]),
+    'shp_simplify_source': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),
+    'shp_simplify_build': (_c.c_int, [_vp, _c.c_uint64, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _vp, _vp]),
+    'shp_simplify_download': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'shp_hull_need': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64),
                                  _c.POINTER(_c.c_int64)]),
     'shp_hull_source': (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.POINTER(_c.c_double)]),

@@ -28,6 +28,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "dsegshape.h"
 #include "outline.h"
 #include "hull.h"
+#include "simplify.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1718,6 +1719,23 @@ API int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *verte
     return run_outline_download(ctx, ring_offsets, vertex_offsets, vertices, ring_area2);
 }
 
+API int shp_outline_junctions(shp_ctx *ctx, int on)
+{
+    CHK(enter(ctx));
+    if (ctx->outline.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no edges counted: shp_outline_edges_dev must come first");
+    ctx->outline.junctions = on ? 1 : 0;
+    return 0;
+}
+
+API int shp_outline_download_junction(shp_ctx *ctx, uint8_t *junction)
+{
+    CHK(enter(ctx));
+    if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+    if (!ctx->outline.has_flags) SHP_FAIL(ctx, SHP_ERR_STATE, "the outlines were traced without junctions: shp_outline_junctions must come first");
+    if (ctx->outline.verts && !junction) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_outline_download_junction(ctx, junction);
+}
+
 API int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_out)
 {
     if (!ctx) return SHP_ERR_ARG;
@@ -1792,6 +1810,86 @@ API int shp_hull_download(shp_ctx *ctx, int64_t *hull_offsets, int64_t *hull_poi
     if (ctx->hull.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no hulls built: shp_hull_build must come first");
     if (!hull_offsets || !hull_area2 || !feret_max2 || (ctx->hull.nh && (!hull_points || !hull_reach))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_hull_download(ctx, hull_offsets, hull_points, hull_reach, hull_area2, feret_max2);
+}
+
+// ---- Douglas-Peucker simplification of the outline rings (simplify.h) -----------------------------------------
+API int shp_simplify_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int64_t max_seg_id, int upload, int64_t *need_out,
+                          int64_t *free_out)
+{
+    CHK(enter(ctx));
+    if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (n_vertices < 0 || n_vertices > (int64_t)SP_MAX_VERTS || n_rings < 0 || n_rings > (int64_t)SP_MAX_VERTS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_simplify_need(ctx, (size_t)n_vertices, (size_t)n_rings, (size_t)max_seg_id, upload, (long long *)need_out,
+                             (long long *)free_out);
+}
+
+API int shp_simplify_source(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t *vertex_offsets, const int64_t *vertices,
+                            const int64_t *ring_area2, const uint8_t *junction, int64_t max_seg_id, int64_t n_rings,
+                            int64_t n_vertices, double *upload_ms_out)
+{
+    CHK(enter(ctx));
+    ctx->simplify.stage = 0;
+    if (upload_ms_out) *upload_ms_out = 0.0;
+    if (!ring_offsets && !vertex_offsets && !vertices && !ring_area2 && !junction) {
+        if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+        if (!ctx->outline.has_flags)
+            SHP_FAIL(ctx, SHP_ERR_STATE, "the outlines were traced without junctions: shp_outline_junctions must come first");
+        if (ctx->outline.verts > SP_MAX_VERTS) SHP_FAIL(ctx, SHP_ERR_ARG, "%u vertices: more than %u", ctx->outline.verts, SP_MAX_VERTS);
+        return run_simplify_source(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr);
+    }
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (n_vertices < 0 || n_vertices > (int64_t)SP_MAX_VERTS || n_rings < 0 || n_rings > (int64_t)SP_MAX_VERTS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "%lld vertices in %lld rings: more than %u", (long long)n_vertices, (long long)n_rings, SP_MAX_VERTS);
+    if (!ring_offsets || !vertex_offsets || (n_rings && !ring_area2) || (n_vertices && (!vertices || !junction)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ring_offsets[0] != 0 || ring_offsets[max_seg_id + 1] != n_rings || vertex_offsets[0] != 0 || vertex_offsets[n_rings] != n_vertices)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "the offsets do not span %lld rings and %lld vertices", (long long)n_rings, (long long)n_vertices);
+    // (the kernels index the vertices by the vertex offsets and the rings by the ring offsets)
+    for (int64_t k = 0; k < n_rings; k++)
+        if (vertex_offsets[k] > vertex_offsets[k + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the vertex offsets do not ascend at ring %lld", (long long)k);
+    for (int64_t i = 0; i <= max_seg_id; i++)
+        if (ring_offsets[i] > ring_offsets[i + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the ring offsets do not ascend at id %lld", (long long)i);
+    return run_simplify_source(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, junction, (uint32_t)max_seg_id, (uint32_t)n_rings,
+                               (uint32_t)n_vertices, upload_ms_out);
+}
+
+API int shp_simplify_build(shp_ctx *ctx, uint64_t tolerance2q, int path, int64_t row_base, int64_t col_base, int64_t row_span,
+                           int64_t col_span, int64_t *counts_out, double *steps_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->simplify.stage < 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no rings to simplify: shp_simplify_source must come first");
+    if (ctx->simplify.resident && (ctx->outline.stage != 2 || ctx->outline.serial != ctx->simplify.outline_serial)) {
+        ctx->simplify.stage = 0;
+        SHP_FAIL(ctx, SHP_ERR_STATE, "the traced outlines have been replaced: shp_simplify_source must come first");
+    }
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (tolerance2q > (1ull << 46)) SHP_FAIL(ctx, SHP_ERR_ARG, "tolerance2q %llu is above 2^46", (unsigned long long)tolerance2q);
+    if (path < 0 || path > 3) SHP_FAIL(ctx, SHP_ERR_ARG, "path %d is none of 0 (auto), 1 (short), 2 (group), 3 (global)", path);
+    if (row_span < 0 || col_span < 0 || row_span > 0x7fffffffll || col_span > 0x7fffffffll ||
+        (unsigned long long)row_span * (unsigned long long)col_span > (1ull << 32))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "spans (%lld, %lld)", (long long)row_span, (long long)col_span);
+    if (row_base < -(1ll << 62) || row_base > (1ll << 62) || col_base < -(1ll << 62) || col_base > (1ll << 62))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "base (%lld, %lld)", (long long)row_base, (long long)col_base);
+    CHK(run_simplify_build(ctx, (unsigned long long)tolerance2q, path, (long long)row_base, (long long)col_base));
+    const SimplifyState &z = ctx->simplify;
+    const int64_t counts[10] = {z.rings, z.verts, z.rounds, z.narcs, z.longest, z.nshort, z.ngroup, z.nglobal, z.kept, 0};
+    for (int i = 0; i < 10; i++) counts_out[i] = counts[i];
+    if (steps_ms_out)
+        for (int i = 0; i < 4; i++) steps_ms_out[i] = z.ms[i];
+    return 0;
+}
+
+API int shp_simplify_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2,
+                              int64_t *source_ring, int64_t *kept_vertex)
+{
+    CHK(enter(ctx));
+    if (ctx->simplify.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no simplified rings: shp_simplify_build must come first");
+    if (!ring_offsets || !vertex_offsets || (ctx->simplify.rings && (!ring_area2 || !source_ring)) ||
+        (ctx->simplify.verts && (!vertices || !kept_vertex)))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_simplify_download(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, source_ring, kept_vertex);
 }
 
 // ---- columns reduced over the neighbour table (nbrreduce.h) -----------------------------------------------

@@ -176,6 +176,8 @@ struct OutlineState {
     const uint32_t *seg = nullptr;
     uint32_t nrows = 0, ncols = 0, S = 0;
     int eight = 0;
+    int junctions = 0;              // the junction switch (shp_outline_junctions): set after the edges, gone with the next ones
+    bool has_flags = false;         // traced with the switch on: ol_jflag holds a flag per vertex
     uint32_t edges = 0, rings = 0, verts = 0, rounds = 0;
     size_t voff64_at = 0, area_at = 0;          // where the int64 vertex offsets and the ring areas lie in ol_ring
     double ms[4] = {};              // device time: sides and scan, successors, doubling rounds, rings and vertices
@@ -210,8 +212,23 @@ struct HullState {
     X(mrg_rep) X(mrg_gsize) X(mrg_hist) X(mrg_rec) X(mrg_bestd) X(mrg_best) X(dmrg_b64) X(dmrg_pairs) \
     X(dmrg_pcnt) X(agg_recode) X(agg_gsize) X(agg_ctr) X(agg_scan) X(agg_offs) X(agg_mem) X(agg_wcol) X(agg_w) \
     X(shape_tab) X(shape_ctr) X(dshape_rec) X(dshape_ctr) X(dshape_rcnt) X(ol_ctr) X(ol_mask) X(ol_off) X(ol_epix) \
-    X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff) X(hl_vtx) X(hl_voff) X(hl_roff) X(hl_area) X(hl_pos) \
-    X(hl_cid) X(hl_ccol) X(hl_crow) X(hl_k) X(hl_v) X(hl_id) X(hl_pts) X(hl_reach) X(hl_ctr)
+    X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff) X(ol_jflag) X(hl_vtx) X(hl_voff) X(hl_roff) X(hl_area) X(hl_pos) \
+    X(hl_cid) X(hl_ccol) X(hl_crow) X(hl_k) X(hl_v) X(hl_id) X(hl_pts) X(hl_reach) X(hl_ctr) \
+    X(sp_vtx) X(sp_voff) X(sp_roff) X(sp_area) X(sp_jflag) X(sp_ctr) X(sp_keep) X(sp_pos) X(sp_ring) X(sp_arc) X(sp_pt) \
+    X(sp_kv) X(sp_out)
+
+// the simplified rings between shp_simplify_source, shp_simplify_build and shp_simplify_download (simplify.h), in
+// buffers of their own (sp_*): the outlines, the hulls, the neighbour table, the group lists and the shape table stay
+// where they are.  resident: rings and junction flags are read in place from the outline buffers.
+struct SimplifyState {
+    int stage = 0;                  // 0 none, 1 rings known, 2 simplified
+    bool resident = false;
+    unsigned long long outline_serial = 0;
+    uint32_t S = 0, nr = 0, nv = 0;
+    uint32_t narcs = 0, longest = 0, rounds = 0, nshort = 0, ngroup = 0, nglobal = 0, kept = 0, rings = 0, verts = 0;
+    size_t off[6] = {};             // where ring offsets, vertex offsets, vertices, areas, source rings, kept vertices lie in sp_out
+    double ms[4] = {};              // device time: anchors and arcs, the rounds, the ring areas and the drop rule, the emission
+};
 
 struct shp_ctx {
     int device = 0;
@@ -240,6 +257,7 @@ struct shp_ctx {
     OutlineState outline;
     unsigned long long outline_calls = 0;       // shp_outline_edges_dev calls of this context: each replaces the outlines
     HullState hull;
+    SimplifyState simplify;
     NbrState nbr;
     MrgState mrg;
     AggState agg;

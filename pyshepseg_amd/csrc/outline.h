@@ -41,6 +41,11 @@
 // Device memory beside the labels (4 bytes a pixel): 5 bytes a pixel (byte, offset); 37 bytes an edge (pixel 4, side
 // and turn flag 1, the two state buffers 16 each; the ring number of an edge lives in the state buffer that is free
 // after the last round); 16 bytes a vertex; 36 bytes a ring plus the sort's 16; 8 bytes an id.
+//
+// The junction switch (shp_outline_junctions, set between the edges and the trace, gone with the next edges): the
+// edges whose start corner is a junction -- three or four of the four neighbouring pairs of the pixels round it differ
+// -- are vertex edges like the turn edges, so a ring gets a collinear vertex where it runs straight through such a
+// corner, and a flag byte per vertex (ol_jflag) says which vertices lie on junctions.  simplify.h cuts the rings there.
 #pragma once
 #include "common.h"
 #include "scan.h"
@@ -105,7 +110,12 @@ struct OlCountFn {          // edges of pixel i
     }
 };
 
-// st[e] = (successor, e if a turn edge else OL_NONE, 0, 1 if a turn edge else 0); epix[e], eside[e] = side | turn << 2
+// st[e] = (successor, e if a vertex edge else OL_NONE, 0, 1 if a vertex edge else 0); epix[e], eside[e] = side | vertex
+// << 2 | junction << 3.  A vertex edge is a turn edge; with JUNC (the junction switch, shp_outline_junctions) also an
+// edge whose start corner is a JUNCTION: of the four pixels round the corner, labels outside the raster read as 0, at
+// least three of the four neighbouring pairs differ.  Those four are this pixel, the pixel across the side and the two
+// behind the corner, all among the 3 x 3; the plain instance keeps no labels and is the kernel it always was.
+template <bool JUNC>
 __global__ __launch_bounds__(256) void k_ol_link(OlGeom g, int eight, const uint8_t *__restrict__ mask,
                                                  const uint32_t *__restrict__ off, uint32_t n, uint4 *__restrict__ st,
                                                  uint32_t *__restrict__ epix, uint8_t *__restrict__ eside)
@@ -119,14 +129,22 @@ __global__ __launch_bounds__(256) void k_ol_link(OlGeom g, int eight, const uint
     const uint32_t a = g.seg[p];
     // eq bit (dy + 1) * 3 + (dx + 1): the pixel at (y + dy, x + dx) is A
     uint32_t eq = 0u;
+    uint32_t lab[9];
 #pragma unroll
     for (int dy = -1; dy <= 1; dy++)
 #pragma unroll
         for (int dx = -1; dx <= 1; dx++) {
             const int yy = y + dy, xx = x + dx;
-            if (yy >= 0 && yy < (int)g.nrows && xx >= 0 && xx < (int)g.ncols &&
-                g.seg[(size_t)yy * g.ncols + (size_t)xx] == a)
-                eq |= 1u << ((dy + 1) * 3 + (dx + 1));
+            if constexpr (JUNC) {
+                const uint32_t v = (yy >= 0 && yy < (int)g.nrows && xx >= 0 && xx < (int)g.ncols)
+                                       ? g.seg[(size_t)yy * g.ncols + (size_t)xx] : 0u;
+                lab[(dy + 1) * 3 + (dx + 1)] = v;
+                if (v == a) eq |= 1u << ((dy + 1) * 3 + (dx + 1));
+            } else {
+                if (yy >= 0 && yy < (int)g.nrows && xx >= 0 && xx < (int)g.ncols &&
+                    g.seg[(size_t)yy * g.ncols + (size_t)xx] == a)
+                    eq |= 1u << ((dy + 1) * 3 + (dx + 1));
+            }
         }
     const uint32_t e0 = off[p];
     constexpr int DY[4] = {0, 1, 0, -1}, DX[4] = {1, 0, -1, 0};
@@ -151,12 +169,21 @@ __global__ __launch_bounds__(256) void k_ol_link(OlGeom g, int eight, const uint
             const int t = (s + 1) & 3;
             succ = e0 + __popc(m & ((1u << t) - 1u));
         }
-        const bool turn = !(RB && !LB);
+        bool turn = !(RB && !LB);
+        uint32_t junc = 0u;
+        if constexpr (JUNC) {
+            // round the start corner: this pixel, the pixel across the side, the pixel left-behind, the pixel right-behind
+            const uint32_t across = lab[(ay + 1) * 3 + (ax + 1)], lb = lab[(1 - dy + ay) * 3 + (1 - dx + ax)];
+            const uint32_t rb = lab[(1 - dy) * 3 + (1 - dx)];
+            const uint32_t degree = (a != across ? 1u : 0u) + (across != lb ? 1u : 0u) + (lb != rb ? 1u : 0u) + (rb != a ? 1u : 0u);
+            junc = degree >= 3u ? 8u : 0u;
+            turn = turn || junc != 0u;
+        }
         if (e >= n) continue;                       // (cannot happen: off[] and mask[] count the same sides)
         if (succ >= n) succ = e;
         st[e] = make_uint4(succ, turn ? e : OL_NONE, 0u, turn ? 1u : 0u);
         epix[e] = p;
-        eside[e] = (uint8_t)((uint32_t)s | (turn ? 4u : 0u));
+        eside[e] = (uint8_t)((uint32_t)s | (turn ? 4u : 0u) | junc);
     }
 }
 
@@ -232,7 +259,7 @@ __global__ __launch_bounds__(256) void k_ol_emit(OlGeom g, const uint4 *__restri
                                                  const uint32_t *__restrict__ epix, const uint8_t *__restrict__ eside, uint32_t n,
                                                  const uint32_t *__restrict__ pos, const uint32_t *__restrict__ T,
                                                  const uint32_t *__restrict__ voff, uint32_t nverts, long long row0,
-                                                 long long col0, longlong2 *__restrict__ vtx)
+                                                 long long col0, longlong2 *__restrict__ vtx, uint8_t *__restrict__ jflag)
 {
     const size_t i = (size_t)blockIdx.x * OL_BLOCK + threadIdx.x;
     if (i >= n) return;
@@ -246,6 +273,7 @@ __global__ __launch_bounds__(256) void k_ol_emit(OlGeom g, const uint4 *__restri
     // start corner: N (y, x), E (y, x + 1), S (y + 1, x + 1), W (y + 1, x)
     if (at >= nverts) return;                       // (cannot happen: c < T for every turn edge of a ring)
     vtx[at] = make_longlong2(row0 + (long long)y + (s >= 2u ? 1 : 0), col0 + (long long)x + ((s == 1u || s == 2u) ? 1 : 0));
+    if (jflag) jflag[at] = (uint8_t)((sd >> 3) & 1u);       // (only with the junction switch)
 }
 
 // the ring of vertex v: the last k with voff[k] <= v
@@ -323,6 +351,7 @@ static int run_outline_need(shp_ctx *ctx, unsigned long long npix, long long edg
         need += ol_grown(ctx->ol_vtx, n * 16) + ol_grown(ctx->ol_ring, (nr + 2) * OL_RING_BYTES);
         need += ol_grown(ctx->sort_k0, nr * 4) + ol_grown(ctx->sort_k1, nr * 4) + ol_grown(ctx->sort_v1, nr * 4) + ol_grown(ctx->pix, nr * 4);
         need += ol_grown(ctx->scan_tmp, scan_tmp_bytes(n));
+        if (ctx->outline.stage == 1 && ctx->outline.junctions) need += ol_grown(ctx->ol_jflag, n);
     }
     size_t fr = 0, tot = 0;
     HIPCHK(ctx, hipMemGetInfo(&fr, &tot));
@@ -385,6 +414,7 @@ static int run_outline_trace(shp_ctx *ctx, long long row0, long long col0)
     volatile uint32_t *h = (volatile uint32_t *)ctx->h_pinned;
     o.stage = 0;
     o.rings = o.verts = o.rounds = 0u;
+    o.has_flags = false;
     CHK(buf_ensure(ctx, ctx->ol_roff, ((size_t)o.S + 2) * 8));
     long long *roff = bp<long long>(ctx->ol_roff);
     if (n == 0u) {                                      // no edges: no rings
@@ -394,6 +424,7 @@ static int run_outline_trace(shp_ctx *ctx, long long row0, long long col0)
         HIPCHK(ctx, hipStreamSynchronize(st));
         o.voff64_at = 0;
         o.area_at = 16;
+        o.has_flags = o.junctions != 0;
         o.stage = 2;
         return 0;
     }
@@ -408,8 +439,12 @@ static int run_outline_trace(shp_ctx *ctx, long long row0, long long col0)
     const unsigned egrid = grid_for(n, OL_BLOCK);
     // ---- step 1, second half: successors, turn edges
     HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-    hipLaunchKernelGGL(k_ol_link, dim3(grid_for(npix, OL_BLOCK)), dim3(OL_BLOCK), 0, st, g, o.eight,
-                       bp<uint8_t>(ctx->ol_mask), bp<uint32_t>(ctx->ol_off), n, buf[0], epix, eside);
+    if (o.junctions)
+        hipLaunchKernelGGL(k_ol_link<true>, dim3(grid_for(npix, OL_BLOCK)), dim3(OL_BLOCK), 0, st, g, o.eight,
+                           bp<uint8_t>(ctx->ol_mask), bp<uint32_t>(ctx->ol_off), n, buf[0], epix, eside);
+    else
+        hipLaunchKernelGGL(k_ol_link<false>, dim3(grid_for(npix, OL_BLOCK)), dim3(OL_BLOCK), 0, st, g, o.eight,
+                           bp<uint8_t>(ctx->ol_mask), bp<uint32_t>(ctx->ol_off), n, buf[0], epix, eside);
     KCHK(ctx);
     HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
     // ---- steps 2 and 3: doubling rounds until one changes no minimum
@@ -463,8 +498,14 @@ static int run_outline_trace(shp_ctx *ctx, long long row0, long long col0)
     if (nv < 4u * nr || nv > n) SHP_FAIL(ctx, SHP_ERR_STATE, "outline: %u vertices in %u rings over %u edges", nv, nr, n);
     CHK(buf_ensure(ctx, ctx->ol_vtx, (size_t)nv * 16));
     longlong2 *vtx = bp<longlong2>(ctx->ol_vtx);
+    uint8_t *jflag = nullptr;
+    if (o.junctions) {
+        CHK(buf_ensure(ctx, ctx->ol_jflag, nv));
+        jflag = bp<uint8_t>(ctx->ol_jflag);
+    }
     hipLaunchKernelGGL(k_ol_emit, dim3(egrid), dim3(OL_BLOCK), 0, st, g, fin, (const uint32_t *)lnum, (const uint32_t *)epix,
-                       (const uint8_t *)eside, n, (const uint32_t *)pos, (const uint32_t *)T, (const uint32_t *)voff, nv, row0, col0, vtx);
+                       (const uint8_t *)eside, n, (const uint32_t *)pos, (const uint32_t *)T, (const uint32_t *)voff, nv, row0, col0, vtx,
+                       jflag);
     KCHK(ctx);
     hipLaunchKernelGGL(k_ol_area, dim3(grid_for(nv, OL_BLOCK)), dim3(OL_BLOCK), 0, st, (const longlong2 *)vtx, (const uint32_t *)voff,
                        nr, nv, row0, col0, area2);
@@ -483,6 +524,7 @@ static int run_outline_trace(shp_ctx *ctx, long long row0, long long col0)
     o.verts = nv;
     o.voff64_at = (size_t)((char *)voff64 - (char *)ctx->ol_ring.p);
     o.area_at = (size_t)((char *)area2 - (char *)ctx->ol_ring.p);
+    o.has_flags = o.junctions != 0;
     o.stage = 2;
     return 0;
 }
@@ -497,5 +539,13 @@ static int run_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *ve
     if (o.rings) HIPCHK(ctx, hipMemcpyAsync(ring_area2, ring + o.area_at, (size_t)o.rings * 8, hipMemcpyDeviceToHost, st));
     if (o.verts) HIPCHK(ctx, hipMemcpyAsync(vertices, ctx->ol_vtx.p, (size_t)o.verts * 16, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));
+    return 0;
+}
+
+static int run_outline_download_junction(shp_ctx *ctx, uint8_t *junction)
+{
+    const OutlineState &o = ctx->outline;
+    if (o.verts) HIPCHK(ctx, hipMemcpyAsync(junction, ctx->ol_jflag.p, o.verts, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }

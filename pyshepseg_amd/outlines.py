@@ -32,6 +32,22 @@ Streaming in row blocks and a multi-rank form do not exist yet (DESIGN section 7
 
 ``calcSegmentHulls`` takes every segment's convex hull from the rings (csrc/hull.h), in place while they are still in
 HBM, and with it the hull-based shape attributes: ``solidity``, ``convexity``, ``feretMin``, ``feretMax``.
+
+``simplifySegmentOutlines`` is a topology-aware Douglas-Peucker simplification of all rings (csrc/simplify.h).  Labels
+outside the raster read as 0; of the four pixels a b / c d round a corner the pairs (a, b), (b, d), (c, d), (a, c) that
+differ number the corner's degree (0, 2, 3 or 4), and a corner of degree >= 3 is a junction, whatever ``fourConnected``
+(the two-label saddle A B / B A has degree 4).  The junction trace, ``traceSegmentOutlines(..., junctions=True)``, makes
+a vertex of every edge that is a turn edge or whose start corner is a junction -- the ring that runs straight through a
+T-junction gets a collinear vertex there -- starts a ring at its vertex edge of the smallest key, and flags the junction
+vertices in ``junction``; ``ringArea2``, ``numParts``, ``numHoles``, ``holeArea`` and the hulls are the plain trace's.
+A ring's anchors are its junction vertices (a ring without any: its vertex of the smallest (row, col)), an arc runs from
+one anchor to the next in ring order, cyclically, and may be closed.  With T = floor(tolerance^2 * 65536): both ends of
+an arc are kept; between kept points a and b, m(q) = |(b - a) x (q - a)| if a != b and |q - a|^2 if a = b; the candidate
+is the point of the largest m, ties to the smallest (row, col); it exceeds the tolerance when m^2 * 65536 > T * |b - a|^2
+(a != b) or m * 65536 > T (a = b), in 128-bit integers; a candidate that exceeds is kept and both halves are treated the
+same way, otherwise nothing between a and b is kept.  The two rings that share an arc run it in opposite directions and
+every quantity is symmetric, so both keep the same corners: along a shared border neighbours keep identical vertices.
+Arcs may still cross each other at large tolerances; that is not checked.
 """
 import ctypes
 import json
@@ -78,9 +94,10 @@ class SegmentOutlines(object):
     ``vertexOffsets``: int64, rings + 1 long; ``vertices``: int64 (n, 2) as (row, col), ``origin`` added;
     ``ringArea2``: int64, positive for outer rings, negative for holes; ``columns``: the int64 columns COLUMNS as the
     statistics' column dictionaries hold them; ``rounds``: pointer-doubling rounds run; ``edges``: boundary sides;
-    ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels, ``deviceStepsMs`` its split."""
+    ``timings``: seconds per step; ``deviceMs``: GPU time of the kernels, ``deviceStepsMs`` its split; ``junction``:
+    uint8, one entry per vertex, 1 where the vertex's corner is a junction (a junction trace), None for a plain trace."""
     def __init__(self, maxSegId, ringOffsets, vertexOffsets, vertices, ringArea2, origin=(0, 0), fourConnected=True,
-                 rounds=0, edges=None, timings=None, deviceMs=None, deviceStepsMs=None):
+                 rounds=0, edges=None, timings=None, deviceMs=None, deviceStepsMs=None, junction=None):
         self.maxSegId = maxSegId
         self.ringOffsets = ringOffsets
         self.vertexOffsets = vertexOffsets
@@ -98,6 +115,8 @@ class SegmentOutlines(object):
         self.residentSerial = None
         self._residentCtx = None
         self.hulls = None           # a SegmentHulls after traceSegmentOutlines(hulls=True)
+        self.junction = junction    # uint8, a flag per vertex, after traceSegmentOutlines(junctions=True); None for a plain trace
+        self.simplified = None      # a SimplifiedOutlines after traceSegmentOutlines(simplify=tolerance)
 
     def _ringRange(self, segId):
         if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
@@ -111,6 +130,26 @@ class SegmentOutlines(object):
         """the id's rings, outer rings and holes in ring order: a list of (k, 2) arrays (views of ``vertices``)"""
         return [self.ring(r) for r in self._ringRange(segId)]
 
+    def _holeShells(self, segId):
+        """{hole: shell}, both ring numbers, for the holes of the id"""
+        rings = list(self._ringRange(segId))
+        shells = [r for r in rings if self.ringArea2[r] > 0]
+        owner = {}
+        for r in rings:
+            if self.ringArea2[r] > 0:
+                continue
+            if len(shells) == 1:
+                owner[r] = shells[0]
+                continue
+            v = self.ring(r)
+            d = numpy.sign(v[1] - v[0])                 # direction of travel (drow, dcol); the pixel lies to its right
+            centre = v[0] + 0.5 * d + 0.5 * numpy.array([d[1], -d[0]])
+            inside = [s for s in shells if _contains(self.ring(s), centre)]
+            if not inside:
+                raise PyShepSegOutlinesError("a hole of segment {} lies in none of its outer rings".format(segId))
+            owner[r] = min(inside, key=lambda s: self.ringArea2[s])
+        return owner
+
     def polygonsOf(self, segId):
         """The id's polygons: a list of [shell, hole, ...], the shells in ring order and every hole with its shell.
 
@@ -119,20 +158,11 @@ class SegmentOutlines(object):
         vertex 0 heading to vertex 1, a pixel of the id) lies strictly inside every shell that encloses the hole."""
         rings = list(self._ringRange(segId))
         shells = [r for r in rings if self.ringArea2[r] > 0]
+        owner = self._holeShells(segId)
         polys = {r: [self.ring(r)] for r in shells}
         for r in rings:
-            if self.ringArea2[r] > 0:
-                continue
-            if len(shells) == 1:
-                polys[shells[0]].append(self.ring(r))
-                continue
-            v = self.ring(r)
-            d = numpy.sign(v[1] - v[0])                 # direction of travel (drow, dcol); the pixel lies to its right
-            centre = v[0] + 0.5 * d + 0.5 * numpy.array([d[1], -d[0]])
-            inside = [s for s in shells if _contains(self.ring(s), centre)]
-            if not inside:
-                raise PyShepSegOutlinesError("a hole of segment {} lies in none of its outer rings".format(segId))
-            polys[min(inside, key=lambda s: self.ringArea2[s])].append(self.ring(r))
+            if r in owner:
+                polys[owner[r]].append(self.ring(r))
         return [polys[r] for r in shells]
 
 
@@ -219,10 +249,14 @@ def _checkArgs(segfile, maxSegId, origin):
     return (seg, devSeg, nrows, ncols, maxSegId, origin)
 
 
-def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0), hulls=False):
+def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0), hulls=False, junctions=False, simplify=None):
     """
     The outline of every segment of a label raster as vertex rings, on the GPU: a SegmentOutlines.  With ``hulls=True``
     its ``hulls`` is the SegmentHulls of calcSegmentHulls, taken while the rings are still in HBM.
+
+    ``junctions=True`` is the junction trace (module docstring): every corner where three or more segments meet is a
+    vertex of all rings through it, and ``junction`` flags those vertices.  ``simplify=tolerance`` implies it and sets
+    ``simplified`` to the SimplifiedOutlines of simplifySegmentOutlines, taken while the rings are still in HBM.
 
     ``segfile`` is what shapes.calcSegmentShapes takes -- a 2-D uint32 array, a ``.npy`` path, a
     TiledSegmentationResult (its ``segimg``), a result whose labels are in HBM (``outDev``, read in place) or a
@@ -238,10 +272,13 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
     free HBM: otherwise PyShepSegOutlinesError names the bytes needed, before anything is allocated.
     """
     (seg, devSeg, nrows, ncols, maxSegId, origin) = _checkArgs(segfile, maxSegId, origin)
+    if simplify is not None:
+        tolerance2q(simplify)
+        junctions = True
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
-    if hulls:
+    if hulls or simplify is not None:
         _outlineSerial(c)
     npix = nrows * ncols
     src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
@@ -276,6 +313,8 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
             raise PyShepSegOutlinesError("segment id {} is above maxSegId {}".format(bad.value, maxSegId))
         if edges.value > MAX_ITEMS:
             raise PyShepSegOutlinesError("{} edges: more than the {} one call can take".format(edges.value, MAX_ITEMS))
+        if junctions:
+            c.check(L.shp_outline_junctions(c.handle, 1))
         c.check(L.shp_outline_need(c.handle, npix, edges.value, ctypes.byref(need), ctypes.byref(free)))
         if need.value > free.value:
             raise PyShepSegOutlinesError("the per-edge arrays of {} edges need {} bytes of device memory, {} are "
@@ -294,6 +333,10 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
         ringArea2 = numpy.empty(nrings, dtype=numpy.int64)
         c.check(L.shp_outline_download(c.handle, _lib.ptr(ringOffsets), _lib.ptr(vertexOffsets), _lib.ptr(vertices),
                                        _lib.ptr(ringArea2)))
+        junction = None
+        if junctions:
+            junction = numpy.empty(nverts, dtype=numpy.uint8)
+            c.check(L.shp_outline_download_junction(c.handle, _lib.ptr(junction)))
         timings['download'] = time.perf_counter() - t1
     finally:
         src.close()
@@ -302,13 +345,17 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
     t1 = time.perf_counter()
     out = SegmentOutlines(maxSegId, ringOffsets, vertexOffsets, vertices, ringArea2, origin=origin,
                           fourConnected=bool(fourConnected), rounds=rounds, edges=int(edges.value), deviceMs=deviceMs,
-                          deviceStepsMs=deviceStepsMs)
+                          deviceStepsMs=deviceStepsMs, junction=junction)
     timings['columns'] = time.perf_counter() - t1
     (out.residentSerial, out._residentCtx) = (serial, c.handle.value)
     if hulls:
         t1 = time.perf_counter()
         out.hulls = calcSegmentHulls(out)
         timings['hulls'] = time.perf_counter() - t1
+    if simplify is not None:
+        t1 = time.perf_counter()
+        out.simplified = simplifySegmentOutlines(out, simplify)
+        timings['simplify'] = time.perf_counter() - t1
     timings['total'] = time.perf_counter() - t0
     out.timings = timings
     return out
@@ -552,3 +599,159 @@ def calcSegmentHulls(o, missing=-9999):
 
 def _segmentSums_f(values, offsets):
     return _perId(values, offsets, numpy.add, 0.0)
+
+
+# ---- Douglas-Peucker simplification of the rings, shared borders staying shared (csrc/simplify.h) ------------------------
+SIMPLIFY_STEPS = ('arcs', 'rounds', 'areas', 'emit')
+SIMPLIFY_PATHS = {'auto': 0, 'short': 1, 'group': 2, 'global': 3}
+MAX_TOLERANCE = 32768.0
+# vertices one simplification can take (csrc/simplify.h: SP_MAX_VERTS)
+MAX_SIMPLIFY_VERTICES = 2 ** 31 - 8192
+
+
+def tolerance2q(tolerance):
+    """T = floor(tolerance^2 * 65536), the integer the GPU compares with: a point at the cross product m from the chord
+    of squared length l exceeds the tolerance when m^2 * 65536 > T * l.  ``tolerance`` is a float64 in vertex units,
+    0 <= tolerance <= 32768 (T <= 2^46)."""
+    try:
+        t = float(tolerance)
+    except (TypeError, ValueError):
+        raise PyShepSegOutlinesError("tolerance must be a number 0 .. {} (got {!r})".format(int(MAX_TOLERANCE), tolerance))
+    if isinstance(tolerance, (bool, numpy.bool_)) or not 0.0 <= t <= MAX_TOLERANCE:       # (a NaN fails both comparisons)
+        raise PyShepSegOutlinesError("tolerance must be a number 0 .. {} (got {!r})".format(int(MAX_TOLERANCE), tolerance))
+    return int(numpy.floor(t * t * 65536.0))
+
+
+class SimplifiedOutlines(SegmentOutlines):
+    """The result of simplifySegmentOutlines: a SegmentOutlines (so toWKT, writeGeoJSON, columnsFromRings and
+    calcSegmentHulls take it) whose rings are the kept vertices of the rings of ``source``.
+
+    ``sourceRing``: int64, the index of each surviving ring in ``source``; ``keptVertex``: int64, the index into
+    ``source.vertices`` of every vertex; ``droppedRings``: int64, per id the rings of ``source`` that did not survive
+    (also in ``columns``); ``junction``: the source's flags of the kept vertices; ``tolerance`` and ``tolerance2q``;
+    ``rounds``: the depth of the recursion, the rounds in which an interval split; ``arcs``, ``longestArc``,
+    ``arcClasses`` (arcs taken by the short, group and global kernels); ``timings``, ``deviceMs``, ``deviceStepsMs``
+    (split into SIMPLIFY_STEPS) as its siblings have them."""
+    def __init__(self, source, ringOffsets, vertexOffsets, vertices, ringArea2, sourceRing, keptVertex, tolerance=0.0,
+                 tolerance2q=0, rounds=0, arcs=None, longestArc=None, arcClasses=None, timings=None, deviceMs=None,
+                 deviceStepsMs=None):
+        junction = None
+        if getattr(source, 'junction', None) is not None:
+            junction = numpy.ascontiguousarray(numpy.asarray(source.junction)[keptVertex])
+        SegmentOutlines.__init__(self, source.maxSegId, ringOffsets, vertexOffsets, vertices, ringArea2, origin=source.origin,
+                                 fourConnected=source.fourConnected, rounds=rounds, edges=source.edges, timings=timings,
+                                 deviceMs=deviceMs, deviceStepsMs=deviceStepsMs, junction=junction)
+        self.source = source
+        self.sourceRing = sourceRing
+        self.keptVertex = keptVertex
+        self.tolerance = tolerance
+        self.tolerance2q = tolerance2q
+        self.arcs = arcs
+        self.longestArc = longestArc
+        self.arcClasses = arcClasses if arcClasses is not None else {}
+        self.droppedRings = (numpy.diff(numpy.asarray(source.ringOffsets)) - numpy.diff(numpy.asarray(ringOffsets))).astype(numpy.int64)
+        self.columns['droppedRings'] = self.droppedRings
+
+    def _holeShells(self, segId):
+        was = self.source._holeShells(segId)
+        now = {int(self.sourceRing[r]): r for r in self._ringRange(segId)}
+        owner = {}
+        for (s, r) in now.items():
+            if self.ringArea2[r] < 0 and was.get(s) in now and self.ringArea2[now[was[s]]] > 0:
+                owner[r] = now[was[s]]
+        return owner
+
+    def polygonsOf(self, segId):
+        """The id's polygons: a list of [shell, hole, ...], the shells in ring order.  A hole belongs to the shell its
+        source ring belongs to in ``source.polygonsOf``, mapped through ``sourceRing`` (the ray test of the base class
+        holds for rectilinear rings only); a hole whose shell was dropped is left out."""
+        return SegmentOutlines.polygonsOf(self, segId)
+
+
+def simplifySegmentOutlines(o, tolerance, path='auto'):
+    """
+    Topology-aware Douglas-Peucker simplification of all rings of a junction trace ``o`` on the GPU
+    (csrc/simplify.h): a SimplifiedOutlines.  ``tolerance`` is in vertex units, 0 <= tolerance <= 32768.
+
+    The rings are cut into arcs at their junction vertices (``o.junction``; a ring without any is one closed arc from
+    its vertex of the smallest (row, col)), and every arc is simplified on its own with both ends kept: between kept
+    points a and b the point of the largest distance from the chord a b is kept if that distance exceeds the
+    tolerance, and both halves are treated the same way (module docstring for the exact integer rule).  An arc is run
+    in opposite directions by the two rings that share it and every quantity is symmetric, so neighbours keep identical
+    vertices along a shared border: no slivers, no overlaps.  Arcs may still cross each other at large tolerances;
+    that is not checked.  A ring is dropped when fewer than three vertices remain or when its new ``ringArea2`` is 0 or
+    differs in sign from its source ring's; the surviving rings keep their order.
+
+    If ``o``'s rings are still the ones its trace left in HBM they are read in place; otherwise the rings and the
+    flags are uploaded once, which also serves rings built by hand (``SegmentOutlines(..., junction=flags)``).
+    ``path`` ('auto', 'short', 'group', 'global') forces one of the three arc size classes of the kernels for all arcs
+    that fit it, so that tests and measurements reach each class at any size; the result does not depend on it.
+
+    Refused before the GPU is touched: an ``o`` without ``junction`` (trace with ``junctions=True``), a tolerance
+    that is negative, NaN or above 32768, flags that are not uint8 of the vertices' length, the coordinate spans
+    calcSegmentHulls refuses, more than 2^31 - 8192 vertices, an unknown ``path``, and a working set larger than the
+    free HBM.
+    """
+    t0 = time.perf_counter()
+    if getattr(o, 'junction', None) is None:
+        raise PyShepSegOutlinesError("these outlines carry no junction flags: trace them with junctions=True")
+    T = tolerance2q(tolerance)
+    (ro, vo, v, a2, base, span) = _checkRings(o)
+    j = numpy.asarray(o.junction)
+    if j.dtype != numpy.uint8 or j.ndim != 1 or len(j) != len(v):
+        raise PyShepSegOutlinesError("junction must be a uint8 array with one entry per vertex ({})".format(len(v)))
+    j = numpy.ascontiguousarray(j)
+    if len(v) > MAX_SIMPLIFY_VERTICES or len(a2) > MAX_SIMPLIFY_VERTICES:
+        raise PyShepSegOutlinesError("{} vertices in {} rings: more than the {} one simplification can take".format(
+            len(v), len(a2), MAX_SIMPLIFY_VERTICES))
+    if not isinstance(path, str) or path not in SIMPLIFY_PATHS:
+        raise PyShepSegOutlinesError("path must be one of 'auto', 'short', 'group', 'global' (got {!r})".format(path))
+    path = SIMPLIFY_PATHS[path]
+    (S, nrings, nverts) = (int(o.maxSegId), len(a2), len(v))
+    c = _lib.ctx()
+    L = c._L
+    timings = {}
+    serial = _outlineSerial(c)
+    resident = (serial is not None and getattr(o, 'residentSerial', None) == serial and
+                getattr(o, '_residentCtx', None) == c.handle.value)
+    (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
+    c.check(L.shp_simplify_need(c.handle, nverts, nrings, S, 0 if resident else 1, ctypes.byref(need), ctypes.byref(free)))
+    if need.value > free.value:
+        raise PyShepSegOutlinesError("the simplification arrays of {} vertices, {} rings and {} ids need {} bytes of device memory, "
+                                     "{} are free".format(nverts, nrings, S + 1, need.value, free.value))
+    timings['need'] = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    ms = ctypes.c_double(0)
+    if resident:
+        c.check(L.shp_simplify_source(c.handle, None, None, None, None, None, S, nrings, nverts, ctypes.byref(ms)))
+    else:
+        c.check(L.shp_simplify_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(v), _lib.ptr(a2), _lib.ptr(j), S, nrings, nverts,
+                                      ctypes.byref(ms)))
+    timings['upload'] = time.perf_counter() - t1
+    timings['uploaded'] = not resident
+    timings['uploadDeviceMs'] = ms.value
+    t1 = time.perf_counter()
+    counts = numpy.zeros(10, dtype=numpy.int64)
+    steps = numpy.zeros(4, dtype=numpy.float64)
+    c.check(L.shp_simplify_build(c.handle, T, path, base[0], base[1], span[0], span[1], _lib.ptr(counts), _lib.ptr(steps)))
+    timings['build'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    (nr2, nv2) = (int(counts[0]), int(counts[1]))
+    ringOffsets = numpy.empty(S + 2, dtype=numpy.int64)
+    vertexOffsets = numpy.empty(nr2 + 1, dtype=numpy.int64)
+    vertices = numpy.empty((nv2, 2), dtype=numpy.int64)
+    ringArea2 = numpy.empty(nr2, dtype=numpy.int64)
+    sourceRing = numpy.empty(nr2, dtype=numpy.int64)
+    keptVertex = numpy.empty(nv2, dtype=numpy.int64)
+    c.check(L.shp_simplify_download(c.handle, _lib.ptr(ringOffsets), _lib.ptr(vertexOffsets), _lib.ptr(vertices), _lib.ptr(ringArea2),
+                                    _lib.ptr(sourceRing), _lib.ptr(keptVertex)))
+    timings['download'] = time.perf_counter() - t1
+    t1 = time.perf_counter()
+    out = SimplifiedOutlines(o, ringOffsets, vertexOffsets, vertices, ringArea2, sourceRing, keptVertex, tolerance=float(tolerance),
+                             tolerance2q=T, rounds=int(counts[2]), arcs=int(counts[3]), longestArc=int(counts[4]),
+                             arcClasses={'short': int(counts[5]), 'group': int(counts[6]), 'global': int(counts[7])},
+                             deviceMs=float(steps.sum()), deviceStepsMs=dict(zip(SIMPLIFY_STEPS, steps.tolist())))
+    timings['columns'] = time.perf_counter() - t1
+    timings['total'] = time.perf_counter() - t0
+    out.timings = timings
+    return out
