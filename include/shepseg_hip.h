@@ -833,8 +833,9 @@ int shp_simplify_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_o
  *  shp_hull_source: the rings to hull.  All four arrays NULL: the context's traced outlines, read in place (the counts
  *    are ignored; SHP_ERR_STATE without traced outlines).  Otherwise host arrays as shp_outline_download fills them
  *    (ring_offsets max_seg_id + 2, vertex_offsets n_rings + 1, vertices n_vertices x 2, ring_area2 n_rings), uploaded
- *    once; only the ends of the two offset arrays are checked here, that they ascend is the caller's to see to (no
- *    kernel indexes by them).  *upload_ms_out (may be NULL): device time of the copies.
+ *    once; both offset arrays must ascend from 0 to their counts, as shp_simplify_source asks (SHP_ERR_ARG "the vertex
+ *    offsets do not ascend at ring ...", "the ring offsets do not ascend at id ..."; earlier versions checked their ends
+ *    only: the two calls now share one check of the arrays).  *upload_ms_out (may be NULL): device time of the copies.
  *  shp_hull_build: (row_base, col_base) = the smallest row and column of all vertices, (row_span, col_span) = H and W.
  *    convex_only != 0: only the left-turn vertices of rings with ring_area2 > 0 are candidates, which holds the hull
  *    vertices of traced rings but not of arbitrary ones.  counts_out[3]: hull points, candidates, points kept after

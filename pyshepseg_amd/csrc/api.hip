@@ -1521,6 +1521,58 @@ static int chk_gathered(shp_ctx *ctx, const void *d_all, int64_t slot, int world
     return 0;
 }
 
+// ---- the rings something built on the outlines takes (rings.h) ----
+// the vertices and rings one call can take; sized: the refusal names the counts and the limit
+static int chk_ring_counts(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, uint32_t limit, bool sized)
+{
+    if (n_vertices >= 0 && n_vertices <= (int64_t)limit && n_rings >= 0 && n_rings <= (int64_t)limit) return 0;
+    if (!sized) SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    SHP_FAIL(ctx, SHP_ERR_ARG, "%lld vertices in %lld rings: more than %u", (long long)n_vertices, (long long)n_rings, limit);
+}
+
+// host arrays to upload (the counts are checked): flags: a junction flag per vertex belongs to them
+static int chk_ring_arrays(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t *vertex_offsets, const int64_t *vertices,
+                           const int64_t *ring_area2, const uint8_t *junction, bool flags, int64_t max_seg_id, int64_t n_rings,
+                           int64_t n_vertices)
+{
+    if (!ring_offsets || !vertex_offsets || (n_rings && !ring_area2) || (n_vertices && (!vertices || (flags && !junction))))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    if (ring_offsets[0] != 0 || ring_offsets[max_seg_id + 1] != n_rings || vertex_offsets[0] != 0 || vertex_offsets[n_rings] != n_vertices)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "the offsets do not span %lld rings and %lld vertices", (long long)n_rings, (long long)n_vertices);
+    // (the kernels index the vertices by the vertex offsets and the rings by the ring offsets)
+    for (int64_t k = 0; k < n_rings; k++)
+        if (vertex_offsets[k] > vertex_offsets[k + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the vertex offsets do not ascend at ring %lld", (long long)k);
+    for (int64_t i = 0; i <= max_seg_id; i++)
+        if (ring_offsets[i] > ring_offsets[i + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the ring offsets do not ascend at id %lld", (long long)i);
+    return 0;
+}
+
+// the smallest row and column of the vertices and their spans H, W: H W <= 2^32 and max(H, W) < 2^31 keep every
+// relative coordinate in 31 bits and every cross product within 2^33
+static int chk_base_spans(shp_ctx *ctx, int64_t row_base, int64_t col_base, int64_t row_span, int64_t col_span)
+{
+    if (row_span < 0 || col_span < 0 || row_span > 0x7fffffffll || col_span > 0x7fffffffll ||
+        (unsigned long long)row_span * (unsigned long long)col_span > (1ull << 32))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "spans (%lld, %lld)", (long long)row_span, (long long)col_span);
+    if (row_base < -(1ll << 62) || row_base > (1ll << 62) || col_base < -(1ll << 62) || col_base > (1ll << 62))
+        SHP_FAIL(ctx, SHP_ERR_ARG, "base (%lld, %lld)", (long long)row_base, (long long)col_base);
+    return 0;
+}
+
+// resident rings must still be the ones taken; if not, the holder's stage goes back to "none" and `source` is named
+static int chk_rings_current(shp_ctx *ctx, const RingSource &src, int &stage, const char *source)
+{
+    if (ring_source_current(ctx, src)) return 0;
+    stage = 0;
+    SHP_FAIL(ctx, SHP_ERR_STATE, "the traced outlines have been replaced: %s must come first", source);
+}
+
+static int need_traced(shp_ctx *ctx)
+{
+    if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+    return 0;
+}
+
 static int need_table(shp_ctx *ctx)
 {
     if (!ctx->nbr_tab.finished)
@@ -1714,7 +1766,7 @@ API int shp_outline_trace(shp_ctx *ctx, int64_t row0, int64_t col0, int64_t *cou
 API int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_offsets, int64_t *vertices, int64_t *ring_area2)
 {
     CHK(enter(ctx));
-    if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+    CHK(need_traced(ctx));
     if (!ring_offsets || !vertex_offsets || (ctx->outline.rings && (!vertices || !ring_area2))) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_outline_download(ctx, ring_offsets, vertex_offsets, vertices, ring_area2);
 }
@@ -1730,7 +1782,7 @@ API int shp_outline_junctions(shp_ctx *ctx, int on)
 API int shp_outline_download_junction(shp_ctx *ctx, uint8_t *junction)
 {
     CHK(enter(ctx));
-    if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+    CHK(need_traced(ctx));
     if (!ctx->outline.has_flags) SHP_FAIL(ctx, SHP_ERR_STATE, "the outlines were traced without junctions: shp_outline_junctions must come first");
     if (ctx->outline.verts && !junction) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     return run_outline_download_junction(ctx, junction);
@@ -1753,8 +1805,7 @@ API int shp_hull_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int64_t
     CHK(enter(ctx));
     if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     CHK(chk_max_seg_id(ctx, max_seg_id));
-    if (n_vertices < 0 || n_vertices > (int64_t)OL_MAX_ITEMS || n_rings < 0 || n_rings > (int64_t)OL_MAX_ITEMS)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(chk_ring_counts(ctx, n_vertices, n_rings, OL_MAX_ITEMS, false));
     return run_hull_need(ctx, (size_t)n_vertices, (size_t)n_rings, (size_t)max_seg_id, upload, (long long *)need_out,
                          (long long *)free_out);
 }
@@ -1766,15 +1817,12 @@ API int shp_hull_source(shp_ctx *ctx, const int64_t *ring_offsets, const int64_t
     ctx->hull.stage = 0;
     if (upload_ms_out) *upload_ms_out = 0.0;
     if (!ring_offsets && !vertex_offsets && !vertices && !ring_area2) {
-        if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+        CHK(need_traced(ctx));
         return run_hull_source(ctx, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr);
     }
     CHK(chk_max_seg_id(ctx, max_seg_id));
-    if (n_vertices < 0 || n_vertices > (int64_t)OL_MAX_ITEMS || n_rings < 0 || n_rings > (int64_t)OL_MAX_ITEMS)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "%lld vertices in %lld rings: more than %u", (long long)n_vertices, (long long)n_rings, OL_MAX_ITEMS);
-    if (!ring_offsets || !vertex_offsets || (n_rings && !ring_area2) || (n_vertices && !vertices)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (ring_offsets[0] != 0 || ring_offsets[max_seg_id + 1] != n_rings || vertex_offsets[0] != 0 || vertex_offsets[n_rings] != n_vertices)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "the offsets do not span %lld rings and %lld vertices", (long long)n_rings, (long long)n_vertices);
+    CHK(chk_ring_counts(ctx, n_vertices, n_rings, OL_MAX_ITEMS, true));
+    CHK(chk_ring_arrays(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, nullptr, false, max_seg_id, n_rings, n_vertices));
     return run_hull_source(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, (uint32_t)max_seg_id, (uint32_t)n_rings,
                            (uint32_t)n_vertices, upload_ms_out);
 }
@@ -1784,16 +1832,9 @@ API int shp_hull_build(shp_ctx *ctx, int64_t row_base, int64_t col_base, int64_t
 {
     CHK(enter(ctx));
     if (ctx->hull.stage < 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no rings to hull: shp_hull_source must come first");
-    if (ctx->hull.resident && (ctx->outline.stage != 2 || ctx->outline.serial != ctx->hull.outline_serial)) {
-        ctx->hull.stage = 0;
-        SHP_FAIL(ctx, SHP_ERR_STATE, "the traced outlines have been replaced: shp_hull_source must come first");
-    }
+    CHK(chk_rings_current(ctx, ctx->hull.src, ctx->hull.stage, "shp_hull_source"));
     if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (row_span < 0 || col_span < 0 || row_span > 0x7fffffffll || col_span > 0x7fffffffll ||
-        (unsigned long long)row_span * (unsigned long long)col_span > (1ull << 32))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "spans (%lld, %lld)", (long long)row_span, (long long)col_span);
-    if (row_base < -(1ll << 62) || row_base > (1ll << 62) || col_base < -(1ll << 62) || col_base > (1ll << 62))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "base (%lld, %lld)", (long long)row_base, (long long)col_base);
+    CHK(chk_base_spans(ctx, row_base, col_base, row_span, col_span));
     CHK(run_hull_build(ctx, (long long)row_base, (long long)col_base, (uint32_t)row_span, (uint32_t)col_span, convex_only ? 1 : 0));
     counts_out[0] = (int64_t)ctx->hull.nh;
     counts_out[1] = (int64_t)ctx->hull.ncand;
@@ -1819,8 +1860,7 @@ API int shp_simplify_need(shp_ctx *ctx, int64_t n_vertices, int64_t n_rings, int
     CHK(enter(ctx));
     if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     CHK(chk_max_seg_id(ctx, max_seg_id));
-    if (n_vertices < 0 || n_vertices > (int64_t)SP_MAX_VERTS || n_rings < 0 || n_rings > (int64_t)SP_MAX_VERTS)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    CHK(chk_ring_counts(ctx, n_vertices, n_rings, SP_MAX_VERTS, false));
     return run_simplify_need(ctx, (size_t)n_vertices, (size_t)n_rings, (size_t)max_seg_id, upload, (long long *)need_out,
                              (long long *)free_out);
 }
@@ -1833,24 +1873,15 @@ API int shp_simplify_source(shp_ctx *ctx, const int64_t *ring_offsets, const int
     ctx->simplify.stage = 0;
     if (upload_ms_out) *upload_ms_out = 0.0;
     if (!ring_offsets && !vertex_offsets && !vertices && !ring_area2 && !junction) {
-        if (ctx->outline.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no traced outlines: shp_outline_trace must come first");
+        CHK(need_traced(ctx));
         if (!ctx->outline.has_flags)
             SHP_FAIL(ctx, SHP_ERR_STATE, "the outlines were traced without junctions: shp_outline_junctions must come first");
         if (ctx->outline.verts > SP_MAX_VERTS) SHP_FAIL(ctx, SHP_ERR_ARG, "%u vertices: more than %u", ctx->outline.verts, SP_MAX_VERTS);
         return run_simplify_source(ctx, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr);
     }
     CHK(chk_max_seg_id(ctx, max_seg_id));
-    if (n_vertices < 0 || n_vertices > (int64_t)SP_MAX_VERTS || n_rings < 0 || n_rings > (int64_t)SP_MAX_VERTS)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "%lld vertices in %lld rings: more than %u", (long long)n_vertices, (long long)n_rings, SP_MAX_VERTS);
-    if (!ring_offsets || !vertex_offsets || (n_rings && !ring_area2) || (n_vertices && (!vertices || !junction)))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
-    if (ring_offsets[0] != 0 || ring_offsets[max_seg_id + 1] != n_rings || vertex_offsets[0] != 0 || vertex_offsets[n_rings] != n_vertices)
-        SHP_FAIL(ctx, SHP_ERR_ARG, "the offsets do not span %lld rings and %lld vertices", (long long)n_rings, (long long)n_vertices);
-    // (the kernels index the vertices by the vertex offsets and the rings by the ring offsets)
-    for (int64_t k = 0; k < n_rings; k++)
-        if (vertex_offsets[k] > vertex_offsets[k + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the vertex offsets do not ascend at ring %lld", (long long)k);
-    for (int64_t i = 0; i <= max_seg_id; i++)
-        if (ring_offsets[i] > ring_offsets[i + 1]) SHP_FAIL(ctx, SHP_ERR_ARG, "the ring offsets do not ascend at id %lld", (long long)i);
+    CHK(chk_ring_counts(ctx, n_vertices, n_rings, SP_MAX_VERTS, true));
+    CHK(chk_ring_arrays(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, junction, true, max_seg_id, n_rings, n_vertices));
     return run_simplify_source(ctx, ring_offsets, vertex_offsets, vertices, ring_area2, junction, (uint32_t)max_seg_id, (uint32_t)n_rings,
                                (uint32_t)n_vertices, upload_ms_out);
 }
@@ -1860,18 +1891,11 @@ API int shp_simplify_build(shp_ctx *ctx, uint64_t tolerance2q, int path, int64_t
 {
     CHK(enter(ctx));
     if (ctx->simplify.stage < 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no rings to simplify: shp_simplify_source must come first");
-    if (ctx->simplify.resident && (ctx->outline.stage != 2 || ctx->outline.serial != ctx->simplify.outline_serial)) {
-        ctx->simplify.stage = 0;
-        SHP_FAIL(ctx, SHP_ERR_STATE, "the traced outlines have been replaced: shp_simplify_source must come first");
-    }
+    CHK(chk_rings_current(ctx, ctx->simplify.src, ctx->simplify.stage, "shp_simplify_source"));
     if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
     if (tolerance2q > (1ull << 46)) SHP_FAIL(ctx, SHP_ERR_ARG, "tolerance2q %llu is above 2^46", (unsigned long long)tolerance2q);
     if (path < 0 || path > 3) SHP_FAIL(ctx, SHP_ERR_ARG, "path %d is none of 0 (auto), 1 (short), 2 (group), 3 (global)", path);
-    if (row_span < 0 || col_span < 0 || row_span > 0x7fffffffll || col_span > 0x7fffffffll ||
-        (unsigned long long)row_span * (unsigned long long)col_span > (1ull << 32))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "spans (%lld, %lld)", (long long)row_span, (long long)col_span);
-    if (row_base < -(1ll << 62) || row_base > (1ll << 62) || col_base < -(1ll << 62) || col_base > (1ll << 62))
-        SHP_FAIL(ctx, SHP_ERR_ARG, "base (%lld, %lld)", (long long)row_base, (long long)col_base);
+    CHK(chk_base_spans(ctx, row_base, col_base, row_span, col_span));
     CHK(run_simplify_build(ctx, (unsigned long long)tolerance2q, path, (long long)row_base, (long long)col_base));
     const SimplifyState &z = ctx->simplify;
     const int64_t counts[10] = {z.rings, z.verts, z.rounds, z.narcs, z.longest, z.nshort, z.ngroup, z.nglobal, z.kept, 0};

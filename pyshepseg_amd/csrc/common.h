@@ -184,14 +184,22 @@ struct OutlineState {
     unsigned long long serial = 0;  // shp_ctx::outline_calls when these edges were counted: which outlines these are
 };
 
-// the hulls of the outline rings between shp_hull_source, shp_hull_build and shp_hull_download (hull.h), in buffers
-// of their own (hl_*): the outline state, the neighbour table, the group lists and the shape table stay where they
-// are.  resident: the rings are read in place from the outline buffers, which must still hold outline_serial.
-struct HullState {
-    int stage = 0;                  // 0 none, 1 rings known, 2 hulls built
+// where the rings come from that something built on the outlines works on (rings.h, which holds everything that reads
+// or writes this; the struct stands here because the states below hold one each).  resident: the rings are read in
+// place from the outline buffers, which must still hold the outlines of outline_serial; otherwise they were uploaded
+// into buffers of the holder's own.
+struct RingSource {
     bool resident = false;
     unsigned long long outline_serial = 0;
-    uint32_t S = 0, nr = 0, nv = 0;
+    uint32_t S = 0, nr = 0, nv = 0;     // the ids 0 .. S, rings, vertices
+};
+
+// the hulls of the outline rings between shp_hull_source, shp_hull_build and shp_hull_download (hull.h), in buffers
+// of their own (hl_*): the outline state, the neighbour table, the group lists and the shape table stay where they
+// are.  src: the rings taken by shp_hull_source, its own instance (the simplification may hold other rings).
+struct HullState {
+    int stage = 0;                  // 0 none, 1 rings known, 2 hulls built
+    RingSource src;
     uint32_t ncand = 0, nkept = 0, nh = 0;      // candidates, points kept of them, hull points
     size_t hoff64_at = 0, area_at = 0, feret_at = 0;    // where the int64 offsets, areas and diameters lie in hl_id
     double ms[5] = {};              // device time: candidates, order, chains, points, reach
@@ -219,12 +227,11 @@ struct HullState {
 
 // the simplified rings between shp_simplify_source, shp_simplify_build and shp_simplify_download (simplify.h), in
 // buffers of their own (sp_*): the outlines, the hulls, the neighbour table, the group lists and the shape table stay
-// where they are.  resident: rings and junction flags are read in place from the outline buffers.
+// where they are.  src: the rings and junction flags taken by shp_simplify_source, its own instance (the hulls may
+// hold other rings).
 struct SimplifyState {
     int stage = 0;                  // 0 none, 1 rings known, 2 simplified
-    bool resident = false;
-    unsigned long long outline_serial = 0;
-    uint32_t S = 0, nr = 0, nv = 0;
+    RingSource src;
     uint32_t narcs = 0, longest = 0, rounds = 0, nshort = 0, ngroup = 0, nglobal = 0, kept = 0, rings = 0, verts = 0;
     size_t off[6] = {};             // where ring offsets, vertex offsets, vertices, areas, source rings, kept vertices lie in sp_out
     double ms[4] = {};              // device time: anchors and arcs, the rounds, the ring areas and the drop rule, the emission

@@ -4,7 +4,7 @@
 //
 // Input: the rings as outline.h leaves them (vertices as (row, col) int64 pairs, int64 vertex offsets per ring, int64
 // ring offsets per id, ringArea2), either still in the context's outline buffers (read in place) or uploaded into
-// buffers of this file's own.  (r0, c0) = the smallest row and column of all vertices; the host has checked that the
+// buffers of this file's own (hl_vtx, hl_voff, hl_roff, hl_area): rings.h decides and makes the view.  (r0, c0) = the smallest row and column of all vertices; the host has checked that the
 // spans H and W satisfy H W <= 2^32 and max(H, W) < 2^31, so coordinates relative to (r0, c0) fit 31 bits, every cross
 // product stays within 2^33 and every squared distance fits int64.  With x = col and y = row a positive ringArea2 is a
 // counter-clockwise polygon, cross(a, b, c) = (b.x - a.x)(c.y - a.y) - (b.y - a.y)(c.x - a.x) > 0 a left turn.
@@ -43,30 +43,15 @@
 #include "scan.h"
 #include "sort.h"
 #include "outline.h"
+#include "rings.h"
 
 #define HL_WAVE_MAX 64u             // kept points of an id up to which its chains are built in registers
 #define HL_CTR_WORDS 8u             // device words of hl_ctr: [0] candidates, [1] kept points, [2] hull points
 
-struct HlSrc {
-    const longlong2 *vtx;           // nv vertices (row, col)
-    const long long *voff;          // nr + 1
-    const long long *roff;          // S + 2
-    const long long *area2;         // nr
-    uint32_t nv, nr, S;
+struct HlSrc : RingView {           // (no flags: jflag is NULL)
     long long r0, c0;
     int convex_only;
 };
-
-// the ring of vertex v (the last k with voff[k] <= v) and the id of ring k (the last i with roff[i] <= k)
-__device__ __forceinline__ uint32_t hl_last_le(const long long *__restrict__ a, uint32_t n, long long v)
-{
-    uint32_t lo = 0u, hi = n;               // a[lo] <= v < a[hi] (a[n] beyond every v)
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (a[mid] <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ long long hl_cross(long long ax, long long ay, long long bx, long long by, long long cx, long long cy)
 {
@@ -76,7 +61,7 @@ __device__ __forceinline__ long long hl_cross(long long ax, long long ay, long l
 // vertex v is a candidate; *ring_out its ring
 __device__ __forceinline__ bool hl_is_cand(const HlSrc &s, uint32_t v, uint32_t *ring_out)
 {
-    const uint32_t k = hl_last_le(s.voff, s.nr, (long long)v);
+    const uint32_t k = ring_last_le(s.voff, s.nr, (long long)v);
     *ring_out = k;
     if (!s.convex_only) return true;
     if (s.area2[k] <= 0) return false;
@@ -107,7 +92,7 @@ __global__ __launch_bounds__(256) void k_hl_cand(HlSrc s, const uint32_t *__rest
     const uint32_t at = pos[v];
     if (at >= ncand) return;                            // (cannot happen: pos counts the same flags)
     const longlong2 p = s.vtx[v];
-    cid[at] = hl_last_le(s.roff, s.S + 1u, (long long)k);
+    cid[at] = ring_last_le(s.roff, s.S + 1u, (long long)k);
     ccol[at] = (uint32_t)(p.y - s.c0);
     crow[at] = (uint32_t)(p.x - s.r0);
 }
@@ -355,6 +340,9 @@ __global__ __launch_bounds__(256) void k_hl_reach(const longlong2 *__restrict__ 
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
+// the buffers uploaded rings go into
+static inline RingBufs hl_ring_bufs(shp_ctx *ctx) { return RingBufs{ctx->hl_vtx, ctx->hl_voff, ctx->hl_roff, ctx->hl_area, nullptr}; }
+
 // bytes of an id's rows in hl_id: poff, hcnt, hstart, hoff (4 each, S + 2 rows), hoff64, area2, feret2 (8 each)
 #define HL_ID_BYTES 40u
 
@@ -362,10 +350,7 @@ __global__ __launch_bounds__(256) void k_hl_reach(const longlong2 *__restrict__ 
 // candidates <= nv and hull points <= nv; upload: the rings go into buffers of this file's own
 static int run_hull_need(shp_ctx *ctx, size_t nv, size_t nr, size_t S, int upload, long long *need_out, long long *free_out)
 {
-    size_t need = 0;
-    if (upload)
-        need += ol_grown(ctx->hl_vtx, nv * 16) + ol_grown(ctx->hl_voff, (nr + 1) * 8) + ol_grown(ctx->hl_area, nr * 8) +
-                ol_grown(ctx->hl_roff, (S + 2) * 8);
+    size_t need = upload ? ring_upload_need(hl_ring_bufs(ctx), nv, nr, S) : 0;
     need += ol_grown(ctx->hl_pos, nv * 4) + ol_grown(ctx->hl_cid, nv * 4) + ol_grown(ctx->hl_ccol, nv * 4) + ol_grown(ctx->hl_crow, nv * 4);
     need += ol_grown(ctx->hl_k, nv * 4) + ol_grown(ctx->hl_v, nv * 4);
     need += ol_grown(ctx->sort_k0, nv * 4) + ol_grown(ctx->sort_k1, nv * 4) + ol_grown(ctx->sort_v1, nv * 4) + ol_grown(ctx->pix, nv * 4);
@@ -387,28 +372,8 @@ static int run_hull_source(shp_ctx *ctx, const int64_t *ring_offsets, const int6
                            const int64_t *ring_area2, uint32_t S, uint32_t nr, uint32_t nv, double *upload_ms_out)
 {
     HullState &h = ctx->hull;
-    hipStream_t st = ctx->stream;
     h = HullState{};
-    if (!ring_offsets) {
-        const OutlineState &o = ctx->outline;
-        h.resident = true;
-        h.outline_serial = o.serial;
-        h.S = o.S; h.nr = o.rings; h.nv = o.verts;
-    } else {
-        CHK(buf_ensure(ctx, ctx->hl_roff, ((size_t)S + 2) * 8));
-        CHK(buf_ensure(ctx, ctx->hl_voff, ((size_t)nr + 1) * 8));
-        CHK(buf_ensure(ctx, ctx->hl_area, (size_t)nr * 8));
-        CHK(buf_ensure(ctx, ctx->hl_vtx, (size_t)nv * 16));
-        HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->hl_roff.p, ring_offsets, ((size_t)S + 2) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->hl_voff.p, vertex_offsets, ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nr) HIPCHK(ctx, hipMemcpyAsync(ctx->hl_area.p, ring_area2, (size_t)nr * 8, hipMemcpyHostToDevice, st));
-        if (nv) HIPCHK(ctx, hipMemcpyAsync(ctx->hl_vtx.p, vertices, (size_t)nv * 16, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (upload_ms_out) *upload_ms_out = ol_elapsed(ctx->ev[0], ctx->ev[1]);
-        h.S = S; h.nr = nr; h.nv = nv;
-    }
+    CHK(ring_source_take(ctx, h.src, hl_ring_bufs(ctx), ring_offsets, vertex_offsets, vertices, ring_area2, nullptr, S, nr, nv, upload_ms_out));
     h.stage = 1;
     return 0;
 }
@@ -420,16 +385,8 @@ static int run_hull_build(shp_ctx *ctx, long long r0, long long c0, uint32_t row
     h.stage = 0;
     h.nh = h.ncand = h.nkept = 0u;
     for (int i = 0; i < 5; i++) h.ms[i] = 0.0;
-    const uint32_t nv = h.nv, nr = h.nr, S = h.S, nid = S + 1u;
-    HlSrc src;
-    if (h.resident) {
-        const char *ring = (const char *)ctx->ol_ring.p;
-        src = HlSrc{bp<longlong2>(ctx->ol_vtx), (const long long *)(ring + ctx->outline.voff64_at), bp<long long>(ctx->ol_roff),
-                    (const long long *)(ring + ctx->outline.area_at), nv, nr, S, r0, c0, convex_only};
-    } else {
-        src = HlSrc{bp<longlong2>(ctx->hl_vtx), bp<long long>(ctx->hl_voff), bp<long long>(ctx->hl_roff), bp<long long>(ctx->hl_area),
-                    nv, nr, S, r0, c0, convex_only};
-    }
+    const uint32_t nv = h.src.nv, nr = h.src.nr, S = h.src.S, nid = S + 1u;
+    const HlSrc src{ring_view(ctx, h.src, hl_ring_bufs(ctx)), r0, c0, convex_only};
     // hl_id: poff, hcnt, hstart, hoff (S + 2 uint32 each, 16-byte aligned starts), then hoff64 (S + 2), area2, feret2 (S + 1)
     const size_t q = ((size_t)S + 2 + 3) & ~(size_t)3;
     CHK(buf_ensure(ctx, ctx->hl_id, q * 16 + ((size_t)S + 2) * 24));
@@ -544,9 +501,9 @@ static int run_hull_download(shp_ctx *ctx, int64_t *hull_offsets, int64_t *hull_
     const HullState &h = ctx->hull;
     hipStream_t st = ctx->stream;
     const char *id = (const char *)ctx->hl_id.p;
-    HIPCHK(ctx, hipMemcpyAsync(hull_offsets, id + h.hoff64_at, ((size_t)h.S + 2) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(hull_area2, id + h.area_at, ((size_t)h.S + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipMemcpyAsync(feret_max2, id + h.feret_at, ((size_t)h.S + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hull_offsets, id + h.hoff64_at, ((size_t)h.src.S + 2) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(hull_area2, id + h.area_at, ((size_t)h.src.S + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(feret_max2, id + h.feret_at, ((size_t)h.src.S + 1) * 8, hipMemcpyDeviceToHost, st));
     if (h.nh) {
         HIPCHK(ctx, hipMemcpyAsync(hull_points, ctx->hl_pts.p, (size_t)h.nh * 16, hipMemcpyDeviceToHost, st));
         HIPCHK(ctx, hipMemcpyAsync(hull_reach, ctx->hl_reach.p, (size_t)h.nh * 8, hipMemcpyDeviceToHost, st));

@@ -3,7 +3,8 @@
 //
 // Input: rings as outline.h leaves them with the junction switch on (vertices as (row, col) int64 pairs, int64 vertex
 // offsets per ring, int64 ring offsets per id, ringArea2, a junction flag per vertex), still in the context's outline
-// buffers (read in place) or uploaded into buffers of this file's own.  (r0, c0) = the smallest row and column of all
+// buffers (read in place) or uploaded into buffers of this file's own (sp_vtx, sp_voff, sp_roff, sp_area, sp_jflag):
+// rings.h decides and makes the view.  (r0, c0) = the smallest row and column of all
 // vertices; the host has checked that the spans H and W satisfy H W <= 2^32 and max(H, W) < 2^31, so coordinates
 // relative to (r0, c0) fit 31 bits, every cross product stays within 2^33 and every squared distance fits int64.
 //
@@ -55,7 +56,7 @@
 #include "common.h"
 #include "scan.h"
 #include "outline.h"
-#include "hull.h"
+#include "rings.h"
 
 #define SP_SHORT_MAX 64u            // points of an arc up to which one wavefront takes it
 #define SP_GROUP_MAX 1024u          // points of an arc up to which one workgroup takes it in LDS
@@ -63,13 +64,7 @@
 // device words of sp_ctr
 enum { SPC_ARCS = 0, SPC_NSHORT, SPC_NGROUP, SPC_NPTS, SPC_LONGEST, SPC_ROUNDS, SPC_KEPT, SPC_RINGS, SPC_VERTS, SPC_FLAG, SPC_WORDS = 16 };
 
-struct SpSrc {
-    const longlong2 *vtx;           // nv vertices (row, col)
-    const long long *voff;          // nr + 1
-    const long long *roff;          // S + 2
-    const long long *area2;         // nr
-    const uint8_t *jflag;           // nv
-    uint32_t nv, nr, S;
+struct SpSrc : RingView {           // (with the flags)
     long long r0, c0;
 };
 
@@ -99,7 +94,7 @@ __device__ __forceinline__ bool sp_exceeds(unsigned long long m, uint32_t ar, ui
 __global__ __launch_bounds__(256) void k_sp_ringof(SpSrc s, uint32_t *__restrict__ vring)
 {
     const size_t i = (size_t)blockIdx.x * OL_BLOCK + threadIdx.x;
-    if (i < s.nv) vring[i] = hl_last_le(s.voff, s.nr, (long long)i);
+    if (i < s.nv) vring[i] = ring_last_le(s.voff, s.nr, (long long)i);
 }
 
 __global__ __launch_bounds__(256) void k_sp_flagged(SpSrc s, const uint32_t *__restrict__ vring, uint32_t *__restrict__ hasj)
@@ -455,6 +450,9 @@ __global__ __launch_bounds__(256) void k_sp_emit_id(SpSrc s, const uint32_t *__r
 }
 
 // ---- host side --------------------------------------------------------------------------------------------
+// the buffers uploaded rings and flags go into
+static inline RingBufs sp_ring_bufs(shp_ctx *ctx) { return RingBufs{ctx->sp_vtx, ctx->sp_voff, ctx->sp_roff, ctx->sp_area, &ctx->sp_jflag}; }
+
 // bytes of a ring's rows in sp_ring: minkey, narea (8 each), hasj, minidx, alive, kcnt, rpos, vo2 (4 each)
 #define SP_RING_BYTES 40u
 #define SP_ARC_BYTES 24u            // avtx, acnt, gcnt, gpoff, slist, glist
@@ -469,10 +467,7 @@ static inline size_t sp_out_bytes(size_t nv2, size_t nr2, size_t S)
 // <= nv, points of the global class <= 2 nv, kept vertices <= nv; upload: the rings go into buffers of this file's own
 static int run_simplify_need(shp_ctx *ctx, size_t nv, size_t nr, size_t S, int upload, long long *need_out, long long *free_out)
 {
-    size_t need = 0;
-    if (upload)
-        need += ol_grown(ctx->sp_vtx, nv * 16) + ol_grown(ctx->sp_voff, (nr + 1) * 8) + ol_grown(ctx->sp_area, nr * 8) +
-                ol_grown(ctx->sp_roff, (S + 2) * 8) + ol_grown(ctx->sp_jflag, nv);
+    size_t need = upload ? ring_upload_need(sp_ring_bufs(ctx), nv, nr, S) : 0;
     need += ol_grown(ctx->sp_ctr, SPC_WORDS * 4) + ol_grown(ctx->sp_keep, nv) + ol_grown(ctx->sp_pos, (nv + 4) * 8);
     need += ol_grown(ctx->sp_ring, (nr + 4) * SP_RING_BYTES) + ol_grown(ctx->sp_arc, (nv + 4) * SP_ARC_BYTES);
     need += ol_grown(ctx->sp_pt, (2 * nv + 4) * SP_PT_BYTES) + ol_grown(ctx->sp_kv, nv * 4);
@@ -491,30 +486,8 @@ static int run_simplify_source(shp_ctx *ctx, const int64_t *ring_offsets, const 
                                double *upload_ms_out)
 {
     SimplifyState &z = ctx->simplify;
-    hipStream_t st = ctx->stream;
     z = SimplifyState{};
-    if (!ring_offsets) {
-        const OutlineState &o = ctx->outline;
-        z.resident = true;
-        z.outline_serial = o.serial;
-        z.S = o.S; z.nr = o.rings; z.nv = o.verts;
-    } else {
-        CHK(buf_ensure(ctx, ctx->sp_roff, ((size_t)S + 2) * 8));
-        CHK(buf_ensure(ctx, ctx->sp_voff, ((size_t)nr + 1) * 8));
-        CHK(buf_ensure(ctx, ctx->sp_area, (size_t)nr * 8));
-        CHK(buf_ensure(ctx, ctx->sp_vtx, (size_t)nv * 16));
-        CHK(buf_ensure(ctx, ctx->sp_jflag, nv));
-        HIPCHK(ctx, hipEventRecord(ctx->ev[0], st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sp_roff.p, ring_offsets, ((size_t)S + 2) * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipMemcpyAsync(ctx->sp_voff.p, vertex_offsets, ((size_t)nr + 1) * 8, hipMemcpyHostToDevice, st));
-        if (nr) HIPCHK(ctx, hipMemcpyAsync(ctx->sp_area.p, ring_area2, (size_t)nr * 8, hipMemcpyHostToDevice, st));
-        if (nv) HIPCHK(ctx, hipMemcpyAsync(ctx->sp_vtx.p, vertices, (size_t)nv * 16, hipMemcpyHostToDevice, st));
-        if (nv) HIPCHK(ctx, hipMemcpyAsync(ctx->sp_jflag.p, junction, nv, hipMemcpyHostToDevice, st));
-        HIPCHK(ctx, hipEventRecord(ctx->ev[1], st));
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (upload_ms_out) *upload_ms_out = ol_elapsed(ctx->ev[0], ctx->ev[1]);
-        z.S = S; z.nr = nr; z.nv = nv;
-    }
+    CHK(ring_source_take(ctx, z.src, sp_ring_bufs(ctx), ring_offsets, vertex_offsets, vertices, ring_area2, junction, S, nr, nv, upload_ms_out));
     z.stage = 1;
     return 0;
 }
@@ -526,16 +499,8 @@ static int run_simplify_build(shp_ctx *ctx, unsigned long long T, int path, long
     z.stage = 0;
     z.narcs = z.longest = z.rounds = z.nshort = z.ngroup = z.nglobal = z.kept = z.rings = z.verts = 0u;
     for (int i = 0; i < 4; i++) z.ms[i] = 0.0;
-    const uint32_t nv = z.nv, nr = z.nr, S = z.S;
-    SpSrc src;
-    if (z.resident) {
-        const char *ring = (const char *)ctx->ol_ring.p;
-        src = SpSrc{bp<longlong2>(ctx->ol_vtx), (const long long *)(ring + ctx->outline.voff64_at), bp<long long>(ctx->ol_roff),
-                    (const long long *)(ring + ctx->outline.area_at), bp<uint8_t>(ctx->ol_jflag), nv, nr, S, r0, c0};
-    } else {
-        src = SpSrc{bp<longlong2>(ctx->sp_vtx), bp<long long>(ctx->sp_voff), bp<long long>(ctx->sp_roff), bp<long long>(ctx->sp_area),
-                    bp<uint8_t>(ctx->sp_jflag), nv, nr, S, r0, c0};
-    }
+    const uint32_t nv = z.src.nv, nr = z.src.nr, S = z.src.S;
+    const SpSrc src{ring_view(ctx, z.src, sp_ring_bufs(ctx)), r0, c0};
     CHK(buf_ensure(ctx, ctx->sp_ctr, SPC_WORDS * 4));
     uint32_t *ctr = bp<uint32_t>(ctx->sp_ctr);
     volatile uint32_t *hp = (volatile uint32_t *)ctx->h_pinned;
@@ -717,7 +682,7 @@ static int run_simplify_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *v
     const SimplifyState &z = ctx->simplify;
     hipStream_t st = ctx->stream;
     const char *out = (const char *)ctx->sp_out.p;
-    HIPCHK(ctx, hipMemcpyAsync(ring_offsets, out + z.off[0], ((size_t)z.S + 2) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(ring_offsets, out + z.off[0], ((size_t)z.src.S + 2) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipMemcpyAsync(vertex_offsets, out + z.off[1], ((size_t)z.rings + 1) * 8, hipMemcpyDeviceToHost, st));
     if (z.rings) {
         HIPCHK(ctx, hipMemcpyAsync(ring_area2, out + z.off[3], (size_t)z.rings * 8, hipMemcpyDeviceToHost, st));

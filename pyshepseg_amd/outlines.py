@@ -87,6 +87,11 @@ def columnsFromRings(ringOffsets, vertexOffsets, ringArea2):
             'holeArea': _segmentSums(numpy.where(ringArea2 < 0, -ringArea2, 0) // 2, ringOffsets)}
 
 
+def _checkSegId(segId, maxSegId):
+    if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= maxSegId:
+        raise PyShepSegOutlinesError("segment id must be an integer 0 .. {} (got {!r})".format(maxSegId, segId))
+
+
 class SegmentOutlines(object):
     """The result of traceSegmentOutlines, for the ids 0 .. ``maxSegId`` (S = maxSegId + 1 rows).
 
@@ -119,8 +124,7 @@ class SegmentOutlines(object):
         self.simplified = None      # a SimplifiedOutlines after traceSegmentOutlines(simplify=tolerance)
 
     def _ringRange(self, segId):
-        if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
-            raise PyShepSegOutlinesError("segment id must be an integer 0 .. {} (got {!r})".format(self.maxSegId, segId))
+        _checkSegId(segId, self.maxSegId)
         return range(int(self.ringOffsets[segId]), int(self.ringOffsets[segId + 1]))
 
     def ring(self, r):
@@ -469,8 +473,7 @@ class SegmentHulls(object):
 
     def hullOf(self, segId):
         """the id's hull: a (k, 2) array (a view of ``hullPoints``)"""
-        if isinstance(segId, (bool, numpy.bool_)) or not isinstance(segId, (int, numpy.integer)) or not 0 <= segId <= self.maxSegId:
-            raise PyShepSegOutlinesError("segment id must be an integer 0 .. {} (got {!r})".format(self.maxSegId, segId))
+        _checkSegId(segId, self.maxSegId)
         return self.hullPoints[int(self.hullOffsets[segId]):int(self.hullOffsets[segId + 1])]
 
 
@@ -523,6 +526,33 @@ def _checkRings(o):
     return (ro, vo, v, a2, base, span)
 
 
+def _takeRings(c, o, arrays, need, source, word, timings, t0):
+    """The rings a hull call or a simplification works on, taken on context ``c``: whether ``o``'s rings are still the
+    ones its trace left in HBM (they are then read in place, and nothing goes up).  ``arrays``: the checked ringOffsets,
+    vertexOffsets, vertices, ringArea2 (and the flags, where ``source`` takes them), which are uploaded otherwise;
+    ``need`` and ``source``: the library's pair of calls; ``word``: what the refusal calls the arrays.  Fills
+    ``timings['need']`` (from ``t0``: with the caller's checks, two passes over the vertices for their extent),
+    ``'upload'``, ``'uploaded'`` and ``'uploadDeviceMs'``."""
+    (S, nrings, nverts) = (int(o.maxSegId), len(arrays[3]), len(arrays[2]))
+    serial = _outlineSerial(c)
+    resident = (serial is not None and getattr(o, 'residentSerial', None) == serial and
+                getattr(o, '_residentCtx', None) == c.handle.value)
+    (bytesNeeded, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
+    c.check(need(c.handle, nverts, nrings, S, 0 if resident else 1, ctypes.byref(bytesNeeded), ctypes.byref(free)))
+    if bytesNeeded.value > free.value:
+        raise PyShepSegOutlinesError("the {} arrays of {} vertices, {} rings and {} ids need {} bytes of device memory, {} are "
+                                     "free".format(word, nverts, nrings, S + 1, bytesNeeded.value, free.value))
+    timings['need'] = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    ms = ctypes.c_double(0)
+    ptrs = [None if resident else _lib.ptr(a) for a in arrays]
+    c.check(source(c.handle, *ptrs, S, nrings, nverts, ctypes.byref(ms)))
+    timings['upload'] = time.perf_counter() - t1
+    timings['uploaded'] = not resident
+    timings['uploadDeviceMs'] = ms.value
+    return resident
+
+
 def calcSegmentHulls(o, missing=-9999):
     """
     The convex hull of every segment of a SegmentOutlines ``o``, on the GPU: a SegmentHulls, with the hull-based shape
@@ -547,29 +577,11 @@ def calcSegmentHulls(o, missing=-9999):
     """
     t0 = time.perf_counter()
     (ro, vo, v, a2, base, span) = _checkRings(o)
-    (S, nrings, nverts) = (int(o.maxSegId), len(a2), len(v))
+    S = int(o.maxSegId)
     c = _lib.ctx()
     L = c._L
     timings = {}
-    serial = _outlineSerial(c)
-    resident = (serial is not None and getattr(o, 'residentSerial', None) == serial and
-                getattr(o, '_residentCtx', None) == c.handle.value)
-    (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
-    c.check(L.shp_hull_need(c.handle, nverts, nrings, S, 0 if resident else 1, ctypes.byref(need), ctypes.byref(free)))
-    if need.value > free.value:
-        raise PyShepSegOutlinesError("the hull arrays of {} vertices, {} rings and {} ids need {} bytes of device memory, {} are "
-                                     "free".format(nverts, nrings, S + 1, need.value, free.value))
-    timings['need'] = time.perf_counter() - t0          # (with the checks: two passes over the vertices for their extent)
-    t1 = time.perf_counter()
-    ms = ctypes.c_double(0)
-    if resident:
-        c.check(L.shp_hull_source(c.handle, None, None, None, None, S, nrings, nverts, ctypes.byref(ms)))
-    else:
-        c.check(L.shp_hull_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(v), _lib.ptr(a2), S, nrings, nverts,
-                                  ctypes.byref(ms)))
-    timings['upload'] = time.perf_counter() - t1
-    timings['uploaded'] = not resident
-    timings['uploadDeviceMs'] = ms.value
+    resident = _takeRings(c, o, (ro, vo, v, a2), L.shp_hull_need, L.shp_hull_source, 'hull', timings, t0)
     t1 = time.perf_counter()
     counts = numpy.zeros(3, dtype=numpy.int64)
     steps = numpy.zeros(5, dtype=numpy.float64)
@@ -590,15 +602,11 @@ def calcSegmentHulls(o, missing=-9999):
     sums = {'numHullVertices': numpy.diff(hullOffsets), 'hullArea2': hullArea2, 'feretMax2': feretMax2}
     columns = dict(sums)
     columns.update(hullColumnsFromSums(sums, hullOffsets, hullPoints, hullReach, _segmentSums(a2, ro),
-                                       _segmentSums_f(_ringLengths(vo, v), ro), missing))
+                                       _perId(_ringLengths(vo, v), ro, numpy.add, 0.0), missing))
     timings['columns'] = time.perf_counter() - t1
     timings['total'] = time.perf_counter() - t0
     return SegmentHulls(S, hullOffsets, hullPoints, hullReach, sums, columns, timings=timings, deviceMs=float(steps.sum()),
                         deviceStepsMs=dict(zip(HULL_STEPS, steps.tolist())), candidates=int(counts[1]), kept=int(counts[2]))
-
-
-def _segmentSums_f(values, offsets):
-    return _perId(values, offsets, numpy.add, 0.0)
 
 
 # ---- Douglas-Peucker simplification of the rings, shared borders staying shared (csrc/simplify.h) ------------------------
@@ -707,29 +715,11 @@ def simplifySegmentOutlines(o, tolerance, path='auto'):
     if not isinstance(path, str) or path not in SIMPLIFY_PATHS:
         raise PyShepSegOutlinesError("path must be one of 'auto', 'short', 'group', 'global' (got {!r})".format(path))
     path = SIMPLIFY_PATHS[path]
-    (S, nrings, nverts) = (int(o.maxSegId), len(a2), len(v))
+    S = int(o.maxSegId)
     c = _lib.ctx()
     L = c._L
     timings = {}
-    serial = _outlineSerial(c)
-    resident = (serial is not None and getattr(o, 'residentSerial', None) == serial and
-                getattr(o, '_residentCtx', None) == c.handle.value)
-    (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
-    c.check(L.shp_simplify_need(c.handle, nverts, nrings, S, 0 if resident else 1, ctypes.byref(need), ctypes.byref(free)))
-    if need.value > free.value:
-        raise PyShepSegOutlinesError("the simplification arrays of {} vertices, {} rings and {} ids need {} bytes of device memory, "
-                                     "{} are free".format(nverts, nrings, S + 1, need.value, free.value))
-    timings['need'] = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    ms = ctypes.c_double(0)
-    if resident:
-        c.check(L.shp_simplify_source(c.handle, None, None, None, None, None, S, nrings, nverts, ctypes.byref(ms)))
-    else:
-        c.check(L.shp_simplify_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(v), _lib.ptr(a2), _lib.ptr(j), S, nrings, nverts,
-                                      ctypes.byref(ms)))
-    timings['upload'] = time.perf_counter() - t1
-    timings['uploaded'] = not resident
-    timings['uploadDeviceMs'] = ms.value
+    _takeRings(c, o, (ro, vo, v, a2, j), L.shp_simplify_need, L.shp_simplify_source, 'simplification', timings, t0)
     t1 = time.perf_counter()
     counts = numpy.zeros(10, dtype=numpy.int64)
     steps = numpy.zeros(4, dtype=numpy.float64)

@@ -20,6 +20,7 @@ import pytest
 import hull_cases as hc
 import neighbour_cases as nc
 import outline_cases as oc
+import simplify_cases as sc
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -373,6 +374,68 @@ def test_sources():
     assert_equal(hulls(by_hand(mo)), mo.hulls)
 
 
+@functools.lru_cache(maxsize=None)
+def two_ring_sets():
+    """A: the junction trace of the worked example (ids 0 .. 3, 3 rings, 19 vertices), with its hulls; B: that of a
+    staircase (ids 0 .. 2, 2 rings, 26 vertices), with its simplification at tolerance 1 (6 vertices remain).  Both from
+    the sequential models, nothing from the GPU."""
+    import types
+    (a, b) = (sc.reference_junction_trace(oc.EXAMPLE), sc.reference_junction_trace(oc.staircase(6)))
+    assert (a['maxSegId'], len(a['ringArea2']), len(a['vertices'])) == (3, 3, 19)
+    assert (b['maxSegId'], len(b['ringArea2']), len(b['vertices'])) == (2, 2, 26)
+    return (a, hc.reference_hulls(types.SimpleNamespace(**a)), b, sc.reference_simplify(b, 1.0))
+
+
+@pytest.mark.parametrize('resident', ['neither', 'hulls', 'simplification'])
+def test_the_hull_source_and_the_simplification_source_stay_independent(resident):
+    """The hulls take rings A, then the simplification takes rings B, and only then both are built and downloaded: each
+    must have worked on its own rings, whether both were uploaded or one of the two reads a trace's rings in place."""
+    from pyshepseg_amd import _lib
+    (a, hulls_a, b, simplified_b) = two_ring_sets()
+    c = _lib.ctx()
+    L = c._L
+
+    def extent(r):
+        (lo, hi) = (r['vertices'].min(axis=0), r['vertices'].max(axis=0))
+        return [int(x) for x in (lo[0], lo[1], hi[0] - lo[0], hi[1] - lo[1])]
+
+    def arrays(r, names, here):
+        ptrs = [None if here else _lib.ptr(np.ascontiguousarray(r[k])) for k in names]
+        return ptrs + [r['maxSegId'], len(r['ringArea2']), len(r['vertices']), None]
+    names = ('ringOffsets', 'vertexOffsets', 'vertices', 'ringArea2')
+    if resident == 'hulls':
+        o = trace(oc.EXAMPLE, junctions=True)
+        assert all(np.array_equal(getattr(o, k), a[k]) for k in names + ('junction',))
+    c.check(L.shp_hull_source(c.handle, *arrays(a, names, resident == 'hulls')))
+    if resident == 'simplification':                    # (its trace replaces no uploaded rings: the hulls' are in hl_*)
+        o = trace(oc.staircase(6), junctions=True)
+        assert all(np.array_equal(getattr(o, k), b[k]) for k in names + ('junction',))
+    c.check(L.shp_simplify_source(c.handle, *arrays(b, names + ('junction',), resident == 'simplification')))
+    counts = np.zeros(3, dtype=np.int64)
+    c.check(L.shp_hull_build(c.handle, *extent(a), 1 if resident == 'hulls' else 0, _lib.ptr(counts), None))
+    nh = int(counts[0])
+    S = a['maxSegId']
+    got = dict(hullOffsets=np.empty(S + 2, dtype=np.int64), hullPoints=np.empty((nh, 2), dtype=np.int64),
+               hullReach=np.empty(nh, dtype=np.int64), hullArea2=np.empty(S + 1, dtype=np.int64),
+               feretMax2=np.empty(S + 1, dtype=np.int64))
+    c.check(L.shp_hull_download(c.handle, *[_lib.ptr(v) for v in got.values()]))
+    for k in ARRAYS:
+        assert got[k].shape == hulls_a[k].shape and np.array_equal(got[k], hulls_a[k]), k
+    assert np.array_equal(got['hullOffsets'], hulls_a['hullOffsets'])
+    assert np.array_equal(got['hullArea2'], hulls_a['sums']['hullArea2']) and np.array_equal(got['feretMax2'], hulls_a['sums']['feretMax2'])
+    counts = np.zeros(10, dtype=np.int64)
+    c.check(L.shp_simplify_build(c.handle, sc.tolerance2q(1.0), 0, *extent(b), _lib.ptr(counts), None))
+    (nr2, nv2) = (int(counts[0]), int(counts[1]))
+    assert (nr2, nv2) == (2, 6)
+    S = b['maxSegId']
+    got = dict(ringOffsets=np.empty(S + 2, dtype=np.int64), vertexOffsets=np.empty(nr2 + 1, dtype=np.int64),
+               vertices=np.empty((nv2, 2), dtype=np.int64), ringArea2=np.empty(nr2, dtype=np.int64),
+               sourceRing=np.empty(nr2, dtype=np.int64), keptVertex=np.empty(nv2, dtype=np.int64))
+    c.check(L.shp_simplify_download(c.handle, *[_lib.ptr(v) for v in got.values()]))
+    for k in got:
+        assert got[k].shape == simplified_b[k].shape and np.array_equal(got[k], simplified_b[k]), k
+
+
 # ---- entry points -----------------------------------------------------------------------------------------------------
 def test_call_order_is_enforced_and_the_other_state_stays():
     from pyshepseg_amd import _lib, neighbours, shapes
@@ -432,6 +495,18 @@ def test_call_order_is_enforced_and_the_other_state_stays():
     refused(L.shp_hull_source(c.handle, _lib.ptr(ro), None, _lib.ptr(o.vertices), _lib.ptr(o.ringArea2), 3, 3, 18, None), 'NULL')
     refused(L.shp_hull_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(o.vertices), _lib.ptr(o.ringArea2), -1, 3, 18, None),
             'max_seg_id')
+    # uploaded offsets that span their counts but descend once, per ring and per id: refused as shp_simplify_source
+    # refuses them, and no rings are taken
+    (vo, ro2) = (o.vertexOffsets.copy(), o.ringOffsets.copy())
+    assert vo.tolist() == [0, 6, 14, 18] and ro2.tolist() == [0, 0, 1, 2, 3]
+    vo[1] = 15
+    ro2[2:4] = [2, 1]
+    refused(L.shp_hull_source(c.handle, _lib.ptr(ro), _lib.ptr(vo), _lib.ptr(o.vertices), _lib.ptr(o.ringArea2), 3, 3, 18, None),
+            'the vertex offsets do not ascend at ring 1')
+    refused(build_call(), 'shp_hull_source must come first')
+    refused(L.shp_hull_source(c.handle, _lib.ptr(ro2), _lib.ptr(o.vertexOffsets), _lib.ptr(o.vertices), _lib.ptr(o.ringArea2), 3, 3, 18,
+                              None), 'the ring offsets do not ascend at id 2')
+    refused(build_call(), 'shp_hull_source must come first')
     # o's rings are no longer resident (the calls above replaced them): the function sees that and uploads
     got = hulls(o)
     assert got.timings['uploaded']
