@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: Mpixels/s segmented on synthetic 6-band 40000x40000 tiled imagery.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c4|c5] [--dump-outputs DIR] [--full]
     (N > 1 without a launcher: bench.py starts the N ranks itself; under
      `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` it is one rank)
 
@@ -16,6 +16,11 @@ Workloads (BASELINE.json configs):
       1.6 Gpx label raster of 50 M segments (4 x 8-pixel blocks), rasters resident in HBM, the
       result columns copied to the host.
 value = image pixels / step time.
+A plain run does what that figure needs and no more: set-up, the warm-up steps, the timed steps, --dump-outputs,
+the result line (with the per-kernel and roofline figures that the timed steps' own device timers give).
+--full adds what takes runs of its own after the timed steps: `cpu_baseline` (the C oracle timed on a window
+of the same image, its mosaic compared with the device's) and, on the default c3 run, `also` (a short c5 run and
+a short c3 run through .npy files); --cpu-sample 0 / --also 0 leave one of them out again.
 --dump-outputs DIR (one GPU): after the timed steps, what the last step computed is written as DIR/<name>.npy
 (float32 / float64, under 64 MB: the arrays too large to keep whole as a fixed seeded sample); the inputs are the
 same on every run, so two builds can be compared output for output.
@@ -55,11 +60,15 @@ def parse():
     ap.add_argument('--overlap', type=int, default=1024)
     ap.add_argument('--workers', type=int, default=int(os.environ.get('SHEPSEG_WORKERS', '36')))
     ap.add_argument('--simple-recode', type=int, default=0, help='diagnostic: simpleTileRecode')
+    ap.add_argument('--full', action='store_true',
+                    help='one GPU: after the timed steps also measure what takes runs of its own, the cpu_baseline '
+                         '(with its comparison of the device mosaic against the oracle) and the "also" runs; '
+                         'a run without it stops at the headline figure')
     ap.add_argument('--also', type=int, default=1,
-                    help='default c3 run on one GPU: append "also": {"c5": ..., "c3_npy": ...} from two short extra '
-                         'runs after the headline timing (0 = skip)')
+                    help='--full, default c3 run on one GPU: append "also": {"c5": ..., "c3_npy": ...} from two short '
+                         'extra runs after the headline timing (0 = skip)')
     ap.add_argument('--cpu-sample', type=int, default=14336,
-                    help='window edge of the cpu_baseline sample (0 = skip)')
+                    help='--full: window edge of the cpu_baseline sample (0 = skip)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed as DIR/<name>.npy '
                          '(float32 / float64, a fixed seeded sample of the arrays too large to keep whole)')
@@ -71,6 +80,8 @@ def parse():
     if args.bands is None:
         args.bands = {'c3': 6, 'c4': 10, 'c5': 1}[args.workload]
     args.seed = 13 if args.workload == 'c4' else 11
+    if not args.full:                 # the extras are --full's: a plain run stops at the headline figure
+        (args.also, args.cpu_sample) = (0, 0)
     return args
 
 

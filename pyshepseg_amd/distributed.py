@@ -1376,7 +1376,7 @@ def bench_main(args, rank, world, local_rank):
                                       "overlap strips point to point, histogram all-reduced" % (
                                           world, "with its E-step sharded by sample rows (labels all-gathered per iteration)"
                                           if fitShardedHere else "on rank 0")},
-            # (cpu_baseline is a one-GPU figure: `python bench.py` prints it; BASELINE.md: the reference's numba
+            # (cpu_baseline is a one-GPU figure: `python bench.py --full` prints it; BASELINE.md: the reference's numba
             #  path does ~1.3 Mpixels/s per core)
             "reference_numba_mpx_per_core": 1.3,
             "roofline": {"bound": "hbm", "kernel": "whole path", "achieved": round(
