@@ -500,7 +500,9 @@ int shp_segpoints_emit(shp_ctx *ctx, uint32_t id_lo, uint32_t id_hi, int64_t *of
  * calcPerSegmentSpatialStatsTiled, :1262-1390 / :1703-1741): every segment's points in the WHOLE raster's visit
  * order (tile_size x tile_size tiles of the img_rows x ncols raster), although its rows lie on several ranks.
  *  shp_dsegpoints_build_dev: this rank's rows [row0, row0 + nrows) in place (d_seg, d_band: nrows x ncols, fewer
- *    than 2^32 pixels; the raster as a whole may hold more).  Sorts the rows' points by id in visit order and judges
+ *    than 2^32 pixels; the raster as a whole may hold more, but one of its tile rows -- min(tile_size, img_rows)
+ *    rows -- may reach 2^32 pixels only when it is the only one: SHP_ERR_ARG otherwise, on every rank alike).
+ *    Sorts the rows' points by id in visit order and judges
  *    every id against the GLOBAL label histogram d_hist: complete here (local label count == d_hist), straddler
  *    (fewer) or absent.  lh_out / pts_out (max_seg_id + 1 uint32 each, host) = labelled pixels / points per id
  *    here.  The straddlers' points are packed as *n_rec_out records of 24 bytes, {uint64 global visit index;

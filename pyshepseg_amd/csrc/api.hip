@@ -2422,6 +2422,12 @@ API int shp_dsegpoints_build_dev(shp_ctx *ctx, const uint32_t *d_seg, const void
         SHP_FAIL(ctx, SHP_ERR_ARG, "shard too large (%lld x %lld px)", (long long)nrows, (long long)ncols);
     if (max_seg_id == 0xffffffffu) SHP_FAIL(ctx, SHP_ERR_ARG, "max_seg_id too large");
     const uint32_t ts = tile_size > 0xffffffffll ? 0xffffffffu : (uint32_t)tile_size;
+    // pts_visit_pos divides by the pixels of a tile row in 32 bits once a shard reaches past its first one; the
+    // test names the whole raster alone, so every rank refuses alike
+    const uint64_t th = (uint64_t)ts < (uint64_t)img_rows ? (uint64_t)ts : (uint64_t)img_rows;
+    if ((uint64_t)img_rows > th && th * (uint64_t)ncols >= 0x100000000ull)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a tile row of %llu x %lld px reaches 2^32 pixels (tile_size %lld)",
+                 (unsigned long long)th, (long long)ncols, (long long)tile_size);
     return run_dsegpoints_build(ctx, d_seg, d_band, dtype, (uint32_t)nrows, (uint32_t)ncols, (uint32_t)row0,
                                 (uint32_t)img_rows, max_seg_id, null_val, ts, d_hist, lh_out, pts_out, d_rec_out,
                                 n_rec_out);
