@@ -760,6 +760,34 @@ int shp_outline_download(shp_ctx *ctx, int64_t *ring_offsets, int64_t *vertex_of
  * of its own at trace time, whether the outlines it once traced are still the resident ones.  No device work. */
 int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_out);
 
+/* ---- per-segment depth: the exact Euclidean distance transform of the labels (depths.calcSegmentDepths) ----------
+ * depth2 of a pixel of label L != 0 is the smallest squared distance (between pixel centres) to a position outside the
+ * raster or of another label (label 0 included); 0 where the label is 0.  The labels are whole in device memory.
+ *  shp_depth_need: *need_out = the bytes the buffers still have to grow by, *free_out = the device's free bytes.
+ *    marked < 0: for shp_depth_transform_dev on nrows x ncols pixels and the table of the ids 0 .. max_seg_id (6 bytes a
+ *    pixel, 20 per column and band of 32 rows, 12 per 64 columns of a row, 88 an id, 16 per pixel / 65 -- per pixel with
+ *    all_runs != 0);
+ *    marked >= 0: for shp_depth_envelope on that many scratch positions (8 bytes each).
+ *  shp_depth_transform_dev: the column step, the window of the row step and the list of the row runs the envelope has
+ *    to solve: those that hold a pixel the window deferred, or, with all_runs != 0, every run (the window is then
+ *    skipped).  counts_out[0] = pixels deferred, [1] = runs marked, [2] = scratch positions they take (their pixels
+ *    and two a run).  d_seg must stay in place until shp_depth_reduce returns.
+ *  shp_depth_envelope: solves the marked runs by the lower envelope of their parabolas.
+ *  shp_depth_reduce: the table of the ids 0 .. max_seg_id with n_cores <= 8 thresholds core_q (host memory): per id
+ *    the pixels, the sum of depth2, the largest (depth2 << 32 | 0xFFFFFFFF - linear pixel index) and per threshold the
+ *    pixels with depth2 > core_q[k].  *bad_label_out: 0, or the largest label above max_seg_id (then there is no
+ *    result and download fails).  steps_ms_out (may be NULL): 4 doubles, device time of the column step, the window,
+ *    the runs and their envelope, the reduction.
+ *  shp_depth_download: max_seg_id + 1 rows of 11 uint64 to host memory; depth2 (may be NULL): nrows x ncols uint32.
+ * Out of order the calls fail with SHP_ERR_STATE ("shp_depth_transform_dev must come first", ...). */
+int shp_depth_need(shp_ctx *ctx, int64_t nrows, int64_t ncols, int64_t max_seg_id, int all_runs, int64_t marked, int64_t *need_out,
+                   int64_t *free_out);
+int shp_depth_transform_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int all_runs, int64_t *counts_out);
+int shp_depth_envelope(shp_ctx *ctx);
+int shp_depth_reduce(shp_ctx *ctx, int64_t max_seg_id, int n_cores, const uint32_t *core_q, uint32_t *bad_label_out,
+                     double *steps_ms_out);
+int shp_depth_download(shp_ctx *ctx, uint64_t *rows, uint32_t *depth2);
+
 /* The junction switch of the trace.  Labels outside the raster read as 0; of the four pixels a b / c d round a corner the
  * pairs (a, b), (b, d), (c, d), (a, c) that differ number its degree, and a corner of degree >= 3 is a junction (three or
  * more segments meet, or two at a saddle), whatever four_connected.

@@ -235,6 +235,12 @@ _SIGS = {
     'shp_outline_download': (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     'shp_outline_serial': (_c.c_int, [_vp, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     'shp_outline_junctions': (_c.c_int, [_vp, _c.c_int]),
+    'shp_depth_need': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.POINTER(_c.c_int64),
+                                  _c.POINTER(_c.c_int64)]),
+    'shp_depth_transform_dev': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int64, _c.c_int, _vp]),
+    'shp_depth_envelope': (_c.c_int, [_vp]),
+    'shp_depth_reduce': (_c.c_int, [_vp, _c.c_int64, _c.c_int, _vp, _c.POINTER(_c.c_uint32), _vp]),
+    'shp_depth_download': (_c.c_int, [_vp, _vp, _vp]),
     'shp_outline_download_junction': (_c.c_int, [_vp, _vp]),
     'shp_simplify_need': (_c.c_int, [_vp, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.POINTER(_c.c_int64),
                                      _c.POINTER(_c.c_int64)]),

@@ -29,6 +29,7 @@ static int read_u32(shp_ctx *ctx, const uint32_t *d, uint32_t *h);
 #include "outline.h"
 #include "hull.h"
 #include "simplify.h"
+#include "segdepth.h"
 #include "comm.h"
 
 #define API extern "C" __attribute__((visibility("default")))
@@ -1796,6 +1797,63 @@ API int shp_outline_serial(shp_ctx *ctx, uint64_t *calls_out, uint64_t *serial_o
     *calls_out = ctx->outline_calls;
     *serial_out = ctx->outline.stage == 2 ? ctx->outline.serial : 0ull;
     return 0;
+}
+
+// ---- per-segment depth: the exact distance transform of the labels (segdepth.h) -----------------------------
+API int shp_depth_need(shp_ctx *ctx, int64_t nrows, int64_t ncols, int64_t max_seg_id, int all_runs, int64_t marked, int64_t *need_out,
+                       int64_t *free_out)
+{
+    CHK(enter(ctx));
+    if (!need_out || !free_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (nrows < 0 || ncols < 0 || nrows >= 0x7fffffffll || ncols >= 0x7fffffffll || nrows * ncols > (int64_t)OL_MAX_ITEMS ||
+        marked > 3 * (int64_t)OL_MAX_ITEMS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "bad argument");
+    return run_depth_need(ctx, (size_t)nrows, (size_t)ncols, (size_t)max_seg_id, all_runs ? 1 : 0, (long long)marked,
+                          (long long *)need_out, (long long *)free_out);
+}
+
+API int shp_depth_transform_dev(shp_ctx *ctx, const uint32_t *d_seg, int64_t nrows, int64_t ncols, int all_runs, int64_t *counts_out)
+{
+    CHK(enter(ctx));
+    if (!counts_out) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_row_block(ctx, d_seg, nrows, ncols));
+    if (nrows == 0 || ncols == 0) nrows = ncols = 0;
+    if (nrows * ncols > (int64_t)OL_MAX_ITEMS)
+        SHP_FAIL(ctx, SHP_ERR_ARG, "a raster of %lld pixels: more than %u", (long long)(nrows * ncols), OL_MAX_ITEMS);
+    return run_depth_transform(ctx, d_seg, (uint32_t)nrows, (uint32_t)ncols, all_runs ? 1 : 0, (long long *)counts_out);
+}
+
+API int shp_depth_envelope(shp_ctx *ctx)
+{
+    CHK(enter(ctx));
+    if (ctx->depth.stage != 1) SHP_FAIL(ctx, SHP_ERR_STATE, "no transform: shp_depth_transform_dev must come first");
+    return run_depth_envelope(ctx);
+}
+
+API int shp_depth_reduce(shp_ctx *ctx, int64_t max_seg_id, int n_cores, const uint32_t *core_q, uint32_t *bad_label_out,
+                         double *steps_ms_out)
+{
+    CHK(enter(ctx));
+    if (ctx->depth.stage != 2) SHP_FAIL(ctx, SHP_ERR_STATE, "no envelope: shp_depth_envelope must come first");
+    if (!bad_label_out || (n_cores > 0 && !core_q)) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    CHK(chk_max_seg_id(ctx, max_seg_id));
+    if (n_cores < 0 || n_cores > (int)DEPTH_CORES) SHP_FAIL(ctx, SHP_ERR_ARG, "%d core areas: at most %u", n_cores, DEPTH_CORES);
+    DepthCores cq{};
+    cq.n = (uint32_t)n_cores;
+    for (int k = 0; k < n_cores; k++) cq.q[k] = core_q[k];
+    CHK(run_depth_reduce(ctx, (uint32_t)max_seg_id, cq, bad_label_out));
+    if (steps_ms_out)
+        for (int i = 0; i < 4; i++) steps_ms_out[i] = ctx->depth.ms[i];
+    return 0;
+}
+
+API int shp_depth_download(shp_ctx *ctx, uint64_t *rows, uint32_t *depth2)
+{
+    CHK(enter(ctx));
+    if (ctx->depth.stage != 3) SHP_FAIL(ctx, SHP_ERR_STATE, "no reduced depths: shp_depth_reduce must come first");
+    if (!rows) SHP_FAIL(ctx, SHP_ERR_ARG, "NULL argument");
+    return run_depth_download(ctx, rows, depth2);
 }
 
 // ---- convex hulls of the outline rings (hull.h) ------------------------------------------------------------

@@ -205,6 +205,18 @@ struct HullState {
     double ms[5] = {};              // device time: candidates, order, chains, points, reach
 };
 
+// the depth transform between shp_depth_transform_dev, shp_depth_envelope, shp_depth_reduce and shp_depth_download
+// (segdepth.h), in buffers of their own (dp_*): the outlines, the hulls, the neighbour table, the group lists and the
+// shape table stay where they are.  seg: the caller's labels, which must stay in place from the first call to the third.
+struct DepthState {
+    int stage = 0;                  // 0 none, 1 transformed up to the marked runs, 2 the envelope done, 3 reduced
+    const uint32_t *seg = nullptr;
+    uint32_t nrows = 0, ncols = 0, S = 0, nruns = 0;
+    int all = 0;                    // every run marked (path 'envelope')
+    unsigned long long deferred = 0, room = 0;      // pixels the window deferred; scratch positions of the marked runs
+    double ms[4] = {};              // device time: column step, window, marked runs and envelope, reduction
+};
+
 // The context's named workspace buffers (grow-only), each named HERE ONLY: the list makes the members of shp_ctx and
 // the entries of shp_ctx::bufs, which is what buf_ensure's regrow log indexes and shp_ctx_destroy frees.
 #define SHP_CTX_BUFS(X) \
@@ -223,7 +235,7 @@ struct HullState {
     X(ol_eside) X(ol_a) X(ol_b) X(ol_ring) X(ol_vtx) X(ol_roff) X(ol_jflag) X(hl_vtx) X(hl_voff) X(hl_roff) X(hl_area) X(hl_pos) \
     X(hl_cid) X(hl_ccol) X(hl_crow) X(hl_k) X(hl_v) X(hl_id) X(hl_pts) X(hl_reach) X(hl_ctr) \
     X(sp_vtx) X(sp_voff) X(sp_roff) X(sp_area) X(sp_jflag) X(sp_ctr) X(sp_keep) X(sp_pos) X(sp_ring) X(sp_arc) X(sp_pt) \
-    X(sp_kv) X(sp_out)
+    X(sp_kv) X(sp_out) X(dp_g) X(dp_d2) X(dp_band) X(dp_runs) X(dp_piece) X(dp_scr) X(dp_tab) X(dp_ctr)
 
 // the simplified rings between shp_simplify_source, shp_simplify_build and shp_simplify_download (simplify.h), in
 // buffers of their own (sp_*): the outlines, the hulls, the neighbour table, the group lists and the shape table stay
@@ -265,6 +277,7 @@ struct shp_ctx {
     unsigned long long outline_calls = 0;       // shp_outline_edges_dev calls of this context: each replaces the outlines
     HullState hull;
     SimplifyState simplify;
+    DepthState depth;
     NbrState nbr;
     MrgState mrg;
     AggState agg;
