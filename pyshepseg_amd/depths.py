@@ -40,9 +40,8 @@ import time
 import numpy
 
 from . import _lib
+from . import labelsource
 from . import outlines
-from . import shapes
-from . import tilingstats
 
 
 class PyShepSegDepthsError(Exception):
@@ -117,20 +116,20 @@ def checkCoreAreas(coreAreas):
 
 
 def _checkArgs(segfile, maxSegId, origin, coreAreas, path, missingStatsValue):
-    """everything that can be refused before the GPU is touched; the argument checks are those of
-    shapes.calcSegmentShapes"""
+    """(the labelsource.Labels of the raster, (row0, col0), the core areas' pairs (name, Q), missing): everything that can
+    be refused before the GPU is touched; the raster, ``maxSegId``, ``missingStatsValue`` and ``origin`` as
+    shapes.calcSegmentShapes takes them"""
+    Err = PyShepSegDepthsError
     cores = checkCoreAreas(coreAreas)
     if path not in PATHS:
-        raise PyShepSegDepthsError("path must be one of {} (got {!r})".format(PATHS, path))
-    try:
-        (seg, devSeg, nrows, ncols, maxSegId, origin, _chunk, missing) = shapes._checkArgs(segfile, maxSegId, origin, None,
-                                                                                           missingStatsValue)
-    except shapes.PyShepSegShapesError as e:
-        raise PyShepSegDepthsError(str(e))
-    if nrows * ncols > outlines.MAX_ITEMS:
-        raise PyShepSegDepthsError("a raster of {} pixels: more than the {} one call can take".format(nrows * ncols,
-                                                                                                     outlines.MAX_ITEMS))
-    return (seg, devSeg, nrows, ncols, maxSegId, origin, cores, missing)
+        raise Err("path must be one of {} (got {!r})".format(PATHS, path))
+    labels = labelsource.resolve(segfile, maxSegId, Err, merged=True, hint=True)
+    missing = labelsource.number(missingStatsValue, 'missingStatsValue', Err)
+    origin = labelsource.checkOrigin(origin, labels.nrows, labels.ncols, Err)
+    if labels.nrows * labels.ncols > outlines.MAX_ITEMS:
+        raise Err("a raster of {} pixels: more than the {} one call can take".format(labels.nrows * labels.ncols,
+                                                                                     outlines.MAX_ITEMS))
+    return (labels, origin, cores, missing)
 
 
 def depthColumnsFromTable(table, ncols, origin, cores, missingStatsValue=-9999):
@@ -183,37 +182,29 @@ def calcSegmentDepths(segfile, maxSegId=None, origin=(0, 0), coreAreas=(), depth
     The raster has at most 2^32 - 8192 pixels, and the working set (module docstring) must fit the free HBM: otherwise
     PyShepSegDepthsError names the bytes needed, before anything is allocated.
     """
-    (seg, devSeg, nrows, ncols, maxSegId, origin, cores, missing) = _checkArgs(segfile, maxSegId, origin, coreAreas, path,
-                                                                              missingStatsValue)
+    (labels, origin, cores, missing) = _checkArgs(segfile, maxSegId, origin, coreAreas, path, missingStatsValue)
+    (nrows, ncols, maxSegId) = (labels.nrows, labels.ncols, labels.maxSegId)
     allRuns = int(path == 'envelope')
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
     npix = nrows * ncols
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     timings = {}
     (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
-    ms = ctypes.c_double(0)
     deviceMs = 0.0
-    try:
+    with labelsource.LabelSource(c, labels) as src:
         # (the table of a maxSegId that is not known yet is checked once it is: below)
         c.check(L.shp_depth_need(c.handle, nrows, ncols, maxSegId if maxSegId is not None else 0, allRuns, -1,
                                  ctypes.byref(need), ctypes.byref(free)))
-        want = need.value + (4 * npix if devSeg is None else 0)
+        want = need.value + (4 * npix if labels.devSeg is None else 0)
         if want > free.value:
             raise PyShepSegDepthsError("the labels, per-pixel arrays and per-id table of {} x {} pixels need {} bytes of device "
                                        "memory, {} are free".format(nrows, ncols, want, free.value))
-        dseg = src.chunk(0, nrows)[0] if npix else None
+        dseg = src.whole()
         timings['upload'] = time.perf_counter() - t0
         if maxSegId is None:
             t1 = time.perf_counter()
-            top = ctypes.c_uint32(0)
-            if npix:
-                c.check(L.shp_shape_label_max_dev(c.handle, dseg, npix, ctypes.byref(top), ctypes.byref(ms)))
-                deviceMs += ms.value
-            if top.value >= 0xFFFFFFFE:
-                raise PyShepSegDepthsError("label {} is too large".format(top.value))
-            maxSegId = top.value
+            (maxSegId, deviceMs) = src.labelMax(PyShepSegDepthsError)
             c.check(L.shp_depth_need(c.handle, nrows, ncols, maxSegId, allRuns, -1, ctypes.byref(need), ctypes.byref(free)))
             if need.value > free.value:
                 raise PyShepSegDepthsError("the per-pixel arrays and the per-id table of {} ids need {} bytes of device memory, "
@@ -245,8 +236,6 @@ def calcSegmentDepths(segfile, maxSegId=None, origin=(0, 0), coreAreas=(), depth
         depth2 = numpy.empty((nrows, ncols), dtype=numpy.uint32) if depthRaster else None
         c.check(L.shp_depth_download(c.handle, _lib.ptr(table), _lib.ptr(depth2) if depthRaster and npix else None))
         timings['download'] = time.perf_counter() - t1
-    finally:
-        src.close()
     deviceStepsMs = dict(zip(STEPS, steps.tolist()))
     deviceMs += float(steps.sum())
     t1 = time.perf_counter()

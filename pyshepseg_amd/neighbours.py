@@ -29,9 +29,8 @@ import time
 import numpy
 
 from . import _lib
-from . import shepseg
+from . import labelsource
 from . import tiling
-from . import tilingstats
 
 
 class PyShepSegNeighboursError(Exception):
@@ -119,23 +118,8 @@ class SegmentNeighboursShare(object):
 
 
 def _checkArgs(segfile, maxSegId):
-    """(host labels or None, device labels or None, rows, columns, maxSegId or None): everything that can be
-    refused before the GPU is touched"""
-    if maxSegId is not None:
-        if int(maxSegId) != maxSegId or maxSegId < 0:
-            raise PyShepSegNeighboursError("maxSegId must be a non-negative integer (got {})".format(maxSegId))
-        maxSegId = int(maxSegId)
-        if maxSegId >= 0xFFFFFFFE:
-            raise PyShepSegNeighboursError("maxSegId {} is too large".format(maxSegId))
-    if getattr(segfile, 'outDev', None):
-        (devSeg, nrows, ncols, _nbytes) = segfile.outDev
-        return (None, devSeg, nrows, ncols, maxSegId)
-    seg = tilingstats._loadArray(getattr(segfile, 'segimg', None) if isinstance(
-        segfile, tiling.TiledSegmentationResult) else segfile)
-    if seg is None or seg.ndim != 2 or seg.dtype != shepseg.SegIdType:
-        raise PyShepSegNeighboursError("segfile must be a 2-D uint32 array, a .npy path of one, or a "
-                                       "segmentation result kept on the device")
-    return (seg, None, seg.shape[0], seg.shape[1], maxSegId)
+    """the labelsource.Labels of the raster: everything that can be refused before the GPU is touched"""
+    return labelsource.resolve(segfile, maxSegId, PyShepSegNeighboursError)
 
 
 def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixels=None):
@@ -151,23 +135,15 @@ def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixel
     The labels stream through the GPU in row blocks of ``chunkPixels`` pixels (default
     tilingstats.STATS_CHUNK_PIXELS), each with the row that follows it; the table does not depend on the blocks.
     """
-    (seg, devSeg, nrows, ncols, maxSegId) = _checkArgs(segfile, maxSegId)
-    if chunkPixels is None:
-        chunkPixels = tilingstats.STATS_CHUNK_PIXELS
-    rowsPerChunk = max(1, min(max(nrows, 1), int(chunkPixels) // max(ncols, 1)))
+    labels = _checkArgs(segfile, maxSegId)
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     timings = {}
-    try:
-        c.check(L.shp_nbr_begin(c.handle, -1 if maxSegId is None else maxSegId, int(bool(fourConnected))))
-        if ncols > 0:
-            for y0 in range(0, nrows, rowsPerChunk):
-                y1 = min(nrows, y0 + rowsPerChunk)
-                more = y1 < nrows
-                (dseg, _planes) = src.chunk(y0, y1 + (1 if more else 0))
-                c.check(L.shp_nbr_accumulate_dev(c.handle, dseg, y1 - y0, ncols, int(more)))
+    with labelsource.LabelSource(c, labels) as src:
+        c.check(L.shp_nbr_begin(c.handle, -1 if labels.maxSegId is None else labels.maxSegId, int(bool(fourConnected))))
+        for (y0, y1, dseg, _above, more) in src.blocks(chunkPixels, below=True):
+            c.check(L.shp_nbr_accumulate_dev(c.handle, dseg, y1 - y0, labels.ncols, int(more)))
         timings['accumulate'] = time.perf_counter() - t0
         t1 = time.perf_counter()
         (S, nent, bad) = (ctypes.c_uint32(0), ctypes.c_int64(0), ctypes.c_uint32(0))
@@ -185,8 +161,6 @@ def findSegmentNeighbours(segfile, fourConnected=True, maxSegId=None, chunkPixel
         c.check(L.shp_nbr_download(c.handle, _lib.ptr(offsets), _lib.ptr(nbrs), _lib.ptr(lens)))
         timings['download'] = time.perf_counter() - t1
         serial = _tableSerial(c)
-    finally:
-        src.close()
     timings['total'] = time.perf_counter() - t0
     nb = SegmentNeighbours(offsets, nbrs, lens, S.value, bool(fourConnected), pairsSeen=int(counters[0]),
                            recordsSorted=int(counters[1]), timings=timings, deviceMs=ms.value,
@@ -239,9 +213,7 @@ def _makeResident(c, nb, timings):
 
 
 def _number(value, name):
-    if isinstance(value, (bool, numpy.bool_)) or not isinstance(value, (int, float, numpy.integer, numpy.floating)):
-        raise PyShepSegNeighboursError("{} must be a number (got {!r})".format(name, value))
-    return float(value)
+    return labelsource.number(value, name, PyShepSegNeighboursError)
 
 
 def _checkReduceArgs(nb, columnSelections, ignoreValue, missingStatsValue):
@@ -436,7 +408,7 @@ def _integerColumn(column, name, nrows):
 
 
 def _checkMergeArgs(nb, keyColumn, ignoreKey, minBorder, segSize, segfile, outfile, keyOptional=False):
-    """(keys int64, ignore or None, minBorder, sizes int64 or None, the raster as _checkArgs gives it or None):
+    """(keys int64, ignore or None, minBorder, sizes int64 or None, the raster's labelsource.Labels or None):
     everything that can be refused before the GPU is touched.  keyOptional: ``keyColumn`` may be None (keys None)"""
     if not isinstance(nb, SegmentNeighbours):
         raise PyShepSegNeighboursError("nb must be a SegmentNeighbours")
@@ -474,7 +446,7 @@ def _checkMergeColumns(nrows, keyColumn, ignoreKey, minBorder, segSize, segfile,
         if outfile is not None:
             raise PyShepSegNeighboursError("outfile needs a segfile to recode")
     else:
-        raster = _checkArgs(segfile, None)[:4]
+        raster = _checkArgs(segfile, None)
         if isinstance(segfile, str) and outfile is None:
             raise PyShepSegNeighboursError("a .npy segfile is recoded into a file: outfile is required")
     return (keys, ignore, minBorder, sizes, raster)
@@ -575,57 +547,36 @@ def _mergeByLinks(nb, links, sizes, raster, outfile, chunkPixels):
 
 
 def _recodeRaster(c, res, raster, S, outfile, chunkPixels, countHist):
-    """the label raster through the groups' recode on the device, in the row blocks of tilingstats._ChunkSource"""
+    """the label raster through the groups' recode on the device, in the row blocks of labelsource.mapBlocks"""
     L = c._L
-    (seg, devSeg, nrows, ncols) = raster
-    if chunkPixels is None:
-        chunkPixels = tilingstats.STATS_CHUNK_PIXELS
-    rowsPerChunk = max(1, min(max(nrows, 1), int(chunkPixels) // max(ncols, 1)))
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
-    (writer, block, out, devOut) = (None, None, None, None)
-    nbytes = nrows * ncols * 4
-    worst = 0
-    try:
-        if outfile is not None:
-            writer = tiling._NpyRowWriter(outfile, nrows, ncols)
-            block = numpy.empty((min(rowsPerChunk, nrows), ncols), dtype=numpy.uint32)
-        elif devSeg is not None:
-            devOut = tiling._devAlloc(c, nbytes)
-        else:
-            out = numpy.empty((nrows, ncols), dtype=numpy.uint32)
-        for y0 in range(0, nrows, rowsPerChunk):
-            y1 = min(nrows, y0 + rowsPerChunk)
-            n = (y1 - y0) * ncols
-            if n == 0:
-                break
-            (dseg, _planes) = src.chunk(y0, y1)
+    nbytes = raster.nrows * raster.ncols * 4
+    worst = [0]
+
+    def recode(y0, y1, dseg, dout):
+        """False once a label was above S: nothing is kept from then on, the blocks still run to find the largest"""
+        (bad, ms) = (ctypes.c_uint32(0), ctypes.c_double(0))
+        c.check(L.shp_nbr_merge_recode_dev(c.handle, dseg, (y1 - y0) * raster.ncols, dout, int(countHist), ctypes.byref(bad),
+                                           ctypes.byref(ms)))
+        res.stepDeviceMs['recode'] += ms.value
+        worst[0] = max(worst[0], bad.value)
+        return not worst[0]
+
+    devOut = None
+    with labelsource.LabelSource(c, raster) as src:
+        try:
+            if outfile is None and raster.devSeg is not None:
+                devOut = tiling._devAlloc(c, nbytes)
+            out = labelsource.mapBlocks(src, chunkPixels, recode, numpy.uint32, outfile=outfile, devOut=devOut)
+            if worst[0]:
+                raise PyShepSegNeighboursError("segment id {} is above maxSegId {}".format(worst[0], S))
+            if countHist:
+                res.hist = numpy.empty(res.maxSegId + 1, dtype=numpy.int64)
+                c.check(L.shp_nbr_merge_groups(c.handle, None, None, None, _lib.ptr(res.hist)))
+            (res.segimg, res.outDev) = (out, None if devOut is None else (devOut.value, raster.nrows, raster.ncols, nbytes))
+            devOut = None
+        finally:
             if devOut is not None:
-                dout = ctypes.c_void_p(devOut.value + 4 * y0 * ncols)
-            else:
-                # (the output starts at the labels' offset from a 16-byte boundary: the kernel then stores whole vectors)
-                dout = ctypes.c_void_p(src.scratch(0, n * 4 + 16).value + (dseg.value & 15))
-            (bad, ms) = (ctypes.c_uint32(0), ctypes.c_double(0))
-            c.check(L.shp_nbr_merge_recode_dev(c.handle, dseg, n, dout, int(countHist), ctypes.byref(bad), ctypes.byref(ms)))
-            res.stepDeviceMs['recode'] += ms.value
-            worst = max(worst, bad.value)
-            if devOut is None and not worst:
-                dest = block[:y1 - y0] if writer is not None else out[y0:y1]
-                c.check(L.shp_dev_download(c.handle, _lib.ptr(dest), dout, n * 4))
-                if writer is not None:
-                    writer.writeRows(y0, y1, dest)
-        if worst:
-            raise PyShepSegNeighboursError("segment id {} is above maxSegId {}".format(worst, S))
-        if countHist:
-            res.hist = numpy.empty(res.maxSegId + 1, dtype=numpy.int64)
-            c.check(L.shp_nbr_merge_groups(c.handle, None, None, None, _lib.ptr(res.hist)))
-        (res.segimg, res.outDev) = (out, None if devOut is None else (devOut.value, nrows, ncols, nbytes))
-        devOut = None
-    finally:
-        if writer is not None:
-            writer.close()
-        src.close()
-        if devOut is not None:
-            tiling._devRelease(c, devOut, nbytes)
+                tiling._devRelease(c, devOut, nbytes)
 
 
 # ---- touching segments that look alike merged into one (csrc/nbrmerge.h, MrgSimRule) --------------------------

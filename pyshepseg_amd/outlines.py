@@ -56,8 +56,7 @@ import time
 import numpy
 
 from . import _lib
-from . import shapes
-from . import tilingstats
+from . import labelsource
 
 
 class PyShepSegOutlinesError(Exception):
@@ -242,15 +241,14 @@ def writeGeoJSON(o, path, ids=None, transform=None, columns=None):
 
 
 def _checkArgs(segfile, maxSegId, origin):
-    """(host labels or None, device labels or None, rows, columns, maxSegId or None, (row0, col0)): everything that
-    can be refused before the GPU is touched; the argument checks are those of shapes.calcSegmentShapes"""
-    try:
-        (seg, devSeg, nrows, ncols, maxSegId, origin, _chunk, _missing) = shapes._checkArgs(segfile, maxSegId, origin, None, -9999)
-    except shapes.PyShepSegShapesError as e:
-        raise PyShepSegOutlinesError(str(e))
-    if nrows * ncols > MAX_ITEMS:
-        raise PyShepSegOutlinesError("a raster of {} pixels: more than the {} one call can take".format(nrows * ncols, MAX_ITEMS))
-    return (seg, devSeg, nrows, ncols, maxSegId, origin)
+    """(the labelsource.Labels of the raster, (row0, col0)): everything that can be refused before the GPU is touched; the
+    raster, ``maxSegId`` and ``origin`` as shapes.calcSegmentShapes takes them"""
+    Err = PyShepSegOutlinesError
+    labels = labelsource.resolve(segfile, maxSegId, Err, merged=True, hint=True)
+    origin = labelsource.checkOrigin(origin, labels.nrows, labels.ncols, Err)
+    if labels.nrows * labels.ncols > MAX_ITEMS:
+        raise Err("a raster of {} pixels: more than the {} one call can take".format(labels.nrows * labels.ncols, MAX_ITEMS))
+    return (labels, origin)
 
 
 def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 0), hulls=False, junctions=False, simplify=None):
@@ -275,7 +273,8 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
     The raster has at most 2^32 - 8192 pixels and as many edges, and the working set (module docstring) must fit the
     free HBM: otherwise PyShepSegOutlinesError names the bytes needed, before anything is allocated.
     """
-    (seg, devSeg, nrows, ncols, maxSegId, origin) = _checkArgs(segfile, maxSegId, origin)
+    (labels, origin) = _checkArgs(segfile, maxSegId, origin)
+    (nrows, ncols, maxSegId) = (labels.nrows, labels.ncols, labels.maxSegId)
     if simplify is not None:
         tolerance2q(simplify)
         junctions = True
@@ -285,28 +284,20 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
     if hulls or simplify is not None:
         _outlineSerial(c)
     npix = nrows * ncols
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     timings = {}
     (need, free) = (ctypes.c_int64(0), ctypes.c_int64(0))
-    ms = ctypes.c_double(0)
     deviceMs = 0.0
-    try:
+    with labelsource.LabelSource(c, labels) as src:
         c.check(L.shp_outline_need(c.handle, npix, -1, ctypes.byref(need), ctypes.byref(free)))
-        want = need.value + (4 * npix if devSeg is None else 0)
+        want = need.value + (4 * npix if labels.devSeg is None else 0)
         if want > free.value:
             raise PyShepSegOutlinesError("the labels and per-pixel arrays of {} x {} pixels need {} bytes of device memory, {} are "
                                          "free".format(nrows, ncols, want, free.value))
-        dseg = src.chunk(0, nrows)[0] if npix else None
+        dseg = src.whole()
         timings['upload'] = time.perf_counter() - t0
         if maxSegId is None:
             t1 = time.perf_counter()
-            top = ctypes.c_uint32(0)
-            if npix:
-                c.check(L.shp_shape_label_max_dev(c.handle, dseg, npix, ctypes.byref(top), ctypes.byref(ms)))
-                deviceMs += ms.value
-            if top.value >= 0xFFFFFFFE:
-                raise PyShepSegOutlinesError("label {} is too large".format(top.value))
-            maxSegId = top.value
+            (maxSegId, deviceMs) = src.labelMax(PyShepSegOutlinesError)
             timings['labelMax'] = time.perf_counter() - t1
         t1 = time.perf_counter()
         (edges, bad) = (ctypes.c_int64(0), ctypes.c_uint32(0))
@@ -342,8 +333,6 @@ def traceSegmentOutlines(segfile, fourConnected=True, maxSegId=None, origin=(0, 
             junction = numpy.empty(nverts, dtype=numpy.uint8)
             c.check(L.shp_outline_download_junction(c.handle, _lib.ptr(junction)))
         timings['download'] = time.perf_counter() - t1
-    finally:
-        src.close()
     deviceStepsMs = dict(zip(('edges', 'successors', 'rounds', 'rings'), steps.tolist()))
     deviceMs += float(steps.sum())
     t1 = time.perf_counter()

@@ -26,8 +26,7 @@ import time
 import numpy
 
 from . import _lib
-from . import neighbours
-from . import tilingstats
+from . import labelsource
 
 
 class PyShepSegShapesError(Exception):
@@ -115,34 +114,13 @@ def shapeColumnsFromSums(counts, sums, missingStatsValue=-9999):
 
 
 def _checkArgs(segfile, maxSegId, origin, chunkPixels, missingStatsValue):
-    """(host labels or None, device labels or None, rows, columns, maxSegId or None, (row0, col0), chunkPixels,
-    missing): everything that can be refused before the GPU is touched"""
-    if maxSegId is None and getattr(segfile, 'maxSegId', None) is not None and not isinstance(segfile, numpy.ndarray):
-        maxSegId = int(segfile.maxSegId)
-    if isinstance(segfile, neighbours.MergedSegments) and not getattr(segfile, 'outDev', None):
-        if segfile.segimg is None:
-            raise PyShepSegShapesError("the MergedSegments holds no recoded raster: neither outDev nor segimg")
-        segfile = segfile.segimg
-    try:
-        (seg, devSeg, nrows, ncols, maxSegId) = neighbours._checkArgs(segfile, maxSegId)
-        missing = neighbours._number(missingStatsValue, 'missingStatsValue')
-    except neighbours.PyShepSegNeighboursError as e:
-        raise PyShepSegShapesError(str(e))
-    try:
-        (row0, col0) = origin
-    except (TypeError, ValueError):
-        raise PyShepSegShapesError("origin must be (row0, col0) (got {!r})".format(origin))
-    for v in (row0, col0):
-        if isinstance(v, (bool, numpy.bool_)) or not isinstance(v, (int, numpy.integer)) or v < 0:
-            raise PyShepSegShapesError("origin must be two non-negative integers (got {!r})".format(origin))
-    (row0, col0) = (int(row0), int(col0))
-    if row0 + nrows > 2 ** 32 or col0 + ncols > 2 ** 32:
-        raise PyShepSegShapesError("origin {} puts a {} x {} raster past coordinate 2^32".format((row0, col0), nrows, ncols))
-    if chunkPixels is None:
-        chunkPixels = tilingstats.STATS_CHUNK_PIXELS
-    if isinstance(chunkPixels, (bool, numpy.bool_)) or not isinstance(chunkPixels, (int, numpy.integer)) or chunkPixels < 1:
-        raise PyShepSegShapesError("chunkPixels must be a positive integer (got {!r})".format(chunkPixels))
-    return (seg, devSeg, nrows, ncols, maxSegId, (row0, col0), int(chunkPixels), missing)
+    """(the labelsource.Labels of the raster, (row0, col0), chunkPixels, missing): everything that can be refused before
+    the GPU is touched"""
+    Err = PyShepSegShapesError
+    labels = labelsource.resolve(segfile, maxSegId, Err, merged=True, hint=True)
+    missing = labelsource.number(missingStatsValue, 'missingStatsValue', Err)
+    origin = labelsource.checkOrigin(origin, labels.nrows, labels.ncols, Err)
+    return (labels, origin, labelsource.checkChunkPixels(chunkPixels, Err), missing)
 
 
 def calcSegmentShapes(segfile, maxSegId=None, origin=(0, 0), chunkPixels=None, missingStatsValue=-9999):
@@ -164,41 +142,22 @@ def calcSegmentShapes(segfile, maxSegId=None, origin=(0, 0), chunkPixels=None, m
     The labels stream through the GPU in row blocks of ``chunkPixels`` pixels (default tilingstats.STATS_CHUNK_PIXELS),
     each with the row above and below it; the result does not depend on the blocks.
     """
-    (seg, devSeg, nrows, ncols, maxSegId, origin, chunkPixels, missing) = _checkArgs(
-        segfile, maxSegId, origin, chunkPixels, missingStatsValue)
-    rowsPerChunk = max(1, min(max(nrows, 1), chunkPixels // max(ncols, 1)))
+    (labels, origin, chunkPixels, missing) = _checkArgs(segfile, maxSegId, origin, chunkPixels, missingStatsValue)
+    maxSegId = labels.maxSegId
     t0 = time.perf_counter()
     c = _lib.ctx()
     L = c._L
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     timings = {}
     deviceMs = 0.0
     ms = ctypes.c_double(0)
-    try:
+    with labelsource.LabelSource(c, labels) as src:
         if maxSegId is None:
-            top = 0
-            if ncols > 0:
-                # resident labels are one array: one reduction; a host raster goes up block by block
-                step = nrows if devSeg is not None else rowsPerChunk
-                for y0 in range(0, nrows, max(step, 1)):
-                    y1 = min(nrows, y0 + step)
-                    (dseg, _planes) = src.chunk(y0, y1)
-                    m = ctypes.c_uint32(0)
-                    c.check(L.shp_shape_label_max_dev(c.handle, dseg, (y1 - y0) * ncols, ctypes.byref(m), ctypes.byref(ms)))
-                    top = max(top, m.value)
-                    deviceMs += ms.value
-            if top >= 0xFFFFFFFE:
-                raise PyShepSegShapesError("label {} is too large".format(top))
-            maxSegId = top
+            (maxSegId, deviceMs) = src.labelMax(PyShepSegShapesError, chunkPixels)
             timings['labelMax'] = time.perf_counter() - t0
         t1 = time.perf_counter()
         c.check(L.shp_shape_begin(c.handle, maxSegId, origin[0], origin[1]))
-        if ncols > 0:
-            for y0 in range(0, nrows, rowsPerChunk):
-                y1 = min(nrows, y0 + rowsPerChunk)
-                (above, below) = (int(y0 > 0), int(y1 < nrows))
-                (dseg, _planes) = src.chunk(y0 - above, y1 + below)
-                c.check(L.shp_shape_accumulate_dev(c.handle, dseg, y1 - y0, ncols, above, below))
+        for (y0, y1, dseg, above, below) in src.blocks(chunkPixels, above=True, below=True):
+            c.check(L.shp_shape_accumulate_dev(c.handle, dseg, y1 - y0, labels.ncols, int(above), int(below)))
         timings['accumulate'] = time.perf_counter() - t1
         t1 = time.perf_counter()
         (S, bad) = (ctypes.c_uint32(0), ctypes.c_uint32(0))
@@ -211,8 +170,6 @@ def calcSegmentShapes(segfile, maxSegId=None, origin=(0, 0), chunkPixels=None, m
         table = numpy.empty((S.value + 1, _TABLE_WORDS), dtype=numpy.uint64)
         c.check(L.shp_shape_download(c.handle, _lib.ptr(table)))
         timings['download'] = time.perf_counter() - t1
-    finally:
-        src.close()
     t1 = time.perf_counter()
     (columns, sums) = columnsFromTable(table, missing)
     timings['derive'] = time.perf_counter() - t1

@@ -23,8 +23,8 @@ import ctypes
 import numpy
 
 from . import _lib
+from . import labelsource
 from . import shepseg
-from . import tiling
 from . import tilingstats
 
 GFT_Integer = 0                                             # gdal.GFT_Integer
@@ -229,52 +229,21 @@ def renderColourTable(segfile, colours, outfile=None, chunkPixels=None):
     nTable = len(cols[0])
     if outfile is not None and not (isinstance(outfile, str) and outfile.endswith('.npy')):
         raise PyShepSegUtilsError("outfile must be None or a .npy path")
-    devSeg = None
-    if getattr(segfile, 'outDev', None):
-        (devSeg, nrows, ncols, _nbytes) = segfile.outDev
-        seg = None
-    else:
-        seg = tilingstats._loadArray(getattr(segfile, 'segimg', None) if isinstance(
-            segfile, tiling.TiledSegmentationResult) else segfile)
-        if seg is None or seg.ndim != 2 or seg.dtype != shepseg.SegIdType:
-            raise PyShepSegUtilsError("segfile must be a 2-D uint32 array, a .npy path of one, or a "
-                                      "segmentation result kept on the device")
-        (nrows, ncols) = seg.shape
-    if chunkPixels is None:
-        chunkPixels = tilingstats.STATS_CHUNK_PIXELS
-    rowsPerChunk = max(1, min(max(nrows, 1), int(chunkPixels) // max(ncols, 1)))
+    labels = labelsource.resolve(segfile, None, PyShepSegUtilsError)
     c = _lib.ctx()
     L = c._L
-    src = tilingstats._ChunkSource(c, seg, [], devSeg=devSeg, devPlanes=[], bandDtype=numpy.uint8, shape=(nrows, ncols))
     dTable = ctypes.c_void_p()
-    writer = None
-    out = None
+
+    def lookup(y0, y1, dseg, dout):
+        c.check(L.shp_colour_lookup_dev(c.handle, dseg, (y1 - y0) * labels.ncols, dTable, nTable, dout))
+        return True
+
     try:
-        c.check(L.shp_dev_alloc(c.handle, nTable * 4, ctypes.byref(dTable)))
-        c.check(L.shp_colour_pack(c.handle, _lib.ptr(cols[0]), _lib.ptr(cols[1]), _lib.ptr(cols[2]), _lib.ptr(cols[3]),
-                                  nTable, dTable))
-        if outfile is not None:
-            writer = tiling._NpyRowWriter(outfile, nrows, ncols, dtype=numpy.uint8, pixelShape=(4,))
-            block = numpy.empty((min(rowsPerChunk, nrows), ncols, 4), dtype=numpy.uint8)
-        else:
-            out = numpy.empty((nrows, ncols, 4), dtype=numpy.uint8)
-        for y0 in range(0, nrows, rowsPerChunk):
-            y1 = min(nrows, y0 + rowsPerChunk)
-            n = (y1 - y0) * ncols
-            if n == 0:
-                break
-            (dseg, _planes) = src.chunk(y0, y1)
-            # (the output starts at the labels' offset from a 16-byte boundary: the kernel then stores whole vectors)
-            dout = ctypes.c_void_p(src.scratch(0, n * 4 + 16).value + (dseg.value & 15))
-            c.check(L.shp_colour_lookup_dev(c.handle, dseg, n, dTable, nTable, dout))
-            dest = block[:y1 - y0] if writer is not None else out[y0:y1]
-            c.check(L.shp_dev_download(c.handle, _lib.ptr(dest), dout, n * 4))
-            if writer is not None:
-                writer.writeRows(y0, y1, dest)
+        with labelsource.LabelSource(c, labels) as src:
+            c.check(L.shp_dev_alloc(c.handle, nTable * 4, ctypes.byref(dTable)))
+            c.check(L.shp_colour_pack(c.handle, _lib.ptr(cols[0]), _lib.ptr(cols[1]), _lib.ptr(cols[2]), _lib.ptr(cols[3]),
+                                      nTable, dTable))
+            return labelsource.mapBlocks(src, chunkPixels, lookup, numpy.uint8, pixelShape=(4,), outfile=outfile)
     finally:
-        if writer is not None:
-            writer.close()
-        src.close()
         if dTable.value:
             c.check(L.shp_dev_free(c.handle, dTable))
-    return out
