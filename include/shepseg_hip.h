@@ -82,6 +82,12 @@ int shp_walk_batch_stats(uint64_t *out, int reset);
  * and the most workgroups in one launch of the replay, then the same two of the pass loop.  The reset of
  * shp_walk_batch_stats clears them too.  Read-only. */
 int shp_walk_batch_blocks(uint64_t *out);
+/* process-wide count of pass-loop launches per compiled instance of the loop (csrc/elim_small.h).  out receives
+ * five values: launches of the generic instance (any band count, either connectivity, diagnostics), of the
+ * 6-band 4-connected and 8-connected instances, of the 10-band 4-connected and 8-connected instances.  A batch
+ * is one launch; jobs that disagree run on the generic instance.  reset != 0 clears the counters after they
+ * are read.  Read-only otherwise. */
+int shp_small_loop_instances(uint64_t *out, int reset);
 
 /* ---- k-means ------------------------------------------------------------------------ */
 /* replaces sklearn KMeans(init=<array>, n_init=1).fit as called by

@@ -39,6 +39,7 @@ _SIGS = {
     'shp_prof_get': (_c.c_int, [_vp, _vp, _vp, _c.c_int, _c.c_int]),
     'shp_walk_batch_stats': (_c.c_int, [_vp, _c.c_int]),
     'shp_walk_batch_blocks': (_c.c_int, [_vp]),
+    'shp_small_loop_instances': (_c.c_int, [_vp, _c.c_int]),
     'shp_kmeans_fit': (_c.c_int, [_vp, _vp, _c.c_int64, _c.c_int, _c.c_int, _vp, _c.c_int,
                                   _c.c_double, _vp, _vp, _c.POINTER(_c.c_int)]),
     'shp_kmeans_fit_typed': (_c.c_int, [_vp, _vp, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _vp,

@@ -1173,6 +1173,16 @@ API int shp_walk_batch_blocks(uint64_t *out)
     return 0;
 }
 
+// pass-loop launches per instance of k_small_loop (elim_small.h SMALL_INSTANCES): the generic one, then 6 bands
+// 4- and 8-connected, then 10 bands 4- and 8-connected; process-wide
+API int shp_small_loop_instances(uint64_t *out, int reset)
+{
+    if (!out) return SHP_ERR_ARG;
+    for (int i = 0; i < SMALL_NINST; i++)
+        out[i] = reset ? g_small_inst[i].exchange(0ull, std::memory_order_relaxed) : g_small_inst[i].load(std::memory_order_relaxed);
+    return 0;
+}
+
 // ---- per-segment statistics (tilingstats) -------------------------------------------------------
 API int shp_segstats_dev(shp_ctx *ctx, const uint32_t *d_seg, const void *d_band, int dtype,
                          int64_t npix, uint32_t max_seg_id, int has_null, int64_t null_val,

@@ -26,6 +26,7 @@
 #include "gridbar.h"
 #include "elim_single.h"
 #include <type_traits>
+#include <atomic>
 
 __device__ __forceinline__ float f32_acc(float acc, long long v)
 {
@@ -487,6 +488,25 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
     return v;
 }
 
+// set bits of the wave-uniform mask m below this lane: two mbcnt instructions on the scalar mask, where
+// (m & lanemask_lt()) keeps a 64-bit mask per lane alive across the whole pass loop
+__device__ __forceinline__ uint32_t rank_below(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+// threadIdx.x through an empty asm statement: an address computed from it at the point of use is not hoisted out of
+// the pass loop (where it would hold two registers through every find, or be spilled, for one use per pass).
+// This leans on how one compiler version allocates: it is worth the last 28 bytes of scratch of the 6-band
+// instances, all of them outside the finds, and no time (LABNOTES 2026-10-21, seventh entry).  If a later compiler
+// hoists or spills differently, the resource report shows it and plain threadIdx.x does as well here.
+__device__ __forceinline__ uint32_t tid_here()
+{
+    uint32_t t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+}
+
 // A source that merges links itself into its target's list at once (the find phase does not read
 // these lists): the list is kept in ascending source id by a lock-free sorted insert (head in
 // tfill[t], links in tlist[s]; inserts only, so a failed CAS simply retries), the first source to
@@ -525,33 +545,44 @@ __device__ __forceinline__ void register_targets(const SmallArgs &a, SmallCnt *c
     uint32_t base = 0;
     if (lane_id() == (unsigned)__builtin_ctzll(m)) base = atomicAdd(&cnt->ntgt, (uint32_t)__popcll(m));
     base = (uint32_t)__shfl((int)base, __builtin_ctzll(m), 64);
-    if (first) a.tgtlist[base + (uint32_t)__popcll(m & lanemask_lt())] = t;
+    if (first) a.tgtlist[base + rank_below(m)] = t;
 }
+
+// The pass loop is compiled once per (band count, connectivity) that is worth an instance of its own, and once in
+// the generic form that reads both from the job record (k_small_loop below).  In a specialised instance the band
+// loops have compile-time bounds, the neighbour count is a constant and the diagnostics are absent.
+#define SMALL_SPEC_MAXNB 12
+constexpr int small_pairs_chunk(int nb) { return nb <= 6 ? nb : nb % 5 == 0 ? 5 : nb % 4 == 0 ? 4 : nb % 3 == 0 ? 3 : 1; }
 
 // distSqr between the mean spectra of source s (n pixels) and of U neighbour segments (shepseg.py:1041-1049: band
 // by band in ascending order, float32 throughout, means by division).  All loads of a chunk of eight bands --
 // the source's row and the U neighbours' rows -- are issued before the first use: written band by band the
 // loop waited for memory once per band and per neighbour, a dozen dependent round trips where one does.
 // Rows of neighbours that do not qualify are passed as s itself (a valid row; the result is ignored).
-template <int U>
+// NB != 0: the band count is a compile-time constant and one chunk holds exactly the NB bands -- no b0 loop, no
+// clamped tail (the instances of k_small_loop below); NB == 0 reads a.nb and goes eight bands at a time.
+template <int U, int NB>
 __device__ __forceinline__ void seg_dist_multi(const SmallArgs &a, uint32_t s, float nf, const uint32_t (&nbe)[U],
                                                const float (&sf)[U], float (&d)[U])
 {
+    static_assert(NB >= 0 && NB <= SMALL_SPEC_MAXNB, "a specialised instance keeps all its bands in one chunk");
+    constexpr int CH = NB ? NB : 8;
+    const int nb = NB ? NB : a.nb;
 #pragma unroll
     for (int u = 0; u < U; u++) d[u] = 0.0f;
-    const float *srow = a.ssum + (size_t)s * a.nb;
-    for (int b0 = 0; b0 < a.nb; b0 += 8) {
-        float xs[8], es[U][8];
+    const float *srow = a.ssum + (size_t)s * nb;
+    for (int b0 = 0; b0 < nb; b0 += CH) {
+        float xs[CH], es[U][CH];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+        for (int j = 0; j < CH; j++) {
+            const int b = NB ? j : (b0 + j < nb ? b0 + j : nb - 1);
             xs[j] = srow[b];
 #pragma unroll
-            for (int u = 0; u < U; u++) es[u][j] = a.ssum[(size_t)nbe[u] * a.nb + b];
+            for (int u = 0; u < U; u++) es[u][j] = a.ssum[(size_t)nbe[u] * nb + b];
         }
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (b0 + j < a.nb) {
+        for (int j = 0; j < CH; j++) {
+            if (NB || b0 + j < nb) {
                 const float x = xs[j] / nf;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
@@ -571,13 +602,15 @@ __device__ __forceinline__ void seg_dist_multi(const SmallArgs &a, uint32_t s, f
 // the FIRST strict minimum in (k, ii outer, jj inner) order (N7) == the lexicographic minimum
 // of (distSqr, k, position): one 64-bit wave reduction (distSqr >= +0, so its float32 bit
 // pattern orders like the value).
+template <int NB, int CONN, bool DIAG>
 __device__ __forceinline__ bool find_merge_wave(uint32_t s, uint32_t target, const SmallArgs &a,
                                                 uint32_t *wpix, SmallCnt *cnt, bool prof = false)
 {
     SP_DECL
     const unsigned lane = lane_id();
     const float nf = (float)target;
-    const uint32_t nq = a.four ? 4u : 8u;
+    const bool four = CONN ? CONN == 4 : a.four != 0;
+    const uint32_t nq = four ? 4u : 8u;
     unsigned long long best = ~0ull;         // (float bits of distSqr << 32) | order
     uint32_t bestnb = 0;
     uint32_t c = s, ci = 0;                  // chain cursor: chunk id, index inside the chunk
@@ -594,7 +627,7 @@ __device__ __forceinline__ bool find_merge_wave(uint32_t s, uint32_t target, con
             if (ci >= cm) {
                 c = cn;
                 if (c == 0) break;
-                if (a.hopstat && lane == 0) atomicAdd(a.hopstat, 1u);
+                if (DIAG && a.hopstat && lane == 0) atomicAdd(a.hopstat, 1u);
                 ci = 0;
                 rec = a.ch[c];
                 co = (uint32_t)__builtin_amdgcn_readfirstlane((int)rec.z);
@@ -625,7 +658,7 @@ __device__ __forceinline__ bool find_merge_wave(uint32_t s, uint32_t target, con
                     const uint32_t p = wpix[kk];
                     const uint32_t r = p / a.ncols, cc = p - r * a.ncols;
                     int di, dj;                  // neighbour `pos` in (ii outer, jj inner) order
-                    if (a.four) {
+                    if (four) {
                         di = (pos == 0u) ? -1 : (pos == 3u) ? 1 : 0;
                         dj = (pos == 1u) ? -1 : (pos == 2u) ? 1 : 0;
                     } else {
@@ -657,7 +690,7 @@ __device__ __forceinline__ bool find_merge_wave(uint32_t s, uint32_t target, con
                     sfv[u] = elig ? (float)szn[u] : nf;
                 }
                 if (__any(any)) {
-                    seg_dist_multi<4>(a, s, nf, nbe, sfv, dv);
+                    seg_dist_multi<4, NB>(a, s, nf, nbe, sfv, dv);
 #pragma unroll
                     for (uint32_t u = 0; u < 4u; u++) {
                         if (szn[u] > target) {
@@ -701,26 +734,30 @@ __device__ __forceinline__ bool find_merge_wave(uint32_t s, uint32_t target, con
 // links the source.  ids: this wavefront's list of `count` sources in LDS.  Returns how many of them merge.
 #define SMALL_BATCH_IDS 256u
 #define SMALL_BATCH_SRC 32u
-template <int U>
+template <int U, int NB>
 __device__ __forceinline__ void seg_dist_pairs(const SmallArgs &a, const uint32_t (&src)[U], float nf,
                                                const uint32_t (&nbe)[U], const float (&sf)[U], float (&d)[U])
 {
+    // four bands at a time: 8 U values in registers; a specialised instance takes chunks that divide NB exactly
+    constexpr int CH = NB ? small_pairs_chunk(NB) : 4;
+    static_assert(NB == 0 || NB % CH == 0, "exact chunks");
+    const int nb = NB ? NB : a.nb;
 #pragma unroll
     for (int u = 0; u < U; u++) d[u] = 0.0f;
-    for (int b0 = 0; b0 < a.nb; b0 += 4) {           // four bands at a time: 8 U values in registers
-        float xs[U][4], es[U][4];
+    for (int b0 = 0; b0 < nb; b0 += CH) {
+        float xs[U][CH], es[U][CH];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int b = b0 + j < a.nb ? b0 + j : a.nb - 1;
+        for (int j = 0; j < CH; j++) {
+            const int b = NB ? b0 + j : (b0 + j < nb ? b0 + j : nb - 1);
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                xs[u][j] = a.ssum[(size_t)src[u] * a.nb + b];
-                es[u][j] = a.ssum[(size_t)nbe[u] * a.nb + b];
+                xs[u][j] = a.ssum[(size_t)src[u] * nb + b];
+                es[u][j] = a.ssum[(size_t)nbe[u] * nb + b];
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (b0 + j < a.nb) {
+        for (int j = 0; j < CH; j++) {
+            if (NB || b0 + j < nb) {
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     const float x = xs[u][j] / nf;
@@ -734,14 +771,15 @@ __device__ __forceinline__ void seg_dist_pairs(const SmallArgs &a, const uint32_
     }
 }
 
-template <int U>
+template <int U, int NB, int CONN>
 __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32_t count, uint32_t target,
                                                      const SmallArgs &a, SmallCnt *cnt, unsigned long long *wkey,
                                                      bool prof = false)
 {
     SP_DECL
     const unsigned lane = lane_id();
-    const uint32_t nq = a.four ? 4u : 8u;
+    const bool four = CONN ? CONN == 4 : a.four != 0;
+    const uint32_t nq = four ? 4u : 8u, nqs = four ? 2u : 3u;  // (nq == 1 << nqs)
     const float nf = (float)target;
     const uint32_t npairs = target * nq;                       // <= 64 U
     uint32_t nsb = (64u * (uint32_t)U) / npairs;
@@ -751,19 +789,22 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
         const uint32_t nsrc = count - i0 < nsb ? count - i0 : nsb;
         const uint32_t nslots = nsrc * npairs;
         if (lane < SMALL_BATCH_SRC) wkey[lane] = ~0ull;
-        uint32_t src[U], si[U], kidx[U], kk[U], pos[U], c[U], cm[U], co[U];
+        // sp: the slot's source of the batch (< 32) above its pair of that source (< 256), one register for both.
+        // The pair is k * nq + position; k and position are a shift and a mask of it (nq is 4 or 8) and are taken
+        // from it where needed, not kept.
+        uint32_t src[U], sp[U], kk[U], c[U], cm[U], co[U];
+#define SLOT_SI(u) (sp[u] >> 8)
+#define SLOT_PR(u) (sp[u] & 255u)
         bool valid[U];
         // ---- the slots' sources and the heads of their pixel lists ----
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t q = (uint32_t)u * 64u + lane;
             valid[u] = q < nslots;
-            si[u] = q / npairs;
-            const uint32_t pr = q - si[u] * npairs;
-            kidx[u] = pr / nq;
-            pos[u] = pr - kidx[u] * nq;
-            kk[u] = kidx[u];
-            src[u] = valid[u] ? ids[i0 + si[u]] : ids[i0];
+            const uint32_t si = q / npairs, pr = q - si * npairs;
+            sp[u] = (si << 8) | pr;
+            kk[u] = pr >> nqs;
+            src[u] = valid[u] ? ids[i0 + si] : ids[i0];
             c[u] = src[u];
         }
         SP_MARK(a.ctl, 8, prof)
@@ -805,12 +846,13 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
         for (int u = 0; u < U; u++) {
             nbid[u] = 0u;
             const uint32_t r = p[u] / a.ncols, cc = p[u] - r * a.ncols;
+            const uint32_t pos = SLOT_PR(u) & (nq - 1u);
             int di, dj;                          // neighbour `pos` in (ii outer, jj inner) order
-            if (a.four) {
-                di = (pos[u] == 0u) ? -1 : (pos[u] == 3u) ? 1 : 0;
-                dj = (pos[u] == 1u) ? -1 : (pos[u] == 2u) ? 1 : 0;
+            if (four) {
+                di = (pos == 0u) ? -1 : (pos == 3u) ? 1 : 0;
+                dj = (pos == 1u) ? -1 : (pos == 2u) ? 1 : 0;
             } else {
-                const uint32_t e = pos[u] < 4u ? pos[u] : pos[u] + 1u;      // skip the centre
+                const uint32_t e = pos < 4u ? pos : pos + 1u;      // skip the centre
                 di = (int)(e / 3u) - 1;
                 dj = (int)(e % 3u) - 1;
             }
@@ -826,7 +868,9 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
         }
         SP_MARK(a.ctl, 11, prof && szn[0] != 0xFFFFFFFFu)
         // ---- distances, each source's minimum ----
-        unsigned long long key[U];
+        // (a slot keeps the float bits of its distance; its key is put together again where it is compared)
+        uint32_t dk[U];
+        bool elg[U];                                 // the slot's neighbour is larger than the source
 #pragma unroll
         for (int u0 = 0; u0 < U; u0 += 4) {
             uint32_t srcg[4], nbe[4];
@@ -835,20 +879,21 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const bool elig = szn[u0 + u] > target;
+                elg[u0 + u] = elig;
                 any |= elig;
                 srcg[u] = src[u0 + u];
                 nbe[u] = elig ? nbid[u0 + u] : src[u0 + u];
                 sfv[u] = elig ? (float)szn[u0 + u] : nf;
-                key[u0 + u] = ~0ull;
+                dk[u0 + u] = 0u;
             }
             if (__any(any)) {
-                seg_dist_pairs<4>(a, srcg, nf, nbe, sfv, dv);
+                seg_dist_pairs<4, NB>(a, srcg, nf, nbe, sfv, dv);
 #pragma unroll
                 for (int u = 0; u < 4; u++)
-                    if (szn[u0 + u] > target) {
-                        key[u0 + u] = ((unsigned long long)__float_as_uint(dv[u]) << 32) |
-                                      (unsigned long long)(kidx[u0 + u] * 8u + pos[u0 + u]);
-                        atomicMin(&wkey[si[u0 + u]], key[u0 + u]);
+                    if (elg[u0 + u]) {
+                        dk[u0 + u] = __float_as_uint(dv[u]);
+                        atomicMin(&wkey[SLOT_SI(u0 + u)], ((unsigned long long)dk[u0 + u] << 32) |
+                                  (unsigned long long)((SLOT_PR(u0 + u) >> nqs) * 8u + (SLOT_PR(u0 + u) & (nq - 1u))));
                     }
             }
         }
@@ -860,7 +905,12 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
         uint32_t *wtgt = (uint32_t *)(wkey + SMALL_BATCH_SRC);
 #pragma unroll
         for (int u = 0; u < U; u++)
-            if ((uint32_t)u * 64u + lane < nslots && key[u] != ~0ull && key[u] == wkey[si[u]]) wtgt[si[u]] = nbid[u];
+            if ((uint32_t)u * 64u + lane < nslots && elg[u] &&
+                (((unsigned long long)dk[u] << 32) |
+                 (unsigned long long)((SLOT_PR(u) >> nqs) * 8u + (SLOT_PR(u) & (nq - 1u)))) == wkey[SLOT_SI(u)])
+                wtgt[SLOT_SI(u)] = nbid[u];
+#undef SLOT_SI
+#undef SLOT_PR
         __builtin_amdgcn_wave_barrier();
         {
             bool won = false, first = false;
@@ -894,8 +944,17 @@ __device__ __forceinline__ uint32_t find_merge_batch(const uint32_t *ids, uint32
 // pinned report block are the job's, so a loop runs exactly as it would alone, and a group whose barrier times
 // out sets only its own `fail` and leaves alone.  The records sit in a buffer nobody writes while the kernel
 // runs (pinned host memory, filled before the launch).
+//
+// Instances.  NB = the band count (0: a.nb of the job), CONN = 4 | 8 (0: a.four of the job), DIAG = the
+// SHEPSEG_SMALL_TIMING bookkeeping (per-pass log, hop counter, phase ticks) and the SMALL_PROF marks.  The generic
+// instance <0, 0, true> serves every job; a specialised one only jobs of exactly its band count and connectivity,
+// without diagnostics (small_instance picks, small_launch launches one instance per batch).  All instances do the
+// same arithmetic in the same order.
+template <int NB, int CONN, bool DIAG>
 __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallArgs *__restrict__ jobs, const uint32_t nblk)
 {
+    static_assert((NB == 0) == (CONN == 0) && (CONN == 0 || CONN == 4 || CONN == 8), "generic, or both fixed");
+    static_assert(DIAG == (NB == 0), "the generic instance carries the diagnostics");
     const uint32_t jb = UNI(blockIdx.x / nblk), bid = UNI(blockIdx.x - jb * nblk);
     const SmallArgs a = jobs[jb];       // (uniform address, nothing stored before it: scalar loads)
     __shared__ uint32_t wpix[4][64];
@@ -907,8 +966,9 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
     __builtin_amdgcn_s_setprio(2);
     const uint32_t G = nblk;
     const uint32_t gtid = bid * 256u + threadIdx.x, gthreads = G * 256u;
-    const uint32_t gwave = gtid >> 6, gwaves = gthreads >> 6;
-    const unsigned lane = lane_id(), w = threadIdx.x >> 6;
+    // (the wavefront's indices are wave-uniform: kept in scalar registers, with everything derived from them)
+    const uint32_t gwave = UNI(gtid >> 6), gwaves = gthreads >> 6;
+    const unsigned lane = lane_id(), w = UNI(threadIdx.x >> 6);
     // where does this workgroup run?  count the launch's workgroups per XCD, meet once with the
     // one-level barrier so that everybody sees the final counts, then use the two-level barrier
     __shared__ SmallBar s_bar;
@@ -927,7 +987,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
         s_bar.poll = a.poll;
     }
     __syncthreads();
-    const SmallBar bar = s_bar;
+    const SmallBar bar = {UNI(s_bar.xcd), UNI(s_bar.nx), UNI(s_bar.nactive), (int)UNI(s_bar.poll)};
     // ---- per-size source lists.  A pass needs the segments of exactly `target` pixels.  Sizes only grow, so
     //      they are: the segments that HAD that size at entry (bysize: the ids below min_seg counting-sorted by
     //      size, built here) plus the targets that GREW to it in an earlier pass (grown[size]: appended by the
@@ -974,7 +1034,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
         __syncthreads();
         if (!(a.bar2 ? small_grid_barrier2(ctl, bar) : small_grid_barrier(ctl, G, a.poll))) return;
     }
-    unsigned long long tmark = wall_clock64();
+    unsigned long long tmark = DIAG ? wall_clock64() : 0ull;
     SP_DECL
     for (uint32_t slot = 0;; slot++) {
         const uint32_t par = slot & 1u;
@@ -1012,15 +1072,17 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
             }
         }
         __syncthreads();
-        if (s_done) {
+        if (UNI(s_done)) {
             // workgroup 0 hands the control block to the host (every other workgroup's counters
             // reached the L2 before the last barrier)
             if (bid == 0)
-                for (uint32_t i = threadIdx.x; i < (uint32_t)(sizeof(SmallCtl) / 4); i += 256u)
+                for (uint32_t i = tid_here(); i < (uint32_t)(sizeof(SmallCtl) / 4); i += 256u)
                     MIRROR_STORE(&a.pin[i], L2LOAD(&((const uint32_t *)ctl)[i]));
             break;
         }
-        const uint32_t target = s_target;
+        // (what every lane reads alike from LDS or memory is moved to scalar registers: the loops it bounds
+        //  become scalar branches, and it stays out of the vector registers the finds need)
+        const uint32_t target = UNI(s_target);
         SmallCnt *cnt = &ctl->cnt[slot % 3u];
         SP_MARK(ctl, 0, sprof)
         // ---- find phase: sources = segments of the target size.  Every wavefront scans its own
@@ -1029,42 +1091,56 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
         //      what it finds at once.  With few (the ~40 late passes of a tile: a few hundred sources of
         //      30-50 pixels) the pass lasts as long as the wavefront that happened to find the most --
         //      four or five dependent find chains where the average is one -- so the sources are only
-        //      LISTED by the scan, the grid meets once more, and the list is dealt round robin. ----
-        const bool balanced = s_count <= SMALL_BALANCED_MAX;
-        const bool from_lists = lists && gover[target] == 0u;
+        //      LISTED by the scan, the grid meets once more, and the list is dealt round robin.
+        //      A wavefront's sources reach it in one of three ways -- taken from the size's lists, found by its
+        //      own scan, dealt from the listed ones -- and each way only fills wids[w]: ONE section below runs
+        //      the finds on it, so that each of the two find functions is in the kernel once. ----
+        const bool balanced = UNI(s_count) <= SMALL_BALANCED_MAX;
+        const bool from_lists = lists && UNI(gover[target]) == 0u;
+        const uint32_t npairs = target * (CONN ? (uint32_t)CONN : a.four ? 4u : 8u);
+        enum { SRC_LISTS, SRC_SCAN, SRC_DEAL };
+        uint32_t mode = from_lists ? SRC_LISTS : SRC_SCAN;
+        // a batch of sources per wavefront up to 256 pairs each, a wavefront per source above; the balanced deal
+        // keeps a wavefront per source from 129 pairs (eight slots per lane would spill: see below)
+        bool batch = npairs <= 256u;
+        // SRC_LISTS: the candidates of this size, dealt in even chunks of at most 256; no scan, no listing barrier
+        uint32_t lb0 = 0, lnb0 = 0, lnc = 0, chunk = 1;
         if (from_lists) {
-            // the candidates of this size, dealt in even chunks of at most 256; no scan, no listing barrier
-            const uint32_t b0 = bstart[target], nb0 = bstart[target + 1u] - b0;
-            const uint32_t nc = nb0 + gcount[target];            // (no overflow: gcount <= cap)
-            const uint32_t npairs = target * (a.four ? 4u : 8u);
+            lb0 = UNI(bstart[target]); lnb0 = UNI(bstart[target + 1u]) - lb0;
+            lnc = lnb0 + UNI(gcount[target]);                         // (no overflow: gcount <= cap)
             // (a third to a half of the candidates are stale, unevenly: a static deal left some wavefront with
             //  three or four sources of 45 pixels where the average is one; so the wavefronts TAKE chunks from
             //  a counter, about four per wavefront)
-            uint32_t chunk = (nc + 4u * gwaves - 1u) / (4u * gwaves);
+            chunk = (lnc + 4u * gwaves - 1u) / (4u * gwaves);
             chunk = chunk < 1u ? 1u : chunk > SMALL_BATCH_IDS ? SMALL_BATCH_IDS : chunk;
-            uint32_t wmerges = 0;
-            for (;;) {
+        }
+        // SRC_SCAN: this wavefront's next four slices of the size table.  SRC_DEAL: its next listed sources
+        const uint32_t stride = gwaves * 64u;
+        uint32_t base = gwave * 64u, di = 0, nlisted = 0;
+        uint32_t wmerges = 0;
+        for (;;) {
+            uint32_t nfound = 0;                 // sources gathered in wids[w]
+            if (mode == SRC_LISTS) {
                 uint32_t c0 = 0;
                 if (lane == 0) c0 = atomicAdd(&cnt->work, chunk);
                 c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c0);
-                if (c0 >= nc) break;
-                const uint32_t nn = nc - c0 < chunk ? nc - c0 : chunk;
+                if (c0 >= lnc) break;
+                const uint32_t nn = lnc - c0 < chunk ? lnc - c0 : chunk;
                 uint32_t id[4];
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) {
                     const uint32_t o = u * 64u + lane, ci = c0 + o;
                     id[u] = 0u;
-                    if (o < nn) id[u] = ci < nb0 ? bysize[b0 + ci] : grown[(size_t)target * cap + (ci - nb0)];
+                    if (o < nn) id[u] = ci < lnb0 ? bysize[lb0 + ci] : grown[(size_t)target * cap + (ci - lnb0)];
                 }
                 uint32_t szv[4];
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) szv[u] = id[u] ? a.segsz[id[u]] : 0xFFFFFFFFu;
-                uint32_t nfound = 0;
 #pragma unroll
                 for (uint32_t u = 0; u < 4u; u++) {
                     const bool ok = id[u] >= a.min_id && id[u] != 0u && szv[u] == target;
                     const unsigned long long m = __ballot(ok);
-                    if (ok) wids[w][nfound + (uint32_t)__popcll(m & lanemask_lt())] = id[u];
+                    if (ok) wids[w][nfound + rank_below(m)] = id[u];
                     nfound += (uint32_t)__popcll(m);
                 }
                 SP_MARK(ctl, 1, sprof)
@@ -1075,112 +1151,91 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
                 gbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)gbase);
                 for (uint32_t q = lane; q < nfound; q += 64u) a.srclist[gbase + q] = wids[w][q];
                 SP_MARK(ctl, 2, sprof)
-#ifdef SMALL_PROF
-                if (npairs <= 256u) wmerges += find_merge_batch<4>(wids[w], nfound, target, a, cnt, wkeys[w], sprof);
-#else
-                if (npairs <= 256u) wmerges += find_merge_batch<4>(wids[w], nfound, target, a, cnt, wkeys[w]);
-#endif
-                else for (uint32_t q = 0; q < nfound; q++) {
-#ifdef SMALL_PROF
-                    wmerges += find_merge_wave((uint32_t)__builtin_amdgcn_readfirstlane((int)wids[w][q]), target, a, wpix[w],
-                                               cnt, sprof) ? 1u : 0u;
-                    if (sprof) ctl->prof[7] += 1;
-#else
-                    wmerges += find_merge_wave((uint32_t)__builtin_amdgcn_readfirstlane((int)wids[w][q]), target, a, wpix[w],
-                                               cnt) ? 1u : 0u;
-#endif
+            } else if (mode == SRC_SCAN) {
+                if (base >= a.S) {
+                    if (!balanced) break;
+                    // every source is listed: the grid meets once more, then the list is dealt round robin
+                    SP_MARK(ctl, 1, sprof)
+                    if (!(a.bar2 ? small_grid_barrier2(ctl, bar) : small_grid_barrier(ctl, G, a.poll))) return;
+                    SP_MARK(ctl, 2, sprof)
+                    nlisted = UNI(cnt->nsrc);
+                    mode = SRC_DEAL;
+                    batch = npairs <= 128u;
+                    chunk = 1u;
+                    if (batch) {
+                        // several sources fit a batch: deal chunks of them (no larger than an even share).  (Eight
+                        // slots per lane, i.e. two sources of 33..64 pixels at once, need 250 registers -- two such
+                        // loops per CU -- or spill at 128: the late passes came out 10 % slower than with a
+                        // wavefront per source.)
+                        chunk = 256u / npairs;
+                        chunk = chunk > SMALL_BATCH_SRC ? SMALL_BATCH_SRC : chunk;
+                        const uint32_t share = (nlisted + gwaves - 1u) / gwaves;
+                        chunk = chunk > share ? (share ? share : 1u) : chunk;
+                    }
+                    di = gwave * chunk;
+                    continue;
                 }
-                __builtin_amdgcn_wave_barrier();
-                SP_MARK(ctl, 3, sprof)
-            }
-            SP_MARK(ctl, 1, sprof)
-            if (wmerges && lane == 0) atomicAdd(&cnt->nmerge, wmerges);
-        } else {
-            const uint32_t stride = gwaves * 64u;
-            uint32_t wmerges = 0;
-            for (uint32_t base = gwave * 64u; base < a.S; base += 4u * stride) {
                 uint32_t sz[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const uint32_t sid = base + (uint32_t)u * stride + lane + 1u;
                     sz[u] = sid <= a.S && sid >= a.min_id ? a.segsz[sid] : 0xFFFFFFFFu;
                 }
-                const uint32_t npairs = target * (a.four ? 4u : 8u);
-                uint32_t nfound = 0;                 // sources of these four slices, gathered in wids[w]
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
-                    unsigned long long m = __ballot(sz[u] == target);
+                    const unsigned long long m = __ballot(sz[u] == target);
                     if (m == 0ull) continue;
-                    const uint32_t b0 = base + (uint32_t)u * stride;
+                    const uint32_t sb0 = base + (uint32_t)u * stride;
                     uint32_t gbase = 0;
                     if (lane == 0) gbase = atomicAdd(&cnt->nsrc, (uint32_t)__popcll(m));
                     gbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)gbase);
-                    const uint32_t rank = (uint32_t)__popcll(m & lanemask_lt());
-                    if (sz[u] == target) a.srclist[gbase + rank] = b0 + lane + 1u;
+                    const uint32_t rank = rank_below(m);
+                    if (sz[u] == target) a.srclist[gbase + rank] = sb0 + lane + 1u;
                     if (balanced) continue;
-                    if (npairs <= 256u) {
-                        if (sz[u] == target) wids[w][nfound + rank] = b0 + lane + 1u;
-                        nfound += (uint32_t)__popcll(m);
-                    } else while (m) {
-                        const uint32_t src = b0 + (uint32_t)__builtin_ctzll(m) + 1u;
-                        m &= m - 1ull;
-                        wmerges += find_merge_wave(src, target, a, wpix[w], cnt) ? 1u : 0u;
-                    }
+                    if (sz[u] == target) wids[w][nfound + rank] = sb0 + lane + 1u;
+                    nfound += (uint32_t)__popcll(m);
                 }
-                if (nfound) {
-                    __builtin_amdgcn_wave_barrier();
-                    wmerges += find_merge_batch<4>(wids[w], nfound, target, a, cnt, wkeys[w]);
-                }
+                base += 4u * stride;
+                if (nfound == 0u) continue;
+            } else {
+                if (di >= nlisted) break;
+                nfound = nlisted - di < chunk ? nlisted - di : chunk;
+                if (lane < nfound) wids[w][lane] = a.srclist[di + lane];
+                di += gwaves * chunk;
             }
-            if (balanced) {
-                SP_MARK(ctl, 1, sprof)
-                if (!(a.bar2 ? small_grid_barrier2(ctl, bar) : small_grid_barrier(ctl, G, a.poll))) return;
-                SP_MARK(ctl, 2, sprof)
-                const uint32_t nlisted = cnt->nsrc;
-                const uint32_t npairs = target * (a.four ? 4u : 8u);
-                if (npairs <= 128u) {
-                    // several sources fit a batch: deal chunks of them (no larger than an even share).  (Eight
-                    // slots per lane, i.e. two sources of 33..64 pixels at once, need 250 registers -- two such
-                    // loops per CU -- or spill at 128: the late passes came out 10 % slower than with a
-                    // wavefront per source.)
-                    uint32_t chunk = 256u / npairs;
-                    chunk = chunk > SMALL_BATCH_SRC ? SMALL_BATCH_SRC : chunk;
-                    const uint32_t share = (nlisted + gwaves - 1u) / gwaves;
-                    chunk = chunk > share ? (share ? share : 1u) : chunk;
-                    for (uint32_t i = gwave * chunk; i < nlisted; i += gwaves * chunk) {
-                        const uint32_t nn = nlisted - i < chunk ? nlisted - i : chunk;
-                        if (lane < nn) wids[w][lane] = a.srclist[i + lane];
-                        __builtin_amdgcn_wave_barrier();
-                        wmerges += find_merge_batch<4>(wids[w], nn, target, a, cnt, wkeys[w]);
-                    }
-                } else
-                for (uint32_t i = gwave; i < nlisted; i += gwaves) {
-                    const uint32_t src = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.srclist[i]);
+            // ---- the finds of wids[w][0 .. nfound) ----
+            __builtin_amdgcn_wave_barrier();
 #ifdef SMALL_PROF
-                    wmerges += find_merge_wave(src, target, a, wpix[w], cnt, sprof) ? 1u : 0u;
-                    if (sprof) ctl->prof[7] += 1;
+            const bool fprof = sprof;
 #else
-                    wmerges += find_merge_wave(src, target, a, wpix[w], cnt) ? 1u : 0u;
+            const bool fprof = false;
 #endif
-                }
-                SP_MARK(ctl, 3, sprof)
+            if (batch) wmerges += find_merge_batch<4, NB, CONN>(wids[w], nfound, target, a, cnt, wkeys[w], fprof);
+            else for (uint32_t q = 0; q < nfound; q++) {
+                wmerges += find_merge_wave<NB, CONN, DIAG>((uint32_t)__builtin_amdgcn_readfirstlane((int)wids[w][q]), target,
+                                                           a, wpix[w], cnt, fprof) ? 1u : 0u;
+#ifdef SMALL_PROF
+                if (sprof) ctl->prof[7] += 1;
+#endif
             }
-            if (wmerges && lane == 0) atomicAdd(&cnt->nmerge, wmerges);
+            __builtin_amdgcn_wave_barrier();
+            SP_MARK(ctl, 3, sprof)
         }
+        if (wmerges && lane == 0) atomicAdd(&cnt->nmerge, wmerges);
         if (!(a.bar2 ? small_grid_barrier2(ctl, bar) : small_grid_barrier(ctl, G, a.poll))) return;
         SP_MARK(ctl, 4, sprof)
-        const uint32_t nsrc = cnt->nsrc;
-        if (gtid == 0) {
+        const uint32_t nsrc = UNI(cnt->nsrc);
+        if (DIAG && gtid == 0) {
             const unsigned long long t = wall_clock64();
             const uint32_t pi = (uint32_t)ctl->tphase[3] & 63u;
             ctl->plog[pi][0] = target; ctl->plog[pi][1] = nsrc; ctl->plog[pi][2] = (uint32_t)(t - tmark); ctl->plog[pi][3] = 0;
             if (a.hopstat) ctl->phops[pi] = atomicExch(a.hopstat, 0u);
             ctl->tphase[0] += t - tmark; tmark = t;
         }
-        if (cnt->nmerge == 0u) {
+        if (UNI(cnt->nmerge) == 0u) {
             // nobody merges (every candidate was further than maxSpectralDiff, or had no larger
             // neighbour): nothing to link, relabel or absorb, the size histogram is unchanged
-            if (gtid == 0) ctl->tphase[3] += 1;
+            if (DIAG && gtid == 0) ctl->tphase[3] += 1;
             continue;
         }
         // ---- merge phase.  The sources linked themselves to their targets during the find phase, so
@@ -1226,7 +1281,7 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
             }
         }
         SP_MARK(ctl, 5, sprof)
-        const uint32_t ntgt = cnt->ntgt;
+        const uint32_t ntgt = UNI(cnt->ntgt);
         // ---- merge step 2: each target absorbs its sources in ascending id (doMerge :1112-1123)
         //      size-histogram updates go through LDS, numElim through a wave reduction ----
         for (uint32_t b = threadIdx.x; b < 256u; b += 256u) lhist[b] = 0;
@@ -1240,15 +1295,18 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
             // the target's sums stay in registers (eight bands at a time) while its sources are added in
             // ascending id; everything a source contributes -- its link, size, chain tail and sums -- is loaded
             // together (band by band, with stores in between, every band was a round trip of its own)
-            for (int b0 = 0; b0 < a.nb; b0 += 8) {
-                float acc[8];
+            // (a specialised instance: all NB bands in one round)
+            constexpr int ACH = NB ? NB : 8;
+            const int nbv = NB ? NB : a.nb;
+            for (int b0 = 0; b0 < nbv; b0 += ACH) {
+                float acc[ACH];
 #pragma unroll
-                for (int j = 0; j < 8; j++) acc[j] = b0 + j < a.nb ? a.ssum[(size_t)t * a.nb + b0 + j] : 0.0f;
+                for (int j = 0; j < ACH; j++) acc[j] = NB || b0 + j < nbv ? a.ssum[(size_t)t * nbv + b0 + j] : 0.0f;
                 for (uint32_t s = a.tfill[t]; s != 0;) {
                     const uint32_t nxt = a.tlist[s];
-                    float add[8];
+                    float add[ACH];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) add[j] = b0 + j < a.nb ? a.ssum[(size_t)s * a.nb + b0 + j] : 0.0f;
+                    for (int j = 0; j < ACH; j++) add[j] = NB || b0 + j < nbv ? a.ssum[(size_t)s * nbv + b0 + j] : 0.0f;
                     if (b0 == 0) {
                         const uint32_t ssz = a.segsz[s], stail = chw[4u * (size_t)s + 3u];
                         sz += ssz;
@@ -1259,12 +1317,12 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
                                                      //  and every pass rewrites it for its own sources)
                     }
 #pragma unroll
-                    for (int j = 0; j < 8; j++)
-                        if (b0 + j < a.nb) { acc[j] = acc[j] + add[j]; a.ssum[(size_t)s * a.nb + b0 + j] = 0.0f; }
+                    for (int j = 0; j < ACH; j++)
+                        if (NB || b0 + j < nbv) { acc[j] = acc[j] + add[j]; a.ssum[(size_t)s * nbv + b0 + j] = 0.0f; }
                     s = nxt;
                 }
 #pragma unroll
-                for (int j = 0; j < 8; j++) if (b0 + j < a.nb) a.ssum[(size_t)t * a.nb + b0 + j] = acc[j];
+                for (int j = 0; j < ACH; j++) if (NB || b0 + j < nbv) a.ssum[(size_t)t * nbv + b0 + j] = acc[j];
             }
             a.segsz[t] = sz;
             chw[4u * (size_t)t + 3u] = tail;
@@ -1285,12 +1343,12 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
             if (target < 256u) atomicSub(&lhist[target], my_elim); else atomicSub(&a.hist[target], my_elim);
         }
         __syncthreads();
-        if (threadIdx.x < a.min_seg && lhist[threadIdx.x] != 0u)
-            atomicAdd(&a.hist[threadIdx.x], lhist[threadIdx.x]);          // wrapping add of the delta
+        const uint32_t ht = tid_here();
+        if (ht < a.min_seg && lhist[ht] != 0u) atomicAdd(&a.hist[ht], lhist[ht]);          // wrapping add of the delta
         SP_MARK(ctl, 6, sprof)
         if (!(a.bar2 ? small_grid_barrier2(ctl, bar) : small_grid_barrier(ctl, G, a.poll))) return;
         SP_MARK(ctl, 15, sprof)
-        if (gtid == 0) {
+        if (DIAG && gtid == 0) {
             const unsigned long long t = wall_clock64();
             ctl->plog[(uint32_t)ctl->tphase[3] & 63u][3] = (uint32_t)(t - tmark);
             ctl->tphase[1] += t - tmark; tmark = t; ctl->tphase[3] += 1;
@@ -1303,13 +1361,70 @@ __global__ __launch_bounds__(256, SMALL_MINWAVES) void k_small_loop(const SmallA
 #define SMALL_MAX_CONCURRENT 20
 static const int g_small_max = getenv("SHEPSEG_SMALL_MAX") ? atoi(getenv("SHEPSEG_SMALL_MAX")) : SMALL_MAX_CONCURRENT;
 
+// The instances of k_small_loop: X(id, band count, connectivity); id 0 is the generic one.
+#define SMALL_INSTANCES(X)          \
+    X(SMALL_INST_GENERIC, 0, 0)     \
+    X(SMALL_INST_6_4, 6, 4)         \
+    X(SMALL_INST_6_8, 6, 8)         \
+    X(SMALL_INST_10_4, 10, 4)       \
+    X(SMALL_INST_10_8, 10, 8)
+enum {
+#define SMALL_INST_ENUM(id, NB, CONN) id,
+    SMALL_INSTANCES(SMALL_INST_ENUM)
+#undef SMALL_INST_ENUM
+    SMALL_NINST
+};
+// pass-loop launches per instance, process-wide (shp_small_loop_instances)
+static std::atomic<unsigned long long> g_small_inst[SMALL_NINST];
+// the instance a job can run on: a specialised one for its exact band count and connectivity, the generic one
+// for everything else, for SHEPSEG_SMALL_TIMING (hopstat set) and for a SMALL_PROF build
+static int small_instance(const SmallArgs &a)
+{
+#ifdef SMALL_PROF
+    (void)a;
+#else
+    if (a.hopstat) return SMALL_INST_GENERIC;
+#define SMALL_INST_PICK(id, NB, CONN) if (NB != 0 && a.nb == NB && (a.four ? 4 : 8) == CONN) return id;
+    SMALL_INSTANCES(SMALL_INST_PICK)
+#undef SMALL_INST_PICK
+#endif
+    return SMALL_INST_GENERIC;
+}
+
 // one launch for nj pass loops; jobs[i]->arg is the tile's SmallArgs, `rec` a pinned block that stays untouched
 // until the kernel has left
 static void small_launch(hipStream_t st, walkbatch::Job *const *jobs, int nj, unsigned small_blocks, void *rec)
 {
     SmallArgs *r = (SmallArgs *)rec;
     for (int i = 0; i < nj; i++) r[i] = *(const SmallArgs *)jobs[i]->arg;
-    hipLaunchKernelGGL(k_small_loop, dim3((unsigned)nj * small_blocks), dim3(256), 0, st, (const SmallArgs *)r, (uint32_t)small_blocks);
+    // one instance per launch: the specialised one all jobs agree on, else the generic one (which reads band
+    // count and connectivity from each job's own record)
+    int inst = small_instance(r[0]);
+    for (int i = 1; i < nj && inst != SMALL_INST_GENERIC; i++)
+        if (small_instance(r[i]) != inst) inst = SMALL_INST_GENERIC;
+    g_small_inst[inst].fetch_add(1ull, std::memory_order_relaxed);
+    const dim3 grid((unsigned)nj * small_blocks);
+    const SmallArgs *cr = r;
+    const uint32_t nblk = (uint32_t)small_blocks;
+    switch (inst) {
+#define SMALL_INST_LAUNCH(id, NB, CONN)                                                                              \
+    case id: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_small_loop<NB, CONN, NB == 0>), grid, dim3(256), 0, st, cr, nblk); break;
+    SMALL_INSTANCES(SMALL_INST_LAUNCH)
+#undef SMALL_INST_LAUNCH
+    }
+}
+// workgroups of 256 threads per CU that every instance can keep resident: the co-residency budget of the grid
+// barriers is sized by the instance with the largest footprint, whichever instance a launch then takes
+static int small_blocks_per_cu()
+{
+    int least = 0;
+#define SMALL_INST_OCC(id, NB, CONN)                                                                                 \
+    { int n = 0;                                                                                                     \
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_small_loop<NB, CONN, NB == 0>, 256, 0) != hipSuccess || n < 1) n = 1; \
+      if (least == 0 || n < least) least = n; }
+    SMALL_INSTANCES(SMALL_INST_OCC)
+#undef SMALL_INST_OCC
+    return least;
 }
 // the leader's side of a batched pass loop: borrow a walker stream, launch, wait, give the stream back
 static int small_lead(shp_ctx *ctx, walkbatch::Job *const *jobs, int nj, unsigned small_blocks, double *ms)
@@ -1416,8 +1531,7 @@ static int run_eliminate_small(shp_ctx *ctx, const void *d_img, int dtype, int n
     // 128 VGPRs = 4 workgroups per CU = 1024 on the device = 16 loops of 64); never more than SHEPSEG_SMALL_MAX.
     // A batch of B loops counts as B against it
     static const int cap = [] {
-        int per_cu = 0, dev = 0, ncu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_small_loop, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        int per_cu = small_blocks_per_cu(), dev = 0, ncu = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 64;
         int c = (int)((unsigned)(per_cu * ncu) / (small_blocks ? small_blocks : 1u));
